@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: trajectory-points/s through Theta-build + residual (+ gradient) + symmetry regulariser.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): damped oscillator, n_ics=50 x steps=2500 x dim=2 fp32, poly-order 5 (p = 21),
 EquivSINDy-c (so2 equivariance constraint, Xi = reshape(Q beta) + const), batched over S independent
@@ -14,11 +14,15 @@ projection of the summed gradient onto (beta, const); and -- for N > 1 -- the RC
 ``--gpus N`` without a torchrun environment starts the N ranks itself (``python -m torch.distributed.run``) BEFORE
 anything touches the GPU and relays rank 0's line.
 
-Prints ONE JSON line (rank 0) following the driver's contract, plus
-  roofline      : the dominant kernel of the step priced against the HBM roof (algorithmic bytes / live HIP-event time;
-                  PMC traffic when profiles/pmc_traffic.json holds it),
-  roofline_legs : the same for every kernel of the step and for the Euler-flow pair of the infinitesimal regulariser
-                  (timed after the K steps on a slice of the resident points; not part of ``value``),
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) following the driver's contract, plus
+  roofline      : the dominant kernel of the step priced against the HBM roof (algorithmic bytes / live HIP-event time
+                  of the K timed steps; PMC traffic when profiles/pmc_traffic.json holds it),
+  roofline_legs : the same for every kernel of the step.
+``--dump-outputs DIR`` writes what the last timed step returned -- loss (S,), d/dbeta (S, q), d/dconst (S, d, 1), fp32 --
+as DIR/<name>.npy (the inputs are seeded: the same arguments give the same inputs in every run).
+``--full`` adds the measurements that take runs of their own (none of them is part of ``value``):
+  roofline_legs : also the Euler-flow pair of the infinitesimal regulariser (timed after the K steps on a slice of the
+                  resident points),
   cpu_baseline  : the CPU oracle ("port" of the reference op sequence) timed on the host cores on a bounded sample of
                   the same step (rank 0, N = 1 only); ``legs``: BASELINE.md section 3's table -- Theta only, closure, one
                   sequential-threshold pass with full / partial mask, all cores and one thread, median of 20,
@@ -59,7 +63,7 @@ def parse(argv=None):
     ap.add_argument("--chunks", type=int, default=0, help="problem chunks per step; chunk c's all-reduce overlaps chunk c+1's kernels (default: 1 on one GPU, 2 when the [loss|grad] buffer is all-reduced)")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--cpu_seconds", type=float, default=12.0)
-    ap.add_argument("--config3", action="store_true", help="run the config[3] Gram + all-reduce leg even in a --profile run")
+    ap.add_argument("--config3", action="store_true", help="run the config[3] Gram + all-reduce leg even without --full or in a --profile run")
     ap.add_argument("--no_sweeps", action="store_true", help="skip the informational seed-sweep timings (N = 1 only)")
     ap.add_argument("--shard", choices=["points", "seeds"], default="points",
                     help="N > 1: 'points' = every rank holds a shard of each problem's trajectories and the packed "
@@ -74,7 +78,24 @@ def parse(argv=None):
                     help="profiling run: only the batched steps (no legs, no single-problem loop, no CPU baseline), so that "
                          "rocprofv3 --stats averages the step's launches alone")
     ap.add_argument("--master_port", type=int, default=0, help="rendezvous port when bench.py starts the ranks itself (0 = pick a free one)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline: Euler-flow legs, single problem, config[3] Gram + "
+                         "all-reduce, seed sweeps, CPU baseline (each still subject to --profile / --no_sweeps / --no_cpu_baseline)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, grad_beta, grad_const; fp32) as DIR/<name>.npy")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+def dump_outputs(out, path):
+    """The closure's return value of the last timed step, as a caller of BatchedClosure.evaluate receives it."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in zip(("loss", "grad_beta", "grad_const"), out):
+        if arr is not None:
+            np.save(os.path.join(path, name + ".npy"), arr.detach().float().cpu().numpy())
 
 
 def spawn_ranks(a):
@@ -486,6 +507,8 @@ def main():
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, a.dump_outputs)
 
     launches_per_step = max(max(len(t_lg.events), len(t_fc.events)) // max(a.steps, 1), 1)
     pts_per_launch = (S / launches_per_step) * n_pts
@@ -502,7 +525,7 @@ def main():
 
     # ---- Euler-flow pair of the infinitesimal regulariser (S2): K = 10 steps + tangent, and its reverse ----
     single = {}
-    if not a.profile:
+    if a.full and not a.profile:
         S2 = min(S, 512)
         n2 = S2 * n_pts
         x2 = x[:S2].reshape(n2, d)
@@ -572,7 +595,7 @@ def main():
 
     # ---- BASELINE config[3]: 64-seed index-table Gram on point shards + ONE fp64 all-reduce of the (64, 12, 12) stack ----
     c3 = None
-    if (not a.profile and not a.no_sweeps) or a.config3:
+    if (a.full and not a.profile and not a.no_sweeps) or a.config3:
         try:
             c3 = config3_leg(eng, dev, rank, world, dist.group.WORLD if use_dist else None, a.rehearse_gloo)
         except Exception as e:                               # an informational leg never fails the bench line
@@ -609,9 +632,9 @@ def main():
         res["single_problem"] = single
     if c3 is not None:
         res["config3_gram_allreduce"] = c3
-    if world == 1 and not a.profile and not a.no_sweeps:
+    if a.full and world == 1 and not a.profile and not a.no_sweeps:
         res["seed_sweeps"] = seed_sweeps(eng, dev)
-    if world == 1 and not a.no_cpu_baseline and not a.profile:
+    if a.full and world == 1 and not a.no_cpu_baseline and not a.profile:
         ns = min(S, 4)
         Xi_s = clos.xi_from(beta, const)[:ns].cpu()
         sym_c = None if sym is None else (sym[0][:ns].cpu(), sym[1][:ns].cpu(), sym[2])

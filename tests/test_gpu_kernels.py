@@ -566,7 +566,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse_gloo", "--problems", "64", "--steps", "3",
-                          "--warmup", "1", "--no_cpu_baseline", "--profile", "--config3", "--master_port", "29533"], env=env, stdout=subprocess.PIPE,
+                          "--warmup", "1", "--no_cpu_baseline", "--profile", "--config3", "--full", "--master_port", "29533"], env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -594,7 +594,7 @@ def test_bench_collective_path_on_rccl_with_one_rank(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force_dist", "--problems", "64", "--steps", "3", "--warmup", "1",
-                          "--no_cpu_baseline", "--profile", "--config3", "--master_port", "29541"], env=env, stdout=subprocess.PIPE,
+                          "--no_cpu_baseline", "--profile", "--config3", "--full", "--master_port", "29541"], env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -605,6 +605,35 @@ def test_bench_collective_path_on_rccl_with_one_rank(tmp_path):
     assert "error" not in c3, c3
     assert c3["allreduce_us"] is not None and c3["allreduce_us"] > 0 and "gloo" not in str(c3.get("allreduce_backend", ""))
     assert c3["allreduced_vs_single_rank_max_rel_err"] == 0.0
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain ``bench.py`` run (no --full) times exactly --steps steps and carries none of the --full legs;
+    ``--dump-outputs DIR`` leaves the last timed step's (loss, grad_beta, grad_const) as fp32 .npy files, and two runs
+    with the same arguments see the same seeded inputs, hence the same outputs."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--problems", "64", "--steps", "3",
+                              "--warmup", "1", "--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                             text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert not {"cpu_baseline", "single_problem", "seed_sweeps", "config3_gram_allreduce"} & set(rec)
+        dumps.append({name: np.load(d / f"{name}.npy") for name in ("loss", "grad_beta", "grad_const")})
+    a, b = dumps
+    assert a["loss"].shape == (64,) and a["grad_beta"].shape[0] == 64 and a["grad_const"].shape == (64, 2, 1)
+    for name in a:
+        assert a[name].dtype == np.float32 and np.isfinite(a[name]).all(), name
+        np.testing.assert_allclose(b[name], a[name], rtol=1e-6, atol=0, err_msg=name)
 
 
 @pytest.mark.parametrize("d,order,fl,K,n", only_compiled([(2, 2, 2, 10, 20000), (2, 3, 0, 3, 4097), (3, 2, 0, 5, 3001), (1, 4, 1, 16, 1000),

@@ -7,8 +7,8 @@ TAG=${1:-r03}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O="$R/gpurun_out"
 mkdir -p "$O"
-cd "$R" && python bench.py > "$O/${TAG}_bench_n1.json" 2> "$O/${TAG}_bench_n1.err" && echo "bench done"
-python bench.py --two_launch_sym --no_cpu_baseline --steps 50 > "$O/${TAG}_bench_n1_two_launch.json" 2>/dev/null && echo "two-launch bench done"
+cd "$R" && python bench.py --full > "$O/${TAG}_bench_n1.json" 2> "$O/${TAG}_bench_n1.err" && echo "bench done"
+python bench.py --full --two_launch_sym --no_cpu_baseline --steps 50 > "$O/${TAG}_bench_n1_two_launch.json" 2>/dev/null && echo "two-launch bench done"
 cd /tmp && export TMPDIR=/tmp
 # per-kernel durations of the bench step (same command, profiling mode: only the K batched steps)
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 "$R/bench.py" --steps 20 --warmup 3 --profile > /dev/null 2>&1 && echo "trace done"
