@@ -153,6 +153,28 @@ int symode_loss_grad_reversed(const float* x, const float* dx, const float* gx, 
                               int d, int order, int flags, const float* xi, const float* mask, float inv_count, float w_sym,
                               float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Gram matrix of the reversed regulariser: for S problems (layouts as in symode_symreg_reversed_batched, n_g >= 1)
+ *     gram_out[s] (d p, d p) fp64 = sum_g sum_n B^T B,   B[i, (j, a)] = J_g(x_n)[i, j] theta_a(x_n) - delta_ij theta_a(g x_n),
+ * rows and columns in Xi's (d, p) row-major order, both triangles filled: the regulariser of symode_symreg_reversed_batched
+ * is inv_count * v^T R v with v = vec(xi * mask).  RAW sums (no inv_count): shards and chunks of points simply add.
+ * Exact fp64 products of the fp32 library, fp64 sums.  The workspace is its own (symode_symreg_reversed_gram_workspace_bytes;
+ * no symode_workspace_init needed).  SYMODE_E_UNSUPPORTED for libraries with d p > 88.
+ * replaces: nothing in the reference; the fixed-data part of model_utils.py:160-168, accumulated once per fit. */
+size_t symode_symreg_reversed_gram_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long n);
+int symode_symreg_reversed_gram(const float* x, const float* gx, const float* jgx, int n_g, long n_problems, long n, int d,
+                                int order, int flags, double* gram_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The closure of the non-latent fit as a quadratic form of fixed fp64 matrices, for S problems (library independent,
+ * d p <= 256): aug_gram (S, p+d, p+d) from symode_aug_gram, rev_gram (S, d p, d p) from symode_symreg_reversed_gram or NULL;
+ * xi, mask (S, d, p) fp32 (mask may be NULL = ones), W = xi * mask, v = vec(W):
+ *     mse = inv_count (tr(W Gtt W^T) - 2 tr(W Gty) + tr(Gyy)),   reg = inv_count v^T R v.
+ * rev_gram == NULL: loss_out (S) = mse, grad_out (S, d, p) = d mse / dxi (masked), as symode_loss_grad;
+ * else loss_out (S, 2) = (mse, reg) and grad_out = d(mse + w_sym reg)/dxi (masked), as symode_loss_grad_reversed.
+ * fp64 arithmetic, one rounding to fp32.  One launch, one wave per problem, no workspace.
+ * replaces: the closure body train.py:663-664 (+ 675-679 with sym_reg_type 'r') + 689, on the data of train.py:626-629. */
+int symode_quad_closure(const double* aug_gram, const double* rev_gram, long n_problems, int d, int p, const float* xi,
+                        const float* mask, double inv_count, float w_sym, float* loss_out, float* grad_out, void* stream);
+
 /* Reverse mode of symode_forward, given g = dL/d(out) (n, d):
  *   grad_x (n, d) = J_Theta(x)^T (xi*mask)^T g   (skipped when grad_x is NULL),
  *   grad_xi (d, p) = (g^T Theta(x)) * mask.
@@ -307,6 +329,11 @@ typedef struct symode_trainer {
     float* log_mask;
     float* log_params;
     int log_epochs;
+    /* Gram-form closure (symode_quad_closure), or NULL: with aug_gram (S, p+d, p+d) fp64 every closure of the trainer is the
+     * quadratic form of these matrices at inv_count / w_sym, and x, dx, gx, jgx and workspace may be NULL; rev_gram
+     * (S, d p, d p) fp64 or NULL adds the reversed regulariser (then the closure is the (mse, regulariser) pair). */
+    const double* aug_gram;
+    const double* rev_gram;
 } symode_trainer;
 
 #define SYMODE_TRAINER_FIELDS 29

@@ -5,6 +5,7 @@
 
 #include "../../include/symode.h"
 #include "ops_table.hpp"
+#include "quad_closure.hpp"
 
 using namespace symode;
 
@@ -120,7 +121,7 @@ size_t workspace_doubles(const LibOps* ops, long S, long n) {
 
 extern "C" {
 
-int symode_abi_version(void) { return 5; }
+int symode_abi_version(void) { return 6; }
 
 void symode_reload_env(void) { knobs() = read_knobs(); }
 
@@ -303,6 +304,35 @@ int symode_loss_grad_reversed(const float* x, const float* dx, const float* gx_,
     }
     return (int)ops->symreg_reversed(x, dx, gx_, jgx, n_g, n_problems, n, xi, mask, inv_count, w_sym, loss2_out, grad_out,
                                      (double*)workspace, gx, (hipStream_t)stream);
+}
+
+size_t symode_symreg_reversed_gram_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long n) {
+    const LibOps* ops = find_ops(d, order, flags);
+    if (!ops || !ops->symreg_reversed_gram || n_g < 1 || n_problems < 1 || n < 1) return 0;
+    return rev_gram_workspace_doubles(ops->d * ops->p, n_problems, n, n_g) * sizeof(double);
+}
+
+int symode_symreg_reversed_gram(const float* x, const float* gx_, const float* jgx, int n_g, long n_problems, long n, int d,
+                                int order, int flags, double* gram_out, void* workspace, size_t workspace_bytes, void* stream) {
+    SYMODE_GET_OPS();
+    if (!ops->symreg_reversed_gram) return SYMODE_E_UNSUPPORTED;
+    if (n < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
+    if (!x || !gx_ || !jgx || !gram_out) return SYMODE_E_NULLPTR;
+    if (misaligned(x, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(gram_out, 8)) return SYMODE_E_ALIGN;
+    if (!workspace || misaligned(workspace, 8)) return SYMODE_E_WORKSPACE;
+    if (workspace_bytes < rev_gram_workspace_doubles(ops->d * ops->p, n_problems, n, n_g) * sizeof(double)) return SYMODE_E_WORKSPACE;
+    return (int)ops->symreg_reversed_gram(x, gx_, jgx, n_g, n_problems, n, gram_out, (double*)workspace, (hipStream_t)stream);
+}
+
+int symode_quad_closure(const double* aug_gram, const double* rev_gram, long n_problems, int d, int p, const float* xi,
+                        const float* mask, double inv_count, float w_sym, float* loss_out, float* grad_out, void* stream) {
+    if (n_problems < 1 || d < 1 || p < 1 || d * p > QUAD_MAX_DP) return SYMODE_E_BADSIZE;
+    if (!aug_gram || !xi || !loss_out || !grad_out) return SYMODE_E_NULLPTR;
+    if (misaligned(aug_gram, 8) || misaligned(rev_gram, 8) || misaligned(xi, 4) || misaligned(mask, 4) || misaligned(loss_out, 4) ||
+        misaligned(grad_out, 4))
+        return SYMODE_E_ALIGN;
+    return (int)launch_quad_closure(aug_gram, rev_gram, n_problems, d, p, xi, mask, inv_count, w_sym, loss_out, grad_out,
+                                    (hipStream_t)stream);
 }
 
 int symode_symreg_reversed(const float* x, const float* gx_, const float* jgx, int n_g, long n, int d, int order,

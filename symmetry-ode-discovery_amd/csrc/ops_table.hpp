@@ -1,6 +1,7 @@
 // One translation unit per state dimension D instantiates every kernel for its libraries.
 #pragma once
 #include "gram.hpp"
+#include "gram_rev.hpp"
 #include "gram_valu.hpp"
 #include "kernels.hpp"
 #include "weak.hpp"
@@ -28,7 +29,8 @@ constexpr LibOps make_ops() {
                   &launch_rk4_traj<Lib>,
                   &launch_euler_jvp<Lib>,
                   &launch_euler_jvp_vjp<Lib>,
-                  &launch_weak_gram<Lib>};
+                  &launch_weak_gram<Lib>,
+                  rev_gram_launcher<Lib>()};
 }
 
 #define SYMODE_OPS_ALL_FLAGS(D, O) make_ops<D, O, 0>(), make_ops<D, O, 1>(), make_ops<D, O, 2>(), make_ops<D, O, 3>()

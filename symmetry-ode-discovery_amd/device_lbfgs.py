@@ -16,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from .engine import TRAINER_FIELDS, SymodeError, TrainerDesc, get_engine
+from .gram_closure import GramStatistics
 
 NEAR_THRESHOLD_BAND = 1e-4            # sindy.NEAR_THRESHOLD_BAND; repeated here to keep imports light
 
@@ -39,22 +40,43 @@ class DeviceTrainer:
 
     def __init__(self, x, dx, poly_order, flags=0, Q=None, use_kron_product=True, allow_constant=True, reversed_sym=None,
                  lr=1.0, threshold=0.1, st_freq=0, w_x=1.0, w_reg=0.0, l1=True, tol=1e-3, max_iter=20, history=100,
-                 tol_grad=1e-7, tol_change=1e-9, inv_count=None, engine=None, detail=None, group=None):
+                 tol_grad=1e-7, tol_change=1e-9, inv_count=None, engine=None, detail=None, group=None, closure="stream",
+                 statistics=None):
         """x, dx (S, N_local, d) device tensors; ``reversed_sym = (gx (S, n_g, N, d), jgx (S, n_g, N, d, d), weight)`` as
         batched.BatchedClosure; ``group``: point shards, [loss | grad] summed over the ranks between closure and update;
-        ``detail``: keep coefficients and mask of every epoch in the record (default: for S <= 64)."""
+        ``detail``: keep coefficients and mask of every epoch in the record (default: for S <= 64).
+        ``closure="gram"``: every closure is the quadratic form of the fixed fp64 matrices [G | R] (gram_closure.py), built
+        here in one pass over x, dx (, gx, jgx) -- or taken from ``statistics``, a GramStatistics of this rank's points, when
+        x, dx, gx, jgx may be None -- and, with ``group``, summed over the ranks in ONE all-reduce at set-up; the fit then
+        runs without any collective and holds no reference to the point data."""
         self.engine = engine or get_engine()
-        if not (x.is_cuda and x.dim() == 3 and x.shape == dx.shape and x.dtype == torch.float32):
-            raise SymodeError("DeviceTrainer expects x, dx as (S, N, d) fp32 device tensors; there is no CPU fallback")
+        if closure not in ("stream", "gram"):
+            raise SymodeError(f"closure must be 'stream' or 'gram', got {closure!r}")
+        self.gram = closure == "gram"
+        self.stats = None
         lib = self.engine.lib
-        self.x, self.dx = x.contiguous(), dx.contiguous()
-        self.S, self.n_points, self.d = x.shape
         self.order, self.flags = int(poly_order), int(flags)
+        if self.gram:
+            self.stats = self._gram_statistics(x, dx, reversed_sym, statistics, group)
+            self.S, self.d, dev = self.stats.S, self.stats.d, self.stats.device
+            self.n_points = self.stats.count
+            self.x = self.dx = None
+            if inv_count is None:
+                inv_count = self.stats.inv_count()
+            group = None                                      # the fit itself needs no collective
+        else:
+            if statistics is not None:
+                raise SymodeError("statistics are for closure='gram'")
+            if not (x.is_cuda and x.dim() == 3 and x.shape == dx.shape and x.dtype == torch.float32):
+                raise SymodeError("DeviceTrainer expects x, dx as (S, N, d) fp32 device tensors; there is no CPU fallback")
+            self.x, self.dx = x.contiguous(), dx.contiguous()
+            self.S, self.n_points, self.d = x.shape
+            dev = x.device
+        self.device = dev
         self.p = self.engine.lib_size(self.d, self.order, self.flags)
         self.dp = self.d * self.p
         self.group = group
         world = dist.get_world_size(group) if group is not None else 1
-        dev = x.device
         self.q_eff = None
         if Q is not None:
             q = effective_Q(Q, self.d, self.p, use_kron_product)
@@ -68,7 +90,9 @@ class DeviceTrainer:
         if self.n > 256 or self.dp > 256 or history > 128:
             raise SymodeError("DeviceTrainer handles at most 256 parameters / coefficients and 128 curvature pairs")
         self.sym = None
-        if reversed_sym is not None:
+        self.pair = reversed_sym is not None
+        self.w_sym = float(reversed_sym[2]) if reversed_sym is not None else 0.0
+        if reversed_sym is not None and not self.gram:
             gx, jgx, weight = reversed_sym
             if gx.dim() != 4 or gx.shape[0] != self.S or tuple(gx.shape[2:]) != tuple(x.shape[1:]) or tuple(jgx.shape) != tuple(gx.shape) + (self.d,):
                 raise SymodeError("reversed_sym operands do not match x")
@@ -84,8 +108,10 @@ class DeviceTrainer:
         self._off = dict(zip(TRAINER_FIELDS, [int(o) for o in offs]))
         self._shape = {"params": (self.S, self.n), "xi": (self.S, self.d, self.p), "mask": (self.S, self.d, self.p),
                        "cl_loss": (self.S, 2), "cl_grad": (self.S, self.dp), "g": (self.S, self.n), "loss": (self.S,)}
-        ws_bytes = lib.symode_workspace_bytes(self.d, self.order, self.flags, self.S, self.n_points)
-        self.ws = self.engine.new_workspace(dev, ws_bytes)
+        self.ws = None
+        if not self.gram:
+            ws_bytes = lib.symode_workspace_bytes(self.d, self.order, self.flags, self.S, self.n_points)
+            self.ws = self.engine.new_workspace(dev, ws_bytes)
         # --- per-epoch records: pinned host memory the kernels write directly (sharded runs: device memory, copied)
         R = self.LOG_RING
         mk = (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)) if self.distributed else \
@@ -101,14 +127,21 @@ class DeviceTrainer:
             dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=group)
             n_global = int(cnt.item())
         T = TrainerDesc()
-        T.x, T.dx = self.x.data_ptr(), self.dx.data_ptr()
-        if self.sym is not None:
-            T.gx, T.jgx, T.n_g, T.w_sym = self.sym[0].data_ptr(), self.sym[1].data_ptr(), self.sym[0].shape[1], self.sym[2]
+        if self.gram:
+            T.x = T.dx = None
+            T.aug_gram = self.stats.G.data_ptr()
+            T.rev_gram = self.stats.R.data_ptr() if self.pair else None
+            T.gx, T.jgx, T.n_g, T.w_sym = None, None, 0, self.w_sym
         else:
-            T.gx, T.jgx, T.n_g, T.w_sym = None, None, 0, 0.0
+            T.x, T.dx = self.x.data_ptr(), self.dx.data_ptr()
+            T.aug_gram = T.rev_gram = None
+            if self.sym is not None:
+                T.gx, T.jgx, T.n_g, T.w_sym = self.sym[0].data_ptr(), self.sym[1].data_ptr(), self.sym[0].shape[1], self.sym[2]
+            else:
+                T.gx, T.jgx, T.n_g, T.w_sym = None, None, 0, 0.0
         T.n_problems, T.n_points, T.d, T.order, T.flags = self.S, self.n_points, self.d, self.order, self.flags
         T.inv_count = float(inv_count) if inv_count is not None else 1.0 / (n_global * self.d)
-        T.workspace, T.workspace_bytes = self.ws.data_ptr(), self.ws.numel() * 8
+        T.workspace, T.workspace_bytes = (None, 0) if self.ws is None else (self.ws.data_ptr(), self.ws.numel() * 8)
         T.q_eff = self.q_eff.data_ptr() if self.q_eff is not None else None
         T.r, T.allow_constant, T.n_params = self.r, int(bool(allow_constant)), self.n
         T.w_x, T.w_reg, T.l1 = float(w_x), float(w_reg), int(bool(l1))
@@ -126,14 +159,30 @@ class DeviceTrainer:
         self.threshold = float(threshold)
 
     # -- plumbing -----------------------------------------------------------------------------------------------------
+    def _gram_statistics(self, x, dx, reversed_sym, statistics, group):
+        """[G | R | count] of this rank's points, summed over ``group`` in one collective."""
+        if statistics is None:
+            if not (x is not None and x.is_cuda and x.dim() == 3 and x.shape == dx.shape and x.dtype == torch.float32):
+                raise SymodeError("DeviceTrainer expects x, dx as (S, N, d) fp32 device tensors; there is no CPU fallback")
+            statistics = GramStatistics(x.shape[0], x.shape[2], self.order, self.flags, regulariser=reversed_sym is not None,
+                                        device=x.device, engine=self.engine)
+            gx, jgx = (reversed_sym[0], reversed_sym[1]) if reversed_sym is not None else (None, None)
+            statistics.add(x, dx, gx, jgx)
+        elif (statistics.order, statistics.flags) != (self.order, self.flags) or statistics.regulariser != (reversed_sym is not None):
+            raise SymodeError("statistics were built for another library or without / with the regulariser")
+        if group is not None:
+            statistics.all_reduce(group)
+        return statistics
+
     def _check(self, rc, what):
         if rc != 0:
             # a launch that failed half-way may have left tickets of the one-launch reductions behind: start them afresh
-            self.engine.lib.symode_workspace_init(self.ws.data_ptr(), self.ws.numel() * 8, self._st())
+            if self.ws is not None:
+                self.engine.lib.symode_workspace_init(self.ws.data_ptr(), self.ws.numel() * 8, self._st())
             self.engine._check(rc, what)
 
     def _st(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.x.device).cuda_stream)
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def field(self, name):
         """A device view of one array of the state block."""
@@ -148,7 +197,7 @@ class DeviceTrainer:
         test = self.log_test[slot].cpu().numpy() if self.distributed else self.log_test[slot].numpy().copy()
         rec = {"code": log[:, 0].astype(np.int64), "mse": log[:, 1], "sym": log[:, 2], "l1": log[:, 3], "update_norm": log[:, 4],
                "update_norm_2": log[:, 5], "near": log[:, 6].astype(np.int64), "epoch": log[:, 7].astype(np.int64),
-               "test": test[:, 0] if self.sym is not None else test.reshape(-1)[:self.S], "xi": None, "mask": None, "params": None}
+               "test": test[:, 0] if self.pair else test.reshape(-1)[:self.S], "xi": None, "mask": None, "params": None}
         if self.detail:
             get = (lambda a: a[slot].cpu().numpy()) if self.distributed else (lambda a: a[slot].numpy().copy())
             rec["xi"] = get(self.log_xi).reshape(self.S, self.d, self.p)
@@ -159,7 +208,7 @@ class DeviceTrainer:
     def _epoch_sharded(self, epoch, test_eval):
         """One epoch with the ranks' partial [loss | grad] summed between closure and update (RCCL / gloo)."""
         lib, st = self.engine.lib, self._st()
-        width = (2 if self.sym is not None else 1) * self.S
+        width = (2 if self.pair else 1) * self.S
         cl = self.state[self._off["cl_loss"]:self._off["cl_grad"] + self.S * self.dp * 4].view(torch.float32)
         # (cl_loss is (S, 2) floats with cl_grad right behind it; the plain closure fills the first S floats only)
         for it in range(self.max_iter):
@@ -185,7 +234,7 @@ class DeviceTrainer:
         per epoch, in order, with the epoch's record (numpy arrays over the problems: code, mse, sym, l1, update_norm,
         near, test, and with ``detail`` xi / mask after the epoch's events); returning True ends the fit.
         Returns dict(Xi, mask, params, epochs, finished, nan, near_threshold) of host tensors."""
-        lib, dev = self.engine.lib, self.x.device
+        lib, dev = self.engine.lib, self.device
         P0 = P0.detach().to(torch.float32).contiguous()
         if tuple(P0.shape) != (self.S, self.n):
             raise SymodeError(f"P0 must be ({self.S}, {self.n}), got {tuple(P0.shape)}")

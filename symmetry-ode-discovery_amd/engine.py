@@ -50,6 +50,11 @@ _SIGNATURES = {
                                  c_void_p]),
     "symode_loss_grad_reversed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p,
                                           c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
+    "symode_symreg_reversed_gram": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, c_size_t, c_void_p]),
+    "symode_quad_closure": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, ctypes.c_double, c_float,
+                                    c_void_p, c_void_p, c_void_p]),
     "symode_vjp": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_size_t, c_void_p]),
     "symode_forward_jvp": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -81,7 +86,7 @@ _SIGNATURES = {
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class TrainerDesc(ctypes.Structure):
@@ -94,7 +99,8 @@ class TrainerDesc(ctypes.Structure):
                 ("max_iter", c_int), ("history", c_int),
                 ("threshold", c_float), ("tol_update", c_float), ("near_band", c_float), ("st_freq", c_int),
                 ("state", c_void_p), ("state_bytes", c_size_t),
-                ("log", c_void_p), ("log_test", c_void_p), ("log_xi", c_void_p), ("log_mask", c_void_p), ("log_params", c_void_p), ("log_epochs", c_int)]
+                ("log", c_void_p), ("log_test", c_void_p), ("log_xi", c_void_p), ("log_mask", c_void_p), ("log_params", c_void_p), ("log_epochs", c_int),
+                ("aug_gram", c_void_p), ("rev_gram", c_void_p)]
 
 
 TRAINER_FIELDS = ("params", "xi", "mask", "cl_loss", "cl_grad", "g", "loss", "act", "n_iter", "d", "t", "old_dirs", "old_stps", "ro",
@@ -414,6 +420,58 @@ class HipEngine:
         if not batched:
             return loss2.reshape(2), grad.reshape(d, p)
         return loss2.reshape(S, 2), grad.reshape(S, d, p)
+
+    def symreg_reversed_gram(self, x, gx, jgx, order, flags=0):
+        """fp64 Gram matrix R of the reversed regulariser (raw sums over points and group elements, no 1/(N d)):
+        x (N, d), gx (n_g, N, d), jgx (n_g, N, d, d) -> (d p, d p); or x (S, N, d), gx (S, n_g, N, d), jgx (S, n_g, N, d, d)
+        -> (S, d p, d p).  Rows / columns in Xi's (d, p) row-major order: the regulariser is v^T R v / (N d), v = vec(Xi * M)."""
+        x, gx, jgx = self._dev(x, "x"), self._dev(gx, "gx"), self._dev(jgx, "jgx")
+        batched = x.dim() == 3
+        S = x.shape[0] if batched else 1
+        n, d = x.shape[-2], x.shape[-1]
+        n_g = gx.shape[1] if batched else gx.shape[0]
+        want_g = (S, n_g, n, d) if batched else (n_g, n, d)
+        if n_g < 1 or tuple(gx.shape) != want_g or tuple(jgx.shape) != want_g + (d,):
+            raise SymodeError(f"gx {tuple(gx.shape)} / jgx {tuple(jgx.shape)} do not match x {tuple(x.shape)}")
+        p = self.lib_size(d, order, flags)
+        need = self.lib.symode_symreg_reversed_gram_workspace_bytes(d, order, flags, n_g, S, n)
+        if need == 0:
+            raise SymodeError(f"symreg_reversed_gram does not support the library d={d} order={order} flags={flags}")
+        ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+        gram = torch.empty(S, d * p, d * p, dtype=torch.float64, device=x.device)
+        self._check(self.lib.symode_symreg_reversed_gram(self._ptr(x), self._ptr(gx), self._ptr(jgx), n_g, S, n, d, order, flags,
+                                                         self._ptr(gram), self._ptr(ws), need, self._stream(x)),
+                    "symode_symreg_reversed_gram")
+        return gram if batched else gram[0]
+
+    def quad_closure(self, G, R, xi, mask, inv_count, w_sym=1.0):
+        """The closure as a quadratic form of fixed fp64 matrices: G (S, p+d, p+d) augmented Gram, R (S, d p, d p) or None,
+        xi / mask (S, d, p) (mask may be None).  Returns what loss_grad (R None: loss (S,)) or loss_grad_reversed (loss2
+        (S, 2)) returns, with grad (S, d, p); unbatched G (p+d, p+d) gives unbatched outputs."""
+        batched = G.dim() == 3
+        G = self._dev(G, "G", torch.float64).reshape(-1, G.shape[-2], G.shape[-1])
+        S, F = G.shape[0], G.shape[1]
+        xi = self._dev(xi, "xi")
+        d = xi.shape[-2]
+        p = F - d
+        if G.shape[2] != F or xi.numel() != S * d * p:
+            raise SymodeError(f"G {tuple(G.shape)} and xi {tuple(xi.shape)} do not match")
+        mask = None if mask is None else self._dev(mask, "mask")
+        if mask is not None and mask.numel() != xi.numel():
+            raise SymodeError("mask does not match xi")
+        if R is not None:
+            R = self._dev(R, "R", torch.float64)
+            if R.numel() != S * (d * p) ** 2:
+                raise SymodeError(f"R {tuple(R.shape)} does not match ({S}, {d * p}, {d * p})")
+        loss = torch.empty(S, 2 if R is not None else 1, dtype=torch.float32, device=G.device)
+        grad = torch.empty(S, d, p, dtype=torch.float32, device=G.device)
+        self._check(self.lib.symode_quad_closure(self._ptr(G), self._ptr(R), S, d, p, self._ptr(xi), self._ptr(mask),
+                                                 float(inv_count), float(w_sym), self._ptr(loss), self._ptr(grad), self._stream(G)),
+                    "symode_quad_closure")
+        loss = loss if R is not None else loss.reshape(S)
+        if not batched:
+            return loss[0], grad[0]
+        return loss, grad
 
     def bind_closure(self, x, dx, xi, mask, order, flags, out, ws, stream, reversed_sym=None, w_sym=1.0):
         """A zero-argument callable that launches the single-problem closure on fixed buffers: every check and every

@@ -148,7 +148,8 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
                           allow_constant=getattr(template, 'allow_constant', True), group=group,
                           **({'engine': engine} if engine is not None else {}))
     sweep = SeedSweepLBFGS(clos, args['lr_sindy'], args['threshold'], args['st_freq'], w_sindy_x=args['w_sindy_x'],
-                           sindy_reg_type=args['sindy_reg_type'], w_sindy_reg=args['w_sindy_reg'])
+                           sindy_reg_type=args['sindy_reg_type'], w_sindy_reg=args['w_sindy_reg'],
+                           gram_closure=bool(args.get('gram_closure')))
     out = sweep.fit(torch.stack(inits).to(dev), args['num_epochs'])
 
     if rank != 0:

@@ -359,8 +359,13 @@ class SeedSweepLBFGS:
     convergence -- evaluated per problem on (S, ...) tensors; the closure of all seeds is ONE launch of the
     fused Theta + residual + gradient kernel (BatchedClosure), all-reduced over point shards if sharded."""
 
-    def __init__(self, closure, lr_sindy, threshold, st_freq, w_sindy_x=1.0, sindy_reg_type="l1", w_sindy_reg=0.0, tol=1e-3):
+    def __init__(self, closure, lr_sindy, threshold, st_freq, w_sindy_x=1.0, sindy_reg_type="l1", w_sindy_reg=0.0, tol=1e-3,
+                 gram_closure=False):
+        """``gram_closure``: the device trainer evaluates every closure as the quadratic form of the seeds' fp64 Gram
+        matrices (gram_closure.py), built once from the closure's data (and summed over the point shards in one
+        all-reduce) instead of streaming the points per evaluation."""
         self.c = closure
+        self.gram_closure = bool(gram_closure)
         self.lr, self.threshold, self.st_freq, self.tol = lr_sindy, threshold, st_freq, tol
         self.w_x, self.reg_type, self.w_reg = w_sindy_x, sindy_reg_type, w_sindy_reg
         if sindy_reg_type not in ("l1", "none"):
@@ -418,11 +423,18 @@ class SeedSweepLBFGS:
     def _fit_native(self, P0, num_epochs, mask0, on_epoch):
         from .device_lbfgs import DeviceTrainer
         c = self.c
-        tr = DeviceTrainer(c.x, c.dx, c.order, c.flags, Q=c.Q, use_kron_product=c.use_kron, allow_constant=c.allow_constant,
+        stats = None
+        if self.gram_closure:
+            from .gram_closure import GramStatistics
+            stats = GramStatistics(c.S, c.d, c.order, c.flags, regulariser=c.sym is not None, device=c.x.device, engine=c.engine)
+            stats.add(c.x, c.dx, *(c.sym[:2] if c.sym is not None else ()))
+        x, dx = (None, None) if stats is not None else (c.x, c.dx)          # the Gram form holds no reference to the points
+        tr = DeviceTrainer(x, dx, c.order, c.flags, Q=c.Q, use_kron_product=c.use_kron, allow_constant=c.allow_constant,
                            reversed_sym=c.sym, lr=self.lr, threshold=self.threshold, st_freq=self.st_freq, w_x=self.w_x,
                            w_reg=self.w_reg if self.reg_type == 'l1' else 0.0, l1=True, tol=self.tol, inv_count=c.inv_count,
                            engine=c.engine, group=(c.group or dist.group.WORLD) if c.distributed else None,
-                           detail=on_epoch is not None and c.S <= 64)
+                           detail=on_epoch is not None and c.S <= 64, closure='stream' if stats is None else 'gram',
+                           statistics=stats)
         self.trainer = tr
         cb = None
         if on_epoch is not None:
@@ -444,6 +456,8 @@ class SeedSweepLBFGS:
         c = self.c
         if self._native_ok(P0):
             return self._fit_native(P0, num_epochs, mask0, on_epoch)
+        if self.gram_closure:
+            raise ValueError('gram_closure=True needs the device trainer (a GPU closure of one chunk, d p <= 256)')
         P = P0.clone().contiguous()
         S = P.shape[0]
         self.mask = torch.ones(S, c.d, c.p, device=P.device) if mask0 is None else mask0.clone()

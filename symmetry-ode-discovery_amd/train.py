@@ -778,14 +778,16 @@ def _lbfgs_phase(regressor, closure, losses, num_epochs, lr_sindy, st_freq, thre
 
 def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_sindy, st_freq, threshold, w_sindy_x,
                      sindy_reg_type, w_sindy_reg, w_sym_reg, losses, save_dir, print_eq, log_interval=0, save_interval=0,
-                     test_log=None, group=None):
+                     test_log=None, group=None, gram_closure=False):
     """The non-latent L-BFGS fit with NOTHING on the host between two epochs (device_lbfgs.DeviceTrainer): closure kernel +
     ONE optimiser launch per inner iteration, the per-epoch logic of train.py:697-725 as one more launch, and a record per
     epoch in pinned memory from which this function produces what the reference produces per epoch -- the convergence /
     thresholding / NaN messages, the loss line, the "test" line (train.py:739-751), the equations, the wandb record and the
     interval checkpoints -- in the reference's order.  The record holds the LAST closure evaluation's terms (what the
     reference's ``losses`` dict holds when the epoch ends) and, for the "test" line, the closure re-evaluated at the
-    epoch's final coefficients and mask.  ``group``: x, dx are this rank's point shard."""
+    epoch's final coefficients and mask.  ``group``: x, dx are this rank's point shard.  ``gram_closure``: the closure is
+    the quadratic form of the batch's fp64 Gram matrices (gram_closure.py), built in one pass and summed over the ranks in
+    one all-reduce; the fit itself then needs no collective."""
     from .device_lbfgs import EVENT_FINAL, EVENT_NAN, EVENT_THRESHOLD_CONVERGED, EVENT_THRESHOLD_PERIOD, DeviceTrainer
     d = x.shape[-1]
     rev = None
@@ -806,7 +808,8 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
                        use_kron_product=getattr(regressor, 'use_kron_product', True),
                        allow_constant=getattr(regressor, 'allow_constant', True), reversed_sym=rev, lr=lr_sindy,
                        threshold=threshold, st_freq=st_freq, w_x=w_sindy_x, w_reg=w_sindy_reg if sindy_reg_type == 'l1' else 0.0,
-                       l1=sindy_reg_type == 'l1', engine=regressor.engine, detail=True, group=group)
+                       l1=sindy_reg_type == 'l1', engine=regressor.engine, detail=True, group=group,
+                       closure='gram' if gram_closure else 'stream')
 
     def adopt(params, mask):                               # a host state into the regressor (two small uploads)
         with torch.no_grad():
@@ -869,7 +872,7 @@ def train_SIGED_lbfgs(
     autoencoder, generator,  # symmetry discovery model
     regressor, regressor_dst, use_latent, distill_latent, lr_sindy, w_sindy_z, w_sindy_x,  # SINDy
     sindy_reg_type, w_sindy_reg, sym_reg_type, w_sym_reg, st_freq, threshold, int_t, int_dt,  # SINDy
-    **kwargs
+    gram_closure=False, **kwargs
 ):
     if distill_latent and not use_latent:
         raise ValueError('Cannot distill without first learning latent space equation. Set use_latent=True.')
@@ -1051,10 +1054,13 @@ def train_SIGED_lbfgs(
         # device, the optimiser's variables move to the host
         shadow = _HostParams(regressor)
         closure = shadow.wrap(closure)
+    if gram_closure and not on_device:
+        raise ValueError('gram_closure=True needs the device trainer: the non-latent fit with MSE [+ L1] [+ the reversed '
+                         'regulariser on a frozen autoencoder] on a GPU, without torch_lbfgs / numpy_lbfgs')
     if on_device:
         _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_sindy, st_freq, threshold, w_sindy_x,
                          sindy_reg_type, w_sindy_reg, w_sym_reg, losses, save_dir, print_eq, log_interval, save_interval,
-                         test_log=test_log, group=kwargs.get('group'))
+                         test_log=test_log, group=kwargs.get('group'), gram_closure=gram_closure)
     else:
         _lbfgs_phase(regressor, closure, losses, num_epochs, lr_sindy, st_freq, threshold, log_interval, save_interval,
                      save_dir, print_eq, on_log=test_log, shadow=shadow)
