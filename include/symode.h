@@ -164,6 +164,18 @@ size_t symode_symreg_reversed_gram_workspace_bytes(int d, int order, int flags, 
 int symode_symreg_reversed_gram(const float* x, const float* gx, const float* jgx, int n_g, long n_problems, long n, int d,
                                 int order, int flags, double* gram_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Same, for n_problems index subsets of ONE shared data set: x (n_src, d), gx (n_g, n_src, d), jgx (n_g, n_src, d, d) fp32;
+ * problem s uses the m rows idx[s*m + k], k < m (int32 row indices < n_src; the caller guarantees the range).
+ * gram_out[s] (d p, d p) is bit-identical to symode_symreg_reversed_gram on the materialised copies x[idx[s]],
+ * gx[:, idx[s]], jgx[:, idx[s]]: the same item order (g m + k), grid and fixed-order finalize.  The workspace query returns
+ * 0 where the library is not supported (d p > 88).
+ * replaces: the per-seed processes of run_scripts/lv_noise99_eq_rreg.sh and selkov_noise20_eq_symreg3.sh, each pushing its
+ * own subsample through model_utils.py:160-168; g(x) and J_g(x) of a fixed LaLiGAN are computed once for all seeds. */
+size_t symode_symreg_reversed_gram_gather_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long m);
+int symode_symreg_reversed_gram_gather(const float* x, const float* gx, const float* jgx, int n_g, long n_src, const int* idx,
+                                       long n_problems, long m, int d, int order, int flags, double* gram_out, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+
 /* The closure of the non-latent fit as a quadratic form of fixed fp64 matrices, for S problems (library independent,
  * d p <= 256): aug_gram (S, p+d, p+d) from symode_aug_gram, rev_gram (S, d p, d p) from symode_symreg_reversed_gram or NULL;
  * xi, mask (S, d, p) fp32 (mask may be NULL = ones), W = xi * mask, v = vec(W):

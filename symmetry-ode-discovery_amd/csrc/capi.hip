@@ -321,7 +321,27 @@ int symode_symreg_reversed_gram(const float* x, const float* gx_, const float* j
     if (misaligned(x, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(gram_out, 8)) return SYMODE_E_ALIGN;
     if (!workspace || misaligned(workspace, 8)) return SYMODE_E_WORKSPACE;
     if (workspace_bytes < rev_gram_workspace_doubles(ops->d * ops->p, n_problems, n, n_g) * sizeof(double)) return SYMODE_E_WORKSPACE;
-    return (int)ops->symreg_reversed_gram(x, gx_, jgx, n_g, n_problems, n, gram_out, (double*)workspace, (hipStream_t)stream);
+    return (int)ops->symreg_reversed_gram(x, gx_, jgx, n_g, n_problems, n, nullptr, 0, gram_out, (double*)workspace,
+                                          (hipStream_t)stream);
+}
+
+size_t symode_symreg_reversed_gram_gather_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long m) {
+    return symode_symreg_reversed_gram_workspace_bytes(d, order, flags, n_g, n_problems, m);   // same grid, same partials
+}
+
+int symode_symreg_reversed_gram_gather(const float* x, const float* gx_, const float* jgx, int n_g, long n_src, const int* idx,
+                                       long n_problems, long m, int d, int order, int flags, double* gram_out, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    SYMODE_GET_OPS();
+    if (!ops->symreg_reversed_gram) return SYMODE_E_UNSUPPORTED;
+    if (m < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535 || n_src < 1 || n_src > 2147483647L) return SYMODE_E_BADSIZE;
+    if (!x || !gx_ || !jgx || !idx || !gram_out) return SYMODE_E_NULLPTR;
+    if (misaligned(x, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(idx, 4) || misaligned(gram_out, 8))
+        return SYMODE_E_ALIGN;
+    if (!workspace || misaligned(workspace, 8)) return SYMODE_E_WORKSPACE;
+    if (workspace_bytes < rev_gram_workspace_doubles(ops->d * ops->p, n_problems, m, n_g) * sizeof(double)) return SYMODE_E_WORKSPACE;
+    return (int)ops->symreg_reversed_gram(x, gx_, jgx, n_g, n_problems, m, idx, n_src, gram_out, (double*)workspace,
+                                          (hipStream_t)stream);
 }
 
 int symode_quad_closure(const double* aug_gram, const double* rev_gram, long n_problems, int d, int p, const float* xi,

@@ -54,20 +54,37 @@ inline size_t rev_gram_workspace_doubles(int dp, long S, long n, int n_g) {
     return (size_t)S * rev_gram_grid(n, S, n_g) * NT * 16;
 }
 
+// Row sources of the item loads.  Item m = g N + k of problem s (N points per problem) reads row xr of x and row gr of
+// (g(x), J_g(x)) (D and D * D floats per row).
+// Dense: x (S, N, d), gx (S, n_g, N, d), jgx (S, n_g, N, d, d), every problem its own copies.
+struct RevRowsDense {
+    __device__ static void rows(const int*, long, long s, long N, int n_g, long m, long& xr, long& gr) {
+        xr = s * N + m % N;
+        gr = s * N * n_g + m;
+    }
+};
+// Gathered: x (n_src, d), gx (n_g, n_src, d), jgx (n_g, n_src, d, d) shared by all problems; point k of problem s is row
+// idx[s N + k] (one 4-byte load per item; the caller guarantees 0 <= idx < n_src).
+struct RevRowsGather {
+    __device__ static void rows(const int* idx, long n_src, long s, long N, int, long m, long& xr, long& gr) {
+        const long g = m / N, r = idx[s * N + (m - g * N)];
+        xr = r;
+        gr = g * n_src + r;
+    }
+};
+
 // grid = (GX, S).  part: (S, GX, NT * 16) fp64; tile t (ti <= tj) element e = 4 r + c is sum b[4 ti + r] b[4 tj + c].
-template <class Lib>
+template <class Lib, class Rows>
 __global__ __launch_bounds__(BLOCK) void rev_gram_kernel(const float* __restrict__ x, const float* __restrict__ gx,
                                                          const float* __restrict__ jgx, int n_g, long N,
+                                                         const int* __restrict__ idx, long n_src,
                                                          double* __restrict__ part) {
     using G = RevGramShape<Lib>;
     constexpr int D = Lib::D, P = Lib::P, DP = G::DP, NT = G::NT, PG = G::PG, ROW = G::ROW, SP = G::SP;
     constexpr int STAGE = SP * D * ROW, COMB = PG * NT * 16;
     __shared__ double lds[STAGE > COMB ? STAGE : COMB];
     const long s = blockIdx.y;
-    const long M = N * n_g;                                  // items m = g N + n: g(x) and J_g(x) are contiguous in m
-    const float* xs = x + s * N * D;
-    const float* gs = gx + s * M * D;
-    const float* js = jgx + s * M * D * D;
+    const long M = N * n_g;                                  // items m = g N + k: g(x) and J_g(x) are contiguous in m
     const int tid = threadIdx.x, tile = tid % NT, grp = tid / NT;
     int ti = 0, rem = tile;                                  // tile -> (ti, tj), row-major over the upper triangle
     while (rem >= G::T - ti) {
@@ -87,13 +104,14 @@ __global__ __launch_bounds__(BLOCK) void rev_gram_kernel(const float* __restrict
             const long m = c * SP + k;
             double* row = lds + (k * D + i) * ROW;
             if (m < M) {
-                const long n = m % N;
+                long xr, gr;
+                Rows::rows(idx, n_src, s, N, n_g, m, xr, gr);
                 float xp[D], gp[D], J[D], th[P], thg[P];
 #pragma unroll
                 for (int j = 0; j < D; ++j) {
-                    xp[j] = xs[n * D + j];
-                    gp[j] = gs[m * D + j];
-                    J[j] = js[(m * D + i) * D + j];
+                    xp[j] = x[xr * D + j];
+                    gp[j] = gx[gr * D + j];
+                    J[j] = jgx[(gr * D + i) * D + j];
                 }
                 Lib::eval(xp, th);
                 Lib::eval(gp, thg);
@@ -187,12 +205,17 @@ __global__ __launch_bounds__(BLOCK) void rev_gram_finalize_kernel(const double* 
     }
 }
 
+// idx == nullptr: dense per-problem copies; else S index rows of n points each into shared (x, gx, jgx) of n_src rows.  The
+// grid and the finalize depend on (n, S, n_g) alone, so a gathered launch adds in the order of the dense one on copies.
 template <class Lib>
-hipError_t launch_symreg_reversed_gram(const float* x, const float* gx, const float* jgx, int n_g, long S, long n, double* gram,
-                                       double* ws, hipStream_t st) {
+hipError_t launch_symreg_reversed_gram(const float* x, const float* gx, const float* jgx, int n_g, long S, long n,
+                                       const int* idx, long n_src, double* gram, double* ws, hipStream_t st) {
     using G = RevGramShape<Lib>;
     const int GX = rev_gram_grid(n, S, n_g);
-    rev_gram_kernel<Lib><<<dim3(GX, (unsigned)S), dim3(BLOCK), 0, st>>>(x, gx, jgx, n_g, n, ws);
+    if (idx)
+        rev_gram_kernel<Lib, RevRowsGather><<<dim3(GX, (unsigned)S), dim3(BLOCK), 0, st>>>(x, gx, jgx, n_g, n, idx, n_src, ws);
+    else
+        rev_gram_kernel<Lib, RevRowsDense><<<dim3(GX, (unsigned)S), dim3(BLOCK), 0, st>>>(x, gx, jgx, n_g, n, nullptr, 0, ws);
     SYMODE_LAUNCH_CHECK();
     rev_gram_finalize_kernel<><<<dim3((G::PARTIAL + WAVE - 1) / WAVE, (unsigned)S), dim3(BLOCK), 0, st>>>(ws, GX, G::DP, gram);
     SYMODE_LAUNCH_CHECK();
@@ -200,7 +223,8 @@ hipError_t launch_symreg_reversed_gram(const float* x, const float* gx, const fl
 }
 
 // The launcher for the ops table, or nullptr (SYMODE_E_UNSUPPORTED) where the tiles would not fit one workgroup.
-using RevGramFn = hipError_t (*)(const float*, const float*, const float*, int, long, long, double*, double*, hipStream_t);
+using RevGramFn = hipError_t (*)(const float*, const float*, const float*, int, long, long, const int*, long, double*, double*,
+                                  hipStream_t);
 template <class Lib>
 constexpr RevGramFn rev_gram_launcher() {
     if constexpr (RevGramShape<Lib>::OK)

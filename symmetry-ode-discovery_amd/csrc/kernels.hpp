@@ -112,8 +112,9 @@ struct LibOps {
     hipError_t (*weak_gram)(const float* x, long T, const float* V, const float* Vd, int K, double* out, double* ws, int gx,
                             hipStream_t st);
     // Gram matrix of the reversed regulariser (gram_rev.hpp); nullptr where the library is not instantiated for it
-    hipError_t (*symreg_reversed_gram)(const float* x, const float* gx_, const float* jgx, int n_g, long S, long n, double* gram,
-                                       double* ws, hipStream_t st);
+    // idx != nullptr: S index rows (S, n) into ONE shared (x, gx, jgx) of n_src rows
+    hipError_t (*symreg_reversed_gram)(const float* x, const float* gx_, const float* jgx, int n_g, long S, long n,
+                                       const int* idx, long n_src, double* gram, double* ws, hipStream_t st);
 };
 
 // ---------------------------------------------------------------------------------------

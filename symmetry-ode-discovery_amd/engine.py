@@ -53,6 +53,9 @@ _SIGNATURES = {
     "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
     "symode_symreg_reversed_gram": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_size_t, c_void_p]),
+    "symode_symreg_reversed_gram_gather_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
+    "symode_symreg_reversed_gram_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_long, c_long, c_int,
+                                                   c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_quad_closure": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, ctypes.c_double, c_float,
                                     c_void_p, c_void_p, c_void_p]),
     "symode_vjp": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -443,6 +446,37 @@ class HipEngine:
                                                          self._ptr(gram), self._ptr(ws), need, self._stream(x)),
                     "symode_symreg_reversed_gram")
         return gram if batched else gram[0]
+
+    def symreg_reversed_gram_gather(self, x, gx, jgx, idx, order, flags=0):
+        """R of S index subsets of ONE shared data set: x (N, d), gx (n_g, N, d), jgx (n_g, N, d, d), idx (S, M) int32 rows
+        -> (S, d p, d p) fp64, bit-identical to ``symreg_reversed_gram`` on the materialised x[idx[s]], gx[:, idx[s]],
+        jgx[:, idx[s]].  The kernel reads the table unchecked, so its range is checked here on EVERY call (one aminmax, one
+        sync): a table refilled through a raw pointer or an alias keeps its version counter, so no verdict is remembered."""
+        x, gx, jgx = self._dev(x, "x"), self._dev(gx, "gx"), self._dev(jgx, "jgx")
+        idx = self._dev(idx, "idx", torch.int32)
+        if x.dim() != 2 or gx.dim() != 3 or idx.dim() != 2:
+            raise SymodeError("symreg_reversed_gram_gather expects x (N, d), gx (n_g, N, d), jgx (n_g, N, d, d) and idx (S, M)")
+        n_src, d = x.shape
+        n_g = gx.shape[0]
+        S, m = idx.shape
+        if n_g < 1 or tuple(gx.shape) != (n_g, n_src, d) or tuple(jgx.shape) != (n_g, n_src, d, d):
+            raise SymodeError(f"gx {tuple(gx.shape)} / jgx {tuple(jgx.shape)} do not match x {tuple(x.shape)}")
+        if S < 1 or m < 1:
+            raise SymodeError(f"idx {tuple(idx.shape)} holds no rows")
+        lo, hi = torch.stack(torch.aminmax(idx)).tolist()
+        if lo < 0 or hi >= n_src:
+            raise SymodeError("idx holds row indices outside [0, N)")
+        p = self.lib_size(d, order, flags)
+        need = self.lib.symode_symreg_reversed_gram_gather_workspace_bytes(d, order, flags, n_g, S, m)
+        if need == 0:
+            raise SymodeError(f"symreg_reversed_gram_gather does not support the library d={d} order={order} flags={flags}")
+        ws = torch.empty(need // 8, dtype=torch.float64, device=x.device)
+        gram = torch.empty(S, d * p, d * p, dtype=torch.float64, device=x.device)
+        self._check(self.lib.symode_symreg_reversed_gram_gather(self._ptr(x), self._ptr(gx), self._ptr(jgx), n_g, n_src,
+                                                                self._ptr(idx), S, m, d, order, flags, self._ptr(gram),
+                                                                self._ptr(ws), need, self._stream(x)),
+                    "symode_symreg_reversed_gram_gather")
+        return gram
 
     def quad_closure(self, G, R, xi, mask, inv_count, w_sym=1.0):
         """The closure as a quadratic form of fixed fp64 matrices: G (S, p+d, p+d) augmented Gram, R (S, d p, d p) or None,

@@ -61,6 +61,24 @@ class GramStatistics:
         return self
 
     @torch.no_grad()
+    def add_gathered(self, x, dx, idx, gx=None, jgx=None):
+        """Accumulate S index subsets of ONE shared data set without materialising them: x, dx (N, d), idx (S, m) int32
+        rows (problem s adds the points x[idx[s]]); gx (n_g, N, d), jgx (n_g, N, d, d) when the statistics carry R.
+        G from ONE gather-Gram launch, R from ONE gathered reversed-Gram launch; the count grows by m."""
+        if x.dim() != 2 or x.shape != dx.shape or x.shape[1] != self.d or idx.dim() != 2 or idx.shape[0] != self.S:
+            raise SymodeError(f"x {tuple(x.shape)} / dx {tuple(dx.shape)} / idx {tuple(idx.shape)} do not match S={self.S}, "
+                              f"d={self.d}")
+        if self.regulariser and (gx is None or jgx is None):
+            raise SymodeError("these statistics carry the reversed regulariser: add_gathered() needs gx and jgx")
+        if idx.shape[1] == 0:
+            return self
+        self.G += self.engine.aug_gram_gather(x, dx, idx, self.order, self.flags)
+        if self.regulariser:
+            self.R += self.engine.symreg_reversed_gram_gather(x, gx, jgx, idx, self.order, self.flags)
+        self._count += float(idx.shape[1])
+        return self
+
+    @torch.no_grad()
     def add_gram(self, G, n_points):
         """Accumulate prebuilt augmented Gram matrices (S, p+d, p+d) of ``n_points`` points each (e.g. from
         ``aug_gram_gather``); only for statistics without R."""

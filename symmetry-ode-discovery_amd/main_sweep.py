@@ -13,7 +13,22 @@ ONE gather-Gram launch over the (seed, point) index table (sweep.SeedSweepSTLSQ)
 (one process per GPU, backend nccl = RCCL over xGMI) every rank holds a contiguous block of trajectories; the per-seed
 ``[loss | grad]`` vectors / Gram matrices are all-reduced and every rank takes identical decisions; rank 0 writes the
 reference's ``eval_results/<save_dir>/seed{n}.npz`` so that ``evaluation.aggregate_results`` works unchanged.
-Plain / constrained SINDy only (no autoencoder terms).
+
+The reversed symmetry regulariser (``--sym_reg_type r --w_sym_reg w``, EquivSINDy-r: lv/noise99_eq_rsymreg.cfg,
+selkov/noise20_eq_symreg3.cfg) is swept too when the config loads a LaLiGAN and freezes it (``--load_laligan NAME
+--fix_laligan``, no ``--use_latent``): autoencoder and generator are read from saved_models/NAME/ as main.py reads them,
+and g(x), J_g(x) -- pointwise, independent of the seed and of Xi -- are computed ONCE (model_utils.precompute_symmreg_r, in
+chunks of at most PRECOMPUTE_CHUNK rows) over the union of the rows this rank's seeds use, then gathered per seed.  The
+regulariser enters with weight w_sym_reg / w_sindy_x as in the per-seed fit (train._train_on_device).  Default: the fused
+stream closure on gathered (S, n_g, m_local, d) copies; ``--gram_closure``: per-seed [G | R] from one gather-Gram and one
+gathered reversed-Gram launch on the shared arrays (GramStatistics.add_gathered), ONE all-reduce of [G | R | count] when
+sharded.  The i / f regularisers (their closure runs the autoencoder on Xi-dependent inputs), a LaLiGAN that is not
+loaded (each per-seed process would draw its own random network) or not frozen, and latent fits are refused with the
+per-seed command to use instead.
+
+A sweep's seed n does NOT reproduce ``python -m symode_amd.main --seed n`` row for row: the sweep draws each seed's
+subsample with the counter hash (seeded_subsamples) and its initial coefficients from its own torch.Generator(seed), as the
+plain sweep always has; the success rate over seeds is what the two estimate alike.
 """
 from __future__ import annotations
 
@@ -24,13 +39,18 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .autoencoder import AutoEncoder
 from .batched import BatchedClosure
 from .dataset import get_dataset
 from .evaluation import aggregate_results, sindy_truth
 from .lie import LieGenerator
 from .parser_utils import get_args
 from .sindy import SINDyRegression
-from .sweep import SeedSweepLBFGS, SeedSweepSTLSQ, seeded_subsamples
+from .sweep import GramClosure, SeedSweepLBFGS, SeedSweepSTLSQ, seeded_subsamples
+
+# rows per precompute_symmreg_r call: the LV config's 512-wide autoencoder keeps ~10 activations of (rows, 512) fp32 alive
+# per JVP column, ~130 MB at 65 536 rows
+PRECOMPUTE_CHUNK = 65536
 
 
 def _pop(argv, flag, default, cast):
@@ -55,6 +75,65 @@ def _write_results(args, seeds, Xi, mask, truth):
                  mse_all=np.mean(mse))
 
 
+def _refusal(args):
+    """None when main_sweep covers the config, else why not and the per-seed command to run instead."""
+    cfg = args.get('config')
+    cmd = (f'python -m symode_amd.main --seed $i --config {cfg}' if cfg else 'python -m symode_amd.main --seed $i ...') + \
+        ' for each seed (the per_seed loop of run_scripts/sweep.sh)'
+    if args['sindy_optimizer'] != 'lbfgs':
+        return f'main_sweep covers the L-BFGS fits (--sindy_optimizer lbfgs); run {cmd}'
+    if args['use_latent']:
+        return f'main_sweep does not cover latent fits (--use_latent); run {cmd}'
+    if args['w_sym_reg'] > 0:
+        if args['sym_reg_type'] != 'r':
+            return (f"main_sweep covers the reversed symmetry regulariser only (--sym_reg_type r), not "
+                    f"'{args['sym_reg_type']}': its closure runs the autoencoder on Xi-dependent inputs; run {cmd}")
+        if args['load_laligan'] is None:
+            return (f'main_sweep needs --load_laligan with the symmetry regulariser: without it every per-seed process '
+                    f'fits against its own random autoencoder; run {cmd}')
+        if not args['fix_laligan']:
+            return f'main_sweep needs --fix_laligan with the symmetry regulariser (g(x), J_g(x) computed once); run {cmd}'
+    return None
+
+
+def _load_laligan(args, dev):
+    """Frozen autoencoder and generator of saved_models/<load_laligan>/, as main._run loads them (main.py:45-63)."""
+    autoencoder = AutoEncoder(**args).to(dev)
+    generator = LieGenerator(**args).to(dev)
+    path = args['load_laligan']
+    autoencoder.load_state_dict(torch.load(f'saved_models/{path}/autoencoder.pt', weights_only=True, map_location=dev))
+    saved = torch.load(f'saved_models/{path}/generator.pt', weights_only=True, map_location=dev)
+    current = generator.state_dict()
+    for name, param in current.items():                       # tolerate older generator files (main.py:52-60)
+        saved.setdefault(name, param)
+    generator.load_state_dict({k: v for k, v in saved.items() if k in current})
+    masks = torch.load(f'saved_models/{path}/generator_mask.pt', weights_only=True, map_location=dev)
+    generator.masks = [m.to(dev) if m is not None else None for m in masks]
+    for module in (autoencoder, generator):
+        module.eval()                                         # batch norm on its running statistics: g(x) is pointwise
+        for param in module.parameters():
+            param.requires_grad = False
+    return autoencoder, generator
+
+
+def symmetry_operands(x, rows, autoencoder, generator, chunk=PRECOMPUTE_CHUNK):
+    """g(x) and J_g(x) of the rows the (S, m) table ``rows`` uses, each computed once: (x_used (U, d), gx (n_g, U, d),
+    jgx (n_g, U, d, d), table (S, m) int32 into the U used rows, ``used`` (U,) their row numbers in x).  Rows in chunks of
+    at most ``chunk`` (precompute_symmreg_r is pointwise: batch norm in eval mode, z_mean the encoder bias)."""
+    from .model_utils import precompute_symmreg_r
+    used = torch.unique(rows)                                            # sorted
+    table = torch.searchsorted(used, rows).to(torch.int32).contiguous()
+    x_used = x[used].contiguous()
+    gxs, jgxs = [], []
+    for a in range(0, x_used.shape[0], chunk):
+        g, j = precompute_symmreg_r(x_used[a:a + chunk], autoencoder, generator, scale=0.01)
+        gxs.append(torch.stack(g))
+        jgxs.append(torch.stack(j))
+    gx = torch.cat(gxs, dim=1).float().contiguous()
+    jgx = torch.cat(jgxs, dim=1).float().contiguous()
+    return x_used, gx, jgx, table, used
+
+
 def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     """``engine`` / ``backend`` exist for the CPU rehearsal of the multi-rank path in tests (gloo + the test engine);
     ``one_gpu``: every rank uses cuda:0 (rehearsal of the HIP path with several ranks on a one-GPU box, gloo collectives)."""
@@ -64,6 +143,10 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     if method not in ('lbfgs', 'stlsq'):
         raise SystemExit(f'--method {method}: lbfgs or stlsq')
     args = vars(get_args(argv=argv))
+    why = _refusal(args)
+    if why is not None:
+        raise SystemExit(why)
+    sym = args['w_sym_reg'] > 0
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     if engine is None:
         if str(args['device']) == 'cpu':
@@ -72,8 +155,6 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
             local = 0 if one_gpu else int(os.environ.get('LOCAL_RANK', '0'))
             torch.cuda.set_device(local)
             args['device'] = torch.device('cuda', local)
-    if args['sindy_optimizer'] != 'lbfgs' or args['use_latent'] or args['w_sym_reg'] > 0:
-        raise SystemExit('main_sweep covers the L-BFGS SINDy / EquivSINDy-c configs (no latent / symmetry-regulariser terms)')
     dev = args['device']
     group = None
     if world > 1:
@@ -107,6 +188,8 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
         return truth
 
     if method == 'stlsq':
+        if sym:
+            raise SystemExit('--method stlsq sweeps the plain least-squares fit (use --method lbfgs with the symmetry regulariser)')
         if args['eq_constraint']:
             raise SystemExit('--method stlsq sweeps the unconstrained library (use --method lbfgs for EquivSINDy-c)')
         idx = seeded_subsamples(n_all, m, seeds, dev)[:, lo:hi]
@@ -124,32 +207,46 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
         return None
 
     # one template regressor fixes the library / constraint; per-seed draws follow the constructor's order
+    if sym:                                                         # loaded BEFORE the template (main.py's order)
+        autoencoder, generator = _load_laligan(args, dev)
     if args['eq_constraint']:
-        gen = LieGenerator(**args)
+        gen = generator if sym else LieGenerator(**args)
         L_list = gen.get_full_basis_list()
         rd = L_list[0].shape[-1] // args['n_comps']
         args['L_list'] = [L[:rd, :rd].detach().cpu() for L in L_list]
     template = SINDyRegression(**args, **({'engine': engine} if engine is not None else {})).to(dev)
-    inits, xs, dxs = [], [], []
+    inits = []
     all_rows = seeded_subsamples(n_all, m, seeds, dev)[:, lo:hi]
-    for (s, g), rows in zip(zip(seeds, gens), all_rows):
+    for s, g in zip(seeds, gens):
         if template.constraint:
             beta = torch.randn(template.Q.shape[1], generator=g)
             const = torch.randn(template.latent_dim, generator=g)
             inits.append(torch.cat([beta, const]))
         else:
             inits.append(torch.randn(template.latent_dim * template.get_term_num(), generator=g))
-        xs.append(x_all[rows])
-        dxs.append(dx_all[rows])
-    X, DX = torch.stack(xs).contiguous(), torch.stack(dxs).contiguous()
-    clos = BatchedClosure(X, DX, template.poly_order, template.include_sine, template.include_exp,
-                          Q=template.Q if template.constraint else None,
-                          use_kron_product=getattr(template, 'use_kron_product', True),
-                          allow_constant=getattr(template, 'allow_constant', True), group=group,
-                          **({'engine': engine} if engine is not None else {}))
+    plumbing = dict(Q=template.Q if template.constraint else None, use_kron_product=getattr(template, 'use_kron_product', True),
+                    allow_constant=getattr(template, 'allow_constant', True), group=group)
+    w_sym = args['w_sym_reg'] / args['w_sindy_x'] if sym else 0.0
+    stats = None
+    if sym:
+        x_used, gx, jgx, table, used = symmetry_operands(x_all, all_rows, autoencoder, generator)
+    if sym and args.get('gram_closure'):
+        # [G | R] of every seed from the shared arrays and the index table: no per-seed copy of the points
+        from .gram_closure import GramStatistics
+        stats = GramStatistics(n_seeds, template.latent_dim, template.poly_order, template.flags, regulariser=True, device=dev,
+                               **({'engine': engine} if engine is not None else {}))
+        stats.add_gathered(x_used, dx_all[used].contiguous(), table, gx, jgx)
+        clos = GramClosure(stats, w_sym=w_sym, **plumbing)
+    else:
+        X, DX = x_all[all_rows].contiguous(), dx_all[all_rows].contiguous()
+        rev = None
+        if sym:                                                     # (S, n_g, m_local, d) per-seed copies of g(x), J_g(x)
+            rev = (gx[:, table.long()].transpose(0, 1).contiguous(), jgx[:, table.long()].transpose(0, 1).contiguous(), w_sym)
+        clos = BatchedClosure(X, DX, template.poly_order, template.include_sine, template.include_exp, reversed_sym=rev,
+                              **plumbing, **({'engine': engine} if engine is not None else {}))
     sweep = SeedSweepLBFGS(clos, args['lr_sindy'], args['threshold'], args['st_freq'], w_sindy_x=args['w_sindy_x'],
                            sindy_reg_type=args['sindy_reg_type'], w_sindy_reg=args['w_sindy_reg'],
-                           gram_closure=bool(args.get('gram_closure')))
+                           gram_closure=bool(args.get('gram_closure')), statistics=stats)
     out = sweep.fit(torch.stack(inits).to(dev), args['num_epochs'])
 
     if rank != 0:

@@ -353,6 +353,37 @@ class BatchedLBFGS:
         return self._loss.clone()
 
 
+class GramClosure:
+    """The coefficient plumbing of batched.BatchedClosure (S, d, p, Q, xi_from, grads_to, evaluate) over prebuilt
+    gram_closure.GramStatistics: the closure of a Gram-form sweep that never holds per-seed copies of the points.
+    ``evaluate`` reads the statistics as they stand (summed over the ranks once the device trainer has all-reduced them)."""
+
+    def __init__(self, statistics, Q=None, use_kron_product=True, allow_constant=True, w_sym=0.0, group=None):
+        self.statistics = statistics
+        self.engine = statistics.engine
+        self.S, self.d, self.p = statistics.S, statistics.d, statistics.p
+        self.order, self.flags = statistics.order, statistics.flags
+        self.Q, self.use_kron, self.allow_constant = Q, use_kron_product, allow_constant
+        self.w_sym = float(w_sym)
+        self.group = group
+        self.distributed = group is not None
+
+    def xi_from(self, beta, const=None):
+        from .batched import BatchedClosure
+        return BatchedClosure.xi_from(self, beta, const)
+
+    def grads_to(self, grad_xi):
+        from .batched import BatchedClosure
+        return BatchedClosure.grads_to(self, grad_xi)
+
+    def evaluate(self, beta, const=None, mask=None):
+        """(loss (S,) = mse [+ w_sym * regulariser], d/dbeta [or d/dXi], d/dconst), as BatchedClosure.evaluate."""
+        Xi = self.xi_from(beta, const)
+        loss, grad, _ = self.statistics.evaluate(Xi, mask, self.w_sym)
+        g_beta, g_const = self.grads_to(grad)
+        return loss, g_beta, g_const
+
+
 class SeedSweepLBFGS:
     """``train_SIGED_lbfgs`` (non-latent, MSE [+ L1]) for S seeds in lockstep: the per-epoch logic of
     train.py:692-725 -- NaN guard, update-norm convergence test, threshold + optimiser reset, final
@@ -360,12 +391,15 @@ class SeedSweepLBFGS:
     fused Theta + residual + gradient kernel (BatchedClosure), all-reduced over point shards if sharded."""
 
     def __init__(self, closure, lr_sindy, threshold, st_freq, w_sindy_x=1.0, sindy_reg_type="l1", w_sindy_reg=0.0, tol=1e-3,
-                 gram_closure=False):
+                 gram_closure=False, statistics=None):
         """``gram_closure``: the device trainer evaluates every closure as the quadratic form of the seeds' fp64 Gram
         matrices (gram_closure.py), built once from the closure's data (and summed over the point shards in one
-        all-reduce) instead of streaming the points per evaluation."""
+        all-reduce) instead of streaming the points per evaluation.  ``statistics``: a prebuilt GramStatistics of this
+        rank's points (e.g. from ``add_gathered``), all-reduced by the trainer; implies the Gram closure, and ``closure``
+        then only supplies the coefficient plumbing (a GramClosure, which holds no points)."""
         self.c = closure
-        self.gram_closure = bool(gram_closure)
+        self.statistics = statistics
+        self.gram_closure = bool(gram_closure) or statistics is not None
         self.lr, self.threshold, self.st_freq, self.tol = lr_sindy, threshold, st_freq, tol
         self.w_x, self.reg_type, self.w_reg = w_sindy_x, sindy_reg_type, w_sindy_reg
         if sindy_reg_type not in ("l1", "none"):
@@ -416,6 +450,8 @@ class SeedSweepLBFGS:
         gloo test doubles and ``SYMODE_LBFGS_FUSED=0``."""
         c = self.c
         eng = getattr(c, 'engine', None)
+        if self.statistics is not None:
+            return bool(P0.is_cuda and P0.shape[1] <= 256 and c.d * c.p <= 256)
         return bool(P0.is_cuda and eng is not None and hasattr(getattr(eng, 'lib', None), 'symode_trainer_run')
                     and os.environ.get('SYMODE_LBFGS_FUSED', '1') == '1' and os.environ.get('SYMODE_LBFGS_MERGED', '1') == '1'
                     and P0.shape[1] <= 256 and c.d * c.p <= 256 and getattr(c, 'n_chunks', 1) == 1)
@@ -423,15 +459,20 @@ class SeedSweepLBFGS:
     def _fit_native(self, P0, num_epochs, mask0, on_epoch):
         from .device_lbfgs import DeviceTrainer
         c = self.c
-        stats = None
-        if self.gram_closure:
+        stats, rev = None, c.sym if self.statistics is None else None
+        if self.statistics is not None:
+            stats = self.statistics
+            if stats.regulariser:
+                rev = (None, None, c.w_sym)
+        elif self.gram_closure:
             from .gram_closure import GramStatistics
             stats = GramStatistics(c.S, c.d, c.order, c.flags, regulariser=c.sym is not None, device=c.x.device, engine=c.engine)
             stats.add(c.x, c.dx, *(c.sym[:2] if c.sym is not None else ()))
         x, dx = (None, None) if stats is not None else (c.x, c.dx)          # the Gram form holds no reference to the points
         tr = DeviceTrainer(x, dx, c.order, c.flags, Q=c.Q, use_kron_product=c.use_kron, allow_constant=c.allow_constant,
-                           reversed_sym=c.sym, lr=self.lr, threshold=self.threshold, st_freq=self.st_freq, w_x=self.w_x,
-                           w_reg=self.w_reg if self.reg_type == 'l1' else 0.0, l1=True, tol=self.tol, inv_count=c.inv_count,
+                           reversed_sym=rev, lr=self.lr, threshold=self.threshold, st_freq=self.st_freq, w_x=self.w_x,
+                           w_reg=self.w_reg if self.reg_type == 'l1' else 0.0, l1=True, tol=self.tol,
+                           inv_count=None if self.statistics is not None else c.inv_count,
                            engine=c.engine, group=(c.group or dist.group.WORLD) if c.distributed else None,
                            detail=on_epoch is not None and c.S <= 64, closure='stream' if stats is None else 'gram',
                            statistics=stats)
