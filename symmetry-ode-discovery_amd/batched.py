@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from .coef_map import CoefMap
 from .engine import get_engine, library_flags
 
 
@@ -59,8 +60,9 @@ def allreduce_sums(sums, params, group):
 
 class BatchedClosure:
     def __init__(self, x, dx, poly_order, include_sine=False, include_exp=False, Q=None, use_kron_product=True,
-                 allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True):
-        """``reversed_sym = (gx (S, n_g, N_local, d), jgx (S, n_g, N_local, d, d), weight)`` adds  weight * the reversed
+                 allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True, coef=None):
+        """``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from Q / use_kron_product / allow_constant).
+        ``reversed_sym = (gx (S, n_g, N_local, d), jgx (S, n_g, N_local, d, d), weight)`` adds  weight * the reversed
         symmetry regulariser (model_utils.py:126-170 on precomputed (g(x), J_g(x))) to every problem's loss and gradient:
         by default residual and regulariser run as ONE launch per chunk (symode_loss_grad_reversed: Theta(x) shared, x read
         once); ``fuse_sym=False`` keeps them as two launches summed into the same packed buffer before the collective."""
@@ -71,8 +73,7 @@ class BatchedClosure:
         self.order = poly_order
         self.flags = library_flags(include_sine, include_exp)
         self.p = self.engine.lib_size(self.d, poly_order, self.flags)
-        self.Q = Q
-        self.use_kron, self.allow_constant = use_kron_product, allow_constant
+        self.coef = coef if coef is not None else CoefMap(self.d, self.p, Q, use_kron_product, allow_constant)
         self.group = group
         self.distributed = group is not None or (world_size or 1) > 1
         self.world = world_size if world_size is not None else (dist.get_world_size(group) if self.distributed else 1)
@@ -103,22 +104,10 @@ class BatchedClosure:
 
     # -- coefficient plumbing (batched get_Xi, sindy.py:169-176) ----------------------------
     def xi_from(self, beta, const=None):
-        if self.Q is None:
-            return beta                                         # beta IS Xi (S, d, p)
-        flat = beta @ self.Q.T                                  # (S, d*p)
-        Xi = flat.view(self.S, self.d, self.p) if self.use_kron else flat.view(self.S, self.p, self.d).transpose(1, 2)
-        if self.allow_constant and const is not None:
-            Xi = Xi.clone()
-            Xi[:, :, 0:1] += const
-        return Xi.contiguous()
+        return self.coef.xi(beta, const)
 
     def grads_to(self, grad_xi):
-        if self.Q is None:
-            return grad_xi, None
-        g = grad_xi if self.use_kron else grad_xi.transpose(1, 2)
-        g_beta = g.reshape(self.S, -1) @ self.Q
-        g_const = grad_xi[:, :, 0:1].clone() if self.allow_constant else None
-        return g_beta, g_const
+        return self.coef.grad(grad_xi)
 
     # -- the hot path -------------------------------------------------------------------------
     def loss_grad_xi(self, Xi, mask=None, alias=False):

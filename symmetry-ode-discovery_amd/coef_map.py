@@ -1,0 +1,131 @@
+"""The map between the optimiser's variables and the coefficient matrix Xi (the reference's ``get_Xi``, sindy.py:169-176:
+``Xi``, or ``Q @ beta`` viewed Kronecker-wise / transposed, plus ``const`` in the constant column), its transpose and the
+layout of the flat vector ``[beta | const]`` -- the one place that spells them out.  Torch and numpy only, no engine.
+
+The forms do NOT share arithmetic, on purpose: one problem is ``Q @ beta`` then ``+ cat([const, 0])``, S problems are
+``beta @ Q.T`` then an in-place add into the constant column, the numpy forms stay in fp32 on the host.  L-BFGS on an
+ill-conditioned library is chaotic in the last bit of every dot product (train.train_SIGED_lbfgs), so each caller keeps
+its operations, operand order and dtype."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+
+class CoefMap:
+    def __init__(self, d, p, Q=None, use_kron_product=True, allow_constant=True):
+        """Q (d p, r), or None: the variables ARE Xi.  ``allow_constant=False`` (--constrain_constant): ``const`` stays a
+        variable that the model does not read (sindy.py:60, 173-175)."""
+        self.d, self.p, self.Q = int(d), int(p), Q
+        self.use_kron, self.allow_constant = bool(use_kron_product), bool(allow_constant)
+        self.r = 0 if Q is None else int(Q.shape[1])
+        self.sizes = (self.d * self.p,) if Q is None else (self.r, self.d)      # of the parameter tensors, in their order
+        self.n_params = sum(self.sizes)
+        self._Qnp = self._Qc = None
+
+    @classmethod
+    def from_regressor(cls, reg):
+        args = (reg.Q, reg.use_kron_product, reg.allow_constant) if reg.constraint else ()
+        return cls(reg.latent_dim, reg.get_term_num(), *args)
+
+    def to(self, device):
+        return self if self.Q is None else CoefMap(self.d, self.p, self.Q.detach().to(device), self.use_kron, self.allow_constant)
+
+    def _numpy_Q(self):
+        if self._Qnp is None:                       # strides as they come: the fp32 gradient product is taken on this array
+            self._Qnp = self.Q.detach().cpu().numpy() if torch.is_tensor(self.Q) else np.asarray(self.Q)
+        return self._Qnp
+
+    def split(self, P):
+        """(beta, const) views of a flat (n,) or (S, n) tensor; (Xi, None) when unconstrained."""
+        lead = P.shape[:-1]
+        if self.Q is None:
+            return P.view(*lead, self.d, self.p), None
+        return P[..., :self.r], P[..., self.r:].reshape(*lead, self.d, 1)
+
+    def join(self, a, b=None):
+        """The flat vector(s) of the pieces; a missing ``const`` piece (a constant the model does not read) is a zero block."""
+        if isinstance(a, np.ndarray):               # one problem, fp32 on the host
+            if self.Q is None:
+                return a.reshape(-1)
+            return np.concatenate([a, np.zeros(self.d, dtype=np.float32) if b is None else b]).astype(np.float32)
+        S = a.shape[0]
+        if self.Q is None:
+            return a.reshape(S, -1)
+        if b is None:
+            b = torch.zeros(S, self.d, 1, device=a.device, dtype=a.dtype)
+        return torch.cat([a, b.reshape(S, -1)], dim=1)
+
+    def draw(self, generator):
+        """Initial flat variables in the order ``SINDyRegression`` draws them (beta, then const)."""
+        return torch.cat([torch.randn(n, generator=generator) for n in self.sizes])
+
+    def update_norm(self, A, B):
+        """sum over the parameter tensors of ||A - B||, per problem (train.py:702-704)."""
+        if self.Q is None:
+            return (A - B).norm(dim=1)
+        r = self.r
+        return (A[:, :r] - B[:, :r]).norm(dim=1) + (A[:, r:] - B[:, r:]).norm(dim=1)
+
+    def xi(self, beta, const=None):
+        """Xi of one problem (beta (r,), const (d, 1): differentiable torch; or fp32 numpy with const (d,)) or of S problems
+        (beta (S, r), const (S, d, 1) or None).  Unconstrained: ``beta`` is Xi."""
+        if self.Q is None:
+            return beta
+        d, p = self.d, self.p
+        if isinstance(beta, np.ndarray):
+            if self._Qc is None:
+                self._Qc = np.ascontiguousarray(self._numpy_Q(), dtype=np.float32)
+            flat = self._Qc @ beta
+            Xi = flat.reshape(d, p).copy() if self.use_kron else flat.reshape(p, d).T.copy()
+            if self.allow_constant:
+                Xi[:, 0] += const
+            return Xi
+        if beta.dim() == 1:
+            flat = self.Q @ beta
+            Xi = flat.view(d, -1) if self.use_kron else flat.view(-1, d).transpose(0, 1)
+            if self.allow_constant:
+                Xi = Xi + torch.cat([const, torch.zeros((Xi.shape[0], Xi.shape[1] - 1), device=Xi.device)], dim=1)
+            return Xi
+        flat = beta @ self.Q.T                                  # (S, d*p)
+        Xi = flat.view(-1, d, p) if self.use_kron else flat.view(-1, p, d).transpose(1, 2)
+        if self.allow_constant and const is not None:
+            Xi = Xi.clone()
+            Xi[:, :, 0:1] += const
+        return Xi.contiguous()
+
+    def grad(self, g_xi, flat=False):
+        """(g_beta, g_const) from dL/dXi -- (S, d, p) torch or (d, p) fp32 numpy; g_const is None for a constant the model
+        does not read.  ``flat=True``: the flat gradient instead (``join`` of the pieces)."""
+        if self.Q is None:
+            g_beta, g_const = g_xi, None
+        elif isinstance(g_xi, np.ndarray):
+            G = g_xi if self.use_kron else g_xi.T
+            g_beta = self._numpy_Q().T @ G.reshape(-1)
+            g_const = g_xi[:, 0] if self.allow_constant else None
+        else:
+            g = g_xi if self.use_kron else g_xi.transpose(1, 2)
+            g_beta = g.reshape(g_xi.shape[0], -1) @ self.Q
+            g_const = g_xi[:, :, 0:1].clone() if self.allow_constant else None
+        return self.join(g_beta, g_const) if flat else (g_beta, g_const)
+
+    def pack(self, reg):
+        """The regressor's variables as one flat (n,) tensor on their device."""
+        return torch.cat([q.detach().reshape(-1) for q in reg.parameters()])
+
+    def adopt(self, reg, params, mask=None):
+        """A flat (n,) state (tensor or numpy, host or device) into the regressor's variables and, in place, its mask."""
+        with torch.no_grad():
+            for dst, src in zip(reg.parameters(), self.split(torch.as_tensor(params))):
+                dst.data.copy_(src)
+            if mask is not None:
+                reg.mask.copy_(torch.as_tensor(mask).view_as(reg.mask))
+
+    def effective_Q(self):
+        """Q as fp32 numpy with its rows in Xi's (d, p) row-major order, so that Xi = (q_eff @ beta).reshape(d, p) on either
+        branch (the transposed view reads Xi[i, t] = flat[t * d + i]): what the device trainer's XiMap reads."""
+        Q = np.ascontiguousarray(self._numpy_Q(), dtype=np.float32)
+        if self.use_kron:
+            return Q
+        rows = (np.arange(self.p)[None, :] * self.d + np.arange(self.d)[:, None]).reshape(-1)
+        return np.ascontiguousarray(Q[rows])

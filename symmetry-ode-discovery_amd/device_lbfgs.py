@@ -15,6 +15,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .coef_map import CoefMap
 from .engine import TRAINER_FIELDS, SymodeError, TrainerDesc, get_engine
 from .gram_closure import GramStatistics
 
@@ -25,24 +26,15 @@ _FIELD_DTYPES = {"act": torch.uint8, "n_iter": torch.int64, "head": torch.int64,
                  "done": torch.uint8, "nan": torch.uint8, "finished": torch.uint8, "epochs": torch.int32, "near": torch.int32}
 
 
-def effective_Q(Q, d, p, use_kron_product):
-    """Q (d p, r) with its rows permuted into Xi's (d, p) row-major order: sindy.py:171-173 reads ``Q @ beta`` as
-    ``view(d, -1)`` on the Kronecker branch and as ``view(-1, d).T`` otherwise."""
-    Q = np.ascontiguousarray(Q.detach().cpu().numpy() if torch.is_tensor(Q) else Q, dtype=np.float32)
-    if use_kron_product:
-        return Q
-    rows = (np.arange(p)[None, :] * d + np.arange(d)[:, None]).reshape(-1)      # Xi[i, t] = flat[t * d + i]
-    return np.ascontiguousarray(Q[rows])
-
-
 class DeviceTrainer:
     LOG_RING = 8                      # epochs of records kept; the host runs at most two epochs ahead of its reading
 
     def __init__(self, x, dx, poly_order, flags=0, Q=None, use_kron_product=True, allow_constant=True, reversed_sym=None,
                  lr=1.0, threshold=0.1, st_freq=0, w_x=1.0, w_reg=0.0, l1=True, tol=1e-3, max_iter=20, history=100,
                  tol_grad=1e-7, tol_change=1e-9, inv_count=None, engine=None, detail=None, group=None, closure="stream",
-                 statistics=None):
-        """x, dx (S, N_local, d) device tensors; ``reversed_sym = (gx (S, n_g, N, d), jgx (S, n_g, N, d, d), weight)`` as
+                 statistics=None, coef=None):
+        """x, dx (S, N_local, d) device tensors; ``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from
+        Q / use_kron_product / allow_constant); ``reversed_sym = (gx (S, n_g, N, d), jgx (S, n_g, N, d, d), weight)`` as
         batched.BatchedClosure; ``group``: point shards, [loss | grad] summed over the ranks between closure and update;
         ``detail``: keep coefficients and mask of every epoch in the record (default: for S <= 64).
         ``closure="gram"``: every closure is the quadratic form of the fixed fp64 matrices [G | R] (gram_closure.py), built
@@ -77,16 +69,13 @@ class DeviceTrainer:
         self.dp = self.d * self.p
         self.group = group
         world = dist.get_world_size(group) if group is not None else 1
+        self.coef = coef if coef is not None else CoefMap(self.d, self.p, Q, use_kron_product, allow_constant)
+        self.r, self.n = self.coef.r, self.coef.n_params
         self.q_eff = None
-        if Q is not None:
-            q = effective_Q(Q, self.d, self.p, use_kron_product)
-            if q.shape[0] != self.dp:
-                raise SymodeError(f"Q has {q.shape[0]} rows, expected d*p = {self.dp}")
-            self.r = q.shape[1]
-            self.q_eff = torch.from_numpy(q).to(dev)
-            self.n = self.r + self.d
-        else:
-            self.r, self.n = 0, self.dp
+        if self.coef.Q is not None:
+            if self.coef.Q.shape[0] != self.dp:
+                raise SymodeError(f"Q has {self.coef.Q.shape[0]} rows, expected d*p = {self.dp}")
+            self.q_eff = torch.from_numpy(self.coef.effective_Q()).to(dev)
         if self.n > 256 or self.dp > 256 or history > 128:
             raise SymodeError("DeviceTrainer handles at most 256 parameters / coefficients and 128 curvature pairs")
         self.sym = None
@@ -101,7 +90,7 @@ class DeviceTrainer:
         self.distributed = group is not None
         # --- state block: ONE allocation, laid out by the library
         offs = (ctypes.c_size_t * len(TRAINER_FIELDS))()
-        nbytes = lib.symode_trainer_layout(self.S, self.n, self.dp, history, 1 if Q is not None else 0, offs)
+        nbytes = lib.symode_trainer_layout(self.S, self.n, self.dp, history, 1 if self.q_eff is not None else 0, offs)
         if nbytes == 0:
             raise SymodeError("symode_trainer_layout refused the problem sizes")
         self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -143,7 +132,7 @@ class DeviceTrainer:
         T.inv_count = float(inv_count) if inv_count is not None else 1.0 / (n_global * self.d)
         T.workspace, T.workspace_bytes = (None, 0) if self.ws is None else (self.ws.data_ptr(), self.ws.numel() * 8)
         T.q_eff = self.q_eff.data_ptr() if self.q_eff is not None else None
-        T.r, T.allow_constant, T.n_params = self.r, int(bool(allow_constant)), self.n
+        T.r, T.allow_constant, T.n_params = self.r, int(self.coef.allow_constant), self.n
         T.w_x, T.w_reg, T.l1 = float(w_x), float(w_reg), int(bool(l1))
         T.lr, T.tol_grad, T.tol_change, T.max_iter, T.history = float(lr), float(tol_grad), float(tol_change), int(max_iter), int(history)
         T.threshold, T.tol_update, T.near_band, T.st_freq = float(threshold), float(tol), NEAR_THRESHOLD_BAND, int(st_freq)

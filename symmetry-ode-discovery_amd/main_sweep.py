@@ -178,7 +178,6 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     m = int(n_all * args['lbfgs_subsample'])
     lo, hi = rank * m // world, (rank + 1) * m // world  # shards may differ by a row: counts are summed over the ranks
     seeds = list(range(args['seed'], args['seed'] + n_seeds))
-    gens = [torch.Generator().manual_seed(s) for s in seeds]
 
     truth = sindy_truth[args['task']]
 
@@ -215,17 +214,9 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
         rd = L_list[0].shape[-1] // args['n_comps']
         args['L_list'] = [L[:rd, :rd].detach().cpu() for L in L_list]
     template = SINDyRegression(**args, **({'engine': engine} if engine is not None else {})).to(dev)
-    inits = []
+    coef = template.coef
     all_rows = seeded_subsamples(n_all, m, seeds, dev)[:, lo:hi]
-    for s, g in zip(seeds, gens):
-        if template.constraint:
-            beta = torch.randn(template.Q.shape[1], generator=g)
-            const = torch.randn(template.latent_dim, generator=g)
-            inits.append(torch.cat([beta, const]))
-        else:
-            inits.append(torch.randn(template.latent_dim * template.get_term_num(), generator=g))
-    plumbing = dict(Q=template.Q if template.constraint else None, use_kron_product=getattr(template, 'use_kron_product', True),
-                    allow_constant=getattr(template, 'allow_constant', True), group=group)
+    inits = [coef.draw(torch.Generator().manual_seed(s)) for s in seeds]
     w_sym = args['w_sym_reg'] / args['w_sindy_x'] if sym else 0.0
     stats = None
     if sym:
@@ -236,14 +227,14 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
         stats = GramStatistics(n_seeds, template.latent_dim, template.poly_order, template.flags, regulariser=True, device=dev,
                                **({'engine': engine} if engine is not None else {}))
         stats.add_gathered(x_used, dx_all[used].contiguous(), table, gx, jgx)
-        clos = GramClosure(stats, w_sym=w_sym, **plumbing)
+        clos = GramClosure(stats, w_sym=w_sym, coef=coef, group=group)
     else:
         X, DX = x_all[all_rows].contiguous(), dx_all[all_rows].contiguous()
         rev = None
         if sym:                                                     # (S, n_g, m_local, d) per-seed copies of g(x), J_g(x)
             rev = (gx[:, table.long()].transpose(0, 1).contiguous(), jgx[:, table.long()].transpose(0, 1).contiguous(), w_sym)
         clos = BatchedClosure(X, DX, template.poly_order, template.include_sine, template.include_exp, reversed_sym=rev,
-                              **plumbing, **({'engine': engine} if engine is not None else {}))
+                              coef=coef, group=group, **({'engine': engine} if engine is not None else {}))
     sweep = SeedSweepLBFGS(clos, args['lr_sindy'], args['threshold'], args['st_freq'], w_sindy_x=args['w_sindy_x'],
                            sindy_reg_type=args['sindy_reg_type'], w_sindy_reg=args['w_sindy_reg'],
                            gram_closure=bool(args.get('gram_closure')), statistics=stats)

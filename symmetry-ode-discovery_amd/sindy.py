@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import library
+from .coef_map import CoefMap
 from .constraint import constraint_M, constraint_Q
 from .engine import get_engine, library_flags
 from .lstsq import lstsq_normal
@@ -158,6 +159,7 @@ class SINDyRegression(nn.Module):
         self.lstsq_driver = kwargs.get("lstsq_driver") or ("gels" if torch.device(device).type == "cuda" else "gelsy")
         self.engine = kwargs.get("engine") or get_engine()
         self.flags = library_flags(self.include_sine, self.include_exp)
+        self._coef_map = None
         n_terms = self.engine.lib_size(latent_dim, poly_order, self.flags)   # raises if not compiled in
         assert n_terms == library.term_count(latent_dim, poly_order, self.include_sine, self.include_exp)
 
@@ -225,16 +227,17 @@ class SINDyRegression(nn.Module):
         self.beta = nn.Parameter(torch.randn((self.Q.shape[1]), device=self.Xi.device))
         self._gram_cache = None
 
+    @property
+    def coef(self):
+        """The variables <-> Xi map of the current Q: rebuilt when Q is replaced (update_Q, or a caller installing another
+        basis of the same subspace)."""
+        c = self._coef_map
+        if c is None or c.Q is not (self.Q if self.constraint else None):
+            c = self._coef_map = CoefMap.from_regressor(self)
+        return c
+
     def get_Xi(self):                                                     # sindy.py:169-176
-        if not self.constraint:
-            return self.Xi
-        if self.use_kron_product:
-            Xi = (self.Q @ self.beta).view(self.latent_dim, -1)
-        else:
-            Xi = (self.Q @ self.beta).view(-1, self.latent_dim).transpose(0, 1)
-        if self.allow_constant:
-            Xi = Xi + torch.cat([self.const, torch.zeros((Xi.shape[0], Xi.shape[1] - 1), device=Xi.device)], dim=1)
-        return Xi
+        return self.coef.xi(self.beta, self.const) if self.constraint else self.Xi
 
     def get_term_num(self):                                               # sindy.py:179-189
         return library.term_count(self.latent_dim, self.poly_order, self.include_sine, self.include_exp)
@@ -449,10 +452,7 @@ def solve_SINDy_one_step(regressor, x, y, w_sindy_reg, st_threshold, **kwargs):
             residual = yy - 2 * b @ cq + b @ Gq @ b
             # get_Xi of THIS solution on the host, in fp32 like the device product (sindy.py:169-176)
             beta_h = (full[:-d] if regressor.allow_constant else full).astype(np.float32)
-            flat_xi = _constraint_on_host(regressor).astype(np.float32) @ beta_h
-            xi_host = flat_xi.reshape(d, p).copy() if regressor.use_kron_product else flat_xi.reshape(p, d).T.copy()
-            if regressor.allow_constant:
-                xi_host[:, 0] += full[-d:].astype(np.float32)
+            xi_host = regressor.coef.xi(beta_h, full[-d:].astype(np.float32))
     # The solution was made on the host: threshold it there too (same fp32 values, same strict >, sindy.py:192-194, 312),
     # then ONE packed copy carries coefficients, mask and residual up -- no device launches, no synchronising allclose
     # (sindy.py:313), no mask download on the next pass.

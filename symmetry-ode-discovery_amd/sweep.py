@@ -16,6 +16,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .coef_map import CoefMap
 from .engine import get_engine, library_flags
 from . import lstsq as _lstsq
 from .sindy import NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_solve_from_gram
@@ -211,7 +212,7 @@ class BatchedLBFGS:
             r = r + self.old_stps[self._rows, slot] * ((al[:, k] - be) * live)[:, None]
         return r
 
-    def _iteration(self, closure, evaluate):
+    def _iteration(self, closure, evaluate=True):
         """One inner iteration of every problem on the persistent buffers (self.P, _loss, _g, _act and the optimiser
         state): everything is updated in place, so the sequence of launches can be captured once and replayed."""
         P, g, loss, act = self.P, self._g, self._loss, self._act
@@ -298,24 +299,6 @@ class BatchedLBFGS:
                 return body(closure)
         self._graph.replay()
 
-    def _iteration_replayed(self, closure):
-        """The iteration is ~60 small launches around one fused closure kernel: launch-bound.  After a few eager runs
-        (lazy initialisations done) it is captured ONCE in a HIP graph and replayed -- same kernels, same buffers."""
-        if self._graph is None or self._graph_closure is not closure:
-            if self._warm < 3 or (self._graph is not None and self._graph_closure is not closure):
-                self._warm += 1
-                return self._iteration(closure, True)
-            try:
-                torch.cuda.synchronize(self.P.device)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    self._iteration(closure, True)
-                self._graph, self._graph_closure = graph, closure
-            except Exception:                                              # pragma: no cover - depends on the runtime
-                self.use_graph = False
-                return self._iteration(closure, True)
-        self._graph.replay()
-
     @torch.no_grad()
     def step(self, closure, frozen=None):
         """closure(P) -> (loss (S,), grad (S, n)).  ``frozen`` (S,) bool: problems that must not move."""
@@ -344,8 +327,8 @@ class BatchedLBFGS:
             if it == self.max_iter:
                 self._iteration(closure, False)
                 break
-            if self.use_graph:
-                self._iteration_replayed(closure)
+            if self.use_graph:                                              # ~60 small launches around one closure kernel
+                self._replayed(self._iteration, closure)
             else:
                 self._iteration(closure, True)
             if it % 5 == 0 and not bool(self._act.any()):                   # the only host sync, every 5th iteration
@@ -354,27 +337,25 @@ class BatchedLBFGS:
 
 
 class GramClosure:
-    """The coefficient plumbing of batched.BatchedClosure (S, d, p, Q, xi_from, grads_to, evaluate) over prebuilt
+    """The closure surface of batched.BatchedClosure (S, d, p, coef, xi_from, grads_to, evaluate) over prebuilt
     gram_closure.GramStatistics: the closure of a Gram-form sweep that never holds per-seed copies of the points.
     ``evaluate`` reads the statistics as they stand (summed over the ranks once the device trainer has all-reduced them)."""
 
-    def __init__(self, statistics, Q=None, use_kron_product=True, allow_constant=True, w_sym=0.0, group=None):
+    def __init__(self, statistics, Q=None, use_kron_product=True, allow_constant=True, w_sym=0.0, group=None, coef=None):
         self.statistics = statistics
         self.engine = statistics.engine
         self.S, self.d, self.p = statistics.S, statistics.d, statistics.p
         self.order, self.flags = statistics.order, statistics.flags
-        self.Q, self.use_kron, self.allow_constant = Q, use_kron_product, allow_constant
+        self.coef = coef if coef is not None else CoefMap(self.d, self.p, Q, use_kron_product, allow_constant)
         self.w_sym = float(w_sym)
         self.group = group
         self.distributed = group is not None
 
     def xi_from(self, beta, const=None):
-        from .batched import BatchedClosure
-        return BatchedClosure.xi_from(self, beta, const)
+        return self.coef.xi(beta, const)
 
     def grads_to(self, grad_xi):
-        from .batched import BatchedClosure
-        return BatchedClosure.grads_to(self, grad_xi)
+        return self.coef.grad(grad_xi)
 
     def evaluate(self, beta, const=None, mask=None):
         """(loss (S,) = mse [+ w_sym * regulariser], d/dbeta [or d/dXi], d/dconst), as BatchedClosure.evaluate."""
@@ -398,6 +379,8 @@ class SeedSweepLBFGS:
         rank's points (e.g. from ``add_gathered``), all-reduced by the trainer; implies the Gram closure, and ``closure``
         then only supplies the coefficient plumbing (a GramClosure, which holds no points)."""
         self.c = closure
+        self.coef = getattr(closure, 'coef', None) or CoefMap(closure.d, closure.p, closure.Q, getattr(closure, 'use_kron', True),
+                                                              getattr(closure, 'allow_constant', True))   # (a duck-typed closure)
         self.statistics = statistics
         self.gram_closure = bool(gram_closure) or statistics is not None
         self.lr, self.threshold, self.st_freq, self.tol = lr_sindy, threshold, st_freq, tol
@@ -405,23 +388,12 @@ class SeedSweepLBFGS:
         if sindy_reg_type not in ("l1", "none"):
             raise ValueError(f"Unknown regularization type: {sindy_reg_type}")
 
-    def _split(self, P):
-        c = self.c
-        if c.Q is None:
-            return P.view(c.S, c.d, c.p), None
-        r = c.Q.shape[1]
-        return P[:, :r], P[:, r:].reshape(c.S, c.d, 1)
-
     def _data_term(self, P, alias=True):
         """loss, gradient of the bare MSE (+ regulariser the closure carries) w.r.t. the flat parameters.  ``alias``:
         the results may be views of the closure's output buffer (they are consumed before the next evaluation)."""
-        c = self.c
-        a, b = self._split(P)
-        loss, ga, gb = c.evaluate(a.contiguous(), b, mask=self.mask, **({'alias': True} if alias and self._can_alias else {}))
-        if gb is None and c.Q is not None:                                  # constrain_constant: const is a parameter the
-            gb = torch.zeros(c.S, c.d, 1, device=P.device, dtype=P.dtype)   # model does not read (sindy.py:60, 173-175)
-        g = ga.reshape(c.S, -1) if gb is None else torch.cat([ga, gb.reshape(c.S, -1)], dim=1)
-        return loss, g
+        a, b = self.coef.split(P)
+        loss, ga, gb = self.c.evaluate(a.contiguous(), b, mask=self.mask, **({'alias': True} if alias and self._can_alias else {}))
+        return loss, self.coef.join(ga, gb)
 
     def _closure(self, P):
         loss, g = self._data_term(P, alias=False)
@@ -433,16 +405,8 @@ class SeedSweepLBFGS:
         return loss, g
 
     def _xi(self, P):
-        a, b = self._split(P)
+        a, b = self.coef.split(P)
         return self.c.xi_from(a.contiguous(), b)
-
-    def _norms(self, A, B):
-        """sum over parameter tensors of ||A - B|| per problem (train.py:702-704)."""
-        c = self.c
-        if c.Q is None:
-            return (A - B).norm(dim=1)
-        r = c.Q.shape[1]
-        return (A[:, :r] - B[:, :r]).norm(dim=1) + (A[:, r:] - B[:, r:]).norm(dim=1)
 
     def _native_ok(self, P0):
         """The device-resident trainer (device_lbfgs.DeviceTrainer: optimiser AND epoch logic as kernels of the library, no
@@ -469,8 +433,8 @@ class SeedSweepLBFGS:
             stats = GramStatistics(c.S, c.d, c.order, c.flags, regulariser=c.sym is not None, device=c.x.device, engine=c.engine)
             stats.add(c.x, c.dx, *(c.sym[:2] if c.sym is not None else ()))
         x, dx = (None, None) if stats is not None else (c.x, c.dx)          # the Gram form holds no reference to the points
-        tr = DeviceTrainer(x, dx, c.order, c.flags, Q=c.Q, use_kron_product=c.use_kron, allow_constant=c.allow_constant,
-                           reversed_sym=rev, lr=self.lr, threshold=self.threshold, st_freq=self.st_freq, w_x=self.w_x,
+        tr = DeviceTrainer(x, dx, c.order, c.flags, coef=self.coef, reversed_sym=rev, lr=self.lr, threshold=self.threshold,
+                           st_freq=self.st_freq, w_x=self.w_x,
                            w_reg=self.w_reg if self.reg_type == 'l1' else 0.0, l1=True, tol=self.tol,
                            inv_count=None if self.statistics is not None else c.inv_count,
                            engine=c.engine, group=(c.group or dist.group.WORLD) if c.distributed else None,
@@ -525,9 +489,9 @@ class SeedSweepLBFGS:
             nan |= bad
             done |= bad
             live = ~done
-            upd = self._norms(P, prev)
+            upd = self.coef.update_norm(P, prev)
             conv = live & (upd < self.tol)
-            final = conv & (self._norms(P, pprev) < self.tol)             # train.py:709-714
+            final = conv & (self.coef.update_norm(P, pprev) < self.tol)             # train.py:709-714
             done |= final
             thr_conv = conv & ~final
             thr_freq = (live & ~conv & (n_iters % self.st_freq == 0)) if self.st_freq > 0 else torch.zeros_like(done)

@@ -293,19 +293,13 @@ class _HostShadow:
     def __init__(self, regressor, x, dx, reversed_sym=None, numpy_vars=True, use_graph=True, zero_copy=True):
         self.reg, self.x, self.dx = regressor, x, dx
         self.params = [p.detach().cpu().clone().requires_grad_(True) for p in regressor.parameters()]
+        self.coef = regressor.coef.to('cpu')
         # numpy mode: ONE flat float32 vector aliases every host parameter (torch views of the same memory)
         self.flat = None
         if numpy_vars:
-            sizes = [p.numel() for p in self.params]
             self.flat = np.concatenate([p.detach().numpy().reshape(-1) for p in self.params]).astype(np.float32)
-            off, views = 0, []
-            for p, n in zip(self.params, sizes):
-                views.append(torch.from_numpy(self.flat[off:off + n]).view(p.shape))
-                off += n
-            self.params = views                               # plain tensors sharing memory with self.flat
+            self.params = [v for v in self.coef.split(torch.from_numpy(self.flat)) if v is not None]   # plain tensors on self.flat
         self.mask = regressor.mask.detach().cpu().clone()
-        self.Q = regressor.Q.detach().cpu() if regressor.constraint else None
-        self._Qnp = self.Q.numpy() if self.Q is not None else None
         d, p = regressor.mask.shape
         dev = x.device
         self.h_xi = torch.empty(d, p).pin_memory()
@@ -412,17 +406,7 @@ class _HostShadow:
         return self.params
 
     def get_Xi(self):                                                                   # sindy.py:169-176 on the host
-        reg = self.reg
-        if not reg.constraint:
-            return self.params[0]
-        beta, const = self.params
-        if reg.use_kron_product:
-            Xi = (self.Q @ beta).view(reg.latent_dim, -1)
-        else:
-            Xi = (self.Q @ beta).view(-1, reg.latent_dim).transpose(0, 1)
-        if reg.allow_constant:
-            Xi = Xi + torch.cat([const, torch.zeros(Xi.shape[0], Xi.shape[1] - 1)], dim=1)
-        return Xi
+        return self.coef.xi(*self.params)
 
     def set_threshold(self, threshold):                                                 # sindy.py:192-194
         with torch.no_grad():
@@ -432,20 +416,12 @@ class _HostShadow:
         self.sync()
 
     def sync(self):
-        with torch.no_grad():
-            for dst, src in zip(self.reg.parameters(), self.params):
-                dst.data.copy_(src.detach())
-            self.reg.mask.copy_(self.mask)              # in place: the captured graph holds this pointer
+        flat = self.flat if self.flat is not None else torch.cat([p.detach().reshape(-1) for p in self.params])
+        self.coef.adopt(self.reg, flat, self.mask)      # (the mask in place: the captured graph holds this pointer)
 
     def grad_to_flat(self, g_xi):
         """Chain rule of get_Xi: dL/d(flat parameters) from dL/dXi (d, p), as numpy float32."""
-        reg = self.reg
-        if not reg.constraint:
-            return g_xi.reshape(-1)
-        G = g_xi if reg.use_kron_product else g_xi.T
-        g_beta = self._Qnp.T @ G.reshape(-1)
-        g_const = g_xi[:, 0] if reg.allow_constant else np.zeros(reg.latent_dim, dtype=np.float32)
-        return np.concatenate([g_beta, g_const]).astype(np.float32)
+        return self.coef.grad(g_xi, flat=True)
 
     def evaluate(self):
         """Returns (Xi on host with graph, [mse, sym] values, [dmse/dXi, dsym/dXi]) -- one sync."""
@@ -798,29 +774,14 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
         rev = (gx.reshape(1, gx.shape[0], -1, d).contiguous(), jgx.reshape(1, jgx.shape[0], -1, d, d).contiguous(),
                w_sym_reg / w_sindy_x)
     xs, dxs = x.reshape(1, -1, d).contiguous(), dx.reshape(1, -1, d).contiguous()
+    coef = regressor.coef
     with torch.no_grad():
-        if regressor.constraint:
-            P0 = torch.cat([regressor.beta.detach().reshape(-1), regressor.const.detach().reshape(-1)]).cpu()[None]
-        else:
-            P0 = regressor.Xi.detach().reshape(1, -1).cpu()
+        P0 = coef.pack(regressor).cpu()[None]
         mask_before = regressor.mask.detach().cpu().numpy().copy()
-    tr = DeviceTrainer(xs, dxs, regressor.poly_order, regressor.flags, Q=regressor.Q if regressor.constraint else None,
-                       use_kron_product=getattr(regressor, 'use_kron_product', True),
-                       allow_constant=getattr(regressor, 'allow_constant', True), reversed_sym=rev, lr=lr_sindy,
+    tr = DeviceTrainer(xs, dxs, regressor.poly_order, regressor.flags, coef=coef, reversed_sym=rev, lr=lr_sindy,
                        threshold=threshold, st_freq=st_freq, w_x=w_sindy_x, w_reg=w_sindy_reg if sindy_reg_type == 'l1' else 0.0,
                        l1=sindy_reg_type == 'l1', engine=regressor.engine, detail=True, group=group,
                        closure='gram' if gram_closure else 'stream')
-
-    def adopt(params, mask):                               # a host state into the regressor (two small uploads)
-        with torch.no_grad():
-            params = torch.as_tensor(params)
-            if regressor.constraint:
-                r = regressor.Q.shape[1]
-                regressor.beta.data.copy_(params[:r].view_as(regressor.beta))
-                regressor.const.data.copy_(params[r:].view_as(regressor.const))
-            else:
-                regressor.Xi.data.copy_(params.view_as(regressor.Xi))
-            regressor.mask.copy_(torch.as_tensor(mask).view_as(regressor.mask))
 
     state = {'mask_before': mask_before}
 
@@ -837,7 +798,7 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
         wandb_log = dict(losses)
         if code == EVENT_FINAL:                                                        # train.py:709-714
             print(f'Final convergence reached at iteration {epoch}; exit training.')
-            adopt(rec['params'][0], rec['mask'][0])
+            coef.adopt(regressor, rec['params'][0], rec['mask'][0])    # a host state into the regressor
             _save(regressor, save_dir, f'regressor_{epoch}.pt')
             return True
         if code in (EVENT_THRESHOLD_CONVERGED, EVENT_THRESHOLD_PERIOD):
@@ -849,7 +810,7 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
         log = log_interval > 0 and (epoch + 1) % log_interval == 0
         save = save_interval > 0 and (epoch + 1) % save_interval == 0
         if log or save:
-            adopt(rec['params'][0], rec['mask'][0])
+            coef.adopt(regressor, rec['params'][0], rec['mask'][0])    # a host state into the regressor
         if log:
             print(', '.join([f'Epoch {epoch}'] + [f'{k}: {v:.4f}' for k, v in losses.items()]))
             if test_log is not None:
@@ -863,7 +824,7 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
 
     out = tr.fit(P0, num_epochs, mask0=torch.from_numpy(mask_before)[None], on_epoch=on_epoch,
                  test_eval=test_log is not None and log_interval > 0)
-    adopt(out['params'][0], out['mask'][0])
+    coef.adopt(regressor, out['params'][0], out['mask'][0])
     return out
 
 
