@@ -92,6 +92,26 @@ int symode_odeint(const float* x, long n, int d, int order, int flags, const flo
 int symode_odeint_traj(const float* x, long n, int d, int order, int flags, const float* xi, const float* mask,
                        int n_steps, float dt, int method, float* traj, void* stream);
 
+/* Roll-out error of n_models models on n_ics held-out trajectories, ONE launch, the predicted trajectories never stored.
+ * x_true (n_ics, n_steps + 1, d) fp32 contiguous: the layout the data sets hold before flattening; the integration
+ * starts from x_true[:, 0].  xi, mask: (n_models, d, p), mask may be NULL.  method as symode_odeint; one thread per
+ * (model, trajectory) runs the steps of symode_odeint_traj and after step k forms
+ *     e = mean_j (x_true[i, k+1, j] - x_pred[j])^2        (fp32: each difference and square rounded, no FMA, the squares
+ *                                                          summed over j in index order, times 1/d -- for d <= 2 bit for bit
+ *                                                          torch's ((x - xp) ** 2).mean(-1); at d = 3 torch adds the three
+ *                                                          squares in another order and may differ in the last place)
+ *   err_out (n_models, n_ics, n_steps) fp32 = e; may be NULL (nothing is written then);
+ *   mean_err_out (n_models, n_ics) fp64 = the fp32 e values added in step order in fp64, over n_steps: NaN / inf when the
+ *                model diverges (no early exit, inf / NaN propagate as in the per-model path);
+ *   horizon_out (n_models, n_ics) int32 = number of leading steps with e <= bound (false for NaN); bound = +inf counts
+ *                the leading finite steps; horizon == n_steps: the bound was never exceeded.
+ * No workspace, no atomics: the outputs are bit-deterministic.  n_ics == 0 or n_models == 0: nothing to do (0).
+ * replaces: eval_ltp_accuracy called once per model, evaluation/eval_ltp.py:31-43 (roll-out model_utils.py:241-254,
+ * error eval_ltp.py:43), for every model of a seed sweep at once. */
+int symode_rollout_error(const float* x_true, long n_ics, int n_steps, int d, int order, int flags, const float* xi,
+                         const float* mask, long n_models, float dt, int method, float bound, float* err_out,
+                         double* mean_err_out, int* horizon_out, void* stream);
+
 /* Augmented Gram matrix in fp64 (MFMA f64): A = [Theta(x) | dx] (n, p+d),
  *   gram_out[s] (p+d, p+d) = A^T A   (row-major, both triangles filled).
  * Every quantity of the ridge-augmented least-squares solve (sindy.py:261-288) and of the

@@ -205,6 +205,21 @@ int symode_odeint_traj(const float* x, long n, int d, int order, int flags, cons
     return (int)ops->odeint_traj(x, n, xi, mask, n_steps, dt, method, traj, (hipStream_t)stream);
 }
 
+int symode_rollout_error(const float* x_true, long n_ics, int n_steps, int d, int order, int flags, const float* xi,
+                         const float* mask, long n_models, float dt, int method, float bound, float* err_out,
+                         double* mean_err_out, int* horizon_out, void* stream) {
+    SYMODE_GET_OPS();
+    if (n_ics < 0 || n_models < 0 || n_steps <= 0 || (method != 0 && method != 1)) return SYMODE_E_BADSIZE;
+    if (n_ics == 0 || n_models == 0) return SYMODE_OK;
+    if (n_ics > 2147483647L / n_models) return SYMODE_E_BADSIZE;            // one lane per (model, trajectory)
+    if (!x_true || !xi || !mean_err_out || !horizon_out) return SYMODE_E_NULLPTR;
+    if (misaligned(x_true, 4) || misaligned(xi, 4) || misaligned(mask, 4) || misaligned(err_out, 4) ||
+        misaligned(mean_err_out, 8) || misaligned(horizon_out, 4))
+        return SYMODE_E_ALIGN;
+    return (int)ops->rollout_error(x_true, n_ics, n_models, xi, mask, n_steps, dt, method, bound, err_out, mean_err_out,
+                                   horizon_out, (hipStream_t)stream);
+}
+
 int symode_loss_grad(const float* x, const float* dx, long n_problems, long n, int d, int order, int flags,
                      const float* xi, const float* mask, float inv_count, float* loss_out, float* grad_out,
                      void* workspace, size_t workspace_bytes, void* stream) {

@@ -115,6 +115,9 @@ struct LibOps {
     // idx != nullptr: S index rows (S, n) into ONE shared (x, gx, jgx) of n_src rows
     hipError_t (*symreg_reversed_gram)(const float* x, const float* gx_, const float* jgx, int n_g, long S, long n,
                                        const int* idx, long n_src, double* gram, double* ws, hipStream_t st);
+    // roll-out error of S models on n_ics truth trajectories (n_ics, n_steps + 1, d) in one launch (rollout.hpp)
+    hipError_t (*rollout_error)(const float* x_true, long n_ics, long S, const float* xi, const float* mask, int n_steps,
+                                float dt, int method, float bound, float* err, double* mean_err, int* horizon, hipStream_t st);
 };
 
 // ---------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #include "gram_rev.hpp"
 #include "gram_valu.hpp"
 #include "kernels.hpp"
+#include "rollout.hpp"
 #include "weak.hpp"
 
 namespace symode {
@@ -30,7 +31,8 @@ constexpr LibOps make_ops() {
                   &launch_euler_jvp<Lib>,
                   &launch_euler_jvp_vjp<Lib>,
                   &launch_weak_gram<Lib>,
-                  rev_gram_launcher<Lib>()};
+                  rev_gram_launcher<Lib>(),
+                  &launch_rollout_error<Lib>};
 }
 
 #define SYMODE_OPS_ALL_FLAGS(D, O) make_ops<D, O, 0>(), make_ops<D, O, 1>(), make_ops<D, O, 2>(), make_ops<D, O, 3>()

@@ -34,6 +34,8 @@ _SIGNATURES = {
                               c_void_p, c_void_p]),
     "symode_odeint_traj": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_int,
                               c_void_p, c_void_p]),
+    "symode_rollout_error": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_float, c_int,
+                                     c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_loss_grad": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_aug_gram": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
@@ -255,6 +257,32 @@ class HipEngine:
         self._check(self.lib.symode_odeint_traj(self._ptr(x), n, d, order, flags, self._ptr(xi), self._ptr(mask), int(n_steps),
                                                 float(dt), m, self._ptr(traj), self._stream(x)), "symode_odeint_traj")
         return traj
+
+    def rollout_error(self, x_true, xi, mask, order, flags, dt, method="rk4", bound=float("inf"), want_error=True):
+        """Roll-out error of S models on held-out trajectories in ONE launch (symode_rollout_error).  x_true (n_ics,
+        n_steps + 1, d): the integration starts at x_true[:, 0]; xi, mask (S, d, p) or (d, p), mask may be None.
+        Returns (err (S, n_ics, n_steps) fp32 -- None with ``want_error=False`` --, mean_err (S, n_ics) fp64, horizon
+        (S, n_ics) int32: leading steps with err <= bound; bound = inf counts the leading finite steps)."""
+        x_true = self._dev(x_true, "x_true")
+        if x_true.dim() != 3:
+            raise SymodeError(f"x_true must be (n_ics, n_steps + 1, d), got {tuple(x_true.shape)}")
+        n_ics, n_points, d = x_true.shape
+        xi = self._dev(xi, "xi")
+        mask = None if mask is None else self._dev(mask, "mask")
+        S = xi.shape[0] if xi.dim() == 3 else 1
+        self._check_coef(xi, mask, d, order, flags, S)
+        m = {"euler": 0, "rk4": 1}.get(method)
+        if m is None:
+            raise ValueError("Unrecognized ODEInt method.")
+        n_steps = n_points - 1
+        err = torch.empty(S, n_ics, max(n_steps, 0), dtype=torch.float32, device=x_true.device) if want_error else None
+        mean_err = torch.empty(S, n_ics, dtype=torch.float64, device=x_true.device)
+        horizon = torch.empty(S, n_ics, dtype=torch.int32, device=x_true.device)
+        self._check(self.lib.symode_rollout_error(self._ptr(x_true), n_ics, n_steps, d, order, flags, self._ptr(xi),
+                                                  self._ptr(mask), S, float(dt), m, float(bound), self._ptr(err),
+                                                  self._ptr(mean_err), self._ptr(horizon), self._stream(x_true)),
+                    "symode_rollout_error")
+        return err, mean_err, horizon
 
     def _check_coef(self, xi, mask, d, order, flags, n_problems=1):
         p = self.lib_size(d, order, flags)

@@ -109,3 +109,60 @@ def eval_ltp_accuracy(regressor, autoencoder, x, dt=None, **kwargs):
     error = torch.mean((x[:, 1:] - x_pred) ** 2, dim=-1)
     res = {'x_pred': x_pred, 't': torch.arange(1, n_steps + 1) * dt, 'error': error}
     return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def _sweep_coefficients(Xi, mask, dev):
+    Xi = torch.as_tensor(Xi, dtype=torch.float32, device=dev)
+    if Xi.dim() != 3:
+        raise ValueError(f'Xi must be (S, d, p), got {tuple(Xi.shape)}')
+    if mask is not None:
+        mask = torch.as_tensor(mask, device=dev).to(torch.float32)
+        if mask.shape != Xi.shape:
+            raise ValueError(f'mask {tuple(mask.shape)} does not match Xi {tuple(Xi.shape)}')
+    return Xi.contiguous(), (None if mask is None else mask.contiguous())
+
+
+@torch.no_grad()
+def eval_ltp_sweep(Xi, mask, x, dt=None, *, poly_order, include_sine, include_exp, task=None, bound_rel=None,
+                   autoencoder=None, engine=None):
+    """Long-term prediction error of ALL S models of a sweep in one launch (symode_rollout_error): what
+    ``eval_ltp_accuracy`` reports for one regressor (reference evaluation/eval_ltp.py:31-43), for Xi, mask (S, d, p)
+    against x (n_ics, n_steps, d); the predicted trajectories are never materialised.  ``dt`` defaults to
+    ``ode_dt_dict[task]`` as in eval_ltp_accuracy.  ``bound_rel`` r sets the horizon's bound to r times the mean
+    variance of x -- the mean over (trajectory, time, dimension) of the squared deviation from each dimension's mean, the
+    error of predicting that mean everywhere; None counts the leading finite steps.  Returns numpy arrays: ``error``
+    (S, n_ics, n_steps - 1), ``t`` (n_steps - 1,), ``mean_error`` (S, n_ics) fp64, ``horizon`` (S, n_ics) int32 (leading
+    steps with error <= bound) and ``mse_step`` (S, n_steps - 1) = error.mean(1).
+    Neither a latent roll-out nor an autoencoder is covered: use eval_ltp_accuracy per model for those."""
+    from .dataset import ode_dt_dict
+    from .engine import get_engine, library_flags
+    if autoencoder is not None or x.dim() != 3:
+        raise NotImplementedError('eval_ltp_sweep rolls out in the observed space only, x (n_ics, n_steps, d) and no '
+                                  'autoencoder; use eval_ltp_accuracy per model for a latent roll-out')
+    if dt is None:
+        dt = ode_dt_dict[task.split('_')[-1]]
+    eng = get_engine() if engine is None else engine
+    Xi, mask = _sweep_coefficients(Xi, mask, x.device)
+    n_steps = x.shape[1] - 1
+    bound = float('inf')
+    if bound_rel is not None:
+        bound = float(bound_rel) * ((x - x.mean(dim=(0, 1))) ** 2).mean().item()
+    err, mean_err, horizon = eng.rollout_error(x.to(torch.float32), Xi, mask, poly_order, library_flags(include_sine, include_exp),
+                                               dt, 'rk4', bound, True)
+    res = {'error': err, 't': torch.arange(1, n_steps + 1) * dt, 'mean_error': mean_err, 'horizon': horizon,
+           'mse_step': err.mean(1)}
+    return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+@torch.no_grad()
+def val_mse_sweep(Xi, mask, x, dx, *, poly_order, include_sine, include_exp, engine=None):
+    """Held-out derivative MSE of all S models, mean((Theta(x) (Xi * mask)^T - dx)^2) per model: ONE augmented Gram of
+    the validation points x, dx (n, d) and the Gram-form closure (symode_quad_closure) on it.  Returns numpy (S,)."""
+    from .engine import get_engine, library_flags
+    eng = get_engine() if engine is None else engine
+    Xi, mask = _sweep_coefficients(Xi, mask, x.device)
+    x, dx = x.reshape(-1, x.shape[-1]).to(torch.float32), dx.reshape(-1, dx.shape[-1]).to(torch.float32)
+    G = eng.aug_gram(x, dx, poly_order, library_flags(include_sine, include_exp))
+    G = G[None].expand(Xi.shape[0], -1, -1).contiguous()
+    loss, _ = eng.quad_closure(G, None, Xi, mask, 1.0 / x.numel())
+    return loss.cpu().numpy()

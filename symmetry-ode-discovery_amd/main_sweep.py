@@ -5,6 +5,7 @@
     python -m symode_amd.main_sweep --config selkov/noise20_eq_sindy.cfg --n_seeds 64 --method stlsq
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m symode_amd.main_sweep \
         --config selkov/noise20_eq_sindy.cfg --n_seeds 64 --method stlsq          # BASELINE config 3: 8 x MI355X
+    python -m symode_amd.main_sweep --config dosc/noise20_sindy.cfg --n_seeds 50 --eval_ltp --ltp_bound_rel 0.1
 
 Every seed gets its own initial coefficients and its own ``--lbfgs_subsample`` draw of the data set
 (main.py:36-38).  ``--method lbfgs`` (default): all seeds are optimised in lockstep by sweep.SeedSweepLBFGS on
@@ -26,6 +27,12 @@ sharded.  The i / f regularisers (their closure runs the autoencoder on Xi-depen
 loaded (each per-seed process would draw its own random network) or not frozen, and latent fits are refused with the
 per-seed command to use instead.
 
+``--eval_ltp`` scores the fitted models on the validation split without the true equation: after the fit rank 0 rolls ALL
+seeds' models out over the validation trajectories in one launch (evaluation.eval_ltp_sweep; ``--ltp_bound_rel R`` sets
+the horizon's error bound to R times the data's variance) and takes their held-out derivative MSE from one Gram matrix
+(evaluation.val_mse_sweep); ``ltp_mean_error`` (n_ics,), ``ltp_horizon`` (n_ics,) and ``val_mse`` join each seed's npz and
+the seeds are listed by median roll-out error.  Every rank holds the same final coefficients: no collective is added.
+
 A sweep's seed n does NOT reproduce ``python -m symode_amd.main --seed n`` row for row: the sweep draws each seed's
 subsample with the counter hash (seeded_subsamples) and its initial coefficients from its own torch.Generator(seed), as the
 plain sweep always has; the success rate over seeds is what the two estimate alike.
@@ -42,7 +49,7 @@ import torch.distributed as dist
 from .autoencoder import AutoEncoder
 from .batched import BatchedClosure
 from .dataset import get_dataset
-from .evaluation import aggregate_results, sindy_truth
+from .evaluation import aggregate_results, eval_ltp_sweep, sindy_truth, val_mse_sweep
 from .lie import LieGenerator
 from .parser_utils import get_args
 from .sindy import SINDyRegression
@@ -62,17 +69,52 @@ def _pop(argv, flag, default, cast):
     return default
 
 
-def _write_results(args, seeds, Xi, mask, truth):
-    """eval_results/<save_dir>/seed{n}.npz per seed (evaluation/eval_eq.py:7-34, main.py:128-138)."""
+def _pop_flag(argv, flag):
+    if flag in argv:
+        argv.remove(flag)
+        return True
+    return False
+
+
+def _score_on_validation(val, Xi, mask, lib, task, bound_rel, dev, engine):
+    """--eval_ltp: per-seed arrays for the npz files, from one roll-out launch and one validation Gram (rank 0)."""
+    order, sine, exp = lib
+    kw = dict(poly_order=order, include_sine=sine, include_exp=exp, **({'engine': engine} if engine is not None else {}))
+    x = val.x.reshape(val.n_ics, val.n_steps, val.input_dim).to(dev)
+    ltp = eval_ltp_sweep(Xi, mask, x, task=task, bound_rel=bound_rel, **kw)
+    mse = val_mse_sweep(Xi, mask, val.x.to(dev), val.dx.to(dev), **kw)
+    return {'ltp_mean_error': ltp['mean_error'], 'ltp_horizon': ltp['horizon'], 'val_mse': mse}
+
+
+def _print_ltp_ranking(seeds, scores, forms):
+    """Seeds by median roll-out error over the validation trajectories (NaN = diverged, last); with a truth table, how
+    many of the best quarter have every equation's form right."""
+    med = np.median(scores['ltp_mean_error'], axis=1)
+    rank = np.argsort(np.where(np.isfinite(med), med, np.inf), kind='stable')
+    print('seeds by median roll-out error on the validation trajectories (seed: median error, median horizon, val MSE):')
+    for k in rank:
+        print(f'  {seeds[k]}: {med[k]:.4e}, {int(np.median(scores["ltp_horizon"][k]))}, {scores["val_mse"][k]:.4e}')
+    if forms is not None:
+        q = max(1, len(seeds) // 4)
+        print(f'correct form among the best {q} by roll-out error: {sum(forms[k] for k in rank[:q])}/{q}')
+
+
+def _write_results(args, seeds, Xi, mask, truth, extra=None):
+    """eval_results/<save_dir>/seed{n}.npz per seed (evaluation/eval_eq.py:7-34, main.py:128-138); ``extra``: further
+    per-seed arrays (name -> array with the seeds on axis 0).  Returns correct_form_all per seed."""
     eval_dir = f'eval_results/{args["save_dir"]}'
     os.makedirs(eval_dir, exist_ok=True)
     tmask = truth != 0
+    forms = []
     for k, s in enumerate(seeds):
         coef = np.where(mask[k], Xi[k], 0.0)
         cf = np.array([float(np.all(mask[k, i] == tmask[i])) for i in range(truth.shape[0])])
         mse = np.array([np.mean((coef[i, tmask[i]] - truth[i, tmask[i]]) ** 2) for i in range(truth.shape[0])])
+        more = {} if extra is None else {name: v[k] for name, v in extra.items()}
         np.savez(f'{eval_dir}/seed{s}.npz', coefficients=coef, correct_form=cf, mse=mse, correct_form_all=np.all(cf),
-                 mse_all=np.mean(mse))
+                 mse_all=np.mean(mse), **more)
+        forms.append(bool(np.all(cf)))
+    return forms
 
 
 def _refusal(args):
@@ -142,6 +184,8 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     method = _pop(argv, '--method', 'lbfgs', str)
     if method not in ('lbfgs', 'stlsq'):
         raise SystemExit(f'--method {method}: lbfgs or stlsq')
+    eval_ltp = _pop_flag(argv, '--eval_ltp')
+    ltp_bound_rel = _pop(argv, '--ltp_bound_rel', None, float)
     args = vars(get_args(argv=argv))
     why = _refusal(args)
     if why is not None:
@@ -162,12 +206,12 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
             dist.init_process_group(backend, **({'device_id': dev} if backend == 'nccl' else {}))
         group = dist.group.WORLD
         if rank == 0:                                               # one rank makes the data files, the others read them
-            train_dataset, _, args = get_dataset(args)
+            train_dataset, val_dataset, args = get_dataset(args)
         dist.barrier()
         if rank != 0:
-            train_dataset, _, args = get_dataset(args)
+            train_dataset, val_dataset, args = get_dataset(args)
     else:
-        train_dataset, _, args = get_dataset(args)
+        train_dataset, val_dataset, args = get_dataset(args)
     # Every seed draws ONE subsample of the whole flattened data set (main.py:36-38: the first batch of a shuffled loader),
     # seeded by the seed alone; rank r works on rows [r m / W, (r+1) m / W) of that draw.  The union over the ranks is
     # the single-process subsample whatever the world size, so an N-rank run fits the same problems as a 1-rank run and
@@ -199,9 +243,15 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
         if rank == 0:
             class _T:                                               # library flags for the truth-table padding
                 include_sine, include_exp = args['include_sine'], args['include_exp']
-            _write_results(args, seeds, Xi.numpy(), mask.numpy().astype(bool), padded_truth(mask.shape[-1], _T))
+            scores = None
+            if eval_ltp:
+                scores = _score_on_validation(val_dataset, Xi.to(dev), mask.to(dev), (args['poly_order'], args['include_sine'], args['include_exp']),
+                                              args['task'], ltp_bound_rel, dev, engine)
+            forms = _write_results(args, seeds, Xi.numpy(), mask.numpy().astype(bool), padded_truth(mask.shape[-1], _T), scores)
             print(f'{n_seeds} seeds x {sw.n_points} points (over {world} rank(s)), STLSQ passes {int(passes.min())}-{int(passes.max())}')
             print(f'near-threshold coefficients (| |coef| - thr | < 1e-4): {sw.near_threshold if sw.near_threshold else "none"}')
+            if eval_ltp:
+                _print_ltp_ranking(seeds, scores, forms)
             return aggregate_results(args['save_dir'], min_seed=seeds[0], max_seed=seeds[-1] + 1)
         return None
 
@@ -242,11 +292,17 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
 
     if rank != 0:
         return None
+    scores = None
+    if eval_ltp:
+        scores = _score_on_validation(val_dataset, out['Xi'].to(dev), out['mask'].to(dev), (template.poly_order, template.include_sine, template.include_exp),
+                                      args['task'], ltp_bound_rel, dev, engine)
     Xi, mask = out['Xi'].cpu().numpy(), out['mask'].cpu().numpy().astype(bool)
-    _write_results(args, seeds, Xi, mask, padded_truth(mask.shape[-1], template))
+    forms = _write_results(args, seeds, Xi, mask, padded_truth(mask.shape[-1], template), scores)
     print(f'{n_seeds} seeds, epochs used {int(out["epochs"].min())}-{int(out["epochs"].max())}, '
           f'finished {int(out["finished"].sum())}, NaN {int(out["nan"].sum())}, '
           f'seeds with near-threshold coefficients {[seeds[i] for i in torch.nonzero(out["near_threshold"]).flatten().tolist()] or "none"}')
+    if eval_ltp:
+        _print_ltp_ranking(seeds, scores, forms)
     return aggregate_results(args['save_dir'], min_seed=seeds[0], max_seed=seeds[-1] + 1)
 
 
