@@ -173,6 +173,37 @@ int symode_loss_grad_reversed(const float* x, const float* dx, const float* gx, 
                               int d, int order, int flags, const float* xi, const float* mask, float inv_count, float w_sym,
                               float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Is J_g(x) the same matrix at every point of each (problem, group element)?  One streaming pass over
+ * jgx (S, n_g, n, d, d), run once per data set: every point's matrix is compared BITWISE (as 32-bit words) with point 0
+ * of its own (s, g) slab -- -0.0 differs from +0.0, a NaN anywhere answers "no" -- and different slabs may hold
+ * different matrices.  table_out (S, n_g, d, d) fp32 = the matrix of point 0 of every slab (always written);
+ * flag_out: ONE int32 on the device = 1 if every slab is constant, else 0 (the caller reads it back; no call synchronises).
+ * d in 1..4 (library independent), n_g >= 1.  True for any linear or affine group action on the observed coordinates and
+ * for a frozen linear autoencoder; then the _constj entries below replace their materialised counterparts.
+ * replaces: nothing in the reference -- precompute_symmreg_r, model_utils.py:172-211, stores vmap(jacfwd(.)) per point
+ * whatever the map is. */
+int symode_jacobian_constant(const float* jgx, int n_g, long n_problems, long n, int d, float* table_out, int* flag_out,
+                             void* stream);
+
+/* symode_symreg_reversed_batched on a point-constant Jacobian: jgx is the compact (S, n_g, d, d) table of
+ * symode_jacobian_constant, nothing of J_g is streamed (8 + 8 n_g instead of 8 + 24 n_g bytes per point at d = 2).
+ * Every other argument, the workspace and the result as there -- bit-identical to that entry on the materialised
+ * (S, n_g, n, d, d) copies of the table; n_g >= 1.
+ * replaces: model_utils.py:160-168 per closure, as symode_symreg_reversed_batched. */
+int symode_symreg_reversed_batched_constj(const float* x, const float* gx, const float* jgx, int n_g, long n_problems, long n,
+                                          int d, int order, int flags, const float* xi, const float* mask, float inv_count,
+                                          float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes,
+                                          void* stream);
+
+/* symode_loss_grad_reversed on a point-constant Jacobian: jgx is the compact (S, n_g, d, d) table (24 instead of 40
+ * bytes per point at d = 2, n_g = 1).  Every other argument, the workspace and the result as there -- bit-identical to
+ * that entry on the materialised copies of the table; n_g >= 1.
+ * replaces: train.py:663-664 + 675-679 + 689 with sym_reg_type 'r', as symode_loss_grad_reversed. */
+int symode_loss_grad_reversed_constj(const float* x, const float* dx, const float* gx, const float* jgx, int n_g, long n_problems,
+                                     long n, int d, int order, int flags, const float* xi, const float* mask, float inv_count,
+                                     float w_sym, float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+
 /* Gram matrix of the reversed regulariser: for S problems (layouts as in symode_symreg_reversed_batched, n_g >= 1)
  *     gram_out[s] (d p, d p) fp64 = sum_g sum_n B^T B,   B[i, (j, a)] = J_g(x_n)[i, j] theta_a(x_n) - delta_ij theta_a(g x_n),
  * rows and columns in Xi's (d, p) row-major order, both triangles filled: the regulariser of symode_symreg_reversed_batched

@@ -60,12 +60,20 @@ def allreduce_sums(sums, params, group):
 
 class BatchedClosure:
     def __init__(self, x, dx, poly_order, include_sine=False, include_exp=False, Q=None, use_kron_product=True,
-                 allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True, coef=None):
+                 allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True, coef=None,
+                 const_jacobian=None):
         """``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from Q / use_kron_product / allow_constant).
         ``reversed_sym = (gx (S, n_g, N_local, d), jgx (S, n_g, N_local, d, d), weight)`` adds  weight * the reversed
         symmetry regulariser (model_utils.py:126-170 on precomputed (g(x), J_g(x))) to every problem's loss and gradient:
         by default residual and regulariser run as ONE launch per chunk (symode_loss_grad_reversed: Theta(x) shared, x read
-        once); ``fuse_sym=False`` keeps them as two launches summed into the same packed buffer before the collective."""
+        once); ``fuse_sym=False`` keeps them as two launches summed into the same packed buffer before the collective.
+        ``const_jacobian``: None (default) -- one detection pass over jgx at set-up (engine.jacobian_constant) asks whether
+        J_g is the same matrix at every point of each (problem, group element), as it is for a linear or affine action or a
+        frozen linear autoencoder; if so the closures get the compact (S, n_g, d, d) table and stream nothing of J_g
+        (bit-identical results); False -- always the materialised (S, n_g, N, d, d) form (A/B, tests).
+        The verdict is remembered with jgx's in-place version counter and data pointer and the pass runs again when either
+        differs at the next evaluation.  What that cannot see: jgx refilled through a raw pointer or another view of its
+        storage made outside torch's version tracking (a foreign kernel writing into it) -- rebuild the closure then."""
         assert x.dim() == 3 and x.shape == dx.shape, "x, dx must be (S, N_local, d)"
         self.engine = engine or get_engine()
         self.x, self.dx = x.contiguous(), dx.contiguous()
@@ -101,6 +109,23 @@ class BatchedClosure:
             self.sym = (gx.contiguous(), jgx.contiguous(), float(weight))
             self.sym_buffers = [torch.empty_like(b) for b in self.buffers]
         self.fuse_sym = fuse_sym
+        self._cj_detect = (const_jacobian is None or bool(const_jacobian)) and self.sym is not None and x.is_cuda \
+            and hasattr(self.engine, 'jacobian_constant')
+        self._cj_seen, self._cj_table = None, None
+        if self._cj_detect:
+            self._jacobian_for_launch()
+
+    def _jacobian_for_launch(self):
+        """What the closures get as J_g: the compact table when the detection pass found every slab constant, else the
+        materialised tensor.  The pass runs once per (version, pointer) of jgx."""
+        jgx = self.sym[1]
+        if not self._cj_detect:
+            return jgx
+        seen = (jgx._version, jgx.data_ptr())
+        if seen != self._cj_seen:
+            table, const = self.engine.jacobian_constant(jgx)
+            self._cj_seen, self._cj_table = seen, (table if const else None)
+        return jgx if self._cj_table is None else self._cj_table
 
     # -- coefficient plumbing (batched get_Xi, sindy.py:169-176) ----------------------------
     def xi_from(self, beta, const=None):
@@ -115,6 +140,7 @@ class BatchedClosure:
         are returned as views of the packed buffer the kernel wrote (no copies; overwritten by the next evaluation)."""
         works = []
         fused = self.sym is not None and self.fuse_sym and hasattr(self.engine, 'loss_grad_reversed')
+        jg = self._jacobian_for_launch() if self.sym is not None else None      # (S, n_g, d, d) table or the (S, n_g, N, d, d) tensor
         for ci, ((a, b), buf) in enumerate(zip(self.chunks, self.buffers)):
             n = b - a
             loss = buf[:n]
@@ -125,7 +151,7 @@ class BatchedClosure:
                 gx, jgx, weight = self.sym
                 sb = self.sym_buffers[ci]
                 l2 = sb[:2 * n].view(n, 2)
-                self.engine.loss_grad_reversed(self.x[a:b], self.dx[a:b], gx[a:b], jgx[a:b], Xi[a:b],
+                self.engine.loss_grad_reversed(self.x[a:b], self.dx[a:b], gx[a:b], jg[a:b], Xi[a:b],
                                                None if mask is None else mask[a:b], self.order, self.flags, w_sym=weight,
                                                inv_count=self.inv_count, out=(l2, grad), **self._ws_kw)
                 torch.add(l2[:, 0], l2[:, 1], alpha=weight, out=loss)
@@ -141,7 +167,7 @@ class BatchedClosure:
                 gx, jgx, weight = self.sym
                 sb = self.sym_buffers[ci]
                 sl, sg = sb[:n], sb[n:].view(n, self.d, self.p)
-                l2, g2 = self.engine.symreg_reversed(self.x[a:b], gx[a:b], jgx[a:b], Xi[a:b], None if mask is None else mask[a:b],
+                l2, g2 = self.engine.symreg_reversed(self.x[a:b], gx[a:b], jg[a:b], Xi[a:b], None if mask is None else mask[a:b],
                                                      self.order, self.flags, out=(sl, sg), inv_count=self.inv_count, **self._ws_kw)
                 if l2.data_ptr() != sl.data_ptr():
                     sl.copy_(l2)

@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "../../include/symode.h"
+#include "jconst.hpp"
 #include "ops_table.hpp"
 #include "quad_closure.hpp"
 
@@ -319,6 +320,58 @@ int symode_loss_grad_reversed(const float* x, const float* dx, const float* gx_,
     }
     return (int)ops->symreg_reversed(x, dx, gx_, jgx, n_g, n_problems, n, xi, mask, inv_count, w_sym, loss2_out, grad_out,
                                      (double*)workspace, gx, (hipStream_t)stream);
+}
+
+// The two closures on a point-constant Jacobian: jgx is the compact (S, n_g, d, d) table (symode_jacobian_constant).
+// Grids and workspace as in their materialised counterparts: the same partial rows, summed in the same order.
+int symode_symreg_reversed_batched_constj(const float* x, const float* gx_, const float* jgx, int n_g, long n_problems, long n,
+                                          int d, int order, int flags, const float* xi, const float* mask, float inv_count,
+                                          float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+    SYMODE_GET_OPS();
+    if (n < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
+    if (!x || !xi || !loss_out || !grad_out || !gx_ || !jgx) return SYMODE_E_NULLPTR;
+    if (misaligned(x, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
+        misaligned(loss_out, 4) || misaligned(grad_out, 4))
+        return SYMODE_E_ALIGN;
+    SYMODE_CHECK_WS(n_problems, n);
+    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
+    if (n_problems == 1) {                                  // (as symode_symreg_reversed_batched)
+        int cap = small_grid_cap(n, true);
+        if (cap > 256 && ops->d * ops->p <= 24 && knobs().small_grid < 0) cap = 256;
+        if (cap > 0 && gx > cap) gx = cap;
+    }
+    return (int)ops->symreg_reversed_constj(x, nullptr, gx_, jgx, n_g, n_problems, n, xi, mask, inv_count, 1.0f, loss_out,
+                                            grad_out, (double*)workspace, gx, (hipStream_t)stream);
+}
+
+int symode_loss_grad_reversed_constj(const float* x, const float* dx, const float* gx_, const float* jgx, int n_g, long n_problems,
+                                     long n, int d, int order, int flags, const float* xi, const float* mask, float inv_count,
+                                     float w_sym, float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    SYMODE_GET_OPS();
+    if (n < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
+    if (!x || !dx || !xi || !loss2_out || !grad_out || !gx_ || !jgx) return SYMODE_E_NULLPTR;
+    if (misaligned(x, 4) || misaligned(dx, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
+        misaligned(loss2_out, 4) || misaligned(grad_out, 4))
+        return SYMODE_E_ALIGN;
+    SYMODE_CHECK_WS(n_problems, n);
+    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
+    if (n_problems == 1) {
+        const int cap = small_grid_cap(n, true);
+        if (cap > 0 && gx > cap) gx = cap;
+    }
+    return (int)ops->symreg_reversed_constj(x, dx, gx_, jgx, n_g, n_problems, n, xi, mask, inv_count, w_sym, loss2_out, grad_out,
+                                            (double*)workspace, gx, (hipStream_t)stream);
+}
+
+int symode_jacobian_constant(const float* jgx, int n_g, long n_problems, long n, int d, float* table_out, int* flag_out,
+                             void* stream) {
+    if (d < 1 || d > 4) return SYMODE_E_UNSUPPORTED;
+    if (n < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535 || n_problems * (long)n_g > 2147483647L) return SYMODE_E_BADSIZE;
+    if (!jgx || !table_out || !flag_out) return SYMODE_E_NULLPTR;
+    if (misaligned(jgx, 4) || misaligned(table_out, 4) || misaligned(flag_out, 4)) return SYMODE_E_ALIGN;
+    return (int)launch_jacobian_constant(jgx, n_problems * (long)n_g, n, d, table_out, flag_out, (hipStream_t)stream);
 }
 
 size_t symode_symreg_reversed_gram_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long n) {

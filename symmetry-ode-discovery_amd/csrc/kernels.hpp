@@ -118,6 +118,10 @@ struct LibOps {
     // roll-out error of S models on n_ics truth trajectories (n_ics, n_steps + 1, d) in one launch (rollout.hpp)
     hipError_t (*rollout_error)(const float* x_true, long n_ics, long S, const float* xi, const float* mask, int n_steps,
                                 float dt, int method, float bound, float* err, double* mean_err, int* horizon, hipStream_t st);
+    // symreg_reversed with a Jacobian that is constant over the points of a (problem, group element): jgx (S, n_g, d, d)
+    hipError_t (*symreg_reversed_constj)(const float* x, const float* dx, const float* gx_, const float* jgx, int n_g, long S,
+                                         long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
+                                         float* grad, double* ws, int gx, hipStream_t st);
 };
 
 // ---------------------------------------------------------------------------------------
@@ -777,8 +781,15 @@ struct JChunk {
 // MSE = true: the whole closure of the reversed-regulariser runs in ONE pass -- the residual r = h(x) - dx shares
 // Theta(x) and h(x) with the regulariser, x is read once (40 instead of 16 + 32 bytes per point at D = 2, n_g = 1):
 //   sums[0] = sum r^2, sums[1] = sum_g sum u^2,  grad = d( sums[0] + w_sym sums[1] ) / dXi  (both under the same 1/(N D)).
-template <class Lib, bool MSE, int RING = 2, int XI_SGPR_FROM = 32>
-__global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __restrict__ x, const float* __restrict__ dx,
+// CJ = true: J_g is the same matrix at every point of a (problem, group element) -- a linear or affine action, a frozen
+// linear autoencoder -- and jgx is the compact (S, n_g, D, D) table: the D*D values are wave-uniform and live in SGPRs,
+// nothing of J_g is streamed (24 instead of 40 bytes per point at D = 2, n_g = 1).  Same arithmetic in the same order on
+// the same chunk-to-lane assignment as the materialised form: the results are bit-identical to it.
+// MINW: waves per SIMD the register allocation has to leave room for (the launcher asks for 3 in the CJ form of the
+// d = 2 polynomial libraries: left alone, the order-5 closure comes out at 169 VGPRs -- one over the 3-wave limit of 168 --
+// although its ring slot is two vectors shorter; asked, it fits in 148 without scratch).
+template <class Lib, bool MSE, int RING = 2, int XI_SGPR_FROM = 32, bool CJ = false, int MINW = 1>
+__global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const float* __restrict__ x, const float* __restrict__ dx,
                                                                 const float* __restrict__ gx,
                                                                 const float* __restrict__ jgx, int n_g, long N, bool vec,
                                                                 const float* __restrict__ xi,
@@ -791,7 +802,7 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
     const float* xs = x + s * N * D;
     const float* ys = MSE ? dx + s * N * D : nullptr;
     const float* gs = gx + s * (long)n_g * N * D;
-    const float* js = jgx + s * (long)n_g * N * D * D;
+    const float* js = jgx + s * (long)n_g * (CJ ? 1 : N) * D * D;
     float w[D * P];
     // two libraries per point live here: Xi in SGPRs from d*p = 32 (3 waves/SIMD at order 5) -- and up to 80, the d = 3
     // order-3 libraries with sine / exp columns (69-78 coefficients would otherwise sit in VGPRs beside 70-79 sums)
@@ -800,6 +811,18 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
 #pragma unroll
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0f;
     const float ws_ = MSE ? w_sym : 1.0f;
+    // CJ: the matrix of group element g, wave-uniform (scalar loads; readfirstlane pins the values to SGPRs)
+    auto load_cj = [&](int g, float (&J)[D * D]) {
+#pragma unroll
+        for (int e = 0; e < D * D; ++e)
+            J[e] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, js[(long)g * D * D + e])));
+    };
+    float J0[D * D];                                 // (CJ) group element 0, loaded once per workgroup
+#pragma unroll
+    for (int e = 0; e < D * D; ++e) J0[e] = 0.0f;
+    if constexpr (CJ) {
+        if (n_g > 0) load_cj(0, J0);
+    }
 
     // one point against one group element: th, h belong to x (shared by all group elements of the point);
     // `extra` (MSE form, first group element only) is the residual r, whose gradient rides on the same Theta(x) products
@@ -848,9 +871,13 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
     };
     // the chunk's points against group element g, operands already in registers
     auto chunk_g = [&](float (&th)[PPT][P], float (&h)[PPT][D], const float4 (&vg)[NV], const float4 (&vj)[NVJ],
-                       float (&extra)[PPT][D]) {
+                       const float (&Jc)[D * D], float (&extra)[PPT][D]) {
         float gp[PPT][D], jf[NVJ * 4], J[PPT][D * D];
         unpack_chunk<D>(vg, gp);
+        if constexpr (CJ) {
+            each_point<PPT>([&](auto i) { one(th[i], h[i], gp[i], Jc, extra[i]); });
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < NVJ; ++i) {
             jf[4 * i + 0] = vj[i].x;
@@ -877,9 +904,13 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
         for (int g = 0; g < n_g; ++g) {
             float gp[D], J[D * D];
             load_point<D>(gs + (long)g * N * D, n, gp);
-            const float* Jp = js + ((long)g * N + n) * D * D;
+            if constexpr (CJ) {
+                load_cj(g, J);
+            } else {
+                const float* Jp = js + ((long)g * N + n) * D * D;
 #pragma unroll
-            for (int e = 0; e < D * D; ++e) J[e] = Jp[e];
+                for (int e = 0; e < D * D; ++e) J[e] = Jp[e];
+            }
             if (g == 0)
                 one(th, h, gp, J, r);
             else
@@ -904,18 +935,20 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
             float xp[PPT][D], yp[PPT][D];
             unpack_chunk<D>(vx, xp);
             if constexpr (MSE) unpack_chunk<D>(vy, yp);
-            auto group = [&](const float4 (&ug)[NV], const float4 (&uj)[NVJ], bool first) {
+            auto group = [&](const float4 (&ug)[NV], const float4 (&uj)[NVJ], const float (&Jc)[D * D], bool first) {
                 float gp[PPT][D], jf[NVJ * 4], J[PPT][D * D];
                 unpack_chunk<D>(ug, gp);
+                if constexpr (!CJ) {
 #pragma unroll
-                for (int i = 0; i < NVJ; ++i) {
-                    jf[4 * i + 0] = uj[i].x;
-                    jf[4 * i + 1] = uj[i].y;
-                    jf[4 * i + 2] = uj[i].z;
-                    jf[4 * i + 3] = uj[i].w;
+                    for (int i = 0; i < NVJ; ++i) {
+                        jf[4 * i + 0] = uj[i].x;
+                        jf[4 * i + 1] = uj[i].y;
+                        jf[4 * i + 2] = uj[i].z;
+                        jf[4 * i + 3] = uj[i].w;
+                    }
+#pragma unroll
+                    for (int e = 0; e < PPT * D * D; ++e) J[e / (D * D)][e % (D * D)] = jf[e];
                 }
-#pragma unroll
-                for (int e = 0; e < PPT * D * D; ++e) J[e / (D * D)][e % (D * D)] = jf[e];
                 auto body = [&](auto i) {
                     float th[P], h[D], r[D];
                     Lib::eval(xp[i], th);
@@ -925,16 +958,25 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
                     if constexpr (MSE) {
                         if (first) resid(h, yp[i], r);
                     }
-                    one(th, h, gp[i], J[i], r);
+                    if constexpr (CJ)
+                        one(th, h, gp[i], Jc, r);
+                    else
+                        one(th, h, gp[i], J[i], r);
                 };
                 each_point<PPT>(body);
             };
-            group(vg, vj, true);
+            group(vg, vj, J0, true);
             for (int g = 1; g < n_g; ++g) {
                 float4 ng[NV], nj[NVJ];
+                float Jg[D * D];
                 load_chunk_raw<D, true>(gs + (long)g * N * D, c, ng);
-                load_j(js + (long)g * N * D * D, c, nj);
-                group(ng, nj, false);
+                if constexpr (CJ) {
+                    load_cj(g, Jg);
+                    group(ng, nj, Jg, false);
+                } else {
+                    load_j(js + (long)g * N * D * D, c, nj);
+                    group(ng, nj, J0, false);
+                }
             }
             return;
         }
@@ -949,19 +991,25 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
             unpack_chunk<D>(vy, yp);
             each_point<PPT>([&](auto i) { resid(h[i], yp[i], r[i]); });
         }
-        chunk_g(th, h, vg, vj, r);
+        chunk_g(th, h, vg, vj, J0, r);
         for (int g = 1; g < n_g; ++g) {
             float4 ng[NV], nj[NVJ];
+            float Jg[D * D];
             load_chunk_raw<D, true>(gs + (long)g * N * D, c, ng);
-            load_j(js + (long)g * N * D * D, c, nj);
-            chunk_g(th, h, ng, nj, zero);
+            if constexpr (CJ) {
+                load_cj(g, Jg);
+                chunk_g(th, h, ng, nj, Jg, zero);
+            } else {
+                load_j(js + (long)g * N * D * D, c, nj);
+                chunk_g(th, h, ng, nj, J0, zero);
+            }
         }
     };
     if constexpr (D == 3) {
         // 12-byte points and 36-byte Jacobians: whole waves fetch their tiles coalesced and redistribute through a
         // wave-private LDS slab (points.hpp, exchange_tile); ragged waves and the tail keep the per-lane loads
         if (vec && n_g > 0) {
-            __shared__ float4 slab3[BLOCK / WAVE][NVJ * WAVE];
+            __shared__ float4 slab3[BLOCK / WAVE][(CJ ? NV : NVJ) * WAVE];
             const int lane = threadIdx.x & (WAVE - 1);
             float4* slab = slab3[threadIdx.x / WAVE];
             const long nchunks = N / PPT;
@@ -976,16 +1024,16 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
                     load_tile_raw<NV, true>(xs, c0, lane, tx);
                     if constexpr (MSE) load_tile_raw<NV, true>(ys, c0, lane, ty);
                     load_tile_raw<NV, true>(gs, c0, lane, tg);
-                    load_tile_raw<NVJ, true>(js, c0, lane, tj);
+                    if constexpr (!CJ) load_tile_raw<NVJ, true>(js, c0, lane, tj);
                     exchange_tile<NV>(tx, ax, slab, lane);
                     if constexpr (MSE) exchange_tile<NV>(ty, ay, slab, lane);
                     exchange_tile<NV>(tg, ag, slab, lane);
-                    exchange_tile<NVJ>(tj, aj, slab, lane);
+                    if constexpr (!CJ) exchange_tile<NVJ>(tj, aj, slab, lane);
                 } else if (in) {
                     load_chunk_raw<D, true>(xs, c, ax);
                     if constexpr (MSE) load_chunk_raw<D, true>(ys, c, ay);
                     load_chunk_raw<D, true>(gs, c, ag);
-                    load_j(js, c, aj);
+                    if constexpr (!CJ) load_j(js, c, aj);
                 }
                 if (in) chunk_all(c, ax, ay, ag, aj);
             }
@@ -998,7 +1046,7 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
         // register ring: RING chunks of x, (dx,) g(x), J_g of the first group element in flight per lane, a slot refilled
         // as soon as its chunk has been consumed (closure_ab: one 2^26-point problem 334 -> 325 us at order 3, the fused
         // closure at order 5 470 -> 442 us; the batched bench shape is VALU / HBM co-limited either way)
-        constexpr int NVT = (MSE ? 3 : 2) * NV + NVJ, OY = NV, OG = (MSE ? 2 : 1) * NV, OJ = OG + NV;
+        constexpr int NVT = (MSE ? 3 : 2) * NV + (CJ ? 0 : NVJ), OY = NV, OG = (MSE ? 2 : 1) * NV, OJ = OG + NV;
         const long nchunks = N / PPT;
         chunk_ring<RING, NVT>(
             nchunks, tid, nthreads,
@@ -1006,14 +1054,16 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
                 float4 tx[NV], tg[NV], tj[NVJ];
                 load_chunk_raw<D, true>(xs, q, tx);
                 load_chunk_raw<D, true>(gs, q, tg);
-                load_j(js, q, tj);
+                if constexpr (!CJ) load_j(js, q, tj);
 #pragma unroll
                 for (int i = 0; i < NV; ++i) {
                     slot[i] = tx[i];
                     slot[OG + i] = tg[i];
                 }
+                if constexpr (!CJ) {
 #pragma unroll
-                for (int i = 0; i < NVJ; ++i) slot[OJ + i] = tj[i];
+                    for (int i = 0; i < NVJ; ++i) slot[OJ + i] = tj[i];
+                }
                 if constexpr (MSE) {
                     float4 ty[NV];
                     load_chunk_raw<D, true>(ys, q, ty);
@@ -1029,8 +1079,10 @@ __global__ __launch_bounds__(BLOCK) void symreg_reversed_kernel(const float* __r
                     ay[i] = MSE ? slot[OY + i] : slot[i];
                     ag[i] = slot[OG + i];
                 }
+                if constexpr (!CJ) {
 #pragma unroll
-                for (int i = 0; i < NVJ; ++i) aj[i] = slot[OJ + i];
+                    for (int i = 0; i < NVJ; ++i) aj[i] = slot[OJ + i];
+                }
                 chunk_all(c, ax, ay, ag, aj);
             });
         const long n = nchunks * PPT + tid;
@@ -1639,7 +1691,8 @@ hipError_t launch_symreg_linear(const float* z, long n, const float* xi, const f
     return launch_finalize(fin, part, 1, gx, NACC, st);
 }
 
-template <class Lib>
+// CJ: jgx is the compact (S, n_g, D, D) table of a point-constant Jacobian (see symreg_reversed_kernel)
+template <class Lib, bool CJ = false>
 hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* gxp, const float* jgx, int n_g, long S, long n,
                                   const float* xi, const float* mask, float inv_count, float w_sym, float* loss, float* grad,
                                   double* ws, int gx, hipStream_t st) {
@@ -1650,15 +1703,17 @@ hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* 
     Finish fin = make_finish(ws, mask, inv_count, 2.0f * inv_count, loss, grad);
     fin.n_loss = mse ? 2 : 1;
     // 16-byte vectors need every slab (problem, group element) to start on a 16-byte boundary
+    // (the compact table of the CJ form is read by scalar loads: it takes no part in this)
     const bool multi = S > 1 || n_g > 1;
-    const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)gxp % 16 == 0) && ((uintptr_t)jgx % 16 == 0) &&
-                     (!mse || (uintptr_t)dx % 16 == 0) && (!multi || ((n * D) % 4 == 0 && (n * D * D) % 4 == 0));
+    const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)gxp % 16 == 0) && (CJ || (uintptr_t)jgx % 16 == 0) &&
+                     (!mse || (uintptr_t)dx % 16 == 0) && (!multi || ((n * D) % 4 == 0 && (CJ || (n * D * D) % 4 == 0)));
+    constexpr int MINW = (CJ && D == 2 && !Lib::SINE && !Lib::EXP) ? 3 : 1;
     if (mse)
-        symreg_reversed_kernel<Lib, true><<<dim3(gx, (unsigned)S), dim3(BLOCK), 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi, mask, w_sym,
-                                                                                       part, fin);
+        symreg_reversed_kernel<Lib, true, 2, 32, CJ, MINW><<<dim3(gx, (unsigned)S), dim3(BLOCK), 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi,
+                                                                                                        mask, w_sym, part, fin);
     else
-        symreg_reversed_kernel<Lib, false><<<dim3(gx, (unsigned)S), dim3(BLOCK), 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec, xi, mask,
-                                                                                        1.0f, part, fin);
+        symreg_reversed_kernel<Lib, false, 2, 32, CJ, MINW><<<dim3(gx, (unsigned)S), dim3(BLOCK), 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec,
+                                                                                                         xi, mask, 1.0f, part, fin);
     SYMODE_LAUNCH_CHECK();
     return launch_finalize(fin, part, S, gx, nacc, st);
 }

@@ -32,7 +32,8 @@ constexpr LibOps make_ops() {
                   &launch_euler_jvp_vjp<Lib>,
                   &launch_weak_gram<Lib>,
                   rev_gram_launcher<Lib>(),
-                  &launch_rollout_error<Lib>};
+                  &launch_rollout_error<Lib>,
+                  &launch_symreg_reversed<Lib, true>};
 }
 
 #define SYMODE_OPS_ALL_FLAGS(D, O) make_ops<D, O, 0>(), make_ops<D, O, 1>(), make_ops<D, O, 2>(), make_ops<D, O, 3>()

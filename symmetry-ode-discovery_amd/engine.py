@@ -52,6 +52,12 @@ _SIGNATURES = {
                                  c_void_p]),
     "symode_loss_grad_reversed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p,
                                           c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "symode_jacobian_constant": (c_int, [c_void_p, c_int, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p]),
+    "symode_symreg_reversed_batched_constj": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int,
+                                                      c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "symode_loss_grad_reversed_constj": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int,
+                                                 c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                 c_void_p]),
     "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
     "symode_symreg_reversed_gram": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_size_t, c_void_p]),
@@ -382,14 +388,17 @@ class HipEngine:
         """Reversed symmetry regulariser on precomputed (g(x), J_g(x)).
         One problem: x (N, d), gx (n_g, N, d), jgx (n_g, N, d, d), xi / mask (d, p) -> (loss scalar, grad (d, p)).
         S problems in one launch: x (S, N, d), gx (S, n_g, N, d), jgx (S, n_g, N, d, d), xi / mask (S, d, p) -> ((S,), (S, d, p)).
-        ``xi`` / ``out`` may be pinned host tensors for the one-problem form; ``inv_count`` as in loss_grad."""
+        ``xi`` / ``out`` may be pinned host tensors for the one-problem form; ``inv_count`` as in loss_grad.
+        A point-constant Jacobian may be given as its compact table, jgx (n_g, d, d) / (S, n_g, d, d) (``jacobian_constant``):
+        the shape alone selects the kernel form that streams nothing of J_g; the results are bit-identical."""
         x, gx, jgx = self._dev(x, "x"), self._dev(gx, "gx"), self._dev(jgx, "jgx")
         batched = x.dim() == 3
         S = x.shape[0] if batched else 1
         n, d = x.shape[-2], x.shape[-1]
         n_g = gx.shape[1] if batched else gx.shape[0]
         want_g = (S, n_g, n, d) if batched else (n_g, n, d)
-        if tuple(gx.shape) != want_g or tuple(jgx.shape) != want_g + (d,):
+        constj = self._is_compact_jacobian(jgx, batched, S, n_g, d)
+        if tuple(gx.shape) != want_g or (not constj and tuple(jgx.shape) != want_g + (d,)):
             raise SymodeError(f"gx {tuple(gx.shape)} / jgx {tuple(jgx.shape)} do not match x {tuple(x.shape)}")
         xi = self._dev_or_pinned(xi, "xi")
         mask = None if mask is None else self._dev(mask, "mask")
@@ -406,19 +415,42 @@ class HipEngine:
         elif ws.numel() * 8 < self.lib.symode_workspace_bytes(d, order, flags, S, n):
             raise SymodeError("private workspace too small for this call")
         inv = 1.0 / (n * d) if inv_count is None else float(inv_count)
-        self._check(self.lib.symode_symreg_reversed_batched(self._ptr(x), self._ptr(gx), self._ptr(jgx), n_g, S, n, d, order,
-                                                            flags, self._ptr(xi), self._ptr(mask), inv, self._ptr(loss),
-                                                            self._ptr(grad), self._ptr(ws), ws.numel() * 8, self._stream(x)),
-                    "symode_symreg_reversed_batched")
+        name = "symode_symreg_reversed_batched_constj" if constj else "symode_symreg_reversed_batched"
+        self._check(getattr(self.lib, name)(self._ptr(x), self._ptr(gx), self._ptr(jgx), n_g, S, n, d, order,
+                                            flags, self._ptr(xi), self._ptr(mask), inv, self._ptr(loss),
+                                            self._ptr(grad), self._ptr(ws), ws.numel() * 8, self._stream(x)), name)
         if not batched:
             return loss.reshape(-1)[0], grad.reshape(d, p)
         return loss, grad
 
+    @staticmethod
+    def _is_compact_jacobian(jgx, batched, S, n_g, d):
+        """jgx given as the (S, n_g, d, d) [one problem: (n_g, d, d)] table of a point-constant Jacobian?  The number of
+        dimensions decides (the materialised form has one more, the point axis)."""
+        return n_g >= 1 and tuple(jgx.shape) == ((S, n_g, d, d) if batched else (n_g, d, d))
+
+    def jacobian_constant(self, jgx):
+        """Is J_g the same matrix at every point of each (problem, group element)?  jgx (S, n_g, N, d, d) or (n_g, N, d, d)
+        -> (table (S, n_g, d, d) or (n_g, d, d), is_constant).  One streaming pass (bitwise comparison with point 0 of every
+        slab: -0.0 != +0.0, a NaN answers False) and ONE synchronisation to read the flag: meant to run once per data set.
+        With is_constant, ``table`` may be passed as ``jgx`` to symreg_reversed / loss_grad_reversed."""
+        jgx = self._dev(jgx, "jgx")
+        if jgx.dim() not in (4, 5) or jgx.shape[-1] != jgx.shape[-2] or jgx.numel() == 0:
+            raise SymodeError(f"jacobian_constant expects jgx (S, n_g, N, d, d) or (n_g, N, d, d), got {tuple(jgx.shape)}")
+        batched = jgx.dim() == 5
+        S = jgx.shape[0] if batched else 1
+        n_g, n, d = jgx.shape[-4], jgx.shape[-3], jgx.shape[-1]
+        table = torch.empty((S, n_g, d, d) if batched else (n_g, d, d), dtype=torch.float32, device=jgx.device)
+        flag = torch.empty(1, dtype=torch.int32, device=jgx.device)
+        self._check(self.lib.symode_jacobian_constant(self._ptr(jgx), n_g, S, n, d, self._ptr(table), self._ptr(flag),
+                                                      self._stream(jgx)), "symode_jacobian_constant")
+        return table, bool(flag.item())
 
     def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None):
         """The closure MSE + w_sym * reversed regulariser in ONE pass (x read once, Theta(x) shared by both terms).
-        Shapes as loss_grad / symreg_reversed.  Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mse, regulariser), grad =
-        d(mse + w_sym * regulariser)/dXi (S, d, p) [or (d, p)]."""
+        Shapes as loss_grad / symreg_reversed (jgx may be the compact table of a point-constant Jacobian, as there).
+        Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mse, regulariser), grad = d(mse + w_sym * regulariser)/dXi
+        (S, d, p) [or (d, p)]."""
         x, dx, gx, jgx = self._dev(x, "x"), self._dev(dx, "dx"), self._dev(gx, "gx"), self._dev(jgx, "jgx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
@@ -427,7 +459,8 @@ class HipEngine:
         n, d = x.shape[-2], x.shape[-1]
         n_g = gx.shape[1] if batched else gx.shape[0]
         want_g = (S, n_g, n, d) if batched else (n_g, n, d)
-        if n_g < 1 or tuple(gx.shape) != want_g or tuple(jgx.shape) != want_g + (d,):
+        constj = self._is_compact_jacobian(jgx, batched, S, n_g, d)
+        if n_g < 1 or tuple(gx.shape) != want_g or (not constj and tuple(jgx.shape) != want_g + (d,)):
             raise SymodeError(f"gx {tuple(gx.shape)} / jgx {tuple(jgx.shape)} do not match x {tuple(x.shape)}")
         xi = self._dev_or_pinned(xi, "xi")
         mask = None if mask is None else self._dev(mask, "mask")
@@ -444,10 +477,10 @@ class HipEngine:
         elif ws.numel() * 8 < self.lib.symode_workspace_bytes(d, order, flags, S, n):
             raise SymodeError("private workspace too small for this call")
         inv = 1.0 / (n * d) if inv_count is None else float(inv_count)
-        self._check(self.lib.symode_loss_grad_reversed(self._ptr(x), self._ptr(dx), self._ptr(gx), self._ptr(jgx), n_g, S, n, d, order,
-                                                       flags, self._ptr(xi), self._ptr(mask), inv, float(w_sym), self._ptr(loss2),
-                                                       self._ptr(grad), self._ptr(ws), ws.numel() * 8, self._stream(x)),
-                    "symode_loss_grad_reversed")
+        name = "symode_loss_grad_reversed_constj" if constj else "symode_loss_grad_reversed"
+        self._check(getattr(self.lib, name)(self._ptr(x), self._ptr(dx), self._ptr(gx), self._ptr(jgx), n_g, S, n, d, order,
+                                            flags, self._ptr(xi), self._ptr(mask), inv, float(w_sym), self._ptr(loss2),
+                                            self._ptr(grad), self._ptr(ws), ws.numel() * 8, self._stream(x)), name)
         if not batched:
             return loss2.reshape(2), grad.reshape(d, p)
         return loss2.reshape(S, 2), grad.reshape(S, d, p)

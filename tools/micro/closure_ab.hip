@@ -3,6 +3,8 @@
 // (8192 x 125 000 points), over launch widths and ring depths -- one process, so variants see the same box.  (The run
 // kept as profiles/r03_closure_ab.txt also held the two-chunk form the ring replaced: ring=0 there; the problem-walking
 // form of the closure measured in profiles/r03_closure_walk.txt lives in commit becc803 only.)
+// `closure_ab constj`: only the ring-depth A/B of the constant-Jacobian form of the fused closure (24 B/point) at the
+// bench's batched shape, beside the materialised form (40 B/point), three interleaved passes.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -I symmetry-ode-discovery_amd/csrc
 //              -o tools/micro/closure_ab tools/micro/closure_ab.hip
 #include <hip/hip_runtime.h>
@@ -10,6 +12,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "kernels.hpp"
@@ -159,6 +162,24 @@ int main(int argc, char** argv) {
     Finish fin2 = fin;
     fin2.n_loss = 2;
 
+    if (argc > 1 && strcmp(argv[1], "constj") == 0) {
+        // the compact table: the first 4 floats per problem of the (random) Jacobian buffer
+        printf("# fused closure, order 5, %ld problems x %ld points, grid.x = 2: us per launch (min of 3 rounds of 5), three passes\n", S, NB);
+#define CJRUN(LABEL, BPP, ...)                                                                                                   \
+    {                                                                                                                            \
+        const double us = time_us([&] { symreg_reversed_kernel<L5, true, __VA_ARGS__><<<dim3(2, (unsigned)S), dim3(BLOCK)>>>(     \
+                                            x, dx, gx, jgx, 1, NB, true, xi5, nullptr, 0.1f, part, fin2); }, 5);                 \
+        printf("pass %d  %-44s %8.1f us  %5.0f GB/s of its own %2.0f B/point\n", pass, LABEL, us, NT * BPP / us * 1e-3, BPP);     \
+    }
+        for (int pass = 0; pass < 3; ++pass) {
+            CJRUN("materialised J, ring 2", 40.0, 2, 32, false, 1)
+            CJRUN("constant J, ring 2, 3 waves/SIMD asked", 24.0, 2, 32, true, 3)
+            CJRUN("constant J, ring 3, 3 waves/SIMD asked", 24.0, 3, 32, true, 3)
+            CJRUN("constant J, ring 2, allocator left alone", 24.0, 2, 32, true, 1)
+        }
+        CK(hipDeviceSynchronize());
+        return 0;
+    }
     printf("# one problem, N = %ld points (d = 2)\n", N1);
     const int grids[] = {128, 256, 512, 768, 1024, 2048};
     for (int g : grids) {
