@@ -422,6 +422,36 @@ int symode_trainer_epoch_end(const symode_trainer* T, int epoch, void* stream);
  * log_test.  Problems that finished earlier cost empty launches only. */
 int symode_trainer_run(const symode_trainer* T, int epoch0, int n_epochs, int test_eval, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Device-resident minibatch Adam trainer: n_epochs whole epochs of train_SIGED's plain branch (no latent space, no symmetry
+ * regulariser) for n_problems independent problems in ONE launch, one workgroup per problem, nothing on the host inside.
+ * A step takes the rows idx[epoch, problem, step, :] of the shared (n_src, d) arrays x / dx -- an entry outside [0, n_src)
+ * is padding: it is not read and does not count in the batch's divisor, -1 is the canonical pad (a short last batch) --
+ * and does   loss = w_x * sum r^2 / (valid rows * d) + w_reg * |params|_1 (l1 != 0),  backward,  torch.optim.Adam.step
+ * (m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, t += 1, p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)).
+ * The parameters are Xi (q_eff NULL, n_params = d p) or [beta | const] with Xi = reshape(q_eff beta) + const in column 0
+ * (q_eff (d p, r), allow_constant, n_params = r + d: the conventions of symode_trainer); the L1 term is over the raw
+ * parameters whatever the mask says.  After every epoch e (global number epoch0 + e) with st_freq > 0 and
+ * (epoch + 1) % st_freq == 0:  mask &= |Xi| > threshold (strict, monotone).  A batch of padding alone is no step.  A
+ * problem whose batch loss is not finite stops there: the step that meets such a loss is not taken, the state stays as that
+ * step found it, and step[s] becomes -t - 1 (t = steps taken); such a problem is left alone by every later launch.  The
+ * loss is the only thing tested: a finite loss whose gradient or second moment overflows still takes its step and may
+ * write non-finite parameters, which the NEXT step's loss then reveals -- the frozen state is the one that step found.  Every sum runs in an order fixed by the
+ * row's position in the batch: two launches on the same inputs agree bit for bit, and so does a fit cut into launches.
+ *   idx     (n_epochs, n_idx_problems, n_steps, batch) int32; n_idx_problems = 1: all problems share the table
+ *   params, m, v (n_problems, n_params), step (n_problems) int32, mask (n_problems, d p): state, read and written back
+ *   xi_out  (n_problems, d p): Xi (unmasked) after the launch
+ *   log     (n_epochs, n_problems, 8): [mean batch MSE over the epoch's steps, mean |params|_1 (as the loss saw it), steps
+ *           taken, coefficients with mask set within near_band of the threshold at this epoch's event, 1 = frozen (NaN),
+ *           1 = thresholding event, epoch, 0]
+ * n_epochs == 0 or n_problems == 0: nothing to do.  n_params and d p are at most 256.
+ * replaces: train.py:491-547 (the per-minibatch loop of train_SIGED and its epoch end) plus torch.optim.Adam.step. */
+int symode_adam_epochs(const float* x, const float* dx, long n_src, const int* idx, long n_idx_problems, int n_epochs,
+                       int n_steps, int batch, long n_problems, int d, int order, int flags, const float* q_eff, int r,
+                       int allow_constant, int n_params, float lr, float beta1, float beta2, float eps, float w_x, float w_reg,
+                       int l1, float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
+                       int* step, float* mask, float* xi_out, float* log, void* stream);
+
 /* HOST function (no GPU work): least squares on the normal equations G = A^T A (n, n), C = A^T b (n, k), fp64
  * row-major host arrays; A had m_rows rows.  driver 0 = LAPACK gelsy semantics (pivoted QR rank rule with
  * rcond < 0 -> torch's default eps_fp32 * max(m_rows, n), minimum-norm solution), driver 1 = gels (full rank).

@@ -1,0 +1,304 @@
+// Device-resident minibatch Adam trainer (symode_adam_epochs): the plain branch of train_SIGED -- train.py:491-547 of the
+// reference, per minibatch MSELoss()(regressor(x), dx) + w_reg |params|_1, backward, torch.optim.Adam.step, and
+// set_threshold every st_freq epochs -- as ONE launch for n_epochs whole epochs of n_problems independent problems.
+#pragma once
+#include <cfloat>
+
+#include "kernels.hpp"
+
+namespace symode {
+
+constexpr int ADAM_BLOCK = 256;       // four wave64: thread j owns parameter j and coefficient j, row b of a batch goes to thread b % 256
+constexpr int ADAM_LOG = 8;           // floats per (epoch, problem) log row, see include/symode.h
+
+struct AdamArgs {
+    const float* x;
+    const float* dx;
+    long n_src;
+    const int* idx;                   // (n_epochs, n_idx_problems, n_steps, batch)
+    long n_idx_problems;
+    int n_epochs, n_steps, batch;
+    long n_problems;
+    const float* q;                   // (d p, r) row-major in Xi's order, or nullptr (the parameters are Xi)
+    int r, allow_const, n_params;
+    float lr, beta1, beta2, eps, w_x, w_reg;
+    int l1;
+    float threshold;
+    int st_freq, epoch0;
+    float near_band;
+    float *params, *m, *v;
+    int* step;
+    float *mask, *xi_out, *log;
+};
+
+// b^n for an integer n >= 0 by squaring: a function of (b, n) alone, so a fit cut into several launches meets the same
+// bias corrections bit for bit
+__device__ __forceinline__ double adam_ipow(double b, int n) {
+    double r = 1.0;
+    while (n > 0) {
+        if (n & 1) r *= b;
+        b *= b;
+        n >>= 1;
+    }
+    return r;
+}
+
+// One workgroup = one problem; everything between two minibatch steps stays on chip:
+//   w_s      Xi * mask, read (broadcast) by every row's residual
+//   part     the four waves' sums of the d p gradient entries, sum r^2 and the valid-row count
+// A step is: rows of the batch through the index table (entries outside [0, n_src) are padding: not read, not counted),
+// Theta(x) and the residual per row, per-thread accumulation over the thread's rows b = tid, tid + 256, ... in that order,
+// wave sums (permlane / DPP butterfly), the four wave partials added in wave order -- no atomics, the order of every sum is
+// fixed by (thread, row) -- then the parameter gradient, the Adam update of parameter j by thread j and, under the
+// constraint, Xi = reshape(Q beta) + const.  Two barriers per step (four under the constraint).
+// The gathers do not depend on the parameters, so they run ahead of the chain of steps: the index of chunk c + 2 and the
+// rows of chunk c + 1 are in flight while chunk c is evaluated, across step and epoch boundaries of the launch.
+template <class Lib>
+__global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs a) {
+    constexpr int D = Lib::D, P = Lib::P, DP = D * P, NV = DP + 2, NW = ADAM_BLOCK / WAVE, SLOTS = (NV + WAVE - 1) / WAVE;
+    static_assert(DP <= ADAM_BLOCK, "thread j owns coefficient j");
+    __shared__ float w_s[DP];
+    __shared__ float part[NW][NV];
+    __shared__ float gxi_s[DP];
+    __shared__ float par_s[ADAM_BLOCK];
+    __shared__ float l1_s[NW];
+    __shared__ int near_s[NW];
+
+    const long s = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
+    const int np = a.n_params, r = a.r;
+    const bool con = a.q != nullptr;
+
+    float p = 0.0f, m = 0.0f, v = 0.0f, mk = 0.0f, xi = 0.0f;
+    if (tid < np) {
+        p = a.params[s * np + tid];
+        m = a.m[s * np + tid];
+        v = a.v[s * np + tid];
+    }
+    if (tid < DP) mk = a.mask[s * DP + tid];
+    int t = a.step[s];                                        // < 0: frozen after a non-finite loss, at step -t - 1
+    bool frozen = t < 0;
+    if (frozen) t = -t - 1;
+
+    // Xi[tid] at the current parameters (sindy.py:169-176); the constrained form reads every parameter through par_s
+    auto coefficient = [&]() __attribute__((always_inline)) {
+        if (con) {
+            par_s[tid] = p;
+            __syncthreads();
+            if (tid < DP) {
+                float f = 0.0f;
+                for (int c = 0; c < r; ++c) f = fmaf(a.q[(long)tid * r + c], par_s[c], f);
+                if (a.allow_const && tid % P == 0) f += par_s[r + tid / P];
+                xi = f;
+            }
+        } else {
+            xi = p;
+        }
+        if (tid < DP) w_s[tid] = xi * mk;
+    };
+    coefficient();
+    __syncthreads();
+
+    const int n_chunks = (a.batch + ADAM_BLOCK - 1) / ADAM_BLOCK;
+    const long sp = a.n_idx_problems == 1 ? 0 : s;
+    struct Cursor { int e, s, k; };
+    auto advance = [&](Cursor& c) __attribute__((always_inline)) {
+        if (++c.k == n_chunks) {
+            c.k = 0;
+            if (++c.s == a.n_steps) {
+                c.s = 0;
+                ++c.e;
+            }
+        }
+    };
+    auto fetch_idx = [&](const Cursor& c) __attribute__((always_inline)) {
+        const int b = c.k * ADAM_BLOCK + tid;
+        int i = -1;
+        if (c.e < a.n_epochs && b < a.batch) i = a.idx[(((long)c.e * a.n_idx_problems + sp) * a.n_steps + c.s) * a.batch + b];
+        return i;
+    };
+    auto fetch_row = [&](int i, float (&xr)[D], float (&dr)[D]) __attribute__((always_inline)) {
+        const bool ok = i >= 0 && (long)i < a.n_src;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            float u = 0.0f, w = 0.0f;
+            if (ok) {
+                u = a.x[(long)i * D + c];
+                w = a.dx[(long)i * D + c];
+            }
+            xr[c] = u;
+            dr[c] = w;
+        }
+        return ok;
+    };
+
+    Cursor c{0, 0, 0}, c2{0, 0, 0};
+    float cx[D], cdx[D];
+    bool cok = fetch_row(fetch_idx(c2), cx, cdx);
+    advance(c2);
+    int nidx = fetch_idx(c2);
+    advance(c2);
+
+    float acc[DP], ss = 0.0f, cnt = 0.0f;
+#pragma unroll
+    for (int j = 0; j < DP; ++j) acc[j] = 0.0f;
+    double loss_sum = 0.0, l1_sum = 0.0;                      // the epoch's running sums (train.py:541-543), uniform over the block
+    int steps = 0;
+    const float om1 = (float)(1.0 - (double)a.beta1), om2 = (float)(1.0 - (double)a.beta2);
+
+    while (c.e < a.n_epochs) {
+        float nx[D], ndx[D];
+        const bool nok = fetch_row(nidx, nx, ndx);
+        const int nnidx = fetch_idx(c2);
+
+        if (cok && !frozen) {
+            float th[P];
+            Lib::eval(cx, th);
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                float f = 0.0f;
+#pragma unroll
+                for (int k = 0; k < P; ++k) f = fmaf(th[k], w_s[i * P + k], f);
+                const float res = f - cdx[i];
+                ss = fmaf(res, res, ss);
+#pragma unroll
+                for (int k = 0; k < P; ++k) acc[i * P + k] = fmaf(res, th[k], acc[i * P + k]);
+            }
+            cnt += 1.0f;
+        }
+
+        if (c.k == n_chunks - 1) {                            // the batch is complete: one optimiser step
+            float keep[SLOTS];
+#pragma unroll
+            for (int q = 0; q < SLOTS; ++q) keep[q] = 0.0f;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                const float tot = wave_sum_dpp(j < DP ? acc[j < DP ? j : 0] : (j == DP ? ss : cnt));
+                if (lane == (j & (WAVE - 1))) keep[j / WAVE] = tot;
+            }
+#pragma unroll
+            for (int q = 0; q < SLOTS; ++q)
+                if (q * WAVE + lane < NV) part[wave][q * WAVE + lane] = keep[q];
+            const float l1w = wave_sum_dpp(tid < np ? fabsf(p) : 0.0f);       // |params|_1 BEFORE the update, as the loss sees it
+            if (lane == 0) l1_s[wave] = l1w;
+            __syncthreads();
+
+            float ss_t = part[0][DP], cnt_t = part[0][DP + 1];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) {
+                ss_t += part[w][DP];
+                cnt_t += part[w][DP + 1];
+            }
+            const bool live = !frozen && cnt_t > 0.0f;       // a batch of padding alone is no step
+            const float loss = ss_t / (cnt_t * (float)D);
+            const bool bad = live && !(fabsf(loss) <= FLT_MAX);
+            if (bad) frozen = true;                           // NaN / inf: the problem keeps its state from here on
+            const bool upd = live && !bad;
+            const float scale = 2.0f / (cnt_t * (float)D);
+            float g_xi = 0.0f;
+            if (upd && tid < DP) {
+                float tot = part[0][tid];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) tot += part[w][tid];
+                g_xi = scale * tot * mk;                      // d mse / d Xi: the model reads Xi * mask
+            }
+            float g_data = g_xi;
+            if (con) {
+                if (tid < DP) gxi_s[tid] = g_xi;
+                __syncthreads();
+                g_data = 0.0f;
+                if (upd && tid < r) {
+                    for (int e = 0; e < DP; ++e) g_data = fmaf(a.q[(long)e * r + tid], gxi_s[e], g_data);
+                } else if (upd && tid < np && a.allow_const) {
+                    g_data = gxi_s[(tid - r) * P];            // column 0 of row tid - r
+                }
+            }
+            if (upd) {
+                ++t;
+                if (tid < np) {
+                    const float sgn = (float)(p > 0.0f) - (float)(p < 0.0f);
+                    const float g = a.l1 ? fmaf(a.w_reg, sgn, a.w_x * g_data) : a.w_x * g_data;
+                    m = fmaf(om1, g - m, m);
+                    v = fmaf(om2, g * g, a.beta2 * v);
+                    const double bc1 = 1.0 - adam_ipow((double)a.beta1, t), bc2 = 1.0 - adam_ipow((double)a.beta2, t);
+                    const float step_size = (float)((double)a.lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+                    p -= step_size * (m / (sqrtf(v) / bc2_sqrt + a.eps));
+                }
+                float l1_t = l1_s[0];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) l1_t += l1_s[w];
+                loss_sum += (double)loss;
+                l1_sum += (double)l1_t;
+                ++steps;
+                coefficient();
+            }
+#pragma unroll
+            for (int j = 0; j < DP; ++j) acc[j] = 0.0f;
+            ss = 0.0f;
+            cnt = 0.0f;
+            __syncthreads();
+
+            if (c.s == a.n_steps - 1) {                       // the epoch is complete (train.py:545-546, sindy.py:192-194)
+                const int epoch = a.epoch0 + c.e;
+                const bool ev = !frozen && a.st_freq > 0 && (epoch + 1) % a.st_freq == 0;
+                bool near = false;
+                if (ev && tid < DP) {
+                    const float av = fabsf(xi);
+                    near = fabsf(av - a.threshold) < a.near_band && mk > 0.0f;
+                    mk = (av > a.threshold && mk > 0.0f) ? 1.0f : 0.0f;       // strict >, monotone
+                    w_s[tid] = xi * mk;
+                }
+                const int near_w = __popcll(__ballot(near));
+                if (lane == 0) near_s[wave] = near_w;
+                __syncthreads();
+                if (tid == 0) {
+                    int near_t = 0;
+                    for (int w = 0; w < NW; ++w) near_t += near_s[w];
+                    float* rec = a.log + ((long)c.e * a.n_problems + s) * ADAM_LOG;
+                    rec[0] = (float)(loss_sum / (double)steps);               // 0 / 0 = NaN: an epoch without a step
+                    rec[1] = (float)(l1_sum / (double)steps);
+                    rec[2] = (float)steps;
+                    rec[3] = (float)near_t;
+                    rec[4] = frozen ? 1.0f : 0.0f;
+                    rec[5] = ev ? 1.0f : 0.0f;
+                    rec[6] = (float)epoch;
+                    rec[7] = 0.0f;
+                }
+                loss_sum = 0.0;
+                l1_sum = 0.0;
+                steps = 0;
+            }
+        }
+
+        cok = nok;
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            cx[i] = nx[i];
+            cdx[i] = ndx[i];
+        }
+        nidx = nnidx;
+        advance(c);
+        advance(c2);
+    }
+
+    if (tid < np) {
+        a.params[s * np + tid] = p;
+        a.m[s * np + tid] = m;
+        a.v[s * np + tid] = v;
+    }
+    if (tid < DP) {
+        a.mask[s * DP + tid] = mk;
+        a.xi_out[s * DP + tid] = xi;
+    }
+    if (tid == 0) a.step[s] = frozen ? -t - 1 : t;
+}
+
+template <class Lib>
+hipError_t launch_adam_epochs(const AdamArgs& a, hipStream_t st) {
+    if (a.n_problems == 0 || a.n_epochs == 0) return hipSuccess;
+    adam_epochs_kernel<Lib><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
+    SYMODE_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+}  // namespace symode

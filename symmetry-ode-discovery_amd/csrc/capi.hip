@@ -532,4 +532,29 @@ int symode_euler_jvp_vjp(const float* x, const float* v, const float* g_x, const
                                    (double*)workspace, gx, (hipStream_t)stream);
 }
 
+int symode_adam_epochs(const float* x, const float* dx, long n_src, const int* idx, long n_idx_problems, int n_epochs,
+                       int n_steps, int batch, long n_problems, int d, int order, int flags, const float* q_eff, int r,
+                       int allow_constant, int n_params, float lr, float beta1, float beta2, float eps, float w_x, float w_reg,
+                       int l1, float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
+                       int* step, float* mask, float* xi_out, float* log, void* stream) {
+    SYMODE_GET_OPS();
+    if (n_epochs < 0 || n_problems < 0) return SYMODE_E_BADSIZE;
+    if (n_epochs == 0 || n_problems == 0) return SYMODE_OK;
+    if (n_problems > 2147483647L || n_src < 1 || n_src > 2147483647L || n_steps < 1 || batch < 1 || epoch0 < 0)
+        return SYMODE_E_BADSIZE;
+    if (n_idx_problems != 1 && n_idx_problems != n_problems) return SYMODE_E_BADSIZE;
+    // thread j of the problem's workgroup owns parameter j: [beta | const] under the constraint, Xi without
+    if (q_eff ? (r < 1 || n_params != r + d) : (n_params != d * ops->p)) return SYMODE_E_BADSIZE;
+    if (n_params > ADAM_BLOCK || d * ops->p > ADAM_BLOCK) return SYMODE_E_BADSIZE;
+    if (!x || !dx || !idx || !params || !m || !v || !step || !mask || !xi_out || !log) return SYMODE_E_NULLPTR;
+    if (misaligned(x, 4) || misaligned(dx, 4) || misaligned(idx, 4) || misaligned(q_eff, 4) || misaligned(params, 4) ||
+        misaligned(m, 4) || misaligned(v, 4) || misaligned(step, 4) || misaligned(mask, 4) || misaligned(xi_out, 4) ||
+        misaligned(log, 4))
+        return SYMODE_E_ALIGN;
+    const AdamArgs a{x, dx, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, q_eff, q_eff ? r : 0,
+                     allow_constant != 0, n_params, lr, beta1, beta2, eps, w_x, w_reg, l1, threshold, st_freq, epoch0,
+                     near_band, params, m, v, step, mask, xi_out, log};
+    return (int)ops->adam_epochs(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

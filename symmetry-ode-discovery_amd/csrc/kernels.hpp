@@ -76,6 +76,8 @@ inline long min_grid_x() {
     return v < 1 ? 1 : v;
 }
 
+struct AdamArgs;      // adam.hpp
+
 // One row of the dispatch table: everything the C ABI needs for one (D, ORDER, FLAGS).
 struct LibOps {
     int d, order, flags, p;
@@ -122,6 +124,8 @@ struct LibOps {
     hipError_t (*symreg_reversed_constj)(const float* x, const float* dx, const float* gx_, const float* jgx, int n_g, long S,
                                          long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
                                          float* grad, double* ws, int gx, hipStream_t st);
+    // n_epochs epochs of minibatch Adam steps for S problems in one launch (adam.hpp)
+    hipError_t (*adam_epochs)(const AdamArgs& a, hipStream_t st);
 };
 
 // ---------------------------------------------------------------------------------------

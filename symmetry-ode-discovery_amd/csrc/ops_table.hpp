@@ -1,5 +1,6 @@
 // One translation unit per state dimension D instantiates every kernel for its libraries.
 #pragma once
+#include "adam.hpp"
 #include "gram.hpp"
 #include "gram_rev.hpp"
 #include "gram_valu.hpp"
@@ -33,7 +34,8 @@ constexpr LibOps make_ops() {
                   &launch_weak_gram<Lib>,
                   rev_gram_launcher<Lib>(),
                   &launch_rollout_error<Lib>,
-                  &launch_symreg_reversed<Lib, true>};
+                  &launch_symreg_reversed<Lib, true>,
+                  &launch_adam_epochs<Lib>};
 }
 
 #define SYMODE_OPS_ALL_FLAGS(D, O) make_ops<D, O, 0>(), make_ops<D, O, 1>(), make_ops<D, O, 2>(), make_ops<D, O, 3>()

@@ -47,6 +47,13 @@ class DeviceBatches:
     def __len__(self):
         return (self.n + self.bs - 1) // self.bs
 
+    def epoch_order(self):
+        """The permutation ``__iter__`` would draw for one epoch (the same single ``torch.randperm`` call, so the global
+        generator advances exactly as one pass over the loader does): batch k of that epoch is rows
+        ``order[k * batch_size:(k + 1) * batch_size]``."""
+        dev = self.arrays[0].device
+        return torch.randperm(self.n, device=dev) if self.shuffle else torch.arange(self.n, device=dev)
+
     def __iter__(self):
         dev = self.arrays[0].device
         order = torch.randperm(self.n, device=dev) if self.shuffle else torch.arange(self.n, device=dev)

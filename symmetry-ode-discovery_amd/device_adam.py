@@ -1,0 +1,109 @@
+"""Minibatch Adam fit of the SINDy coefficients with whole epochs per launch (symode_adam_epochs, csrc/adam.hpp): the plain
+branch of ``train.train_SIGED`` -- per minibatch ``w_x * mse + w_reg * |params|_1``, backward, ``torch.optim.Adam.step``, and
+``set_threshold`` every ``st_freq`` epochs -- for S independent problems (seeds) on ONE shared data set, one workgroup per
+problem, nothing on the host inside a launch.
+
+Covered: the observed-space fit, unconstrained or under the equivariance constraint (any ``CoefMap``), L1 regulariser.
+Not covered (the callers refuse them): the latent branch, the symmetry regularisers, several ranks.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .engine import get_engine, library_flags
+from .sindy import NEAR_THRESHOLD_BAND
+
+# Bytes of index table handed to one launch: an epoch's table is 4 bytes per (problem, row) -- 0.5 MB for one problem on the
+# 125 000-row sets, 32 MB for 64 seeds with their own shuffles -- and epochs_per_launch of them are stacked, next to the
+# int64 permutations they are cut from.  Beyond this bound a launch takes fewer epochs.
+TABLE_BYTES = 256 << 20
+
+LOG_COLUMNS = ('loss_sindy_x', 'loss_sindy_reg', 'steps', 'near', 'nan', 'event', 'epoch')
+
+
+class DeviceAdam:
+    def __init__(self, x, dx, poly_order, include_sine, include_exp, coef, lr, w_sindy_x, w_sindy_reg, threshold, st_freq,
+                 batch_size, betas=(0.9, 0.999), eps=1e-8, engine=None):
+        """x, dx (n, d) fp32 on the device, shared by all problems; ``coef``: the CoefMap of the parametrisation."""
+        self.engine = engine or get_engine()
+        self.x, self.dx = x.contiguous(), dx.contiguous()
+        self.n, self.d = self.x.shape
+        self.order, self.flags = int(poly_order), library_flags(include_sine, include_exp)
+        self.coef = coef.to(self.x.device)
+        if (self.coef.d, self.coef.p) != (self.d, self.engine.lib_size(self.d, self.order, self.flags)):
+            raise ValueError(f'coefficient map is ({self.coef.d}, {self.coef.p}), the library of the data is '
+                             f'({self.d}, {self.engine.lib_size(self.d, self.order, self.flags)})')
+        self.q_eff = None
+        if self.coef.Q is not None:
+            self.q_eff = torch.from_numpy(self.coef.effective_Q()).to(self.x.device).contiguous()
+        self.lr, self.w_x, self.w_reg = float(lr), float(w_sindy_x), float(w_sindy_reg)
+        self.threshold, self.st_freq = float(threshold), int(st_freq)
+        self.batch = int(batch_size)
+        if self.batch < 1:
+            raise ValueError(f'batch_size {batch_size} < 1')
+        self.steps = (self.n + self.batch - 1) // self.batch
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+
+    def table(self, order):
+        """One epoch's (S or 1, n) permutation cut into (S or 1, steps, batch) int32 row numbers, the short last batch
+        padded with -1 (which the kernel neither reads nor counts)."""
+        if order.dim() != 2 or order.shape[1] != self.n:
+            raise ValueError(f'an epoch order must be (S or 1, {self.n}), got {tuple(order.shape)}')
+        pad = self.steps * self.batch - self.n
+        t = order.to(torch.int32)
+        if pad:
+            t = torch.cat([t, torch.full((t.shape[0], pad), -1, dtype=torch.int32, device=t.device)], dim=1)
+        return t.view(t.shape[0], self.steps, self.batch)
+
+    def fit(self, params0, n_epochs, orders, mask0=None, on_epoch=None, epochs_per_launch=16, boundary=None, epoch0=0,
+            state=None):
+        """``params0`` (S, n_params); ``orders`` yields one (S or 1, n) integer permutation on the device per epoch, drawn
+        in epoch order.  ``on_epoch(epoch, record)`` is called for every epoch after its launch was read back, with that
+        epoch's own record: the LOG_COLUMNS as (S,) numpy arrays, and ``record['state']`` = {params, mask, Xi} (device
+        tensors, valid until the next launch) when the epoch is the last of its launch, else None.  ``boundary(epoch)``
+        true ends the launch after that epoch (a caller that needs the state there).  ``state``: (m, v, step) of an
+        earlier fit to continue.  Returns Xi, mask, params (device), log (n_epochs, S, 8) numpy, nan (S,) bool and m, v,
+        step."""
+        dev = self.x.device
+        params = params0.detach().to(dev, torch.float32).clone().contiguous()
+        S = params.shape[0]
+        if params.shape != (S, self.coef.n_params):
+            raise ValueError(f'params0 must be (S, {self.coef.n_params}), got {tuple(params0.shape)}')
+        mask = (torch.ones(S, self.d, self.coef.p, device=dev) if mask0 is None
+                else mask0.detach().to(dev, torch.float32).reshape(S, self.d, self.coef.p).clone().contiguous())
+        if state is None:
+            m, v, step = torch.zeros_like(params), torch.zeros_like(params), torch.zeros(S, dtype=torch.int32, device=dev)
+        else:
+            m, v, step = (t.detach().to(dev).clone().contiguous() for t in state)
+        xi = self.coef.xi(*self.coef.split(params)).reshape(S, self.d, self.coef.p) if n_epochs == 0 else None
+        orders = iter(orders)
+        logs = []
+        done = 0
+        while done < n_epochs:
+            tables = []
+            while done + len(tables) < n_epochs:
+                t = self.table(next(orders))
+                if t.shape[0] not in (1, S) or (tables and t.shape[0] != tables[0].shape[0]):
+                    raise ValueError(f'an epoch order must have 1 or {S} rows, all epochs alike; got {t.shape[0]}')
+                tables.append(t)
+                epoch = epoch0 + done + len(tables) - 1
+                full = len(tables) >= max(1, int(epochs_per_launch)) or (len(tables) + 1) * t.numel() * 4 > TABLE_BYTES
+                if full or (boundary is not None and boundary(epoch)):
+                    break
+            idx = torch.stack(tables).contiguous()
+            xi, log = self.engine.adam_epochs(self.x, self.dx, idx, params, m, v, step, mask, self.order, self.flags,
+                                              lr=self.lr, betas=self.betas, eps=self.eps, w_x=self.w_x, w_reg=self.w_reg,
+                                              l1=True, threshold=self.threshold, st_freq=self.st_freq, epoch0=epoch0 + done,
+                                              near_band=NEAR_THRESHOLD_BAND, q_eff=self.q_eff,
+                                              allow_constant=self.coef.allow_constant)
+            log = log.cpu().numpy()
+            logs.append(log)
+            if on_epoch is not None:
+                for k in range(len(tables)):
+                    rec = {name: log[k, :, c] for c, name in enumerate(LOG_COLUMNS)}
+                    rec['state'] = {'params': params, 'mask': mask, 'Xi': xi} if k == len(tables) - 1 else None
+                    on_epoch(epoch0 + done + k, rec)
+            done += len(tables)
+        log = np.concatenate(logs) if logs else np.zeros((0, S, 8), dtype=np.float32)
+        return {'Xi': xi, 'mask': mask, 'params': params, 'log': log, 'nan': step < 0, 'm': m, 'v': v, 'step': step}

@@ -92,6 +92,9 @@ _SIGNATURES = {
     "symode_trainer_update": (c_int, [c_void_p, c_int, c_void_p]),
     "symode_trainer_epoch_end": (c_int, [c_void_p, c_int, c_void_p]),
     "symode_trainer_run": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "symode_adam_epochs": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_long, c_int, c_int, c_int,
+                                   c_void_p, c_int, c_int, c_int] + [c_float] * 6 + [c_int, c_float, c_int, c_int, c_float]
+                           + [c_void_p] * 8),
     "symode_host_stlsq_sweep": (c_int, [c_void_p, c_int, c_int, c_int, c_long, ctypes.c_double, ctypes.c_double, c_int, c_int,
                                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
@@ -289,6 +292,59 @@ class HipEngine:
                                                   self._ptr(mean_err), self._ptr(horizon), self._stream(x_true)),
                     "symode_rollout_error")
         return err, mean_err, horizon
+
+    def adam_epochs(self, x, dx, idx, params, m, v, step, mask, order, flags=0, *, lr, betas=(0.9, 0.999), eps=1e-8, w_x=1.0,
+                    w_reg=0.0, l1=True, threshold=0.0, st_freq=0, epoch0=0, near_band=1e-4, q_eff=None, allow_constant=True):
+        """``idx.shape[0]`` whole epochs of minibatch Adam steps for S problems in ONE launch (symode_adam_epochs).
+        x, dx (n_src, d) fp32; idx (n_epochs, S or 1, n_steps, batch) int32 row numbers; params, m, v (S, n_params) fp32,
+        step (S,) int32 and mask (S, d, p) fp32 are the state, UPDATED IN PLACE (so they must be contiguous); q_eff
+        (d p, r) fp32 or None (the parameters are Xi).  ``idx`` is NOT range-checked here: the kernel treats every entry
+        outside [0, n_src) as padding -- not read, not counted in the batch's divisor (-1 is the canonical pad).
+        Returns (xi (S, d, p), log (n_epochs, S, 8)); log columns: mean batch MSE, mean |params|_1, steps taken,
+        near-threshold coefficients at the epoch's event, frozen-after-NaN flag, thresholding event, epoch, 0."""
+        x, dx = self._dev(x, "x"), self._dev(dx, "dx")
+        if x.dim() != 2 or dx.shape != x.shape:
+            raise SymodeError(f"x and dx must both be (n_src, d), got {tuple(x.shape)} and {tuple(dx.shape)}")
+        n_src, d = x.shape
+        p = self.lib_size(d, order, flags)
+        if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 4 or not idx.is_contiguous():
+            raise SymodeError("idx must be a contiguous (n_epochs, S or 1, n_steps, batch) int32 CUDA/HIP tensor")
+        for name, t in (("dx", dx), ("idx", idx), ("params", params), ("m", m), ("v", v), ("step", step), ("mask", mask), ("q_eff", q_eff)):
+            if isinstance(t, torch.Tensor) and t.device != x.device:
+                raise SymodeError(f"{name} is on {t.device}, x on {x.device}: all tensors of one launch live on one device")
+        state = {"params": params, "m": m, "v": v, "mask": mask}
+        for name, t in state.items():
+            if self._dev(t, name) is not t:
+                raise SymodeError(f"{name} is updated in place and must be contiguous")
+        if self._dev(step, "step", torch.int32) is not step:
+            raise SymodeError("step is updated in place and must be contiguous")
+        if params.dim() != 2 or m.shape != params.shape or v.shape != params.shape:
+            raise SymodeError(f"params, m, v must share one (S, n_params) shape, got {tuple(params.shape)}, {tuple(m.shape)}, {tuple(v.shape)}")
+        S, n_params = params.shape
+        if step.shape != (S,):
+            raise SymodeError(f"step must be ({S},), got {tuple(step.shape)}")
+        if mask.numel() != S * d * p:
+            raise SymodeError(f"mask has {mask.numel()} elements, expected {S}x{d}x{p}")
+        n_epochs, n_tab, n_steps, batch = idx.shape
+        if n_tab not in (1, S):
+            raise SymodeError(f"idx holds {n_tab} tables, expected 1 or {S}")
+        r = 0
+        if q_eff is not None:
+            q_eff = self._dev(q_eff, "q_eff")
+            if q_eff.dim() != 2 or q_eff.shape[0] != d * p:
+                raise SymodeError(f"q_eff must be ({d * p}, r), got {tuple(q_eff.shape)}")
+            r = q_eff.shape[1]
+        if n_params != (r + d if q_eff is not None else d * p):
+            raise SymodeError(f"params has {n_params} columns, expected {r + d if q_eff is not None else d * p}")
+        xi = torch.empty(S, d, p, dtype=torch.float32, device=x.device)
+        log = torch.empty(n_epochs, S, 8, dtype=torch.float32, device=x.device)
+        self._check(self.lib.symode_adam_epochs(
+            self._ptr(x), self._ptr(dx), n_src, self._ptr(idx), n_tab, n_epochs, n_steps, batch, S, d, order, flags,
+            self._ptr(q_eff), r, int(bool(allow_constant)), n_params, float(lr), float(betas[0]), float(betas[1]), float(eps),
+            float(w_x), float(w_reg), int(bool(l1)), float(threshold), int(st_freq), int(epoch0), float(near_band),
+            self._ptr(params), self._ptr(m), self._ptr(v), self._ptr(step), self._ptr(mask), self._ptr(xi), self._ptr(log),
+            self._stream(x)), "symode_adam_epochs")
+        return xi, log
 
     def _check_coef(self, xi, mask, d, order, flags, n_problems=1):
         p = self.lib_size(d, order, flags)

@@ -6,6 +6,7 @@
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m symode_amd.main_sweep \
         --config selkov/noise20_eq_sindy.cfg --n_seeds 64 --method stlsq          # BASELINE config 3: 8 x MI355X
     python -m symode_amd.main_sweep --config dosc/noise20_sindy.cfg --n_seeds 50 --eval_ltp --ltp_bound_rel 0.1
+    python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --batch_size 256 --num_epochs 1000 --n_seeds 64
 
 Every seed gets its own initial coefficients and its own ``--lbfgs_subsample`` draw of the data set
 (main.py:36-38).  ``--method lbfgs`` (default): all seeds are optimised in lockstep by sweep.SeedSweepLBFGS on
@@ -33,9 +34,18 @@ the horizon's error bound to R times the data's variance) and takes their held-o
 (evaluation.val_mse_sweep); ``ltp_mean_error`` (n_ics,), ``ltp_horizon`` (n_ics,) and ``val_mse`` join each seed's npz and
 the seeds are listed by median roll-out error.  Every rank holds the same final coefficients: no collective is added.
 
+``--sindy_optimizer adam`` (the parser's default optimiser) sweeps the minibatch Adam fit of train_SIGED's plain branch --
+no ``--use_latent``, ``w_sym_reg == 0``, with or without ``--eq_constraint`` -- on device_adam.DeviceAdam: one workgroup
+per seed runs whole epochs per launch (symode_adam_epochs).  Every epoch of every seed is a pass over the WHOLE data set in
+batches of ``--batch_size`` (``--lbfgs_subsample`` does not apply, as in main.py); seed s shuffles with its own device
+generator seeded with s (one ``torch.rand(n)`` per epoch, stable argsort), so a seed's fit depends on the seed alone, not on
+``--n_seeds`` or ``--seed``.  Adam with the latent branch or a symmetry regulariser is refused, and so is Adam on several
+ranks (one process per seed block is the way to use several GPUs there).
+
 A sweep's seed n does NOT reproduce ``python -m symode_amd.main --seed n`` row for row: the sweep draws each seed's
-subsample with the counter hash (seeded_subsamples) and its initial coefficients from its own torch.Generator(seed), as the
-plain sweep always has; the success rate over seeds is what the two estimate alike.
+subsample with the counter hash (seeded_subsamples) -- under Adam each seed's shuffles from its own generator, where main
+shuffles with the global one after drawing the model -- and its initial coefficients from its own torch.Generator(seed), as
+the plain sweep always has; the success rate over seeds is what the two estimate alike.
 """
 from __future__ import annotations
 
@@ -117,15 +127,24 @@ def _write_results(args, seeds, Xi, mask, truth, extra=None):
     return forms
 
 
-def _refusal(args):
-    """None when main_sweep covers the config, else why not and the per-seed command to run instead."""
+def _refusal(args, method='lbfgs'):
+    """None when main_sweep covers the config, else why not and the per-seed command to run instead.  ``--method stlsq`` is
+    accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules apply to the default method."""
     cfg = args.get('config')
     cmd = (f'python -m symode_amd.main --seed $i --config {cfg}' if cfg else 'python -m symode_amd.main --seed $i ...') + \
         ' for each seed (the per_seed loop of run_scripts/sweep.sh)'
-    if args['sindy_optimizer'] != 'lbfgs':
+    if method == 'stlsq' and args['sindy_optimizer'] != 'lbfgs':
         return f'main_sweep covers the L-BFGS fits (--sindy_optimizer lbfgs); run {cmd}'
+    if args['sindy_optimizer'] not in ('lbfgs', 'adam'):
+        return f'main_sweep covers the L-BFGS and Adam fits (--sindy_optimizer lbfgs | adam); run {cmd}'
     if args['use_latent']:
         return f'main_sweep does not cover latent fits (--use_latent); run {cmd}'
+    if args['sindy_optimizer'] == 'adam':
+        if args['w_sym_reg'] > 0:
+            return f'main_sweep covers Adam fits without a symmetry regulariser (w_sym_reg 0) only; run {cmd}'
+        if args.get('sindy_reg_type', 'l1') != 'l1':
+            return f"main_sweep covers Adam fits with --sindy_reg_type l1 only; run {cmd}"
+        return None
     if args['w_sym_reg'] > 0:
         if args['sym_reg_type'] != 'r':
             return (f"main_sweep covers the reversed symmetry regulariser only (--sym_reg_type r), not "
@@ -176,6 +195,39 @@ def symmetry_operands(x, rows, autoencoder, generator, chunk=PRECOMPUTE_CHUNK):
     return x_used, gx, jgx, table, used
 
 
+def _adam_sweep(args, seeds, template, coef, inits, x_all, dx_all, val_dataset, padded_truth, eval_ltp, ltp_bound_rel, dev,
+                engine):
+    """--sindy_optimizer adam: all seeds on DeviceAdam, every seed with its own shuffles of the whole data set."""
+    from .device_adam import DeviceAdam
+    n_all, n_seeds = x_all.shape[0], len(seeds)
+    trainer = DeviceAdam(x_all, dx_all, template.poly_order, template.include_sine, template.include_exp, coef, args['lr_sindy'],
+                         args['w_sindy_x'], args['w_sindy_reg'], args['threshold'], args['st_freq'], args['batch_size'],
+                         engine=engine)
+    gens = [torch.Generator(device=dev).manual_seed(s) for s in seeds]
+    keys = torch.empty(n_seeds, n_all, device=dev)
+
+    def orders():
+        for _ in range(args['num_epochs']):
+            for k, g in enumerate(gens):                            # row k is a function of seed k alone
+                torch.rand(n_all, generator=g, out=keys[k])
+            yield torch.argsort(keys, dim=1, stable=True)
+
+    out = trainer.fit(torch.stack(inits).to(dev), args['num_epochs'], orders())
+    scores = None
+    if eval_ltp:
+        scores = _score_on_validation(val_dataset, out['Xi'], out['mask'], (template.poly_order, template.include_sine, template.include_exp),
+                                      args['task'], ltp_bound_rel, dev, engine)
+    Xi, mask = out['Xi'].cpu().numpy(), out['mask'].cpu().numpy().astype(bool)
+    forms = _write_results(args, seeds, Xi, mask, padded_truth(mask.shape[-1], template), scores)
+    near = out['log'][:, :, 3].sum(axis=0) if len(out['log']) else np.zeros(n_seeds)
+    print(f'{n_seeds} seeds, {args["num_epochs"]} epochs x {trainer.steps} Adam steps of {trainer.batch} rows, '
+          f'NaN {int(out["nan"].sum())}, '
+          f'seeds with near-threshold coefficients {[seeds[i] for i in np.nonzero(near)[0].tolist()] or "none"}')
+    if eval_ltp:
+        _print_ltp_ranking(seeds, scores, forms)
+    return aggregate_results(args['save_dir'], min_seed=seeds[0], max_seed=seeds[-1] + 1)
+
+
 def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     """``engine`` / ``backend`` exist for the CPU rehearsal of the multi-rank path in tests (gloo + the test engine);
     ``one_gpu``: every rank uses cuda:0 (rehearsal of the HIP path with several ranks on a one-GPU box, gloo collectives)."""
@@ -187,11 +239,15 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     eval_ltp = _pop_flag(argv, '--eval_ltp')
     ltp_bound_rel = _pop(argv, '--ltp_bound_rel', None, float)
     args = vars(get_args(argv=argv))
-    why = _refusal(args)
+    why = _refusal(args, method)
     if why is not None:
         raise SystemExit(why)
     sym = args['w_sym_reg'] > 0
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
+    adam = args['sindy_optimizer'] == 'adam'                                # (--method stlsq was refused above)
+    if adam and world > 1:
+        raise SystemExit('main_sweep runs the Adam fits in one process (no collective over seeds): give every GPU its own '
+                         'block of seeds, python -m symode_amd.main_sweep --seed <first> --n_seeds <count> ... per process')
     if engine is None:
         if str(args['device']) == 'cpu':
             raise SystemExit('symode_amd runs the SINDy path on the GPU only (no CPU fallback): a HIP device is required')
@@ -265,8 +321,11 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
         args['L_list'] = [L[:rd, :rd].detach().cpu() for L in L_list]
     template = SINDyRegression(**args, **({'engine': engine} if engine is not None else {})).to(dev)
     coef = template.coef
-    all_rows = seeded_subsamples(n_all, m, seeds, dev)[:, lo:hi]
     inits = [coef.draw(torch.Generator().manual_seed(s)) for s in seeds]
+    if adam:
+        return _adam_sweep(args, seeds, template, coef, inits, x_all, dx_all, val_dataset, padded_truth, eval_ltp, ltp_bound_rel,
+                           dev, engine)
+    all_rows = seeded_subsamples(n_all, m, seeds, dev)[:, lo:hi]
     w_sym = args['w_sym_reg'] / args['w_sindy_x'] if sym else 0.0
     stats = None
     if sym:

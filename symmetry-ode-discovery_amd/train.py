@@ -1054,6 +1054,66 @@ def train_SIGED_lbfgs(
                  save_interval, save_dir, print_eq, shadow=shadow_dst)
 
 
+def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir, regressor,
+                          use_latent, lr_sindy, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg, st_freq, threshold,
+                          print_eq):
+    """train_SIGED's plain branch on DeviceAdam: the same shuffles (one ``randperm`` per epoch from the global generator, as
+    the loader draws them), prints, wandb records, test loss and checkpoints at the same epochs, produced from the
+    launch's log and from the state adopted into the regressor at those epochs and at the end."""
+    from .dataset import DeviceBatches
+    if use_latent:
+        raise ValueError('device_adam covers the observed-space fit only: use_latent is set')
+    if w_sym_reg != 0:
+        raise ValueError(f'device_adam covers fits without a symmetry regulariser: w_sym_reg is {w_sym_reg}, not 0')
+    if sindy_reg_type != 'l1':
+        raise ValueError(f"device_adam covers sindy_reg_type 'l1', not '{sindy_reg_type}'")
+    if not isinstance(train_loader, DeviceBatches):
+        raise ValueError(f'device_adam needs train_loader to be a DeviceBatches, got {type(train_loader).__name__}')
+    if train_loader.window != 0:
+        raise ValueError(f'device_adam needs single-row items: train_loader.window is {train_loader.window}, not 0')
+    x, dx = train_loader.arrays
+    if not (x.is_cuda and dx.is_cuda):
+        raise ValueError('device_adam needs the data set resident on the device (DeviceBatches kept it in host memory)')
+    from .device_adam import DeviceAdam
+    coef = regressor.coef
+    trainer = DeviceAdam(x, dx, regressor.poly_order, regressor.include_sine, regressor.include_exp, coef, lr_sindy, w_sindy_x,
+                         w_sindy_reg, threshold, st_freq, train_loader.bs, engine=regressor.engine)
+    last_mask = [regressor.mask.detach().clone()]
+
+    def at(epoch, every):
+        return (epoch + 1) % every == 0
+
+    def boundary(epoch):
+        return at(epoch, log_interval) or at(epoch, save_interval) or (st_freq > 0 and at(epoch, st_freq))
+
+    def on_epoch(epoch, rec):
+        wandb_log = {'loss_sindy_x': float(rec['loss_sindy_x'][0]), 'loss_sindy_z': 0.0,
+                     'loss_sindy_reg': float(rec['loss_sindy_reg'][0]), 'loss_sym_reg': 0.0}
+        state = rec['state']
+        if st_freq > 0 and at(epoch, st_freq) and not rec['nan'][0]:                   # train.py:545-546
+            regressor.note_near_threshold(state['Xi'][0], last_mask[0], threshold, 'set_threshold (device Adam)')
+            last_mask[0] = state['mask'][0].clone()
+        if at(epoch, log_interval) or at(epoch, save_interval):
+            coef.adopt(regressor, state['params'][0], state['mask'][0])
+        if at(epoch, log_interval):
+            print(', '.join([f'Epoch {epoch}'] + [f'{k}: {v:.4f}' for k, v in wandb_log.items()]))
+            with torch.no_grad():
+                tl = [regressor.mse_loss(xt.to(device), dxt.to(device)).item() for xt, dxt in test_loader]
+            if tl:
+                wandb_log['test_loss_sindy_x'] = float(np.mean(tl))
+                print(f"Epoch {epoch}, test_loss_sindy_x: {wandb_log['test_loss_sindy_x']:.4f}")
+            if print_eq:
+                regressor.print()
+        wandb.log(wandb_log)
+        if at(epoch, save_interval):
+            _save(regressor, save_dir, f'regressor_{epoch}.pt')
+
+    regressor.train()
+    out = trainer.fit(coef.pack(regressor)[None], num_epochs, (train_loader.epoch_order()[None] for _ in range(num_epochs)),
+                      mask0=regressor.mask[None], on_epoch=on_epoch, boundary=boundary)
+    coef.adopt(regressor, out['params'][0], out['mask'][0])
+
+
 def train_SIGED(
     train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir,  # global
     autoencoder, discriminator, generator,  # symmetry discovery model
@@ -1063,7 +1123,13 @@ def train_SIGED(
     int_t, int_dt,  # SINDy
     **kwargs
 ):
-    """Mini-batch Adam variant                                                       (train.py:382-614)."""
+    """Mini-batch Adam variant                                                       (train.py:382-614).
+    ``device_adam=True`` (--device_adam): the plain branch runs whole epochs per launch on the device (device_adam.py);
+    any other configuration is refused, not silently run the usual way."""
+    if kwargs.get('device_adam'):
+        return _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir,
+                                     regressor, use_latent, lr_sindy, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg,
+                                     st_freq, threshold, kwargs.get('print_eq'))
     optimizer_sindy = torch.optim.Adam(regressor.parameters(), lr=lr_sindy)
     symm_loss = make_symmreg_pttrain(autoencoder, generator)
     for epoch in range(num_epochs):
