@@ -146,7 +146,12 @@ int symode_symreg_linear(const float* z, long n, int d, int order, int flags, co
                          const float* L, int n_gen, float* loss_out, float* grad_out, void* workspace,
                          size_t workspace_bytes, void* stream);
 
-/* S4, reversed symmetry regulariser with (g(x), J_g(x)) precomputed once
+/* The five entries of the reversed symmetry closure (this one, _batched, symode_loss_grad_reversed and the two _constj
+ * forms) are ONE implementation behind five signatures: the same argument checks in the same order, one grid rule, one
+ * launcher.  They differ only in whether dx joins (the fused closure, which also keeps more workgroups on one large
+ * problem), whether jgx is the compact table (_constj), and in n_g = 0, which the materialised regulariser alone accepts.
+ *
+ * S4, reversed symmetry regulariser with (g(x), J_g(x)) precomputed once
  * (model_utils.py:126-170; g and J_g do not depend on xi, model_utils.py:172-211):
  *   loss = sum_g mean_{n,j} ( J_g(x_n) h(x_n) - h(g(x_n)) )^2,  h = Theta(.)(xi*mask)^T,
  *   grad (d, p) = dloss/dxi (masked).  gx: (n_g, n, d), jgx: (n_g, n, d, d). */

@@ -118,6 +118,46 @@ size_t workspace_doubles(const LibOps* ops, long S, long n) {
     return (size_t)WS_HEADER_DOUBLES + (a > b ? a : b);      // [magic + tickets | partial rows]
 }
 
+#define SYMODE_GET_OPS()                              \
+    const LibOps* ops = find_ops(d, order, flags);    \
+    if (!ops) return SYMODE_E_UNSUPPORTED;
+
+#define SYMODE_CHECK_WS(S_, n_)                                                              \
+    if (!workspace || misaligned(workspace, 8)) return SYMODE_E_WORKSPACE;                   \
+    if (workspace_bytes < workspace_doubles(ops, (S_), (n_)) * sizeof(double)) return SYMODE_E_WORKSPACE;
+
+// The reversed-symmetry closure: the one path from its five C entries to LibOps::symreg_reversed.
+//   fused   MSE + w_sym * regulariser on (x, dx), loss (S, 2); else the regulariser alone, loss (S) (dx, w_sym unused)
+//   constj  jgx is the compact (S, n_g, d, d) table of a point-constant Jacobian (symode_jacobian_constant), not the
+//           materialised (S, n_g, n, d, d) tensor: the same grids and workspace, the same partial rows summed in the same order
+// The forms differ in the three places marked (1)-(3), and nowhere else.
+int reversed_closure(bool fused, bool constj, const float* x, const float* dx, const float* gx_, const float* jgx, int n_g,
+                     long n_problems, long n, int d, int order, int flags, const float* xi, const float* mask, float inv_count,
+                     float w_sym, float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
+    SYMODE_GET_OPS();
+    // (1) no group element at all (the regulariser is 0) is a call only the materialised regulariser accepts
+    const int min_n_g = (fused || constj) ? 1 : 0;
+    if (n < 1 || n_g < min_n_g || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
+    if (!x || (fused && !dx) || !xi || !loss_out || !grad_out || (n_g > 0 && (!gx_ || !jgx))) return SYMODE_E_NULLPTR;
+    if (!fused) dx = nullptr;                               // (the launcher takes "dx given" for "fused")
+    if (misaligned(x, 4) || misaligned(dx, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
+        misaligned(loss_out, 4) || misaligned(grad_out, 4))
+        return SYMODE_E_ALIGN;
+    SYMODE_CHECK_WS(n_problems, n);
+    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
+    if (n_problems == 1) {
+        int cap = small_grid_cap(n, true);
+        // (2) the regulariser alone, 32 B/point: the small libraries stream best from ONE workgroup per CU like the other
+        //  reductions -- order 3 at 2^26 points 314 us = 0.855 of HBM on 256 workgroups against 338 on 512; order 4-5 want the
+        //  second one: 340 against 374 us.  The fused closure (40 B/point) keeps the cap of small_grid_cap.
+        if (!fused && cap > 256 && ops->d * ops->p <= 24 && knobs().small_grid < 0) cap = 256;
+        if (cap > 0 && gx > cap) gx = cap;
+    }
+    // (3) without dx there is no second term to weigh the regulariser against: its weight is 1
+    return (int)ops->symreg_reversed(x, dx, gx_, jgx, constj, n_g, n_problems, n, xi, mask, inv_count, fused ? w_sym : 1.0f,
+                                     loss_out, grad_out, (double*)workspace, gx, (hipStream_t)stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -158,14 +198,6 @@ int symode_workspace_init(void* workspace, size_t workspace_bytes, void* stream)
         (unsigned long long*)workspace, words);
     return (int)hipGetLastError();
 }
-
-#define SYMODE_GET_OPS()                              \
-    const LibOps* ops = find_ops(d, order, flags);    \
-    if (!ops) return SYMODE_E_UNSUPPORTED;
-
-#define SYMODE_CHECK_WS(S_, n_)                                                              \
-    if (!workspace || misaligned(workspace, 8)) return SYMODE_E_WORKSPACE;                   \
-    if (workspace_bytes < workspace_doubles(ops, (S_), (n_)) * sizeof(double)) return SYMODE_E_WORKSPACE;
 
 int symode_theta(const float* x, long n, int d, int order, int flags, float* theta_out, void* stream) {
     SYMODE_GET_OPS();
@@ -281,88 +313,36 @@ int symode_symreg_linear(const float* z, long n, int d, int order, int flags, co
                                    (hipStream_t)stream);
 }
 
+// The five entries of the reversed-symmetry closure are forwards to reversed_closure() above: batched or not, with or
+// without dx, jgx materialised or the compact (S, n_g, d, d) table (_constj).
 int symode_symreg_reversed_batched(const float* x, const float* gx_, const float* jgx, int n_g, long n_problems, long n, int d,
                                    int order, int flags, const float* xi, const float* mask, float inv_count,
                                    float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
-    SYMODE_GET_OPS();
-    if (n < 1 || n_g < 0 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
-    if (!x || !xi || !loss_out || !grad_out || (n_g > 0 && (!gx_ || !jgx))) return SYMODE_E_NULLPTR;
-    if (misaligned(x, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
-        misaligned(loss_out, 4) || misaligned(grad_out, 4))
-        return SYMODE_E_ALIGN;
-    SYMODE_CHECK_WS(n_problems, n);
-    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
-    if (n_problems == 1) {
-        // (32 B/point: the small libraries stream best from ONE workgroup per CU like the other reductions -- order 3 at 2^26
-        //  points 314 us = 0.855 of HBM on 256 workgroups against 338 on 512; order 4-5 want the second one: 340 against 374 us)
-        int cap = small_grid_cap(n, true);
-        if (cap > 256 && ops->d * ops->p <= 24 && knobs().small_grid < 0) cap = 256;
-        if (cap > 0 && gx > cap) gx = cap;
-    }
-    return (int)ops->symreg_reversed(x, nullptr, gx_, jgx, n_g, n_problems, n, xi, mask, inv_count, 1.0f, loss_out, grad_out,
-                                     (double*)workspace, gx, (hipStream_t)stream);
+    return reversed_closure(false, false, x, nullptr, gx_, jgx, n_g, n_problems, n, d, order, flags, xi, mask, inv_count, 1.0f,
+                            loss_out, grad_out, workspace, workspace_bytes, stream);
 }
 
 int symode_loss_grad_reversed(const float* x, const float* dx, const float* gx_, const float* jgx, int n_g, long n_problems, long n,
                               int d, int order, int flags, const float* xi, const float* mask, float inv_count, float w_sym,
                               float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
-    SYMODE_GET_OPS();
-    if (n < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
-    if (!x || !dx || !xi || !loss2_out || !grad_out || !gx_ || !jgx) return SYMODE_E_NULLPTR;
-    if (misaligned(x, 4) || misaligned(dx, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
-        misaligned(loss2_out, 4) || misaligned(grad_out, 4))
-        return SYMODE_E_ALIGN;
-    SYMODE_CHECK_WS(n_problems, n);
-    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
-    if (n_problems == 1) {
-        const int cap = small_grid_cap(n, true);
-        if (cap > 0 && gx > cap) gx = cap;
-    }
-    return (int)ops->symreg_reversed(x, dx, gx_, jgx, n_g, n_problems, n, xi, mask, inv_count, w_sym, loss2_out, grad_out,
-                                     (double*)workspace, gx, (hipStream_t)stream);
+    return reversed_closure(true, false, x, dx, gx_, jgx, n_g, n_problems, n, d, order, flags, xi, mask, inv_count, w_sym,
+                            loss2_out, grad_out, workspace, workspace_bytes, stream);
 }
 
-// The two closures on a point-constant Jacobian: jgx is the compact (S, n_g, d, d) table (symode_jacobian_constant).
-// Grids and workspace as in their materialised counterparts: the same partial rows, summed in the same order.
 int symode_symreg_reversed_batched_constj(const float* x, const float* gx_, const float* jgx, int n_g, long n_problems, long n,
                                           int d, int order, int flags, const float* xi, const float* mask, float inv_count,
                                           float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes,
                                           void* stream) {
-    SYMODE_GET_OPS();
-    if (n < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
-    if (!x || !xi || !loss_out || !grad_out || !gx_ || !jgx) return SYMODE_E_NULLPTR;
-    if (misaligned(x, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
-        misaligned(loss_out, 4) || misaligned(grad_out, 4))
-        return SYMODE_E_ALIGN;
-    SYMODE_CHECK_WS(n_problems, n);
-    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
-    if (n_problems == 1) {                                  // (as symode_symreg_reversed_batched)
-        int cap = small_grid_cap(n, true);
-        if (cap > 256 && ops->d * ops->p <= 24 && knobs().small_grid < 0) cap = 256;
-        if (cap > 0 && gx > cap) gx = cap;
-    }
-    return (int)ops->symreg_reversed_constj(x, nullptr, gx_, jgx, n_g, n_problems, n, xi, mask, inv_count, 1.0f, loss_out,
-                                            grad_out, (double*)workspace, gx, (hipStream_t)stream);
+    return reversed_closure(false, true, x, nullptr, gx_, jgx, n_g, n_problems, n, d, order, flags, xi, mask, inv_count, 1.0f,
+                            loss_out, grad_out, workspace, workspace_bytes, stream);
 }
 
 int symode_loss_grad_reversed_constj(const float* x, const float* dx, const float* gx_, const float* jgx, int n_g, long n_problems,
                                      long n, int d, int order, int flags, const float* xi, const float* mask, float inv_count,
                                      float w_sym, float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-    SYMODE_GET_OPS();
-    if (n < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
-    if (!x || !dx || !xi || !loss2_out || !grad_out || !gx_ || !jgx) return SYMODE_E_NULLPTR;
-    if (misaligned(x, 4) || misaligned(dx, 4) || misaligned(gx_, 4) || misaligned(jgx, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
-        misaligned(loss2_out, 4) || misaligned(grad_out, 4))
-        return SYMODE_E_ALIGN;
-    SYMODE_CHECK_WS(n_problems, n);
-    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
-    if (n_problems == 1) {
-        const int cap = small_grid_cap(n, true);
-        if (cap > 0 && gx > cap) gx = cap;
-    }
-    return (int)ops->symreg_reversed_constj(x, dx, gx_, jgx, n_g, n_problems, n, xi, mask, inv_count, w_sym, loss2_out, grad_out,
-                                            (double*)workspace, gx, (hipStream_t)stream);
+    return reversed_closure(true, true, x, dx, gx_, jgx, n_g, n_problems, n, d, order, flags, xi, mask, inv_count, w_sym,
+                            loss2_out, grad_out, workspace, workspace_bytes, stream);
 }
 
 int symode_jacobian_constant(const float* jgx, int n_g, long n_problems, long n, int d, float* table_out, int* flag_out,
@@ -427,8 +407,8 @@ int symode_symreg_reversed(const float* x, const float* gx_, const float* jgx, i
                            int flags, const float* xi, const float* mask, float* loss_out, float* grad_out,
                            void* workspace, size_t workspace_bytes, void* stream) {
     if (n < 1 || d < 1) return SYMODE_E_BADSIZE;
-    return symode_symreg_reversed_batched(x, gx_, jgx, n_g, 1, n, d, order, flags, xi, mask, 1.0f / ((float)n * (float)d),
-                                          loss_out, grad_out, workspace, workspace_bytes, stream);
+    return reversed_closure(false, false, x, nullptr, gx_, jgx, n_g, 1, n, d, order, flags, xi, mask, 1.0f / ((float)n * (float)d),
+                            1.0f, loss_out, grad_out, workspace, workspace_bytes, stream);
 }
 
 int symode_weak_gram(const float* x, long n_t, int d, int order, int flags, const float* V, const float* V_drv, int n_test,

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "library.hpp"
 #include "points.hpp"
@@ -92,9 +93,10 @@ struct LibOps {
     hipError_t (*symreg_linear)(const float* z, long n, const float* xi, const float* mask, const float* L, int n_gen,
                                 float* loss, float* grad, double* ws, int gx, hipStream_t st);
     // dx == nullptr: the regulariser alone (loss (S)); else the fused closure MSE + w_sym * regulariser (loss (S, 2))
-    hipError_t (*symreg_reversed)(const float* x, const float* dx, const float* gx_, const float* jgx, int n_g, long S, long n,
-                                  const float* xi, const float* mask, float inv_count, float w_sym, float* loss, float* grad,
-                                  double* ws, int gx, hipStream_t st);
+    // constj: the Jacobian is constant over the points of a (problem, group element) and jgx its (S, n_g, d, d) table
+    hipError_t (*symreg_reversed)(const float* x, const float* dx, const float* gx_, const float* jgx, bool constj, int n_g, long S,
+                                  long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
+                                  float* grad, double* ws, int gx, hipStream_t st);
     hipError_t (*aug_gram)(const float* x, const float* dx, long S, long n, const int* idx, double* gram, double* ws,
                            int gx_mfma, int gx_valu, int gx_m4, hipStream_t st);
     hipError_t (*vjp)(const float* x, const float* g, long n, const float* xi, const float* mask, float* grad_x,
@@ -120,10 +122,6 @@ struct LibOps {
     // roll-out error of S models on n_ics truth trajectories (n_ics, n_steps + 1, d) in one launch (rollout.hpp)
     hipError_t (*rollout_error)(const float* x_true, long n_ics, long S, const float* xi, const float* mask, int n_steps,
                                 float dt, int method, float bound, float* err, double* mean_err, int* horizon, hipStream_t st);
-    // symreg_reversed with a Jacobian that is constant over the points of a (problem, group element): jgx (S, n_g, d, d)
-    hipError_t (*symreg_reversed_constj)(const float* x, const float* dx, const float* gx_, const float* jgx, int n_g, long S,
-                                         long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
-                                         float* grad, double* ws, int gx, hipStream_t st);
     // n_epochs epochs of minibatch Adam steps for S problems in one launch (adam.hpp)
     hipError_t (*adam_epochs)(const AdamArgs& a, hipStream_t st);
 };
@@ -1695,11 +1693,11 @@ hipError_t launch_symreg_linear(const float* z, long n, const float* xi, const f
     return launch_finalize(fin, part, 1, gx, NACC, st);
 }
 
-// CJ: jgx is the compact (S, n_g, D, D) table of a point-constant Jacobian (see symreg_reversed_kernel)
-template <class Lib, bool CJ = false>
-hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* gxp, const float* jgx, int n_g, long S, long n,
-                                  const float* xi, const float* mask, float inv_count, float w_sym, float* loss, float* grad,
-                                  double* ws, int gx, hipStream_t st) {
+// constj: jgx is the compact (S, n_g, D, D) table of a point-constant Jacobian (the CJ kernels, see symreg_reversed_kernel)
+template <class Lib>
+hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* gxp, const float* jgx, bool constj, int n_g, long S,
+                                  long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
+                                  float* grad, double* ws, int gx, hipStream_t st) {
     constexpr int D = Lib::D;
     const bool mse = dx != nullptr;
     const int nacc = (mse ? 2 : 1) + D * Lib::P;
@@ -1709,15 +1707,23 @@ hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* 
     // 16-byte vectors need every slab (problem, group element) to start on a 16-byte boundary
     // (the compact table of the CJ form is read by scalar loads: it takes no part in this)
     const bool multi = S > 1 || n_g > 1;
-    const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)gxp % 16 == 0) && (CJ || (uintptr_t)jgx % 16 == 0) &&
-                     (!mse || (uintptr_t)dx % 16 == 0) && (!multi || ((n * D) % 4 == 0 && (CJ || (n * D * D) % 4 == 0)));
-    constexpr int MINW = (CJ && D == 2 && !Lib::SINE && !Lib::EXP) ? 3 : 1;
-    if (mse)
-        symreg_reversed_kernel<Lib, true, 2, 32, CJ, MINW><<<dim3(gx, (unsigned)S), dim3(BLOCK), 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi,
-                                                                                                        mask, w_sym, part, fin);
+    const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)gxp % 16 == 0) && (constj || (uintptr_t)jgx % 16 == 0) &&
+                     (!mse || (uintptr_t)dx % 16 == 0) && (!multi || ((n * D) % 4 == 0 && (constj || (n * D * D) % 4 == 0)));
+    const dim3 grid(gx, (unsigned)S), block(BLOCK);
+    const auto launch = [&](auto cj) {                  // the kernel family: CJ as a compile-time constant
+        constexpr bool CJ = decltype(cj)::value;
+        constexpr int MINW = (CJ && D == 2 && !Lib::SINE && !Lib::EXP) ? 3 : 1;
+        if (mse)
+            symreg_reversed_kernel<Lib, true, 2, 32, CJ, MINW><<<grid, block, 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi, mask, w_sym,
+                                                                                     part, fin);
+        else
+            symreg_reversed_kernel<Lib, false, 2, 32, CJ, MINW><<<grid, block, 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec, xi, mask,
+                                                                                      1.0f, part, fin);
+    };
+    if (constj)
+        launch(std::true_type{});
     else
-        symreg_reversed_kernel<Lib, false, 2, 32, CJ, MINW><<<dim3(gx, (unsigned)S), dim3(BLOCK), 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec,
-                                                                                                         xi, mask, 1.0f, part, fin);
+        launch(std::false_type{});
     SYMODE_LAUNCH_CHECK();
     return launch_finalize(fin, part, S, gx, nacc, st);
 }

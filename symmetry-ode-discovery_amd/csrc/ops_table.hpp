@@ -34,7 +34,6 @@ constexpr LibOps make_ops() {
                   &launch_weak_gram<Lib>,
                   rev_gram_launcher<Lib>(),
                   &launch_rollout_error<Lib>,
-                  &launch_symreg_reversed<Lib, true>,
                   &launch_adam_epochs<Lib>};
 }
 

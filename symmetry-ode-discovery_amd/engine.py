@@ -228,9 +228,7 @@ class HipEngine:
         x = self._dev(x, "x")
         d = x.shape[-1]
         n = x.numel() // d
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        self._check_coef(xi, mask, d, order, flags)
+        xi, mask, _ = self._coef(xi, mask, d, order, flags)
         out = torch.empty_like(x)
         self._check(self.lib.symode_forward(self._ptr(x), n, d, order, flags, self._ptr(xi), self._ptr(mask),
                                             self._ptr(out), self._stream(x)), "symode_forward")
@@ -240,12 +238,8 @@ class HipEngine:
         x = self._dev(x, "x")
         d = x.shape[-1]
         n = x.numel() // d
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        self._check_coef(xi, mask, d, order, flags)
-        m = {"euler": 0, "rk4": 1}.get(method)
-        if m is None:
-            raise ValueError("Unrecognized ODEInt method.")
+        xi, mask, _ = self._coef(xi, mask, d, order, flags)
+        m = self._method_code(method)
         out = torch.empty_like(x)
         self._check(self.lib.symode_odeint(self._ptr(x), n, d, order, flags, self._ptr(xi), self._ptr(mask), int(n_steps),
                                            float(dt), m, self._ptr(out), self._stream(x)), "symode_odeint")
@@ -256,12 +250,8 @@ class HipEngine:
         x = self._dev(x, "x")
         d = x.shape[-1]
         n = x.numel() // d
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        self._check_coef(xi, mask, d, order, flags)
-        m = {"euler": 0, "rk4": 1}.get(method)
-        if m is None:
-            raise ValueError("Unrecognized ODEInt method.")
+        xi, mask, _ = self._coef(xi, mask, d, order, flags)
+        m = self._method_code(method)
         traj = torch.empty(int(n_steps), n, d, dtype=torch.float32, device=x.device)
         self._check(self.lib.symode_odeint_traj(self._ptr(x), n, d, order, flags, self._ptr(xi), self._ptr(mask), int(n_steps),
                                                 float(dt), m, self._ptr(traj), self._stream(x)), "symode_odeint_traj")
@@ -276,13 +266,9 @@ class HipEngine:
         if x_true.dim() != 3:
             raise SymodeError(f"x_true must be (n_ics, n_steps + 1, d), got {tuple(x_true.shape)}")
         n_ics, n_points, d = x_true.shape
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        S = xi.shape[0] if xi.dim() == 3 else 1
-        self._check_coef(xi, mask, d, order, flags, S)
-        m = {"euler": 0, "rk4": 1}.get(method)
-        if m is None:
-            raise ValueError("Unrecognized ODEInt method.")
+        S = xi.shape[0] if isinstance(xi, torch.Tensor) and xi.dim() == 3 else 1
+        xi, mask, _ = self._coef(xi, mask, d, order, flags, S)
+        m = self._method_code(method)
         n_steps = n_points - 1
         err = torch.empty(S, n_ics, max(n_steps, 0), dtype=torch.float32, device=x_true.device) if want_error else None
         mean_err = torch.empty(S, n_ics, dtype=torch.float64, device=x_true.device)
@@ -355,36 +341,91 @@ class HipEngine:
             raise SymodeError(f"mask has {mask.numel()} elements, expected {n_problems}x{d}x{p}")
         return p
 
+    def _coef(self, xi, mask, d, order, flags, n_problems=1, pinned_ok=False):
+        """The coefficient operands of every entry point: (xi, mask or None, p), fp32 and contiguous, sizes checked
+        against the library.  ``pinned_ok``: xi may be a pinned host tensor (the closures' zero-copy form)."""
+        xi = self._dev_or_pinned(xi, "xi") if pinned_ok else self._dev(xi, "xi")
+        mask = None if mask is None else self._dev(mask, "mask")
+        return xi, mask, self._check_coef(xi, mask, d, order, flags, n_problems)
+
+    @staticmethod
+    def _method_code(method):
+        m = {"euler": 0, "rk4": 1}.get(method)
+        if m is None:
+            raise ValueError("Unrecognized ODEInt method.")
+        return m
+
+    # -- the closures: loss_grad, symreg_reversed, loss_grad_reversed and bind_closure share everything below ----------
+    @staticmethod
+    def _problems(x):
+        """(batched, S, n, d) of x (S, N, d) or (N, d)."""
+        batched = x.dim() == 3
+        return batched, x.shape[0] if batched else 1, x.shape[-2], x.shape[-1]
+
+    def _reversed_operands(self, x, gx, jgx, min_n_g=1, compact_ok=False):
+        """(g(x), J_g(x)) checked against x: (gx, jgx, n_g, constj).  ``constj``: jgx is the compact table of a
+        point-constant Jacobian, (S, n_g, d, d) [one problem: (n_g, d, d)] -- the number of dimensions decides (the
+        materialised form has one more, the point axis); recognised only with ``compact_ok``."""
+        gx, jgx = self._dev(gx, "gx"), self._dev(jgx, "jgx")
+        batched, S, n, d = self._problems(x)
+        n_g = gx.shape[1] if batched else gx.shape[0]
+        want_g = (S, n_g, n, d) if batched else (n_g, n, d)
+        constj = compact_ok and n_g >= 1 and tuple(jgx.shape) == want_g[:-2] + (d, d)
+        if n_g < min_n_g or tuple(gx.shape) != want_g or (not constj and tuple(jgx.shape) != want_g + (d,)):
+            raise SymodeError(f"gx {tuple(gx.shape)} / jgx {tuple(jgx.shape)} do not match x {tuple(x.shape)}")
+        return gx, jgx, n_g, constj
+
+    def _closure_prologue(self, x, S, n, d, p, order, flags, n_loss, out, ws, inv_count):
+        """Outputs (allocated, or the caller's ``out`` checked), scratch (the engine's, or a private ``ws`` checked) and
+        the 1/count factor of a closure call: (loss, grad, ws, inv)."""
+        if out is None:
+            loss = torch.empty((S, n_loss) if n_loss > 1 else S, dtype=torch.float32, device=x.device)
+            grad = torch.empty(S, d, p, dtype=torch.float32, device=x.device)
+        else:
+            loss, grad = (self._dev_or_pinned(o, "out") for o in out)
+            if loss.numel() != n_loss * S or grad.numel() != S * d * p:
+                raise SymodeError(f"out buffers hold {loss.numel()} / {grad.numel()} elements, expected {n_loss * S} / {S * d * p}")
+        if ws is None:
+            ws = self.workspace(x.device, d, order, flags, S, n)
+        elif ws.numel() * 8 < self.lib.symode_workspace_bytes(d, order, flags, S, n):
+            raise SymodeError("private workspace too small for this call")
+        return loss, grad, ws, 1.0 / (n * d) if inv_count is None else float(inv_count)
+
+    def _closure_call(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, stream):
+        """One closure launch, ready to go: (entry name, its argument tuple, the tensors the arguments point into, what
+        the caller gets back).  ``dx`` None: the regulariser alone; ``rev`` None: the MSE alone, else what
+        _reversed_operands returned.  The ONE statement of the closures' C signatures: the eager methods call
+        ``getattr(lib, name)(*args)``, bind_closure converts ``args`` once and keeps the call."""
+        batched, S, n, d = self._problems(x)
+        xi, mask, p = self._coef(xi, mask, d, order, flags, S, pinned_ok=True)
+        fused = dx is not None and rev is not None
+        loss, grad, ws, inv = self._closure_prologue(x, S, n, d, p, order, flags, 2 if fused else 1, out, ws, inv_count)
+        head = (self._ptr(x),) if dx is None else (self._ptr(x), self._ptr(dx))
+        keep = (x, dx, xi, mask, loss, grad, ws)
+        name = "symode_loss_grad"
+        if rev is not None:
+            gx, jgx, n_g, constj = rev
+            head += (self._ptr(gx), self._ptr(jgx), n_g)
+            keep += (gx, jgx)
+            name = ("symode_loss_grad_reversed" if fused else "symode_symreg_reversed_batched") + ("_constj" if constj else "")
+        args = head + (S, n, d, order, flags, self._ptr(xi), self._ptr(mask), inv) + ((float(w_sym),) if fused else ()) \
+            + (self._ptr(loss), self._ptr(grad), self._ptr(ws), ws.numel() * 8, stream)
+        # the outputs in the caller's form: the batch axis is there only if x had one
+        loss, grad = loss.reshape(S, 2) if fused else loss.reshape(S), grad.reshape(S, d, p)
+        return name, args, keep, (loss, grad) if batched else (loss[0], grad[0])
+
+    def _closure(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws):
+        name, args, _, result = self._closure_call(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, self._stream(x))
+        self._check(getattr(self.lib, name)(*args), name)
+        return result
+
     def loss_grad(self, x, dx, xi, mask, order, flags=0, inv_count=None, out=None, ws=None):
         """x, dx: (S, N, d) or (N, d); xi, mask: (S, d, p) or (d, p).  Returns (loss (S,), grad (S, d, p)).
         ``xi`` and ``out`` may be pinned host tensors (zero-copy); ``ws`` a private workspace from new_workspace()."""
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
-        batched = x.dim() == 3
-        S = x.shape[0] if batched else 1
-        n, d = x.shape[-2], x.shape[-1]
-        xi = self._dev_or_pinned(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        p = self._check_coef(xi, mask, d, order, flags, S)
-        if out is None:
-            loss = torch.empty(S, dtype=torch.float32, device=x.device)
-            grad = torch.empty(S, d, p, dtype=torch.float32, device=x.device)
-        else:
-            loss, grad = (self._dev_or_pinned(o, "out") for o in out)
-            if loss.numel() != S or grad.numel() != S * d * p:
-                raise SymodeError(f"out buffers hold {loss.numel()} / {grad.numel()} elements, expected {S} / {S * d * p}")
-        if ws is None:
-            ws = self.workspace(x.device, d, order, flags, S, n)
-        elif ws.numel() * 8 < self.lib.symode_workspace_bytes(d, order, flags, S, n):
-            raise SymodeError("private workspace too small for this call")
-        inv = 1.0 / (n * d) if inv_count is None else float(inv_count)
-        self._check(self.lib.symode_loss_grad(self._ptr(x), self._ptr(dx), S, n, d, order, flags, self._ptr(xi),
-                                              self._ptr(mask), inv, self._ptr(loss), self._ptr(grad), self._ptr(ws),
-                                              ws.numel() * 8, self._stream(x)), "symode_loss_grad")
-        if not batched:
-            return loss[0], grad[0]
-        return loss, grad
+        return self._closure(x, dx, None, xi, mask, order, flags, None, inv_count, out, ws)
 
     def aug_gram(self, x, dx, order, flags=0):
         """fp64 augmented Gram [Theta | dx]^T [Theta | dx]: (S, p+d, p+d) or (p+d, p+d)."""
@@ -428,9 +469,7 @@ class HipEngine:
     def symreg_linear(self, z, xi, mask, L, order, flags=0):
         z = self._dev(z, "z")
         n, d = z.shape[-2], z.shape[-1]
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        p = self._check_coef(xi, mask, d, order, flags)
+        xi, mask, p = self._coef(xi, mask, d, order, flags)
         L = self._dev(L, "L").reshape(-1, d, d)
         loss = torch.empty(1, dtype=torch.float32, device=z.device)
         grad = torch.empty(d, p, dtype=torch.float32, device=z.device)
@@ -447,43 +486,9 @@ class HipEngine:
         ``xi`` / ``out`` may be pinned host tensors for the one-problem form; ``inv_count`` as in loss_grad.
         A point-constant Jacobian may be given as its compact table, jgx (n_g, d, d) / (S, n_g, d, d) (``jacobian_constant``):
         the shape alone selects the kernel form that streams nothing of J_g; the results are bit-identical."""
-        x, gx, jgx = self._dev(x, "x"), self._dev(gx, "gx"), self._dev(jgx, "jgx")
-        batched = x.dim() == 3
-        S = x.shape[0] if batched else 1
-        n, d = x.shape[-2], x.shape[-1]
-        n_g = gx.shape[1] if batched else gx.shape[0]
-        want_g = (S, n_g, n, d) if batched else (n_g, n, d)
-        constj = self._is_compact_jacobian(jgx, batched, S, n_g, d)
-        if tuple(gx.shape) != want_g or (not constj and tuple(jgx.shape) != want_g + (d,)):
-            raise SymodeError(f"gx {tuple(gx.shape)} / jgx {tuple(jgx.shape)} do not match x {tuple(x.shape)}")
-        xi = self._dev_or_pinned(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        p = self._check_coef(xi, mask, d, order, flags, S)
-        if out is None:
-            loss = torch.empty(S, dtype=torch.float32, device=x.device)
-            grad = torch.empty(S, d, p, dtype=torch.float32, device=x.device)
-        else:
-            loss, grad = (self._dev_or_pinned(o, "out") for o in out)
-            if loss.numel() != S or grad.numel() != S * d * p:
-                raise SymodeError(f"out buffers hold {loss.numel()} / {grad.numel()} elements, expected {S} / {S * d * p}")
-        if ws is None:
-            ws = self.workspace(x.device, d, order, flags, S, n)
-        elif ws.numel() * 8 < self.lib.symode_workspace_bytes(d, order, flags, S, n):
-            raise SymodeError("private workspace too small for this call")
-        inv = 1.0 / (n * d) if inv_count is None else float(inv_count)
-        name = "symode_symreg_reversed_batched_constj" if constj else "symode_symreg_reversed_batched"
-        self._check(getattr(self.lib, name)(self._ptr(x), self._ptr(gx), self._ptr(jgx), n_g, S, n, d, order,
-                                            flags, self._ptr(xi), self._ptr(mask), inv, self._ptr(loss),
-                                            self._ptr(grad), self._ptr(ws), ws.numel() * 8, self._stream(x)), name)
-        if not batched:
-            return loss.reshape(-1)[0], grad.reshape(d, p)
-        return loss, grad
-
-    @staticmethod
-    def _is_compact_jacobian(jgx, batched, S, n_g, d):
-        """jgx given as the (S, n_g, d, d) [one problem: (n_g, d, d)] table of a point-constant Jacobian?  The number of
-        dimensions decides (the materialised form has one more, the point axis)."""
-        return n_g >= 1 and tuple(jgx.shape) == ((S, n_g, d, d) if batched else (n_g, d, d))
+        x = self._dev(x, "x")
+        rev = self._reversed_operands(x, gx, jgx, min_n_g=0, compact_ok=True)
+        return self._closure(x, None, rev, xi, mask, order, flags, None, inv_count, out, ws)
 
     def jacobian_constant(self, jgx):
         """Is J_g the same matrix at every point of each (problem, group element)?  jgx (S, n_g, N, d, d) or (n_g, N, d, d)
@@ -507,52 +512,19 @@ class HipEngine:
         Shapes as loss_grad / symreg_reversed (jgx may be the compact table of a point-constant Jacobian, as there).
         Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mse, regulariser), grad = d(mse + w_sym * regulariser)/dXi
         (S, d, p) [or (d, p)]."""
-        x, dx, gx, jgx = self._dev(x, "x"), self._dev(dx, "dx"), self._dev(gx, "gx"), self._dev(jgx, "jgx")
+        x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
-        batched = x.dim() == 3
-        S = x.shape[0] if batched else 1
-        n, d = x.shape[-2], x.shape[-1]
-        n_g = gx.shape[1] if batched else gx.shape[0]
-        want_g = (S, n_g, n, d) if batched else (n_g, n, d)
-        constj = self._is_compact_jacobian(jgx, batched, S, n_g, d)
-        if n_g < 1 or tuple(gx.shape) != want_g or (not constj and tuple(jgx.shape) != want_g + (d,)):
-            raise SymodeError(f"gx {tuple(gx.shape)} / jgx {tuple(jgx.shape)} do not match x {tuple(x.shape)}")
-        xi = self._dev_or_pinned(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        p = self._check_coef(xi, mask, d, order, flags, S)
-        if out is None:
-            loss2 = torch.empty(S, 2, dtype=torch.float32, device=x.device)
-            grad = torch.empty(S, d, p, dtype=torch.float32, device=x.device)
-        else:
-            loss2, grad = (self._dev_or_pinned(o, "out") for o in out)
-            if loss2.numel() != 2 * S or grad.numel() != S * d * p:
-                raise SymodeError(f"out buffers hold {loss2.numel()} / {grad.numel()} elements, expected {2 * S} / {S * d * p}")
-        if ws is None:
-            ws = self.workspace(x.device, d, order, flags, S, n)
-        elif ws.numel() * 8 < self.lib.symode_workspace_bytes(d, order, flags, S, n):
-            raise SymodeError("private workspace too small for this call")
-        inv = 1.0 / (n * d) if inv_count is None else float(inv_count)
-        name = "symode_loss_grad_reversed_constj" if constj else "symode_loss_grad_reversed"
-        self._check(getattr(self.lib, name)(self._ptr(x), self._ptr(dx), self._ptr(gx), self._ptr(jgx), n_g, S, n, d, order,
-                                            flags, self._ptr(xi), self._ptr(mask), inv, float(w_sym), self._ptr(loss2),
-                                            self._ptr(grad), self._ptr(ws), ws.numel() * 8, self._stream(x)), name)
-        if not batched:
-            return loss2.reshape(2), grad.reshape(d, p)
-        return loss2.reshape(S, 2), grad.reshape(S, d, p)
+        rev = self._reversed_operands(x, gx, jgx, compact_ok=True)
+        return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws)
 
     def symreg_reversed_gram(self, x, gx, jgx, order, flags=0):
         """fp64 Gram matrix R of the reversed regulariser (raw sums over points and group elements, no 1/(N d)):
         x (N, d), gx (n_g, N, d), jgx (n_g, N, d, d) -> (d p, d p); or x (S, N, d), gx (S, n_g, N, d), jgx (S, n_g, N, d, d)
         -> (S, d p, d p).  Rows / columns in Xi's (d, p) row-major order: the regulariser is v^T R v / (N d), v = vec(Xi * M)."""
-        x, gx, jgx = self._dev(x, "x"), self._dev(gx, "gx"), self._dev(jgx, "jgx")
-        batched = x.dim() == 3
-        S = x.shape[0] if batched else 1
-        n, d = x.shape[-2], x.shape[-1]
-        n_g = gx.shape[1] if batched else gx.shape[0]
-        want_g = (S, n_g, n, d) if batched else (n_g, n, d)
-        if n_g < 1 or tuple(gx.shape) != want_g or tuple(jgx.shape) != want_g + (d,):
-            raise SymodeError(f"gx {tuple(gx.shape)} / jgx {tuple(jgx.shape)} do not match x {tuple(x.shape)}")
+        x = self._dev(x, "x")
+        gx, jgx, n_g, _ = self._reversed_operands(x, gx, jgx)
+        batched, S, n, d = self._problems(x)
         p = self.lib_size(d, order, flags)
         need = self.lib.symode_symreg_reversed_gram_workspace_bytes(d, order, flags, n_g, S, n)
         if need == 0:
@@ -627,37 +599,19 @@ class HipEngine:
     def bind_closure(self, x, dx, xi, mask, order, flags, out, ws, stream, reversed_sym=None, w_sym=1.0):
         """A zero-argument callable that launches the single-problem closure on fixed buffers: every check and every
         ctypes conversion is done once, here (a latency-bound caller -- one L-BFGS closure is 8 us of GPU time -- pays
-        ~15 us of Python per call otherwise).  ``out`` = (loss, grad) [(loss2, grad) with ``reversed_sym = (gx, jgx)``];
-        ``xi`` / ``out`` may be pinned host tensors; ``stream`` a torch stream.  The callable keeps the tensors alive."""
+        ~15 us of Python per call otherwise).  ``out`` = (loss, grad) [(loss2, grad) with ``reversed_sym = (gx, jgx)``,
+        materialised]; ``xi`` / ``out`` may be pinned host tensors; ``stream`` a torch stream.  The callable keeps the
+        tensors alive."""
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
-        n, d = x.shape[-2], x.shape[-1]
-        xi = self._dev_or_pinned(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        p = self._check_coef(xi, mask, d, order, flags, 1)
-        loss, grad = (self._dev_or_pinned(o, "out") for o in out)
-        if grad.numel() != d * p or loss.numel() != (2 if reversed_sym is not None else 1):
-            raise SymodeError("out buffers do not match the closure's outputs")
-        if ws.numel() * 8 < self.lib.symode_workspace_bytes(d, order, flags, 1, n):
-            raise SymodeError("private workspace too small for this call")
-        keep = (x, dx, xi, mask, loss, grad, ws, stream)
-        st = c_void_p(stream.cuda_stream)
-        inv = c_float(1.0 / (n * d))
-        if reversed_sym is None:
-            fn = self.lib.symode_loss_grad
-            args = (self._ptr(x), self._ptr(dx), c_long(1), c_long(n), c_int(d), c_int(order), c_int(flags), self._ptr(xi),
-                    self._ptr(mask), inv, self._ptr(loss), self._ptr(grad), self._ptr(ws), c_size_t(ws.numel() * 8), st)
-        else:
-            gx, jgx = self._dev(reversed_sym[0], "gx"), self._dev(reversed_sym[1], "jgx")
-            n_g = gx.shape[0]
-            if tuple(gx.shape) != (n_g, n, d) or tuple(jgx.shape) != (n_g, n, d, d) or n_g < 1:
-                raise SymodeError("gx / jgx do not match x")
-            keep += (gx, jgx)
-            fn = self.lib.symode_loss_grad_reversed
-            args = (self._ptr(x), self._ptr(dx), self._ptr(gx), self._ptr(jgx), c_int(n_g), c_long(1), c_long(n), c_int(d),
-                    c_int(order), c_int(flags), self._ptr(xi), self._ptr(mask), inv, c_float(float(w_sym)), self._ptr(loss),
-                    self._ptr(grad), self._ptr(ws), c_size_t(ws.numel() * 8), st)
+        if x.dim() != 2 or out is None or ws is None:
+            raise SymodeError("a bound closure is one problem, x (N, d), on the caller's out buffers and private workspace")
+        rev = None if reversed_sym is None else self._reversed_operands(x, *reversed_sym)
+        name, args, keep, _ = self._closure_call(x, dx, rev, xi, mask, order, flags, w_sym, None, out, ws,
+                                                 c_void_p(stream.cuda_stream))
+        fn = getattr(self.lib, name)
+        args = tuple(a if isinstance(a, t) else t(a) for t, a in zip(fn.argtypes, args))
 
-        def launch(_fn=fn, _args=args, _keep=keep):
+        def launch(_fn=fn, _args=args, _keep=keep + (stream,)):
             rc = _fn(*_args)
             if rc != 0:
                 self._check(rc, "bound closure")
@@ -684,9 +638,7 @@ class HipEngine:
         """Reverse mode of forward: returns (grad_x (N, d) or None, grad_xi (d, p))."""
         x, g = self._dev(x, "x"), self._dev(g, "g")
         n, d = x.shape[-2], x.shape[-1]
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        p = self._check_coef(xi, mask, d, order, flags)
+        xi, mask, p = self._coef(xi, mask, d, order, flags)
         gx = torch.empty_like(x) if need_grad_x else None
         gxi = torch.empty(d, p, dtype=torch.float32, device=x.device)
         ws = self.workspace(x.device, d, order, flags, 1, n)
@@ -700,9 +652,7 @@ class HipEngine:
         x, v = self._dev(x, "x"), self._dev(v, "v")
         d = x.shape[-1]
         n = x.numel() // d
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        self._check_coef(xi, mask, d, order, flags)
+        xi, mask, _ = self._coef(xi, mask, d, order, flags)
         out = torch.empty_like(x) if need_out else None
         jv = torch.empty_like(x)
         self._check(self.lib.symode_forward_jvp(self._ptr(x), self._ptr(v), n, d, order, flags, self._ptr(xi),
@@ -717,9 +667,7 @@ class HipEngine:
         g_out = None if g_out is None else self._dev(g_out, "g_out")
         d = x.shape[-1]
         n = x.numel() // d
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        p = self._check_coef(xi, mask, d, order, flags)
+        xi, mask, p = self._coef(xi, mask, d, order, flags)
         gx, gv = torch.empty_like(x), torch.empty_like(x)
         gxi = torch.empty(d, p, dtype=torch.float32, device=x.device)
         ws = self.workspace(x.device, d, order, flags, 1, n)
@@ -759,9 +707,7 @@ class HipEngine:
         x, v = self._dev(x, "x"), self._dev(v, "v")
         d = x.shape[-1]
         n = x.numel() // d
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        self._check_coef(xi, mask, d, order, flags)
+        xi, mask, _ = self._coef(xi, mask, d, order, flags)
         xo, to = torch.empty_like(x), torch.empty_like(x)
         self._check(self.lib.symode_euler_jvp(self._ptr(x), self._ptr(v), n, d, order, flags, self._ptr(xi), self._ptr(mask),
                                               int(n_steps), float(dt), self._ptr(xo), self._ptr(to), self._stream(x)),
@@ -773,9 +719,7 @@ class HipEngine:
         x, v, g_x, g_t = (self._dev(a, nm) for a, nm in ((x, "x"), (v, "v"), (g_x, "g_x"), (g_t, "g_t")))
         d = x.shape[-1]
         n = x.numel() // d
-        xi = self._dev(xi, "xi")
-        mask = None if mask is None else self._dev(mask, "mask")
-        p = self._check_coef(xi, mask, d, order, flags)
+        xi, mask, p = self._coef(xi, mask, d, order, flags)
         gx, gv = torch.empty_like(x), torch.empty_like(x)
         gxi = torch.empty(d, p, dtype=torch.float32, device=x.device)
         ws = self.workspace(x.device, d, order, flags, 1, n)

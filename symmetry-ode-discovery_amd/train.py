@@ -334,14 +334,22 @@ class _HostShadow:
     def _kw(self):
         return {'ws': self.ws} if self.ws is not None else {}
 
-    def _launch_zero_copy(self):
+    def _launch(self, xi, out):
+        """The closure's kernels on coefficients ``xi``, [loss | grad] of every term into ``out``: the pinned host pair
+        (zero-copy) or the device pair of the copy path."""
         reg, (d, p), n = self.reg, self.mask.shape, self.n_out
-        reg.engine.loss_grad(self.x, self.dx, self.h_xi, reg.mask, reg.poly_order, reg.flags,
-                             out=(self.h_out[:1], self.h_out[1:n].view(d, p)), **self._kw())
+        reg.engine.loss_grad(self.x, self.dx, xi, reg.mask, reg.poly_order, reg.flags,
+                             out=(out[:1], out[1:n].view(d, p)), **self._kw())
         if self.reversed_sym is not None:
             gx, jgx = self.reversed_sym
-            reg.engine.symreg_reversed(self.x, gx, jgx, self.h_xi, reg.mask, reg.poly_order, reg.flags,
-                                       out=(self.h_out[n:n + 1], self.h_out[n + 1:].view(d, p)), **self._kw())
+            reg.engine.symreg_reversed(self.x, gx, jgx, xi, reg.mask, reg.poly_order, reg.flags,
+                                       out=(out[n:n + 1], out[n + 1:].view(d, p)), **self._kw())
+
+    def _launch_copy(self):
+        """Upload coefficients, the fused kernels, download [loss | grad]: everything between the two host buffers."""
+        self.d_xi.copy_(self.h_xi, non_blocking=True)
+        self._launch(self.d_xi, self.d_out)
+        self.h_out.copy_(self.d_out, non_blocking=True)
 
     def evaluate_fused(self, w_ratio):
         """Reversed-regulariser closure as ONE launch (symode_loss_grad_reversed): returns (Xi, mse, sym, d(mse + w_ratio sym)/dXi)
@@ -361,27 +369,15 @@ class _HostShadow:
     def _zero_copy_works(self):
         try:
             self.h_xi.copy_(self.get_Xi().detach())
-            self._launch()
+            self._launch_copy()
             torch.cuda.synchronize(self.x.device)
             want = self.h_out.clone()
             self.h_out.fill_(float('nan'))
-            self._launch_zero_copy()
+            self._launch(self.h_xi, self.h_out)
             torch.cuda.synchronize(self.x.device)
             return bool(torch.equal(want, self.h_out))
         except Exception:                               # pragma: no cover - depends on the runtime
             return False
-
-    def _launch(self):
-        """Upload coefficients, the fused kernels, download [loss | grad]: everything between the two host buffers."""
-        reg, (d, p), n = self.reg, self.mask.shape, self.n_out
-        self.d_xi.copy_(self.h_xi, non_blocking=True)
-        reg.engine.loss_grad(self.x, self.dx, self.d_xi, reg.mask, reg.poly_order, reg.flags,
-                             out=(self.d_out[:1], self.d_out[1:n].view(d, p)), **self._kw())
-        if self.reversed_sym is not None:
-            gx, jgx = self.reversed_sym
-            reg.engine.symreg_reversed(self.x, gx, jgx, self.d_xi, reg.mask, reg.poly_order, reg.flags,
-                                       out=(self.d_out[n:n + 1], self.d_out[n + 1:].view(d, p)), **self._kw())
-        self.h_out.copy_(self.d_out, non_blocking=True)
 
     def _capture(self):
         """Copy path: the closure's device work is launch-bound (a ~6 us kernel between two tiny copies): capture it once
@@ -392,12 +388,12 @@ class _HostShadow:
             side.wait_stream(torch.cuda.current_stream(self.x.device))
             with torch.cuda.stream(side):
                 for _ in range(2):
-                    self._launch()                      # warm-up: lazy inits
+                    self._launch_copy()                 # warm-up: lazy inits
             torch.cuda.current_stream(self.x.device).wait_stream(side)
             torch.cuda.synchronize(self.x.device)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._launch()
+                self._launch_copy()
             self._graph = g
         except Exception:                               # pragma: no cover - depends on the runtime
             self._graph = None
@@ -434,11 +430,11 @@ class _HostShadow:
             self._stream.synchronize()
         else:
             if self.zero_copy:
-                self._launch_zero_copy()
+                self._launch(self.h_xi, self.h_out)
             elif self._graph is not None:
                 self._graph.replay()
             else:
-                self._launch()
+                self._launch_copy()
             torch.cuda.current_stream(self.x.device).synchronize()
         vals = [self.h_out[k * n].clone() for k in range(len(self.h_out) // n)]
         grads = [self.h_out[k * n + 1:(k + 1) * n].view(d, p).clone() for k in range(len(self.h_out) // n)]

@@ -524,6 +524,66 @@ def test_zero_copy_closure_matches_copy_path(eng):
     assert torch.equal(vals[0], vals2[0]) and torch.equal(grads[0], grads2[0])
 
 
+@pytest.fixture(scope="module")
+def bound_case(eng):
+    """d = 2, order 3, 1001 points, a mask with a few zeros, pinned xi / out buffers, a private workspace."""
+    torch.manual_seed(7)
+    n, d, order, n_g = 1001, 2, 3, 2
+    p = eng.lib_size(d, order, 0)
+    x, dx = (torch.randn(n, d) * 0.5).cuda(), torch.randn(n, d).cuda()
+    gx = (x[None] + 0.05 * torch.randn(n_g, n, d).cuda()).contiguous()
+    jgx = (torch.eye(d) + 0.05 * torch.randn(n_g, n, d, d)).cuda()
+    xi = (torch.randn(d, p) * 0.3).pin_memory()
+    mask = torch.ones(d, p)
+    mask[0, 3] = mask[1, 0] = mask[1, 7] = 0.0
+    ws = eng.new_workspace(x.device, eng.lib.symode_workspace_bytes(d, order, 0, 1, n))
+    return dict(n=n, d=d, p=p, order=order, x=x, dx=dx, gx=gx, jgx=jgx, xi=xi, mask=mask.cuda(), ws=ws,
+                stream=torch.cuda.current_stream(x.device))
+
+
+def _pinned_out(n_loss, d, p):
+    buf = torch.full((n_loss + d * p,), float("nan")).pin_memory()
+    return buf, (buf[:n_loss], buf[n_loss:].view(d, p))
+
+
+@pytest.mark.parametrize("fused", [False, True])
+def test_bound_closure_is_the_eager_call_bit_for_bit(eng, bound_case, fused):
+    """bind_closure launches the same entry with the same arguments as loss_grad / loss_grad_reversed on the same
+    buffers (same kernel, same grid: bit-deterministic reductions), and does so again on a second call."""
+    c = bound_case
+    d, p, n_loss = c["d"], c["p"], 2 if fused else 1
+    want_buf, want_out = _pinned_out(n_loss, d, p)
+    if fused:
+        eng.loss_grad_reversed(c["x"], c["dx"], c["gx"], c["jgx"], c["xi"], c["mask"], c["order"], 0, w_sym=0.3,
+                               out=want_out, ws=c["ws"])
+    else:
+        eng.loss_grad(c["x"], c["dx"], c["xi"], c["mask"], c["order"], 0, out=want_out, ws=c["ws"])
+    c["stream"].synchronize()
+    assert torch.isfinite(want_buf).all()
+    got_buf, got_out = _pinned_out(n_loss, d, p)
+    bound = eng.bind_closure(c["x"], c["dx"], c["xi"], c["mask"], c["order"], 0, got_out, c["ws"], c["stream"],
+                             reversed_sym=(c["gx"], c["jgx"]) if fused else None, w_sym=0.3)
+    bound()
+    c["stream"].synchronize()
+    assert torch.equal(got_buf, want_buf)
+    first = got_buf.clone()
+    got_buf.fill_(float("nan"))
+    bound()
+    c["stream"].synchronize()
+    assert torch.equal(got_buf, first)
+
+
+@pytest.mark.parametrize("fused", [False, True])
+def test_bound_closure_refuses_mismatched_out(eng, bound_case, fused):
+    from symode_amd.engine import SymodeError
+    c = bound_case
+    d, p, n_loss = c["d"], c["p"], 2 if fused else 1
+    rev = (c["gx"], c["jgx"]) if fused else None
+    for out in (_pinned_out(n_loss + 1, d, p)[1], _pinned_out(n_loss, d, p - 1)[1]):
+        with pytest.raises(SymodeError):
+            eng.bind_closure(c["x"], c["dx"], c["xi"], c["mask"], c["order"], 0, out, c["ws"], c["stream"], reversed_sym=rev)
+
+
 # ------------------------------------------------------------- batched reversed symmetry regulariser
 @pytest.mark.parametrize("S,n,n_g,d,order,fl", [c for c in [(1, 20000, 1, 2, 2, 2), (3, 4096, 2, 2, 3, 0), (2, 1001, 1, 2, 5, 0), (1, 777, 3, 3, 2, 1),
                                                             (4, 512, 1, 1, 4, 0), (2, 300, 2, 4, 2, 0)] if only_compiled([c[3:5]])])

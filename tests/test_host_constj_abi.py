@@ -93,6 +93,55 @@ def test_fused_closure_constj_argument_validation_needs_no_gpu(lib):
     assert need > 8 and call(a17=need - 8) == -4 and call(a17=0) == -4
 
 
+# The four batched entries of the reversed closure share one validation path.  Per entry: where its operands sit.
+_REG = dict(ptrs=(0, 1, 2, 9, 12, 13), mask=10, n_g=3, S=4, n=5, lib=(6, 7, 8), ws=14, ws_bytes=15,
+            # (x, gx, jgx, n_g, S, n, d, order, flags, xi, mask, inv_count, loss, grad, ws, ws_bytes, stream)
+            ok=lambda big: [JUNK, JUNK, JUNK, 1, 1, 100, 2, 3, 0, JUNK, NULL, 1.0, JUNK, JUNK, JUNK, big, NULL])
+_FUSED = dict(ptrs=(0, 1, 2, 3, 10, 14, 15), mask=11, n_g=4, S=5, n=6, lib=(7, 8, 9), ws=16, ws_bytes=17,
+              # (x, dx, gx, jgx, n_g, S, n, d, order, flags, xi, mask, inv_count, w_sym, loss2, grad, ws, ws_bytes, stream)
+              ok=lambda big: [JUNK, JUNK, JUNK, JUNK, 1, 1, 100, 2, 3, 0, JUNK, NULL, 1.0, 0.1, JUNK, JUNK, JUNK, big, NULL])
+BATCHED_ENTRIES = {"symode_symreg_reversed_batched": _REG, "symode_symreg_reversed_batched_constj": _REG,
+                   "symode_loss_grad_reversed": _FUSED, "symode_loss_grad_reversed_constj": _FUSED}
+
+
+@pytest.mark.parametrize("name", sorted(BATCHED_ENTRIES))
+def test_batched_reversed_entries_share_one_table_of_bad_arguments(lib, name):
+    f, lay = getattr(lib, name), BATCHED_ENTRIES[name]
+    ok = lay["ok"](1 << 34)
+
+    def call(**kw):
+        a = list(ok)
+        for k, v in kw.items():
+            a[lay[k] if isinstance(lay.get(k), int) else int(k[1:])] = v
+        return f(*a)
+
+    k_d, k_order, k_flags = lay["lib"]
+    bad_lib = [{f"a{k_d}": 9}, {f"a{k_order}": 6}, {f"a{k_flags}": 4}]
+    for kw in bad_lib:
+        assert call(**kw) == -1, kw                                            # library outside the compiled set
+    assert call(S=0) == -3 and call(S=65536) == -3 and call(n=0) == -3
+    for k in lay["ptrs"]:
+        assert call(**{f"a{k}": NULL}) == -2, k                                # every required pointer
+    for k in lay["ptrs"] + (lay["mask"],):                                     # (mask may be null, not odd)
+        assert call(**{f"a{k}": ODD}) == -5, k
+    need = lib.symode_workspace_bytes(2, 3, 0, 1, 100)
+    assert need > 8
+    assert call(ws=NULL) == -4 and call(ws=ctypes.c_void_p(0x1004)) == -4 and call(ws_bytes=need - 8) == -4
+    # n_g = 0: a regulariser of no group element is what only the materialised regulariser accepts (it goes on to the
+    # later checks: here it stops at the workspace)
+    if name == "symode_symreg_reversed_batched":
+        assert call(n_g=0, ws=NULL) == -4 and call(n_g=0, a1=NULL, a2=NULL, ws=NULL) == -4
+    else:
+        assert call(n_g=0) == -3
+    assert call(n_g=-1) == -3
+    # the order of the checks: library, sizes, null, alignment, workspace
+    p0 = lay["ptrs"][0]
+    assert call(**bad_lib[0], S=0) == -1
+    assert call(S=0, **{f"a{p0}": NULL}) == -3
+    assert call(**{f"a{p0}": NULL, f"a{lay['ptrs'][1]}": ODD}) == -2
+    assert call(**{f"a{p0}": ODD}, ws=NULL) == -5
+
+
 def test_python_layer_names_the_new_entry_points():
     import inspect
     from symode_amd.batched import BatchedClosure
