@@ -457,6 +457,27 @@ int symode_adam_epochs(const float* x, const float* dx, long n_src, const int* i
                        int l1, float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
                        int* step, float* mask, float* xi_out, float* log, void* stream);
 
+/* symode_adam_epochs with the reversed symmetry regulariser (EquivSINDy-r) in every minibatch loss:
+ *   loss = w_x * sum_b |h(x_b) - dx_b|^2 / (valid rows * d)
+ *        + w_sym * sum_g sum_b |J_g(x_b) h(x_b) - h(g x_b)|^2 / (valid rows * d) + w_reg * |params|_1,   h(y) = Theta(y) (Xi * mask)^T,
+ * on operands computed once per data set (they depend neither on Xi nor on the problem), shared by all problems:
+ *   gx      (n_g, n_src, d)     g(x) of every source row, per group element
+ *   jgx     (n_g, n_src, d, d)  J_g(x), jgx[g, i, a, b] = d g(x_i)_a / d x_b
+ * A valid entry i of idx reads x[i], dx[i], gx[:, i] and jgx[:, i]; a padding entry (outside [0, n_src)) reads none of the
+ * four arrays and does not count.  Every other argument, the state, the freezing rule (applied to MSE + regulariser) and
+ * the fixed order of every sum are those of symode_adam_epochs; log column 7 is the mean over the epoch's steps of the batch
+ * regulariser (unweighted, the value train.py logs as loss_sym_reg).  n_g == 0 (gx, jgx may be NULL) computes what
+ * symode_adam_epochs computes, bit for bit, and writes 0 into column 7.  The regulariser's gradient is accumulated at
+ * weight w_sym / w_x next to the residual's, so n_g > 0 with w_x <= 0 (or NaN) is refused with SYMODE_E_BADSIZE; n_g < 0 too.
+ * replaces: train.py:491-547 with loss_sym_reg = symmreg_r (model_utils.py:160-168, the JVP as the explicit matvec on the
+ * operands of model_utils.py:172-211) plus torch.optim.Adam.step. */
+int symode_adam_epochs_reversed(const float* x, const float* dx, const float* gx, const float* jgx, int n_g, long n_src,
+                                const int* idx, long n_idx_problems, int n_epochs, int n_steps, int batch, long n_problems,
+                                int d, int order, int flags, const float* q_eff, int r, int allow_constant, int n_params,
+                                float lr, float beta1, float beta2, float eps, float w_x, float w_reg, float w_sym, int l1,
+                                float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
+                                int* step, float* mask, float* xi_out, float* log, void* stream);
+
 /* HOST function (no GPU work): least squares on the normal equations G = A^T A (n, n), C = A^T b (n, k), fp64
  * row-major host arrays; A had m_rows rows.  driver 0 = LAPACK gelsy semantics (pivoted QR rank rule with
  * rcond < 0 -> torch's default eps_fp32 * max(m_rows, n), minimum-norm solution), driver 1 = gels (full rank).

@@ -1,6 +1,8 @@
 // Device-resident minibatch Adam trainer (symode_adam_epochs): the plain branch of train_SIGED -- train.py:491-547 of the
 // reference, per minibatch MSELoss()(regressor(x), dx) + w_reg |params|_1, backward, torch.optim.Adam.step, and
 // set_threshold every st_freq epochs -- as ONE launch for n_epochs whole epochs of n_problems independent problems.
+// symode_adam_epochs_reversed is the same launch with the reversed symmetry regulariser (model_utils.py:160-168 of the
+// reference, the JVP as the explicit matvec on precomputed g(x), J_g(x)) added to every minibatch loss.
 #pragma once
 #include <cfloat>
 
@@ -29,6 +31,11 @@ struct AdamArgs {
     float *params, *m, *v;
     int* step;
     float *mask, *xi_out, *log;
+    // the reversed variant alone (adam_epochs_kernel<Lib, true>); the plain kernel reads none of these
+    const float* gx;                  // (n_g, n_src, d)
+    const float* jgx;                 // (n_g, n_src, d, d)
+    int n_g;
+    float w_ratio;                    // w_sym / w_x (0 with n_g == 0): the C entry refuses w_x <= 0 with n_g > 0
 };
 
 // b^n for an integer n >= 0 by squaring: a function of (b, n) alone, so a fit cut into several launches meets the same
@@ -53,9 +60,21 @@ __device__ __forceinline__ double adam_ipow(double b, int n) {
 // constraint, Xi = reshape(Q beta) + const.  Two barriers per step (four under the constraint).
 // The gathers do not depend on the parameters, so they run ahead of the chain of steps: the index of chunk c + 2 and the
 // rows of chunk c + 1 are in flight while chunk c is evaluated, across step and epoch boundaries of the launch.
-template <class Lib>
+//
+// REV adds  w_sym * sum_g sum_b |r|^2 / (valid rows * d),  r = J_g(x_b) h(x_b) - h(g x_b),  h = Theta(.) (Xi * mask)^T,  to the
+// loss of every batch.  A valid row gathers gx[g, i, :] and jgx[g, i, :, :] with the row number i of x and dx (padding reads
+// none of the four arrays); these gathers run ONE group element ahead of the evaluation -- element g + 1 of the row while
+// element g is evaluated, element 0 of the next chunk's row during the last one, hence across the optimiser step -- so n_g
+// is a run-time number at a fixed register cost.  The gradient
+//   (2 w_sym / (rows d)) sum_g sum_b [ (J_g^T r)_i theta_k(x_b) - r_i theta_k(g x_b) ]
+// lands in the SAME d p accumulators as the residual's: r is scaled by w_sym / w_x before it is accumulated, and the
+// optimiser multiplies the sum by w_x as before.  The MSE sums are untouched, so with n_g == 0 every value of the plain
+// kernel is reproduced bit for bit.  sum |r|^2 (unscaled) is one more reduced value; a batch is non-finite when
+// MSE + regulariser is.
+template <class Lib, bool REV = false>
 __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs a) {
-    constexpr int D = Lib::D, P = Lib::P, DP = D * P, NV = DP + 2, NW = ADAM_BLOCK / WAVE, SLOTS = (NV + WAVE - 1) / WAVE;
+    constexpr int D = Lib::D, P = Lib::P, DP = D * P, NV = DP + 2 + (REV ? 1 : 0), NW = ADAM_BLOCK / WAVE,
+                  SLOTS = (NV + WAVE - 1) / WAVE;
     static_assert(DP <= ADAM_BLOCK, "thread j owns coefficient j");
     __shared__ float w_s[DP];
     __shared__ float part[NW][NV];
@@ -131,18 +150,30 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
         }
         return ok;
     };
+    // g(x), J_g(x) of group element g at row i: the validity predicate of fetch_row, and nothing at all without elements
+    auto fetch_sym = [&](int g, int i, float (&gr)[D], float (&jr)[D * D]) __attribute__((always_inline)) {
+        const bool ok = g < a.n_g && i >= 0 && (long)i < a.n_src;
+        const long at = (long)g * a.n_src + i;
+#pragma unroll
+        for (int c = 0; c < D; ++c) gr[c] = ok ? a.gx[at * D + c] : 0.0f;
+#pragma unroll
+        for (int c = 0; c < D * D; ++c) jr[c] = ok ? a.jgx[at * (D * D) + c] : 0.0f;
+    };
 
     Cursor c{0, 0, 0}, c2{0, 0, 0};
     float cx[D], cdx[D];
-    bool cok = fetch_row(fetch_idx(c2), cx, cdx);
+    int cidx = fetch_idx(c2);
+    bool cok = fetch_row(cidx, cx, cdx);
+    float cg[D], cj[D * D];
+    if constexpr (REV) fetch_sym(0, cidx, cg, cj);
     advance(c2);
     int nidx = fetch_idx(c2);
     advance(c2);
 
-    float acc[DP], ss = 0.0f, cnt = 0.0f;
+    float acc[DP], ss = 0.0f, cnt = 0.0f, sr = 0.0f;
 #pragma unroll
     for (int j = 0; j < DP; ++j) acc[j] = 0.0f;
-    double loss_sum = 0.0, l1_sum = 0.0;                      // the epoch's running sums (train.py:541-543), uniform over the block
+    double loss_sum = 0.0, l1_sum = 0.0, sym_sum = 0.0;       // the epoch's running sums (train.py:541-543), uniform over the block
     int steps = 0;
     const float om1 = (float)(1.0 - (double)a.beta1), om2 = (float)(1.0 - (double)a.beta2);
 
@@ -151,20 +182,56 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
         const bool nok = fetch_row(nidx, nx, ndx);
         const int nnidx = fetch_idx(c2);
 
-        if (cok && !frozen) {
-            float th[P];
+        const bool eval = cok && !frozen;
+        float th[P], hx[D];
+        if (eval) {
             Lib::eval(cx, th);
 #pragma unroll
             for (int i = 0; i < D; ++i) {
                 float f = 0.0f;
 #pragma unroll
                 for (int k = 0; k < P; ++k) f = fmaf(th[k], w_s[i * P + k], f);
+                hx[i] = f;
                 const float res = f - cdx[i];
                 ss = fmaf(res, res, ss);
 #pragma unroll
                 for (int k = 0; k < P; ++k) acc[i * P + k] = fmaf(res, th[k], acc[i * P + k]);
             }
             cnt += 1.0f;
+        }
+        if constexpr (REV) {
+            for (int g = 0; g < a.n_g; ++g) {
+                float ng[D], nj[D * D];
+                const bool last = g + 1 == a.n_g;
+                fetch_sym(last ? 0 : g + 1, last ? nidx : cidx, ng, nj);
+                if (eval) {
+                    float tg[P], rs[D];
+                    Lib::eval(cg, tg);
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        float hg = 0.0f, jh = 0.0f;
+#pragma unroll
+                        for (int k = 0; k < P; ++k) hg = fmaf(tg[k], w_s[i * P + k], hg);
+#pragma unroll
+                        for (int j = 0; j < D; ++j) jh = fmaf(cj[i * D + j], hx[j], jh);
+                        const float rr = jh - hg;
+                        sr = fmaf(rr, rr, sr);
+                        rs[i] = a.w_ratio * rr;
+                    }
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        float u = 0.0f;                       // (J_g^T r)_i
+#pragma unroll
+                        for (int j = 0; j < D; ++j) u = fmaf(cj[j * D + i], rs[j], u);
+#pragma unroll
+                        for (int k = 0; k < P; ++k) acc[i * P + k] = fmaf(u, th[k], fmaf(-rs[i], tg[k], acc[i * P + k]));
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < D; ++i) cg[i] = ng[i];
+#pragma unroll
+                for (int i = 0; i < D * D; ++i) cj[i] = nj[i];
+            }
         }
 
         if (c.k == n_chunks - 1) {                            // the batch is complete: one optimiser step
@@ -173,7 +240,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
             for (int q = 0; q < SLOTS; ++q) keep[q] = 0.0f;
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
-                const float tot = wave_sum_dpp(j < DP ? acc[j < DP ? j : 0] : (j == DP ? ss : cnt));
+                const float tot = wave_sum_dpp(j < DP ? acc[j < DP ? j : 0] : (j == DP ? ss : (j == DP + 1 ? cnt : sr)));
                 if (lane == (j & (WAVE - 1))) keep[j / WAVE] = tot;
             }
 #pragma unroll
@@ -191,7 +258,14 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
             }
             const bool live = !frozen && cnt_t > 0.0f;       // a batch of padding alone is no step
             const float loss = ss_t / (cnt_t * (float)D);
-            const bool bad = live && !(fabsf(loss) <= FLT_MAX);
+            float reg = 0.0f;
+            if constexpr (REV) {
+                float sr_t = part[0][DP + 2];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) sr_t += part[w][DP + 2];
+                reg = sr_t / (cnt_t * (float)D);
+            }
+            const bool bad = live && !(fabsf(REV ? loss + reg : loss) <= FLT_MAX);
             if (bad) frozen = true;                           // NaN / inf: the problem keeps its state from here on
             const bool upd = live && !bad;
             const float scale = 2.0f / (cnt_t * (float)D);
@@ -229,6 +303,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 for (int w = 1; w < NW; ++w) l1_t += l1_s[w];
                 loss_sum += (double)loss;
                 l1_sum += (double)l1_t;
+                if constexpr (REV) sym_sum += (double)reg;
                 ++steps;
                 coefficient();
             }
@@ -236,6 +311,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
             for (int j = 0; j < DP; ++j) acc[j] = 0.0f;
             ss = 0.0f;
             cnt = 0.0f;
+            sr = 0.0f;
             __syncthreads();
 
             if (c.s == a.n_steps - 1) {                       // the epoch is complete (train.py:545-546, sindy.py:192-194)
@@ -262,15 +338,17 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                     rec[4] = frozen ? 1.0f : 0.0f;
                     rec[5] = ev ? 1.0f : 0.0f;
                     rec[6] = (float)epoch;
-                    rec[7] = 0.0f;
+                    rec[7] = REV ? (float)(sym_sum / (double)steps) : 0.0f;
                 }
                 loss_sum = 0.0;
                 l1_sum = 0.0;
+                sym_sum = 0.0;
                 steps = 0;
             }
         }
 
         cok = nok;
+        cidx = nidx;
 #pragma unroll
         for (int i = 0; i < D; ++i) {
             cx[i] = nx[i];
@@ -297,6 +375,14 @@ template <class Lib>
 hipError_t launch_adam_epochs(const AdamArgs& a, hipStream_t st) {
     if (a.n_problems == 0 || a.n_epochs == 0) return hipSuccess;
     adam_epochs_kernel<Lib><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
+    SYMODE_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+template <class Lib>
+hipError_t launch_adam_epochs_reversed(const AdamArgs& a, hipStream_t st) {
+    if (a.n_problems == 0 || a.n_epochs == 0) return hipSuccess;
+    adam_epochs_kernel<Lib, true><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
     SYMODE_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -124,6 +124,8 @@ struct LibOps {
                                 float dt, int method, float bound, float* err, double* mean_err, int* horizon, hipStream_t st);
     // n_epochs epochs of minibatch Adam steps for S problems in one launch (adam.hpp)
     hipError_t (*adam_epochs)(const AdamArgs& a, hipStream_t st);
+    // the same with the reversed symmetry regulariser in every minibatch loss (a.gx, a.jgx, a.n_g, a.w_ratio)
+    hipError_t (*adam_epochs_reversed)(const AdamArgs& a, hipStream_t st);
 };
 
 // ---------------------------------------------------------------------------------------

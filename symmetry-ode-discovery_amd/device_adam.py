@@ -3,8 +3,11 @@ branch of ``train.train_SIGED`` -- per minibatch ``w_x * mse + w_reg * |params|_
 ``set_threshold`` every ``st_freq`` epochs -- for S independent problems (seeds) on ONE shared data set, one workgroup per
 problem, nothing on the host inside a launch.
 
-Covered: the observed-space fit, unconstrained or under the equivariance constraint (any ``CoefMap``), L1 regulariser.
-Not covered (the callers refuse them): the latent branch, the symmetry regularisers, several ranks.
+Covered: the observed-space fit, unconstrained or under the equivariance constraint (any ``CoefMap``), L1 regulariser, and
+the reversed symmetry regulariser on operands g(x), J_g(x) computed once for the data set (``reversed_sym``,
+symode_adam_epochs_reversed: ``+ w_sym * sum_g mean |J_g(x) h(x) - h(g x)|^2`` per minibatch).
+Not covered (the callers refuse them): the latent branch, the i / f symmetry regularisers (they run the autoencoder on
+Xi-dependent inputs), several ranks.
 """
 from __future__ import annotations
 
@@ -20,12 +23,15 @@ from .sindy import NEAR_THRESHOLD_BAND
 TABLE_BYTES = 256 << 20
 
 LOG_COLUMNS = ('loss_sindy_x', 'loss_sindy_reg', 'steps', 'near', 'nan', 'event', 'epoch')
+# records of a trainer with ``reversed_sym``: column 7 is the epoch mean of the batch regulariser (unweighted)
+LOG_COLUMNS_REVERSED = LOG_COLUMNS + ('loss_sym_reg',)
 
 
 class DeviceAdam:
     def __init__(self, x, dx, poly_order, include_sine, include_exp, coef, lr, w_sindy_x, w_sindy_reg, threshold, st_freq,
-                 batch_size, betas=(0.9, 0.999), eps=1e-8, engine=None):
-        """x, dx (n, d) fp32 on the device, shared by all problems; ``coef``: the CoefMap of the parametrisation."""
+                 batch_size, betas=(0.9, 0.999), eps=1e-8, engine=None, reversed_sym=None):
+        """x, dx (n, d) fp32 on the device, shared by all problems; ``coef``: the CoefMap of the parametrisation;
+        ``reversed_sym``: (gx (n_g, n, d), jgx (n_g, n, d, d), w_sym) on the device of x, or None."""
         self.engine = engine or get_engine()
         self.x, self.dx = x.contiguous(), dx.contiguous()
         self.n, self.d = self.x.shape
@@ -44,6 +50,21 @@ class DeviceAdam:
             raise ValueError(f'batch_size {batch_size} < 1')
         self.steps = (self.n + self.batch - 1) // self.batch
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.reversed_sym = None
+        if reversed_sym is not None:
+            gx, jgx, w_sym = reversed_sym
+            for name, t, shape in (('gx', gx, (self.n, self.d)), ('jgx', jgx, (self.n, self.d, self.d))):
+                if not isinstance(t, torch.Tensor) or t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != shape:
+                    raise ValueError(f'reversed_sym {name} must be (n_g, {", ".join(map(str, shape))}) like x '
+                                     f'{tuple(self.x.shape)}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}')
+                if t.device != self.x.device or t.dtype != torch.float32:
+                    raise ValueError(f'reversed_sym {name} must be fp32 on {self.x.device}, got {t.dtype} on {t.device}')
+            if gx.shape[0] != jgx.shape[0]:
+                raise ValueError(f'reversed_sym holds {gx.shape[0]} group elements in gx, {jgx.shape[0]} in jgx')
+            if gx.shape[0] > 0 and not self.w_x > 0:
+                raise ValueError(f'reversed_sym needs w_sindy_x > 0 (the regulariser is weighed against it), got {self.w_x}')
+            self.reversed_sym = (gx.contiguous(), jgx.contiguous(), float(w_sym))
+        self.log_columns = LOG_COLUMNS if self.reversed_sym is None else LOG_COLUMNS_REVERSED
 
     def table(self, order):
         """One epoch's (S or 1, n) permutation cut into (S or 1, steps, batch) int32 row numbers, the short last batch
@@ -60,7 +81,7 @@ class DeviceAdam:
             state=None):
         """``params0`` (S, n_params); ``orders`` yields one (S or 1, n) integer permutation on the device per epoch, drawn
         in epoch order.  ``on_epoch(epoch, record)`` is called for every epoch after its launch was read back, with that
-        epoch's own record: the LOG_COLUMNS as (S,) numpy arrays, and ``record['state']`` = {params, mask, Xi} (device
+        epoch's own record: the LOG_COLUMNS (with ``reversed_sym``: LOG_COLUMNS_REVERSED) as (S,) numpy arrays, and ``record['state']`` = {params, mask, Xi} (device
         tensors, valid until the next launch) when the epoch is the last of its launch, else None.  ``boundary(epoch)``
         true ends the launch after that epoch (a caller that needs the state there).  ``state``: (m, v, step) of an
         earlier fit to continue.  Returns Xi, mask, params (device), log (n_epochs, S, 8) numpy, nan (S,) bool and m, v,
@@ -92,16 +113,20 @@ class DeviceAdam:
                 if full or (boundary is not None and boundary(epoch)):
                     break
             idx = torch.stack(tables).contiguous()
-            xi, log = self.engine.adam_epochs(self.x, self.dx, idx, params, m, v, step, mask, self.order, self.flags,
-                                              lr=self.lr, betas=self.betas, eps=self.eps, w_x=self.w_x, w_reg=self.w_reg,
-                                              l1=True, threshold=self.threshold, st_freq=self.st_freq, epoch0=epoch0 + done,
-                                              near_band=NEAR_THRESHOLD_BAND, q_eff=self.q_eff,
-                                              allow_constant=self.coef.allow_constant)
+            kw = dict(lr=self.lr, betas=self.betas, eps=self.eps, w_x=self.w_x, w_reg=self.w_reg, l1=True,
+                      threshold=self.threshold, st_freq=self.st_freq, epoch0=epoch0 + done, near_band=NEAR_THRESHOLD_BAND,
+                      q_eff=self.q_eff, allow_constant=self.coef.allow_constant)
+            if self.reversed_sym is None:
+                xi, log = self.engine.adam_epochs(self.x, self.dx, idx, params, m, v, step, mask, self.order, self.flags, **kw)
+            else:
+                gx, jgx, w_sym = self.reversed_sym
+                xi, log = self.engine.adam_epochs_reversed(self.x, self.dx, gx, jgx, idx, params, m, v, step, mask, self.order,
+                                                           self.flags, w_sym=w_sym, **kw)
             log = log.cpu().numpy()
             logs.append(log)
             if on_epoch is not None:
                 for k in range(len(tables)):
-                    rec = {name: log[k, :, c] for c, name in enumerate(LOG_COLUMNS)}
+                    rec = {name: log[k, :, c] for c, name in enumerate(self.log_columns)}
                     rec['state'] = {'params': params, 'mask': mask, 'Xi': xi} if k == len(tables) - 1 else None
                     on_epoch(epoch0 + done + k, rec)
             done += len(tables)

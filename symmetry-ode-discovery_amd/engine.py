@@ -95,6 +95,9 @@ _SIGNATURES = {
     "symode_adam_epochs": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_long, c_int, c_int, c_int,
                                    c_void_p, c_int, c_int, c_int] + [c_float] * 6 + [c_int, c_float, c_int, c_int, c_float]
                            + [c_void_p] * 8),
+    "symode_adam_epochs_reversed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_long, c_int, c_int,
+                                            c_int, c_long, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_float] * 7
+                                    + [c_int, c_float, c_int, c_int, c_float] + [c_void_p] * 8),
     "symode_host_stlsq_sweep": (c_int, [c_void_p, c_int, c_int, c_int, c_long, ctypes.c_double, ctypes.c_double, c_int, c_int,
                                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
@@ -280,7 +283,8 @@ class HipEngine:
         return err, mean_err, horizon
 
     def adam_epochs(self, x, dx, idx, params, m, v, step, mask, order, flags=0, *, lr, betas=(0.9, 0.999), eps=1e-8, w_x=1.0,
-                    w_reg=0.0, l1=True, threshold=0.0, st_freq=0, epoch0=0, near_band=1e-4, q_eff=None, allow_constant=True):
+                    w_reg=0.0, l1=True, threshold=0.0, st_freq=0, epoch0=0, near_band=1e-4, q_eff=None, allow_constant=True,
+                    _reversed=None):
         """``idx.shape[0]`` whole epochs of minibatch Adam steps for S problems in ONE launch (symode_adam_epochs).
         x, dx (n_src, d) fp32; idx (n_epochs, S or 1, n_steps, batch) int32 row numbers; params, m, v (S, n_params) fp32,
         step (S,) int32 and mask (S, d, p) fp32 are the state, UPDATED IN PLACE (so they must be contiguous); q_eff
@@ -324,6 +328,15 @@ class HipEngine:
             raise SymodeError(f"params has {n_params} columns, expected {r + d if q_eff is not None else d * p}")
         xi = torch.empty(S, d, p, dtype=torch.float32, device=x.device)
         log = torch.empty(n_epochs, S, 8, dtype=torch.float32, device=x.device)
+        if _reversed is not None:
+            gx, jgx, n_g, w_sym = _reversed
+            self._check(self.lib.symode_adam_epochs_reversed(
+                self._ptr(x), self._ptr(dx), self._ptr(gx), self._ptr(jgx), n_g, n_src, self._ptr(idx), n_tab, n_epochs, n_steps,
+                batch, S, d, order, flags, self._ptr(q_eff), r, int(bool(allow_constant)), n_params, float(lr), float(betas[0]),
+                float(betas[1]), float(eps), float(w_x), float(w_reg), float(w_sym), int(bool(l1)), float(threshold),
+                int(st_freq), int(epoch0), float(near_band), self._ptr(params), self._ptr(m), self._ptr(v), self._ptr(step),
+                self._ptr(mask), self._ptr(xi), self._ptr(log), self._stream(x)), "symode_adam_epochs_reversed")
+            return xi, log
         self._check(self.lib.symode_adam_epochs(
             self._ptr(x), self._ptr(dx), n_src, self._ptr(idx), n_tab, n_epochs, n_steps, batch, S, d, order, flags,
             self._ptr(q_eff), r, int(bool(allow_constant)), n_params, float(lr), float(betas[0]), float(betas[1]), float(eps),
@@ -331,6 +344,33 @@ class HipEngine:
             self._ptr(params), self._ptr(m), self._ptr(v), self._ptr(step), self._ptr(mask), self._ptr(xi), self._ptr(log),
             self._stream(x)), "symode_adam_epochs")
         return xi, log
+
+    def adam_epochs_reversed(self, x, dx, gx, jgx, idx, params, m, v, step, mask, order, flags=0, *, w_sym, **kw):
+        """``adam_epochs`` with the reversed symmetry regulariser in every minibatch loss (symode_adam_epochs_reversed):
+        ``w_x * mse + w_sym * sum_g mean |J_g(x) h(x) - h(g x)|^2 + w_reg * |params|_1`` on gx (n_g, n_src, d) and jgx
+        (n_g, n_src, d, d) fp32, computed once for the data set and gathered by the same row numbers as x and dx (padding
+        reads none of them).  n_g = 0 (gx, jgx may be None) is ``adam_epochs`` bit for bit.  The other arguments and the
+        return value are those of ``adam_epochs``; log column 7 is the epoch mean of the batch regulariser (unweighted).
+        n_g > 0 needs w_x > 0."""
+        x = self._dev(x, "x")
+        if x.dim() != 2:
+            raise SymodeError(f"x must be (n_src, d), got {tuple(x.shape)}")
+        n_src, d = x.shape
+        n_g = 0
+        if gx is not None or jgx is not None:
+            if gx is None or jgx is None:
+                raise SymodeError("gx and jgx are given together or not at all")
+            gx, jgx = self._dev(gx, "gx"), self._dev(jgx, "jgx")
+            if gx.dim() != 3 or gx.shape[1:] != (n_src, d) or jgx.shape != (gx.shape[0], n_src, d, d):
+                raise SymodeError(f"gx must be (n_g, {n_src}, {d}) and jgx (n_g, {n_src}, {d}, {d}), got {tuple(gx.shape)} and "
+                                  f"{tuple(jgx.shape)}")
+            if gx.device != x.device or jgx.device != x.device:
+                raise SymodeError(f"gx / jgx are on {gx.device} / {jgx.device}, x on {x.device}: all tensors of one launch "
+                                  "live on one device")
+            n_g = gx.shape[0]
+        if n_g == 0:
+            gx = jgx = None
+        return self.adam_epochs(x, dx, idx, params, m, v, step, mask, order, flags, _reversed=(gx, jgx, n_g, w_sym), **kw)
 
     def _check_coef(self, xi, mask, d, order, flags, n_problems=1):
         p = self.lib_size(d, order, flags)

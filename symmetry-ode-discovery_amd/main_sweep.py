@@ -39,7 +39,8 @@ no ``--use_latent``, ``w_sym_reg == 0``, with or without ``--eq_constraint`` -- 
 per seed runs whole epochs per launch (symode_adam_epochs).  Every epoch of every seed is a pass over the WHOLE data set in
 batches of ``--batch_size`` (``--lbfgs_subsample`` does not apply, as in main.py); seed s shuffles with its own device
 generator seeded with s (one ``torch.rand(n)`` per epoch, stable argsort), so a seed's fit depends on the seed alone, not on
-``--n_seeds`` or ``--seed``.  Adam with the latent branch or a symmetry regulariser is refused, and so is Adam on several
+``--n_seeds`` or ``--seed``.  Adam with the latent branch or a symmetry regulariser is refused (for the reversed one use
+``python -m symode_amd.main --device_adam`` per seed), and so is Adam on several
 ranks (one process per seed block is the way to use several GPUs there).
 
 A sweep's seed n does NOT reproduce ``python -m symode_amd.main --seed n`` row for row: the sweep draws each seed's
@@ -61,14 +62,10 @@ from .batched import BatchedClosure
 from .dataset import get_dataset
 from .evaluation import aggregate_results, eval_ltp_sweep, sindy_truth, val_mse_sweep
 from .lie import LieGenerator
+from .model_utils import PRECOMPUTE_CHUNK, symmetry_operands  # noqa: F401  (their home: the device Adam trainer shares them)
 from .parser_utils import get_args
 from .sindy import SINDyRegression
 from .sweep import GramClosure, SeedSweepLBFGS, SeedSweepSTLSQ, seeded_subsamples
-
-# rows per precompute_symmreg_r call: the LV config's 512-wide autoencoder keeps ~10 activations of (rows, 512) fp32 alive
-# per JVP column, ~130 MB at 65 536 rows
-PRECOMPUTE_CHUNK = 65536
-
 
 def _pop(argv, flag, default, cast):
     if flag in argv:
@@ -175,24 +172,6 @@ def _load_laligan(args, dev):
         for param in module.parameters():
             param.requires_grad = False
     return autoencoder, generator
-
-
-def symmetry_operands(x, rows, autoencoder, generator, chunk=PRECOMPUTE_CHUNK):
-    """g(x) and J_g(x) of the rows the (S, m) table ``rows`` uses, each computed once: (x_used (U, d), gx (n_g, U, d),
-    jgx (n_g, U, d, d), table (S, m) int32 into the U used rows, ``used`` (U,) their row numbers in x).  Rows in chunks of
-    at most ``chunk`` (precompute_symmreg_r is pointwise: batch norm in eval mode, z_mean the encoder bias)."""
-    from .model_utils import precompute_symmreg_r
-    used = torch.unique(rows)                                            # sorted
-    table = torch.searchsorted(used, rows).to(torch.int32).contiguous()
-    x_used = x[used].contiguous()
-    gxs, jgxs = [], []
-    for a in range(0, x_used.shape[0], chunk):
-        g, j = precompute_symmreg_r(x_used[a:a + chunk], autoencoder, generator, scale=0.01)
-        gxs.append(torch.stack(g))
-        jgxs.append(torch.stack(j))
-    gx = torch.cat(gxs, dim=1).float().contiguous()
-    jgx = torch.cat(jgxs, dim=1).float().contiguous()
-    return x_used, gx, jgx, table, used
 
 
 def _adam_sweep(args, seeds, template, coef, inits, x_all, dx_all, val_dataset, padded_truth, eval_ltp, ltp_bound_rel, dev,

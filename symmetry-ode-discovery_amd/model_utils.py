@@ -505,6 +505,28 @@ def precompute_symmreg_r(x, autoencoder, generator, z_mean=None, scale=0.01):
     return gx_list, Jgx_list
 
 
+# rows per precompute_symmreg_r call: the LV config's 512-wide autoencoder keeps ~10 activations of (rows, 512) fp32 alive
+# per JVP column, ~130 MB at 65 536 rows
+PRECOMPUTE_CHUNK = 65536
+
+
+def symmetry_operands(x, rows, autoencoder, generator, chunk=PRECOMPUTE_CHUNK):
+    """g(x) and J_g(x) of the rows the (S, m) table ``rows`` uses, each computed once: (x_used (U, d), gx (n_g, U, d),
+    jgx (n_g, U, d, d), table (S, m) int32 into the U used rows, ``used`` (U,) their row numbers in x).  Rows in chunks of
+    at most ``chunk`` (precompute_symmreg_r is pointwise: batch norm in eval mode, z_mean the encoder bias)."""
+    used = torch.unique(rows)                                            # sorted
+    table = torch.searchsorted(used, rows).to(torch.int32).contiguous()
+    x_used = x[used].contiguous()
+    gxs, jgxs = [], []
+    for a in range(0, x_used.shape[0], chunk):
+        g, j = precompute_symmreg_r(x_used[a:a + chunk], autoencoder, generator, scale=0.01)
+        gxs.append(torch.stack(g))
+        jgxs.append(torch.stack(j))
+    gx = torch.cat(gxs, dim=1).float().contiguous()
+    jgx = torch.cat(jgxs, dim=1).float().contiguous()
+    return x_used, gx, jgx, table, used
+
+
 class _ReversedFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xi, mask, x, gx, jgx, reg):

@@ -60,8 +60,9 @@ _MAIN_ARGS = [
 # Flags of this project beyond the reference's surface and the three above, kept apart from _MAIN_ARGS (whose length is
 # pinned against the reference parser): --gram_closure runs the device trainer's closure as the quadratic form of the
 # batch's fp64 Gram matrices, built in one pass over the data (one all-reduce when sharded) instead of streaming the points
-# per evaluation (gram_closure.py).  --device_adam runs the plain minibatch Adam fit (--sindy_optimizer adam, no latent space, no
-# symmetry regulariser) as whole epochs per launch on the device (device_adam.py) instead of one Python iteration per batch.
+# per evaluation (gram_closure.py).  --device_adam runs the plain minibatch Adam fit (--sindy_optimizer adam, no latent space;
+# a symmetry regulariser only as --sym_reg_type r with --fix_laligan) as whole epochs per launch on the device
+# (device_adam.py) instead of one Python iteration per batch.
 _EXTRA_ARGS = [("gram_closure", _FLAG, None), ("device_adam", _FLAG, None)]
 
 # parser_utils.py:122-171

@@ -1052,15 +1052,24 @@ def train_SIGED_lbfgs(
 
 def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir, regressor,
                           use_latent, lr_sindy, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg, st_freq, threshold,
-                          print_eq):
+                          print_eq, sym_reg_type=None, autoencoder=None, generator=None):
     """train_SIGED's plain branch on DeviceAdam: the same shuffles (one ``randperm`` per epoch from the global generator, as
     the loader draws them), prints, wandb records, test loss and checkpoints at the same epochs, produced from the
-    launch's log and from the state adopted into the regressor at those epochs and at the end."""
+    launch's log and from the state adopted into the regressor at those epochs and at the end.  ``w_sym_reg > 0`` with
+    ``sym_reg_type 'r'`` and a frozen autoencoder and generator adds ``w_sym_reg * symmreg_r`` to every minibatch loss:
+    g(x), J_g(x) are computed once over the loader's rows."""
     from .dataset import DeviceBatches
     if use_latent:
         raise ValueError('device_adam covers the observed-space fit only: use_latent is set')
-    if w_sym_reg != 0:
-        raise ValueError(f'device_adam covers fits without a symmetry regulariser: w_sym_reg is {w_sym_reg}, not 0')
+    if w_sym_reg < 0:
+        raise ValueError(f'w_sym_reg is {w_sym_reg}: a weight is not negative')
+    sym = w_sym_reg > 0
+    if sym and sym_reg_type != 'r':
+        raise ValueError(f"device_adam covers w_sym_reg > 0 (here {w_sym_reg}) with sym_reg_type 'r' only, not "
+                         f"'{sym_reg_type}': the i / f regularisers run the autoencoder on Xi-dependent inputs")
+    if sym and any(q.requires_grad for module in (autoencoder, generator) for q in module.parameters()):
+        raise ValueError('device_adam with w_sym_reg > 0 needs a frozen autoencoder and generator (--fix_laligan: no parameter '
+                         'requires grad): g(x), J_g(x) are computed once')
     if sindy_reg_type != 'l1':
         raise ValueError(f"device_adam covers sindy_reg_type 'l1', not '{sindy_reg_type}'")
     if not isinstance(train_loader, DeviceBatches):
@@ -1072,8 +1081,13 @@ def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_int
         raise ValueError('device_adam needs the data set resident on the device (DeviceBatches kept it in host memory)')
     from .device_adam import DeviceAdam
     coef = regressor.coef
+    rev = None
+    if sym:                                                   # the weight as it stands: w_x * mse + w_sym_reg * regulariser
+        from .model_utils import symmetry_operands
+        _, gx, jgx, _, _ = symmetry_operands(x, torch.arange(x.shape[0], device=x.device)[None], autoencoder, generator)
+        rev = (gx, jgx, w_sym_reg)
     trainer = DeviceAdam(x, dx, regressor.poly_order, regressor.include_sine, regressor.include_exp, coef, lr_sindy, w_sindy_x,
-                         w_sindy_reg, threshold, st_freq, train_loader.bs, engine=regressor.engine)
+                         w_sindy_reg, threshold, st_freq, train_loader.bs, engine=regressor.engine, reversed_sym=rev)
     last_mask = [regressor.mask.detach().clone()]
 
     def at(epoch, every):
@@ -1084,7 +1098,8 @@ def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_int
 
     def on_epoch(epoch, rec):
         wandb_log = {'loss_sindy_x': float(rec['loss_sindy_x'][0]), 'loss_sindy_z': 0.0,
-                     'loss_sindy_reg': float(rec['loss_sindy_reg'][0]), 'loss_sym_reg': 0.0}
+                     'loss_sindy_reg': float(rec['loss_sindy_reg'][0]),
+                     'loss_sym_reg': float(rec['loss_sym_reg'][0]) if sym else 0.0}
         state = rec['state']
         if st_freq > 0 and at(epoch, st_freq) and not rec['nan'][0]:                   # train.py:545-546
             regressor.note_near_threshold(state['Xi'][0], last_mask[0], threshold, 'set_threshold (device Adam)')
@@ -1120,12 +1135,14 @@ def train_SIGED(
     **kwargs
 ):
     """Mini-batch Adam variant                                                       (train.py:382-614).
-    ``device_adam=True`` (--device_adam): the plain branch runs whole epochs per launch on the device (device_adam.py);
-    any other configuration is refused, not silently run the usual way."""
+    ``device_adam=True`` (--device_adam): the plain branch runs whole epochs per launch on the device (device_adam.py),
+    with ``sym_reg_type='r'`` and a frozen LaLiGAN also under the reversed symmetry regulariser; any other configuration is
+    refused, not silently run the usual way."""
     if kwargs.get('device_adam'):
         return _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir,
                                      regressor, use_latent, lr_sindy, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg,
-                                     st_freq, threshold, kwargs.get('print_eq'))
+                                     st_freq, threshold, kwargs.get('print_eq'), sym_reg_type=kwargs.get('sym_reg_type'),
+                                     autoencoder=autoencoder, generator=generator)
     optimizer_sindy = torch.optim.Adam(regressor.parameters(), lr=lr_sindy)
     symm_loss = make_symmreg_pttrain(autoencoder, generator)
     for epoch in range(num_epochs):
