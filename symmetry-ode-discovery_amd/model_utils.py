@@ -527,6 +527,21 @@ def symmetry_operands(x, rows, autoencoder, generator, chunk=PRECOMPUTE_CHUNK):
     return x_used, gx, jgx, table, used
 
 
+def reversed_operands(x, autoencoder, generator, chunk=None):
+    """(gx (n_g, N, d), jgx (n_g, N, d, d)) of the reversed regulariser for every row of ``x``: stacked over the group
+    elements, fp32, contiguous -- what train.py's three trainers start from.  Each of them then applies its own layout and
+    weight convention: the device L-BFGS trainer a leading problem axis and w_sym_reg / w_sindy_x, the host shadow neither,
+    the device Adam trainer the weight as it stands.
+    ``chunk=None``: precompute_symmreg_r on the whole batch in one piece (the L-BFGS fits); a row count: through
+    symmetry_operands in pieces of that many rows (the Adam trainer's data set).  A GEMM over another row count may round
+    differently, so each caller keeps the chunking it has always had."""
+    if chunk is None:
+        gx, jgx = precompute_symmreg_r(x, autoencoder, generator, scale=0.01)
+        return torch.stack(gx).float().contiguous(), torch.stack(jgx).float().contiguous()
+    _, gx, jgx, _, _ = symmetry_operands(x, torch.arange(x.shape[0], device=x.device)[None], autoencoder, generator, chunk)
+    return gx, jgx
+
+
 class _ReversedFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xi, mask, x, gx, jgx, reg):
