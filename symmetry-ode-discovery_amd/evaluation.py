@@ -22,12 +22,19 @@ sindy_truth = {
 }
 
 
-def eval_sindy_regressor(regressor, truth, threshold=0.05):
-    """Returns (coef, correct_form, mse, correct_form_all, mse_all) -- eval_eq.py:7-34."""
-    with torch.no_grad():
-        coef = (regressor.get_Xi() if regressor.constraint else regressor.Xi).cpu().numpy()
-        mask = regressor.mask.bool().cpu().numpy()
-    coef = np.where(mask, coef, 0.0)
+def truth_table(task, n_terms, include_sine, include_exp):
+    """sindy_truth[task] for a library of ``n_terms`` columns: a higher polynomial order only appends columns, so the table
+    extends with zeros (not so with sine / exp terms in the library)."""
+    truth = sindy_truth[task]
+    if truth.shape[1] < n_terms and not (include_sine or include_exp):
+        truth = np.concatenate([truth, np.zeros((truth.shape[0], n_terms - truth.shape[1]))], axis=1)
+    return truth
+
+
+def score_coefficients(Xi, mask, truth):
+    """Returns (coef, correct_form, mse, correct_form_all, mse_all) of one model, Xi (d, p) and boolean mask (d, p) as numpy
+    arrays -- eval_eq.py:7-34."""
+    coef = np.where(mask, Xi, 0.0)
     truth_mask = truth != 0
     n_eqs = coef.shape[0]
     correct_form = np.zeros(n_eqs)
@@ -36,6 +43,13 @@ def eval_sindy_regressor(regressor, truth, threshold=0.05):
         correct_form[i] = np.all(mask[i, :] == truth_mask[i, :])
         mse[i] = np.mean((coef[i, truth_mask[i, :]] - truth[i, truth_mask[i, :]]) ** 2)
     return coef, correct_form, mse, np.all(correct_form), np.mean(mse)
+
+
+def eval_sindy_regressor(regressor, truth, threshold=0.05):
+    """score_coefficients of a regressor's coefficients and mask."""
+    with torch.no_grad():
+        Xi = (regressor.get_Xi() if regressor.constraint else regressor.Xi).cpu().numpy()
+    return score_coefficients(Xi, regressor.mask.bool().cpu().numpy(), truth)
 
 
 result_dir = 'eval_results'

@@ -9,6 +9,8 @@ eval_results/<save_dir>/seed{seed}.npz, as main.py:18-140 of the reference.  Mul
 """
 from __future__ import annotations
 
+import contextlib
+import io
 import os
 
 import numpy as np
@@ -17,9 +19,10 @@ import torch
 from . import train as T
 from .autoencoder import AutoEncoder
 from .dataset import get_dataset, make_loader
-from .evaluation import eval_sindy_regressor, sindy_truth
+from .evaluation import eval_sindy_regressor, truth_table
 from .lie import Discriminator, LieGenerator
-from .parser_utils import get_args
+from .model_utils import constraint_basis, load_laligan
+from .parser_utils import get_args, init_ranks
 from .sindy import SINDyRegression
 
 
@@ -38,19 +41,11 @@ def main(argv=None, backend='nccl', one_gpu=False):
     args = vars(args)
     if str(args['device']) == 'cpu':
         raise SystemExit('symode_amd runs the SINDy path on the GPU only (no CPU fallback): a HIP device is required')
-    group = None
-    if world > 1:
-        import contextlib
-        import io
+    if world > 1 and (args['mt_data'] or args['sindy_optimizer'] != 'lbfgs' or args['use_latent']):
+        raise SystemExit('multi-rank runs of symode_amd.main cover the non-latent L-BFGS fits (point shards)')
+    group = init_ranks(args, world, one_gpu, backend)
+    if group is not None:
         import torch.distributed as dist
-        if args['mt_data'] or args['sindy_optimizer'] != 'lbfgs' or args['use_latent']:
-            raise SystemExit('multi-rank runs of symode_amd.main cover the non-latent L-BFGS fits (point shards)')
-        local = 0 if one_gpu else int(os.environ.get('LOCAL_RANK', '0'))
-        torch.cuda.set_device(local)
-        args['device'] = torch.device('cuda', local)
-        if not dist.is_initialized():
-            dist.init_process_group(backend, **({'device_id': args['device']} if backend == 'nccl' else {}))
-        group = dist.group.WORLD
         if rank != 0:                                       # one rank makes the data files and talks
             dist.barrier()
             with contextlib.redirect_stdout(io.StringIO()):
@@ -80,25 +75,15 @@ def _run(args, seed, group, rank, world, datasets=None):
     discriminator = Discriminator(**args).to(args['device'])
     generator = LieGenerator(**args).to(args['device'])
 
-    laligan_path = args['load_laligan']
-    if laligan_path is not None:
-        autoencoder.load_state_dict(torch.load(f'saved_models/{laligan_path}/autoencoder.pt', weights_only=True))
-        saved = torch.load(f'saved_models/{laligan_path}/generator.pt', weights_only=True)
-        current = generator.state_dict()
-        for name, param in current.items():                       # tolerate older generator files (main.py:52-60)
-            saved.setdefault(name, param)
-        generator.load_state_dict({k: v for k, v in saved.items() if k in current})
-        masks = torch.load(f'saved_models/{laligan_path}/generator_mask.pt', weights_only=True)
-        generator.masks = [m.to(args['device']) if m is not None else None for m in masks]
+    if args['load_laligan'] is not None:
+        load_laligan(autoencoder, generator, args['load_laligan'], args['device'])
     if args['fix_laligan']:
         for module in (autoencoder, generator, discriminator):
             for param in module.parameters():
                 param.requires_grad = False
 
     if args['eq_constraint']:
-        L_list = generator.get_full_basis_list()
-        repr_dim = L_list[0].shape[-1] // args['n_comps']
-        args['L_list'] = [L[:repr_dim, :repr_dim].detach().cpu() for L in L_list]      # main.py:72-76
+        args['L_list'] = constraint_basis(generator, args['n_comps'])
     regressor = SINDyRegression(**args).to(args['device'])
     if args['distill_latent']:
         args_distill = dict(args, eq_constraint=False, use_latent=False, L_list=[])
@@ -139,12 +124,8 @@ def _run(args, seed, group, rank, world, datasets=None):
         T.wandb.finish()
         return regressor
     print('\n=== Evaluation ===\n')
-    true_eq = sindy_truth[args['task']]
     regressor_eval = regressor_dst if args['distill_latent'] else regressor
-    n_terms = regressor_eval.mask.shape[1]
-    if true_eq.shape[1] < n_terms and not (regressor_eval.include_sine or regressor_eval.include_exp):
-        # a higher polynomial order only appends columns: the truth table extends with zeros
-        true_eq = np.concatenate([true_eq, np.zeros((true_eq.shape[0], n_terms - true_eq.shape[1]))], axis=1)
+    true_eq = truth_table(args['task'], regressor_eval.mask.shape[1], regressor_eval.include_sine, regressor_eval.include_exp)
     coef, cf, mse, cf_all, mse_all = eval_sindy_regressor(regressor_eval, true_eq)
     print(f'Near-threshold coefficients (| |coef| - thr | < 1e-4): {regressor_eval.near_threshold or "none"}')
     print(f'Correct form: {cf}')

@@ -505,6 +505,27 @@ def precompute_symmreg_r(x, autoencoder, generator, z_mean=None, scale=0.01):
     return gx_list, Jgx_list
 
 
+def load_laligan(autoencoder, generator, name, device, map_location=None):
+    """The state of saved_models/<name>/ (autoencoder.pt, generator.pt, generator_mask.pt, as main.py writes them) into an
+    existing autoencoder and generator; the generator's masks go to ``device``."""
+    path = f'saved_models/{name}'
+    autoencoder.load_state_dict(torch.load(f'{path}/autoencoder.pt', weights_only=True, map_location=map_location))
+    saved = torch.load(f'{path}/generator.pt', weights_only=True, map_location=map_location)
+    current = generator.state_dict()
+    for key, param in current.items():                        # tolerate older generator files (main.py:52-60)
+        saved.setdefault(key, param)
+    generator.load_state_dict({k: v for k, v in saved.items() if k in current})
+    masks = torch.load(f'{path}/generator_mask.pt', weights_only=True, map_location=map_location)
+    generator.masks = [m.to(device) if m is not None else None for m in masks]
+
+
+def constraint_basis(generator, n_comps):
+    """--eq_constraint: the generator's Lie algebra basis cut to one component's block, on the host (main.py:72-76)."""
+    L_list = generator.get_full_basis_list()
+    repr_dim = L_list[0].shape[-1] // n_comps
+    return [L[:repr_dim, :repr_dim].detach().cpu() for L in L_list]
+
+
 # rows per precompute_symmreg_r call: the LV config's 512-wide autoencoder keeps ~10 activations of (rows, 512) fp32 alive
 # per JVP column, ~130 MB at 65 536 rows
 PRECOMPUTE_CHUNK = 65536

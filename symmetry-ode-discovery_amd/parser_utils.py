@@ -106,6 +106,22 @@ def _device(gpu):
     return torch.device('cuda:{}'.format(gpu) if torch.cuda.is_available() and gpu != -1 else 'cpu')
 
 
+def init_ranks(args, world, one_gpu, backend, set_device=True):
+    """Several ranks (``world`` = WORLD_SIZE > 1): this rank's GPU -- LOCAL_RANK, or cuda:0 on every rank with ``one_gpu`` --
+    becomes args['device'] (``set_device=False``: a rehearsal that keeps the parsed device) and the process group is
+    initialised if it is not yet.  Returns the group, None for one rank."""
+    if world <= 1:
+        return None
+    import torch.distributed as dist
+    if set_device:
+        local = 0 if one_gpu else int(os.environ.get('LOCAL_RANK', '0'))
+        torch.cuda.set_device(local)
+        args['device'] = torch.device('cuda', local)
+    if not dist.is_initialized():
+        dist.init_process_group(backend, **({'device_id': args['device']} if backend == 'nccl' else {}))
+    return dist.group.WORLD
+
+
 def get_args(construct_parser=False, argv=None):
     parser = _build(_MAIN_ARGS + _EXTRA_ARGS)
     if construct_parser:

@@ -62,8 +62,7 @@ class SeedSweepSTLSQ:
             assert idx.dim() == 2 and idx.shape[0] == n_seeds
             self.idx = idx.to(torch.int32).to(x.device).contiguous()
             self.m_local = idx.shape[1]
-        # a seed's Gram is a sum over its rows: visit them in ascending order (near-sequential reads of x, dx)
-        if idx is not None:
+            # a seed's Gram is a sum over its rows: visit them in ascending order (near-sequential reads of x, dx)
             if not idx_sorted:                               # (seeded_subsamples' tables already are)
                 self.idx = torch.sort(self.idx, dim=1).values.contiguous()
         else:
