@@ -178,6 +178,20 @@ int symode_loss_grad_reversed(const float* x, const float* dx, const float* gx, 
                               int d, int order, int flags, const float* xi, const float* mask, float inv_count, float w_sym,
                               float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The whole closure of the LATENT fit in one pass over the points.  With the autoencoder frozen (eval mode, not among
+ * the optimiser's variables) z = enc(x), dz = J_enc(x) dx and A_n = J_dec(z_n) are data; a thin QR A_n = Q_n B_n turns
+ * |A_n h - dx_n|^2 into |B_n h - y_n|^2 + const with y_n = Q_n^T dx_n (B = A, y = dx when the observed and the latent
+ * dimension agree):
+ *     loss2_out[s] = inv_count * ( sum r_z^2 , sum r_x^2 ),   r_z = h(z) - dz,  r_x = B h(z) - y,  h = Theta(.)(xi*mask)^T,
+ *     grad_out[s]  = d( loss2[0] + w_pair * loss2[1] ) / dxi   (masked);  w_pair = 0 still produces loss2[1].
+ * z, dz, y (S, n, d); B (S, n, d, d) row-major; xi / mask (S, d, p); loss2 (S, 2), grad (S, d, p).  inv_count, the
+ * workspace (symode_workspace_bytes / _init) and the argument checks as in symode_loss_grad_reversed.
+ * replaces: train.py:647-661 + 689 (--use_latent: autoencoder forward, compute_dz, compute_dx, the two MSE terms and
+ * their backward, per closure). */
+int symode_loss_grad_latent(const float* z, const float* dz, const float* B, const float* y, long n_problems, long n, int d,
+                            int order, int flags, const float* xi, const float* mask, float inv_count, float w_pair,
+                            float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Is J_g(x) the same matrix at every point of each (problem, group element)?  One streaming pass over
  * jgx (S, n_g, n, d, d), run once per data set: every point's matrix is compared BITWISE (as 32-bit words) with point 0
  * of its own (s, g) slab -- -0.0 differs from +0.0, a NaN anywhere answers "no" -- and different slabs may hold

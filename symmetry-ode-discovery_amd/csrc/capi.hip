@@ -329,6 +329,26 @@ int symode_loss_grad_reversed(const float* x, const float* dx, const float* gx_,
                             loss2_out, grad_out, workspace, workspace_bytes, stream);
 }
 
+int symode_loss_grad_latent(const float* z, const float* dz, const float* B, const float* y, long n_problems, long n, int d, int order,
+                            int flags, const float* xi, const float* mask, float inv_count, float w_pair, float* loss2_out,
+                            float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
+    SYMODE_GET_OPS();
+    if (n < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
+    if (!z || !dz || !B || !y || !xi || !loss2_out || !grad_out) return SYMODE_E_NULLPTR;
+    if (misaligned(z, 4) || misaligned(dz, 4) || misaligned(B, 4) || misaligned(y, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
+        misaligned(loss2_out, 4) || misaligned(grad_out, 4))
+        return SYMODE_E_ALIGN;
+    SYMODE_CHECK_WS(n_problems, n);
+    // the grid rule of the fused reversed closure: the same 40 bytes per point at d = 2, the same partial rows
+    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
+    if (n_problems == 1) {
+        const int cap = small_grid_cap(n, true);
+        if (cap > 0 && gx > cap) gx = cap;
+    }
+    return (int)ops->latent_closure(z, dz, B, y, n_problems, n, xi, mask, inv_count, w_pair, loss2_out, grad_out, (double*)workspace,
+                                    gx, (hipStream_t)stream);
+}
+
 int symode_symreg_reversed_batched_constj(const float* x, const float* gx_, const float* jgx, int n_g, long n_problems, long n,
                                           int d, int order, int flags, const float* xi, const float* mask, float inv_count,
                                           float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes,

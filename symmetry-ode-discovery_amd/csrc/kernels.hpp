@@ -126,6 +126,10 @@ struct LibOps {
     hipError_t (*adam_epochs)(const AdamArgs& a, hipStream_t st);
     // the same with the reversed symmetry regulariser in every minibatch loss (a.gx, a.jgx, a.n_g, a.w_ratio)
     hipError_t (*adam_epochs_reversed)(const AdamArgs& a, hipStream_t st);
+    // the closure of the latent fit (latent.hpp): z, dz, y (S, n, d), B (S, n, d, d); loss2 (S, 2), grad (S, d, p)
+    hipError_t (*latent_closure)(const float* z, const float* dz, const float* B, const float* y, long S, long n, const float* xi,
+                                 const float* mask, float inv_count, float w_pair, float* loss2, float* grad, double* ws, int gx,
+                                 hipStream_t st);
 };
 
 // ---------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@
 #include "gram_rev.hpp"
 #include "gram_valu.hpp"
 #include "kernels.hpp"
+#include "latent.hpp"
 #include "rollout.hpp"
 #include "weak.hpp"
 
@@ -35,7 +36,8 @@ constexpr LibOps make_ops() {
                   rev_gram_launcher<Lib>(),
                   &launch_rollout_error<Lib>,
                   &launch_adam_epochs<Lib>,
-                  &launch_adam_epochs_reversed<Lib>};
+                  &launch_adam_epochs_reversed<Lib>,
+                  &launch_latent_closure<Lib>};
 }
 
 #define SYMODE_OPS_ALL_FLAGS(D, O) make_ops<D, O, 0>(), make_ops<D, O, 1>(), make_ops<D, O, 2>(), make_ops<D, O, 3>()

@@ -6,7 +6,7 @@ problem, nothing on the host inside a launch.
 Covered: the observed-space fit, unconstrained or under the equivariance constraint (any ``CoefMap``), L1 regulariser, and
 the reversed symmetry regulariser on operands g(x), J_g(x) computed once for the data set (``reversed_sym``,
 symode_adam_epochs_reversed: ``+ w_sym * sum_g mean |J_g(x) h(x) - h(g x)|^2`` per minibatch).
-Not covered (the callers refuse them): the latent branch, the i / f symmetry regularisers (they run the autoencoder on
+Not covered (the callers refuse them): the latent branch (its L-BFGS fit has a fused route of its own, train._train_latent_on_device), the i / f symmetry regularisers (they run the autoencoder on
 Xi-dependent inputs), several ranks.
 """
 from __future__ import annotations

@@ -32,7 +32,7 @@ class DeviceTrainer:
     def __init__(self, x, dx, poly_order, flags=0, Q=None, use_kron_product=True, allow_constant=True, reversed_sym=None,
                  lr=1.0, threshold=0.1, st_freq=0, w_x=1.0, w_reg=0.0, l1=True, tol=1e-3, max_iter=20, history=100,
                  tol_grad=1e-7, tol_change=1e-9, inv_count=None, engine=None, detail=None, group=None, closure="stream",
-                 statistics=None, coef=None):
+                 statistics=None, coef=None, latent=None):
         """x, dx (S, N_local, d) device tensors; ``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from
         Q / use_kron_product / allow_constant); ``reversed_sym = (gx (S, n_g, N, d), jgx (S, n_g, N, d, d), weight)`` as
         batched.BatchedClosure; ``group``: point shards, [loss | grad] summed over the ranks between closure and update;
@@ -40,11 +40,22 @@ class DeviceTrainer:
         ``closure="gram"``: every closure is the quadratic form of the fixed fp64 matrices [G | R] (gram_closure.py), built
         here in one pass over x, dx (, gx, jgx) -- or taken from ``statistics``, a GramStatistics of this rank's points, when
         x, dx, gx, jgx may be None -- and, with ``group``, summed over the ranks in ONE all-reduce at set-up; the fit then
-        runs without any collective and holds no reference to the point data."""
+        runs without any collective and holds no reference to the point data.
+        ``closure="latent"``: the latent fit (train.py:647-661) on the operands of ``model_utils.latent_operands``: x := z,
+        dx := dz, ``latent = (B (S, N, d, d), y (S, N, d), w_pair)``, w_x := w_sindy_z; every closure is one
+        symode_loss_grad_latent launch (mse = loss_sindy_z, sym = mean |B h - y|^2).  The reference's closure, term for term:
+        the x-term enters the loss VALUE with w_pair and the GRADIENT not at all -- its compute_dx (autoencoder.py:106-108) is
+        a functional jvp without create_graph, whose result is cut from the graph, so loss_sindy_x is logged and added but
+        never differentiated.  One rank, streamed points only: ``group`` and ``statistics`` are refused."""
         self.engine = engine or get_engine()
-        if closure not in ("stream", "gram"):
-            raise SymodeError(f"closure must be 'stream' or 'gram', got {closure!r}")
+        if closure not in ("stream", "gram", "latent"):
+            raise SymodeError(f"closure must be 'stream', 'gram' or 'latent', got {closure!r}")
         self.gram = closure == "gram"
+        self.latent = closure == "latent"
+        if self.latent:
+            reversed_sym = self._latent_as_pair(x, latent, reversed_sym, group, statistics, w_x)
+        elif latent is not None:
+            raise SymodeError("latent operands are for closure='latent'")
         self.stats = None
         lib = self.engine.lib
         self.order, self.flags = int(poly_order), int(flags)
@@ -163,6 +174,26 @@ class DeviceTrainer:
             statistics.all_reduce(group)
         return statistics
 
+    @staticmethod
+    def _latent_as_pair(z, latent, reversed_sym, group, statistics, w_sindy_z):
+        """The latent operands in the place of a one-element reversed fit -- gx := y, jgx := B, n_g := 1, w_sym := w_pair --
+        so that the update and epoch-end kernels see a pair closure; the closure launch itself is _epoch_latent's."""
+        if group is not None:
+            raise SymodeError("closure='latent' does not take group=... (point shards): the multi-rank latent fit is not implemented")
+        if statistics is not None:
+            raise SymodeError("closure='latent' does not take statistics: there is no Gram form of the latent closure")
+        if reversed_sym is not None:
+            raise SymodeError("closure='latent' does not take reversed_sym: the latent fit has no symmetry regulariser")
+        if not w_sindy_z > 0:
+            raise SymodeError(f"closure='latent' needs w_sindy_z > 0 (w_x), got {w_sindy_z}: the x-term is weighed against it")
+        if latent is None or len(latent) != 3:
+            raise SymodeError("closure='latent' needs latent=(B, y, w_pair)")
+        B, y, w_pair = latent
+        ok = torch.is_tensor(z) and z.dim() == 3 and all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (B, y))
+        if not ok or tuple(y.shape) != tuple(z.shape) or tuple(B.shape) != tuple(z.shape) + (z.shape[-1],):
+            raise SymodeError("latent operands do not match z: B (S, N, d, d) and y (S, N, d) as fp32 device tensors")
+        return y.unsqueeze(1), B.unsqueeze(1), float(w_pair)
+
     def _check(self, rc, what):
         if rc != 0:
             # a launch that failed half-way may have left tickets of the one-launch reductions behind: start them afresh
@@ -216,6 +247,28 @@ class DeviceTrainer:
                                                    ctypes.c_void_p(tg.data_ptr()), st), "symode_trainer_closure")
             dist.all_reduce(self.log_test[slot], group=self.group)
 
+    def _epoch_latent(self, epoch, test_eval):
+        """One epoch of the latent fit: the descriptor cannot name a third closure kind, so the host enqueues what
+        symode_trainer_run would -- closure, update, ..., epoch end (, the closure at the epoch's final state) -- with
+        symode_loss_grad_latent as the closure, all on the current stream, no wait in between.  The launch's own w_pair is 0:
+        loss2[1] is produced whatever its weight and the gradient is that of the z-term alone, as in the reference (see
+        __init__); the update kernel weighs loss2[1] into the value by the descriptor's w_sym = w_pair."""
+        lib, st, T = self.engine.lib, self._st(), self.T
+        xi, mask = self.field("xi").data_ptr(), self.field("mask").data_ptr()
+
+        def closure(loss, grad):
+            self._check(lib.symode_loss_grad_latent(T.x, T.dx, T.jgx, T.gx, self.S, self.n_points, self.d, self.order, self.flags,
+                                                    xi, mask, T.inv_count, 0.0, loss, grad, T.workspace, T.workspace_bytes, st),
+                        "symode_loss_grad_latent")
+
+        cl_loss, cl_grad = self.field("cl_loss").data_ptr(), self.field("cl_grad").data_ptr()
+        for it in range(self.max_iter):
+            closure(cl_loss, cl_grad)
+            self._check(lib.symode_trainer_update(self._Tp, 2 if it == 0 else 1, st), "symode_trainer_update")
+        self._check(lib.symode_trainer_epoch_end(self._Tp, epoch, st), "symode_trainer_epoch_end")
+        if test_eval:
+            closure(self.log_test[epoch % self.LOG_RING].data_ptr(), self.field("test_grad").data_ptr())
+
     # -- the fit --------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def fit(self, P0, num_epochs, mask0=None, on_epoch=None, test_eval=False):
@@ -243,6 +296,8 @@ class DeviceTrainer:
         def enqueue(e):
             if self.distributed:
                 self._epoch_sharded(e, test_eval)
+            elif self.latent:
+                self._epoch_latent(e, test_eval)
             else:
                 self._check(lib.symode_trainer_run(self._Tp, e, 1, 1 if test_eval else 0, self._st()), "symode_trainer_run")
             ev = torch.cuda.Event()

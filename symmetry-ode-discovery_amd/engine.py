@@ -58,6 +58,8 @@ _SIGNATURES = {
     "symode_loss_grad_reversed_constj": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int,
                                                  c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
                                                  c_void_p]),
+    "symode_loss_grad_latent": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
+                                        c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
     "symode_symreg_reversed_gram": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_size_t, c_void_p]),
@@ -557,6 +559,27 @@ class HipEngine:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
         rev = self._reversed_operands(x, gx, jgx, compact_ok=True)
         return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws)
+
+    def loss_grad_latent(self, z, dz, B, y, xi, mask, order, flags=0, w_pair=1.0, inv_count=None, out=None, ws=None):
+        """The closure of the latent fit in ONE pass (symode_loss_grad_latent): z, dz, y (S, N, d) or (N, d), B (S, N, d, d)
+        or (N, d, d) -- the operands of ``model_utils.latent_operands`` --, xi / mask (S, d, p) or (d, p).
+        Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mean |h(z) - dz|^2, mean |B h(z) - y|^2), grad = d(loss2[0] + w_pair *
+        loss2[1])/dXi (S, d, p) [or (d, p)].  ``xi`` / ``out`` / ``ws`` / ``inv_count`` as in loss_grad."""
+        z, dz, B, y = self._dev(z, "z"), self._dev(dz, "dz"), self._dev(B, "B"), self._dev(y, "y")
+        batched, S, n, d = self._problems(z)
+        if dz.shape != z.shape or y.shape != z.shape or tuple(B.shape) != tuple(z.shape) + (d,):
+            raise SymodeError(f"dz {tuple(dz.shape)} / y {tuple(y.shape)} / B {tuple(B.shape)} do not match z {tuple(z.shape)}")
+        for name, t in (("dz", dz), ("B", B), ("y", y)):
+            if t.device != z.device:
+                raise SymodeError(f"{name} is on {t.device}, z on {z.device}: all tensors of one launch live on one device")
+        xi, mask, p = self._coef(xi, mask, d, order, flags, S, pinned_ok=True)
+        loss, grad, ws, inv = self._closure_prologue(z, S, n, d, p, order, flags, 2, out, ws, inv_count)
+        self._check(self.lib.symode_loss_grad_latent(self._ptr(z), self._ptr(dz), self._ptr(B), self._ptr(y), S, n, d, order, flags,
+                                                     self._ptr(xi), self._ptr(mask), inv, float(w_pair), self._ptr(loss),
+                                                     self._ptr(grad), self._ptr(ws), ws.numel() * 8, self._stream(z)),
+                    "symode_loss_grad_latent")
+        loss, grad = loss.reshape(S, 2), grad.reshape(S, d, p)
+        return (loss, grad) if batched else (loss[0], grad[0])
 
     def symreg_reversed_gram(self, x, gx, jgx, order, flags=0):
         """fp64 Gram matrix R of the reversed regulariser (raw sums over points and group elements, no 1/(N d)):

@@ -63,7 +63,9 @@ _MAIN_ARGS = [
 # per evaluation (gram_closure.py).  --device_adam runs the plain minibatch Adam fit (--sindy_optimizer adam, no latent space;
 # a symmetry regulariser only as --sym_reg_type r with --fix_laligan) as whole epochs per launch on the device
 # (device_adam.py) instead of one Python iteration per batch.
-_EXTRA_ARGS = [("gram_closure", _FLAG, None), ("device_adam", _FLAG, None)]
+# --fused_latent (with --use_latent and the L-BFGS optimiser; ignored without --use_latent) runs the latent fit with one fused
+# closure kernel and the device trainer (train._train_latent_on_device) instead of autograd through the autoencoder per closure.
+_EXTRA_ARGS = [("gram_closure", _FLAG, None), ("device_adam", _FLAG, None), ("fused_latent", _FLAG, None)]
 
 # parser_utils.py:122-171
 _SINDY_ARGS = [

@@ -26,8 +26,8 @@ import torch
 from .batched import allreduce_sums
 from .host_closure import _HostParams, _HostShadow, _NoZeroGrad  # noqa: F401  (their old home: bench.py, tools/ and tests import them from here)
 from .host_lbfgs import _new_lbfgs, _NumpyLBFGS, _PlainLBFGS  # noqa: F401
-from .model_utils import (PRECOMPUTE_CHUNK, _EulerFlow, make_fsymmreg_pttrain, make_rsymmreg_pttrain, make_symmreg_pttrain,
-                          odeint, reversed_operands, symmreg_linear)
+from .model_utils import (PRECOMPUTE_CHUNK, _EulerFlow, latent_operands, make_fsymmreg_pttrain, make_rsymmreg_pttrain,
+                          make_symmreg_pttrain, odeint, reversed_operands, symmreg_linear)
 from .sindy import solve_SINDy, solve_SINDy_one_step
 
 try:                                    # wandb is optional (absent offline; README: WANDB_MODE=disabled)
@@ -369,7 +369,7 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
     closure re-evaluated at the epoch's final coefficients and mask.  ``group``: x, dx are this rank's point shard.
     ``gram_closure``: the closure is the quadratic form of the batch's fp64 Gram matrices (gram_closure.py), built in one
     pass and summed over the ranks in one all-reduce; the fit itself then needs no collective."""
-    from .device_lbfgs import EVENT_FINAL, EVENT_NAN, EVENT_THRESHOLD_CONVERGED, EVENT_THRESHOLD_PERIOD, DeviceTrainer
+    from .device_lbfgs import DeviceTrainer
     d = x.shape[-1]
     rev = None
     if w_sym_reg > 0.0:
@@ -386,6 +386,22 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
                        l1=sindy_reg_type == 'l1', engine=regressor.engine, detail=True, group=group,
                        closure='gram' if gram_closure else 'stream')
 
+    def terms(rec):
+        out = {'loss_sindy_x': float(rec['mse'][0])}
+        if rev is not None:
+            out['loss_sym_reg'] = float(rec['sym'][0])
+        if sindy_reg_type == 'l1':
+            out['loss_sindy_reg'] = float(rec['l1'][0])
+        return out
+
+    return _fit_on_device(tr, regressor, P0, mask_before, num_epochs, threshold, terms, losses, report, test_log)
+
+
+def _fit_on_device(tr, regressor, P0, mask_before, num_epochs, threshold, terms, losses, report, test_log):
+    """Run a DeviceTrainer and produce from its per-epoch records what the reference produces per epoch, in its order
+    (shared by _train_on_device and _train_latent_on_device).  ``terms(record)``: the epoch's entries of ``losses``."""
+    from .device_lbfgs import EVENT_FINAL, EVENT_NAN, EVENT_THRESHOLD_CONVERGED, EVENT_THRESHOLD_PERIOD
+    coef = regressor.coef
     state = {'mask_before': mask_before}
 
     def on_epoch(epoch, rec):
@@ -393,11 +409,7 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
         if code == EVENT_NAN:                                                          # train.py:697-699
             print(f'NaN encountered at iteration {epoch}; exit training.')
             return True
-        losses['loss_sindy_x'] = float(rec['mse'][0])
-        if rev is not None:
-            losses['loss_sym_reg'] = float(rec['sym'][0])
-        if sindy_reg_type == 'l1':
-            losses['loss_sindy_reg'] = float(rec['l1'][0])
+        losses.update(terms(rec))
         adopt = partial(coef.adopt, regressor, rec['params'][0], rec['mask'][0])      # a host state into the regressor
         if code == EVENT_FINAL:                                                        # train.py:709-714
             print(f'Final convergence reached at iteration {epoch}; exit training.')
@@ -420,15 +432,62 @@ def _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_si
     return out
 
 
+def _train_latent_on_device(regressor, x, dx, autoencoder, num_epochs, lr_sindy, st_freq, threshold, w_sindy_z, w_sindy_x,
+                            sindy_reg_type, w_sindy_reg, losses, report, test_log=None):
+    """The latent L-BFGS fit (train.py:647-661) as _train_on_device runs the observed-space one: z, dz and the QR-reduced
+    decoder Jacobian are computed once (model_utils.latent_operands -- the autoencoder is frozen data under this optimiser),
+    every closure is one symode_loss_grad_latent launch, optimiser and epoch logic stay on the device.  Same messages, same
+    ``report`` records (loss_sindy_z, loss_sindy_x [, loss_sindy_reg]), same "test" line (test_loss_sindy_z at the epoch's
+    final coefficients and mask), same checkpoints as the host_params route."""
+    from .device_lbfgs import DeviceTrainer
+    z, dz, B, y, e0, D = latent_operands(x, dx, autoencoder)
+    n, d = z.shape
+    x_const = e0 / (n * D)                       # the part of loss_sindy_x no coefficient reaches: |dx - Q Q^T dx|^2
+    coef = regressor.coef
+    with torch.no_grad():
+        P0 = coef.pack(regressor).cpu()[None]
+        mask_before = regressor.mask.detach().cpu().numpy().copy()
+    # the trainer's loss value is w_x * (loss2[0] + w_pair * loss2[1]) with both sums under 1 / (n d); like the reference's,
+    # its gradient is the z-term's alone (compute_dx cuts the x-term from the graph: device_lbfgs.DeviceTrainer)
+    tr = DeviceTrainer(z[None].float(), dz[None].float(), regressor.poly_order, regressor.flags, coef=coef, lr=lr_sindy,
+                       threshold=threshold, st_freq=st_freq, w_x=w_sindy_z, w_reg=w_sindy_reg if sindy_reg_type == 'l1' else 0.0,
+                       l1=sindy_reg_type == 'l1', engine=regressor.engine, detail=True, closure='latent',
+                       latent=(B[None].float(), y[None].float(), (w_sindy_x / w_sindy_z) * (d / D)))
+
+    def terms(rec):
+        out = {'loss_sindy_z': float(rec['mse'][0]), 'loss_sindy_x': float(rec['sym'][0]) * d / D + x_const}
+        if sindy_reg_type == 'l1':
+            out['loss_sindy_reg'] = float(rec['l1'][0])
+        return out
+
+    return _fit_on_device(tr, regressor, P0, mask_before, num_epochs, threshold, terms, losses, report, test_log)
+
+
 def _lbfgs_route(is_cuda, use_latent, w_sym_reg, sym_reg_type, w_sindy_x, sindy_reg_type, frozen, group, host_lbfgs,
-                 torch_lbfgs, numpy_lbfgs, gram_closure, torch_optim_env, mask_numel, has_trainer):
-    """Which of the four ways train_SIGED_lbfgs runs a fit ("The four routes"), from its arguments alone.
+                 torch_lbfgs, numpy_lbfgs, gram_closure, torch_optim_env, mask_numel, has_trainer, fused_latent=False,
+                 w_sindy_z=1.0, has_latent=True):
+    """Which of the five ways train_SIGED_lbfgs runs a fit ("The five routes"), from its arguments alone.
     ``fused``: the closure is made only of fused kernels.  'device': a fused fit on _train_on_device, the DEFAULT; 'shadow':
     a fused fit that asked for torch's / numpy's optimiser or that the device trainer does not cover, variables on a
     _HostShadow, one rank; 'host_params': an autograd closure on the GPU, variables on a _HostParams; 'plain': the
-    regressor's own parameters (CPU, host_lbfgs=False).  ``torch_optim_env``: SYMODE_TORCH_OPTIM=1."""
+    regressor's own parameters (CPU, host_lbfgs=False).  ``torch_optim_env``: SYMODE_TORCH_OPTIM=1.
+    'latent' (opt-in, ``fused_latent`` with ``use_latent``; ignored without it): the latent fit on _train_latent_on_device;
+    what it does not cover is refused by name, never rerouted.  ``w_sindy_z`` and ``has_latent`` (the library exports
+    symode_loss_grad_latent) are read on that route only."""
     if group is not None and use_latent:
         raise ValueError('group=... (point shards) is implemented for the non-latent fit.')
+    if fused_latent and use_latent:
+        needs = (('a GPU', is_cuda), ('host_lbfgs=True', host_lbfgs),
+                 ('the device optimiser: no torch_lbfgs / numpy_lbfgs / SYMODE_TORCH_OPTIM=1',
+                  not (torch_lbfgs or numpy_lbfgs or torch_optim_env)),
+                 ('w_sindy_z > 0', w_sindy_z > 0), ("sindy_reg_type 'l1' or 'none'", sindy_reg_type in ('l1', 'none')),
+                 ('at most 256 coefficients', mask_numel <= 256),
+                 ('symode_loss_grad_latent and the device trainer in the library', has_latent and has_trainer),
+                 ('gram_closure=False: the latent closure has no Gram form', not gram_closure))
+        for what, ok in needs:
+            if not ok:
+                raise ValueError(f'fused_latent=True needs {what}')
+        return 'latent'
     fused = is_cuda and not use_latent and host_lbfgs and (w_sym_reg <= 0.0 or (sym_reg_type == 'r' and frozen))
     if (fused and not (torch_lbfgs or numpy_lbfgs or torch_optim_env) and w_sindy_x > 0
             and sindy_reg_type in ('l1', 'none') and has_trainer and mask_numel <= 256):
@@ -590,11 +649,11 @@ def _test_log(epoch, value=None, *, regressor, x, dx, autoencoder, test_loader, 
     n = len(test_loader) if hasattr(test_loader, '__len__') else sum(1 for _ in test_loader)
     if n > 0:
         with torch.no_grad():
-            if use_latent:
+            if use_latent and value is None:
                 z, _ = autoencoder(x)
                 key, v = 'test_loss_sindy_z', regressor.mse_loss(z, autoencoder.compute_dz(x, dx)).item()
             elif value is not None:
-                key, v = 'test_loss_sindy_x', value
+                key, v = 'test_loss_sindy_z' if use_latent else 'test_loss_sindy_x', value
             elif group is not None:                                                # this rank's shard -> the batch mean
                 n_loc = float(x.numel())
                 red = allreduce_sums([regressor.mse_loss(x, dx) * n_loc, torch.tensor(n_loc, device=x.device)], [], group)
@@ -616,7 +675,7 @@ def train_SIGED_lbfgs(
     autoencoder, generator,  # symmetry discovery model
     regressor, regressor_dst, use_latent, distill_latent, lr_sindy, w_sindy_z, w_sindy_x,  # SINDy
     sindy_reg_type, w_sindy_reg, sym_reg_type, w_sym_reg, st_freq, threshold, int_t, int_dt,  # SINDy
-    gram_closure=False, **kwargs
+    gram_closure=False, fused_latent=False, **kwargs
 ):
     """Full-batch L-BFGS fit (train.py:617-852): read the one batch, pick the route (_lbfgs_route), build that route's
     closure, run phase 1, optionally distill the latent equation into data space (phase 2).
@@ -644,7 +703,8 @@ def train_SIGED_lbfgs(
         numpy_lbfgs=kwargs.get('numpy_lbfgs', False), gram_closure=gram_closure,
         frozen=not any(p.requires_grad for m in (autoencoder, generator) for p in m.parameters()),
         torch_optim_env=os.environ.get('SYMODE_TORCH_OPTIM', '0') == '1', mask_numel=regressor.mask.numel(),
-        has_trainer=hasattr(getattr(regressor.engine, 'lib', None), 'symode_trainer_run'))
+        has_trainer=hasattr(getattr(regressor.engine, 'lib', None), 'symode_trainer_run'), fused_latent=fused_latent,
+        w_sindy_z=w_sindy_z, has_latent=hasattr(getattr(regressor.engine, 'lib', None), 'symode_loss_grad_latent'))
     report = _EpochReport(regressor, log_interval, save_interval, save_dir, kwargs.get('print_eq', False))
     test_log = partial(_test_log, regressor=regressor, x=x, dx=dx, autoencoder=autoencoder, test_loader=test_loader,
                        use_latent=use_latent, group=group)
@@ -652,6 +712,9 @@ def train_SIGED_lbfgs(
         _train_on_device(regressor, x, dx, autoencoder, generator, num_epochs, lr_sindy, st_freq, threshold, w_sindy_x,
                          sindy_reg_type, w_sindy_reg, w_sym_reg, losses, report, test_log=test_log, group=group,
                          gram_closure=gram_closure)
+    elif route == 'latent':
+        _train_latent_on_device(regressor, x, dx, autoencoder, num_epochs, lr_sindy, st_freq, threshold, w_sindy_z, w_sindy_x,
+                                sindy_reg_type, w_sindy_reg, losses, report, test_log=test_log)
     else:
         if route == 'shadow':
             # host shadow: (n_g, N, d) / (n_g, N, d, d) as they come, the closure weighs the regulariser by w_sym_reg itself
