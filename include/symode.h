@@ -355,11 +355,14 @@ int symode_lbfgs_accept(const float* new_loss, const float* new_g, float* loss, 
                         const float* params, float w_x, float w_reg, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
- * Device-resident L-BFGS trainer: train_SIGED_lbfgs (non-latent branch) for n_problems independent problems with NOTHING
- * on the host between two epochs.  An epoch is
+ * Device-resident L-BFGS trainer: train_SIGED_lbfgs for n_problems independent problems with NOTHING on the host between
+ * two epochs.  An epoch is
  *     closure, BEGIN-update, (closure, ACCEPT-update) x (max_iter - 1), epoch-end
- * -- 2 max_iter + 1 launches: the closure is symode_loss_grad (or symode_loss_grad_reversed when gx / jgx are given), the
- * update launches are the kernel of symode_lbfgs_accept_update extended by the coefficient map of the equivariance
+ * -- 2 max_iter + 1 launches.  The closure is one of three, named by the descriptor's `closure`:
+ *     SYMODE_CLOSURE_STREAM  symode_loss_grad, or symode_loss_grad_reversed when n_g > 0 (one pass over the points),
+ *     SYMODE_CLOSURE_GRAM    symode_quad_closure (the quadratic form of matrices built once; no point data),
+ *     SYMODE_CLOSURE_LATENT  symode_loss_grad_latent (the latent fit on operands computed once).
+ * The update launches are the kernel of symode_lbfgs_accept_update extended by the coefficient map of the equivariance
  * constraint (Xi = reshape(Q beta) + const and its chain rule, sindy.py:169-176, formed inside the launch), and the
  * epoch-end launch is the per-epoch logic of train.py:697-725: NaN guard, the two update norms, convergence- / period-
  * triggered thresholding (strict >, monotone, sindy.py:192-195) with optimiser reset, twice-converged stop.  Every epoch
@@ -367,11 +370,14 @@ int symode_lbfgs_accept(const float* new_loss, const float* new_g, float* loss, 
  * may be pinned host memory: the host reads it after synchronising on the epoch and produces the reference's prints,
  * wandb record and checkpoints from it.
  * replaces: train.py:630-725 (torch.optim.LBFGS.step + the epoch logic), per seed. */
+#define SYMODE_CLOSURE_STREAM 0 /* symode_loss_grad, or symode_loss_grad_reversed when n_g > 0 */
+#define SYMODE_CLOSURE_GRAM 1   /* symode_quad_closure on aug_gram / rev_gram */
+#define SYMODE_CLOSURE_LATENT 2 /* symode_loss_grad_latent */
 typedef struct symode_trainer {
     /* closure data, read only: S = n_problems problems back to back */
     const float* x;            /* (S, n_points, d) */
     const float* dx;           /* (S, n_points, d) */
-    const float* gx;           /* (S, n_g, n_points, d) reversed-regulariser operands, or NULL (plain MSE closure) */
+    const float* gx;           /* (S, n_g, n_points, d) reversed-regulariser operands; n_g == 0: not read (plain MSE) */
     const float* jgx;          /* (S, n_g, n_points, d, d) */
     int n_g;
     float w_sym;               /* regulariser weight relative to the MSE: data term = mse + w_sym * regulariser */
@@ -411,11 +417,24 @@ typedef struct symode_trainer {
     float* log_mask;
     float* log_params;
     int log_epochs;
-    /* Gram-form closure (symode_quad_closure), or NULL: with aug_gram (S, p+d, p+d) fp64 every closure of the trainer is the
+    /* Gram-form closure (SYMODE_CLOSURE_GRAM): with aug_gram (S, p+d, p+d) fp64 every closure of the trainer is the
      * quadratic form of these matrices at inv_count / w_sym, and x, dx, gx, jgx and workspace may be NULL; rev_gram
      * (S, d p, d p) fp64 or NULL adds the reversed regulariser (then the closure is the (mse, regulariser) pair). */
     const double* aug_gram;
     const double* rev_gram;
+    /* Which closure every evaluation of this trainer is (SYMODE_CLOSURE_*).  The kind alone decides: what it needs is
+     * checked before anything is launched, and pointers that belong to another kind are never read.
+     *   STREAM  symode_loss_grad on x, dx (workspace), or symode_loss_grad_reversed on x, dx, gx, jgx when n_g > 0 (then
+     *           the closure is the (mse, regulariser) pair);
+     *   GRAM    symode_quad_closure on aug_gram (/ rev_gram: the pair), see above;
+     *   LATENT  symode_loss_grad_latent on x := z, dx := dz, latent_B, latent_y (workspace); always the pair
+     *           (loss_sindy_z, loss2[1]).  w_sym is the weight of loss2[1] in the loss VALUE; the closure itself is launched
+     *           with w_pair = 0, so the gradient is the z-term's alone -- as in the reference, whose compute_dx
+     *           (autoencoder.py:106-108) is a functional jvp without create_graph: its result is cut from the graph, so
+     *           loss_sindy_x is logged and added but never differentiated. */
+    int closure;
+    const float* latent_B;     /* (S, n_points, d, d) */
+    const float* latent_y;     /* (S, n_points, d) */
 } symode_trainer;
 
 #define SYMODE_TRAINER_FIELDS 29

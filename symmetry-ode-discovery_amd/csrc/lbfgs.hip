@@ -678,7 +678,12 @@ inline size_t trainer_layout(long S, int n, int dp, int H, bool constrained, siz
     return at;
 }
 
+// The closure the descriptor names: which entry point evaluates it, and whether it yields the (mse, regulariser) pair or the
+// mse alone.  Made and validated by trainer_state; only the `case`s of symode_trainer_closure read a kind's pointers again.
+struct TrainerClosure { int kind; bool pair; };
+
 struct TrainerState {
+    TrainerClosure closure;
     float *params, *xi, *mask, *cl_loss, *cl_grad, *g, *loss;
     unsigned char* act;
     long* n_iter;
@@ -700,9 +705,16 @@ inline int trainer_state(const symode_trainer* T, TrainerState& st, int& dp) {
     if (T->n_problems < 1 || T->n_problems > 65535 || T->n_points < 1 || T->n_params != (con ? T->r + T->d : dp) || T->n_params > WAVE * LB_MAXC ||
         dp > WAVE * LB_MAXC || T->history < 1 || T->history > LB_MAXH || T->max_iter < 1 || T->log_epochs < 1 || (con && T->r < 1))
         return SYMODE_E_BADSIZE;
-    if (!T->state || !T->log || !T->log_test) return SYMODE_E_NULLPTR;
-    // the Gram form needs no point data; the streaming form needs the points and the reduction scratch
-    if (!T->aug_gram && (!T->x || !T->dx || !T->workspace || (T->gx && !T->jgx))) return SYMODE_E_NULLPTR;
+    // per kind: what the closure reads (the streamed kinds: the points and the reduction scratch) and whether it is the pair
+    auto points = [T] { return T->x && T->dx && T->workspace; };
+    bool ok;
+    switch (T->closure) {
+        case SYMODE_CLOSURE_STREAM: st.closure = {T->closure, T->n_g > 0}; ok = points() && (T->n_g <= 0 || (T->gx && T->jgx)); break;
+        case SYMODE_CLOSURE_GRAM: st.closure = {T->closure, T->rev_gram != nullptr}; ok = T->aug_gram != nullptr; break;
+        case SYMODE_CLOSURE_LATENT: st.closure = {T->closure, true}; ok = points() && T->latent_B && T->latent_y; break;
+        default: return SYMODE_E_BADSIZE;
+    }
+    if (!T->state || !T->log || !T->log_test || !ok) return SYMODE_E_NULLPTR;
     size_t off[TF_COUNT_FIELDS];
     if (T->state_bytes < trainer_layout(T->n_problems, T->n_params, dp, T->history, con, off)) return SYMODE_E_WORKSPACE;
     if (((uintptr_t)T->state % 256) != 0) return SYMODE_E_ALIGN;
@@ -843,9 +855,6 @@ __global__ __launch_bounds__(WAVE) void trainer_epoch_kernel(EpochArgs a) {
     }
 }
 
-// the closure yields the (mse, regulariser) pair: streaming form with (g(x), J_g(x)), Gram form with the regulariser's Gram
-inline int trainer_pair(const symode_trainer* T) { return T->aug_gram ? T->rev_gram != nullptr : T->gx != nullptr; }
-
 inline XiMap trainer_map(const symode_trainer* T, const TrainerState& st, int dp) {
     return XiMap{T->q_eff, st.xi, T->r, dp, dp / T->d, T->allow_constant};
 }
@@ -885,14 +894,22 @@ extern "C" int symode_trainer_closure(const symode_trainer* T, float* loss_out, 
     if (int rc = trainer_state(T, st, dp)) return rc;
     float* lo = loss_out ? loss_out : st.cl_loss;
     float* go = grad_out ? grad_out : st.cl_grad;
-    if (T->aug_gram != nullptr)
-        return symode_quad_closure(T->aug_gram, T->rev_gram, T->n_problems, T->d, dp / T->d, st.xi, st.mask, (double)T->inv_count,
-                                   T->w_sym, lo, go, stream);
-    if (T->gx != nullptr)
-        return symode_loss_grad_reversed(T->x, T->dx, T->gx, T->jgx, T->n_g, T->n_problems, T->n_points, T->d, T->order, T->flags,
-                                         st.xi, st.mask, T->inv_count, T->w_sym, lo, go, T->workspace, T->workspace_bytes, stream);
-    return symode_loss_grad(T->x, T->dx, T->n_problems, T->n_points, T->d, T->order, T->flags, st.xi, st.mask, T->inv_count, lo, go,
-                            T->workspace, T->workspace_bytes, stream);
+    switch (st.closure.kind) {
+        case SYMODE_CLOSURE_GRAM:
+            return symode_quad_closure(T->aug_gram, T->rev_gram, T->n_problems, T->d, dp / T->d, st.xi, st.mask, (double)T->inv_count,
+                                       T->w_sym, lo, go, stream);
+        case SYMODE_CLOSURE_LATENT:                          // w_pair = 0: the gradient is the z-term's alone (symode.h)
+            return symode_loss_grad_latent(T->x, T->dx, T->latent_B, T->latent_y, T->n_problems, T->n_points, T->d, T->order,
+                                           T->flags, st.xi, st.mask, T->inv_count, 0.0f, lo, go, T->workspace, T->workspace_bytes,
+                                           stream);
+        default:                                             // SYMODE_CLOSURE_STREAM: trainer_state lets no fourth value through
+            if (st.closure.pair)
+                return symode_loss_grad_reversed(T->x, T->dx, T->gx, T->jgx, T->n_g, T->n_problems, T->n_points, T->d, T->order,
+                                                 T->flags, st.xi, st.mask, T->inv_count, T->w_sym, lo, go, T->workspace,
+                                                 T->workspace_bytes, stream);
+            return symode_loss_grad(T->x, T->dx, T->n_problems, T->n_points, T->d, T->order, T->flags, st.xi, st.mask, T->inv_count,
+                                    lo, go, T->workspace, T->workspace_bytes, stream);
+    }
 }
 
 extern "C" int symode_trainer_update(const symode_trainer* T, int mode, void* stream) {
@@ -901,10 +918,9 @@ extern "C" int symode_trainer_update(const symode_trainer* T, int mode, void* st
     int dp;
     if (int rc = trainer_state(T, st, dp)) return rc;
     if (mode != LB_ACCEPT && mode != LB_BEGIN) return SYMODE_E_BADSIZE;
-    const int pair = trainer_pair(T);
     return launch_lbfgs_update(mode, st.params, st.g, st.loss, st.act, st.n_iter, st.d, st.t, st.old_dirs, st.old_stps, st.ro, st.head,
                                st.count, st.h_diag, st.prev_g, st.prev_loss, T->n_problems, T->n_params, T->history, T->lr, T->tol_change,
-                               AcceptArgs{st.cl_loss, st.cl_grad, T->tol_grad, 1, T->w_x, T->l1 ? T->w_reg : 0.0f, pair, T->w_sym},
+                               AcceptArgs{st.cl_loss, st.cl_grad, T->tol_grad, 1, T->w_x, T->l1 ? T->w_reg : 0.0f, st.closure.pair, T->w_sym},
                                trainer_map(T, st, dp), TrainerHook{st.done, st.l1_last}, stream);
 }
 
@@ -917,7 +933,7 @@ extern "C" int symode_trainer_epoch_end(const symode_trainer* T, int epoch, void
     if ((T->log_xi == nullptr) != (T->log_mask == nullptr) || (T->log_xi == nullptr) != (T->log_params == nullptr)) return SYMODE_E_NULLPTR;
     EpochArgs a{st.params, st.prev, st.pprev, st.xi, st.mask, st.n_iter, st.head, st.count, st.h_diag, st.n_iters, st.done, st.nan,
                 st.finished, st.epochs, st.near, st.cl_loss, st.l1_last, T->log, T->log_xi, T->log_mask, T->log_params, T->n_params,
-                T->q_eff ? T->r : 0, dp, trainer_pair(T), T->st_freq, epoch, epoch % T->log_epochs, T->threshold, T->tol_update,
+                T->q_eff ? T->r : 0, dp, st.closure.pair, T->st_freq, epoch, epoch % T->log_epochs, T->threshold, T->tol_update,
                 T->near_band};
     trainer_epoch_kernel<<<dim3((unsigned)T->n_problems), dim3(WAVE), 0, (hipStream_t)stream>>>(a);
     hipError_t e = hipGetLastError();

@@ -1,7 +1,7 @@
-"""``train_SIGED_lbfgs`` (non-latent branch, reference train.py:617-766) for S problems with the optimiser AND the
-per-epoch logic resident on the GPU: the host enqueues whole epochs (``symode_trainer_run``: closure, optimiser launch,
-... , epoch-end launch -- 2 * max_iter + 1 launches, include/symode.h) and reads one small record per epoch from
-pinned memory.  No stock torch GPU op runs between the first and the last epoch, so a one-seed process pays no
+"""``train_SIGED_lbfgs`` (reference train.py:617-766; its latent branch on precomputed operands) for S problems with the
+optimiser AND the per-epoch logic resident on the GPU: the host enqueues whole epochs (``symode_trainer_run``: closure,
+optimiser launch, ... , epoch-end launch -- 2 * max_iter + 1 launches, include/symode.h) and reads one small record per
+epoch from pinned memory.  No stock torch GPU op runs between the first and the last epoch, so a one-seed process pays no
 code-object loading beyond this library's own kernels.
 
 The arithmetic is torch.optim.LBFGS's (no line search) statement by statement, as in ``sweep.BatchedLBFGS`` (the
@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 
 from .coef_map import CoefMap
-from .engine import TRAINER_FIELDS, SymodeError, TrainerDesc, get_engine
+from .engine import CLOSURE_GRAM, CLOSURE_LATENT, CLOSURE_STREAM, TRAINER_FIELDS, SymodeError, TrainerDesc, get_engine
 from .gram_closure import GramStatistics
 
 NEAR_THRESHOLD_BAND = 1e-4            # sindy.NEAR_THRESHOLD_BAND; repeated here to keep imports light
@@ -43,27 +43,29 @@ class DeviceTrainer:
         runs without any collective and holds no reference to the point data.
         ``closure="latent"``: the latent fit (train.py:647-661) on the operands of ``model_utils.latent_operands``: x := z,
         dx := dz, ``latent = (B (S, N, d, d), y (S, N, d), w_pair)``, w_x := w_sindy_z; every closure is one
-        symode_loss_grad_latent launch (mse = loss_sindy_z, sym = mean |B h - y|^2).  The reference's closure, term for term:
-        the x-term enters the loss VALUE with w_pair and the GRADIENT not at all -- its compute_dx (autoencoder.py:106-108) is
-        a functional jvp without create_graph, whose result is cut from the graph, so loss_sindy_x is logged and added but
-        never differentiated.  One rank, streamed points only: ``group`` and ``statistics`` are refused."""
+        symode_loss_grad_latent launch (mse = loss_sindy_z, sym = mean |B h - y|^2).  The x-term enters the loss VALUE with
+        w_pair and the GRADIENT not at all, as in the reference (SYMODE_CLOSURE_LATENT, include/symode.h).  One rank, streamed
+        points only: ``group`` and ``statistics`` are refused."""
         self.engine = engine or get_engine()
-        if closure not in ("stream", "gram", "latent"):
+        kinds = {"stream": CLOSURE_STREAM, "gram": CLOSURE_GRAM, "latent": CLOSURE_LATENT}
+        if closure not in kinds:
             raise SymodeError(f"closure must be 'stream', 'gram' or 'latent', got {closure!r}")
-        self.gram = closure == "gram"
-        self.latent = closure == "latent"
+        self.kind = kinds[closure]
+        self.gram, self.latent = self.kind == CLOSURE_GRAM, self.kind == CLOSURE_LATENT
+        self.order, self.flags = int(poly_order), int(flags)
+        # --- the closure kind and its operands: the only per-kind part of the set-up (with _descriptor's branch)
+        self.stats = self.sym = self.latent_ops = self.x = self.dx = None
+        self.pair = self.latent or reversed_sym is not None
+        self.w_sym = float(reversed_sym[2]) if reversed_sym is not None else 0.0
         if self.latent:
-            reversed_sym = self._latent_as_pair(x, latent, reversed_sym, group, statistics, w_x)
+            B, y, self.w_sym = self._latent_operands(x, latent, reversed_sym, group, statistics, w_x)
+            self.latent_ops = (B.contiguous(), y.contiguous())
         elif latent is not None:
             raise SymodeError("latent operands are for closure='latent'")
-        self.stats = None
-        lib = self.engine.lib
-        self.order, self.flags = int(poly_order), int(flags)
         if self.gram:
             self.stats = self._gram_statistics(x, dx, reversed_sym, statistics, group)
             self.S, self.d, dev = self.stats.S, self.stats.d, self.stats.device
             self.n_points = self.stats.count
-            self.x = self.dx = None
             if inv_count is None:
                 inv_count = self.stats.inv_count()
             group = None                                      # the fit itself needs no collective
@@ -75,6 +77,11 @@ class DeviceTrainer:
             self.x, self.dx = x.contiguous(), dx.contiguous()
             self.S, self.n_points, self.d = x.shape
             dev = x.device
+            if reversed_sym is not None:
+                gx, jgx, weight = reversed_sym
+                if gx.dim() != 4 or gx.shape[0] != self.S or tuple(gx.shape[2:]) != tuple(x.shape[1:]) or tuple(jgx.shape) != tuple(gx.shape) + (self.d,):
+                    raise SymodeError("reversed_sym operands do not match x")
+                self.sym = (gx.contiguous(), jgx.contiguous(), float(weight))
         self.device = dev
         self.p = self.engine.lib_size(self.d, self.order, self.flags)
         self.dp = self.d * self.p
@@ -89,29 +96,17 @@ class DeviceTrainer:
             self.q_eff = torch.from_numpy(self.coef.effective_Q()).to(dev)
         if self.n > 256 or self.dp > 256 or history > 128:
             raise SymodeError("DeviceTrainer handles at most 256 parameters / coefficients and 128 curvature pairs")
-        self.sym = None
-        self.pair = reversed_sym is not None
-        self.w_sym = float(reversed_sym[2]) if reversed_sym is not None else 0.0
-        if reversed_sym is not None and not self.gram:
-            gx, jgx, weight = reversed_sym
-            if gx.dim() != 4 or gx.shape[0] != self.S or tuple(gx.shape[2:]) != tuple(x.shape[1:]) or tuple(jgx.shape) != tuple(gx.shape) + (self.d,):
-                raise SymodeError("reversed_sym operands do not match x")
-            self.sym = (gx.contiguous(), jgx.contiguous(), float(weight))
         self.detail = (self.S <= 64) if detail is None else bool(detail)
         self.distributed = group is not None
         # --- state block: ONE allocation, laid out by the library
         offs = (ctypes.c_size_t * len(TRAINER_FIELDS))()
-        nbytes = lib.symode_trainer_layout(self.S, self.n, self.dp, history, 1 if self.q_eff is not None else 0, offs)
+        nbytes = self.engine.lib.symode_trainer_layout(self.S, self.n, self.dp, history, 1 if self.q_eff is not None else 0, offs)
         if nbytes == 0:
             raise SymodeError("symode_trainer_layout refused the problem sizes")
         self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self._off = dict(zip(TRAINER_FIELDS, [int(o) for o in offs]))
         self._shape = {"params": (self.S, self.n), "xi": (self.S, self.d, self.p), "mask": (self.S, self.d, self.p),
                        "cl_loss": (self.S, 2), "cl_grad": (self.S, self.dp), "g": (self.S, self.n), "loss": (self.S,)}
-        self.ws = None
-        if not self.gram:
-            ws_bytes = lib.symode_workspace_bytes(self.d, self.order, self.flags, self.S, self.n_points)
-            self.ws = self.engine.new_workspace(dev, ws_bytes)
         # --- per-epoch records: pinned host memory the kernels write directly (sharded runs: device memory, copied)
         R = self.LOG_RING
         mk = (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)) if self.distributed else \
@@ -126,37 +121,42 @@ class DeviceTrainer:
             cnt = torch.tensor([float(self.n_points)], dtype=torch.float64, device=dev)
             dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=group)
             n_global = int(cnt.item())
+        self.T = self._descriptor(float(inv_count) if inv_count is not None else 1.0 / (n_global * self.d), w_x, w_reg, l1, lr,
+                                  tol_grad, tol_change, max_iter, history, threshold, tol, st_freq)
+        self._Tp = ctypes.byref(self.T)
+        self.max_iter = int(max_iter)
+        self.threshold = float(threshold)
+
+    def _descriptor(self, inv_count, w_x, w_reg, l1, lr, tol_grad, tol_change, max_iter, history, threshold, tol, st_freq):
+        """The symode_trainer of this fit: the closure kind with the operands it names (what it does not name stays NULL / 0),
+        then what every kind shares.  The streamed kinds get their reduction scratch here."""
         T = TrainerDesc()
+        T.closure, T.w_sym = self.kind, self.w_sym
+        self.ws = None
         if self.gram:
-            T.x = T.dx = None
             T.aug_gram = self.stats.G.data_ptr()
             T.rev_gram = self.stats.R.data_ptr() if self.pair else None
-            T.gx, T.jgx, T.n_g, T.w_sym = None, None, 0, self.w_sym
         else:
             T.x, T.dx = self.x.data_ptr(), self.dx.data_ptr()
-            T.aug_gram = T.rev_gram = None
-            if self.sym is not None:
-                T.gx, T.jgx, T.n_g, T.w_sym = self.sym[0].data_ptr(), self.sym[1].data_ptr(), self.sym[0].shape[1], self.sym[2]
-            else:
-                T.gx, T.jgx, T.n_g, T.w_sym = None, None, 0, 0.0
-        T.n_problems, T.n_points, T.d, T.order, T.flags = self.S, self.n_points, self.d, self.order, self.flags
-        T.inv_count = float(inv_count) if inv_count is not None else 1.0 / (n_global * self.d)
-        T.workspace, T.workspace_bytes = (None, 0) if self.ws is None else (self.ws.data_ptr(), self.ws.numel() * 8)
+            ws_bytes = self.engine.lib.symode_workspace_bytes(self.d, self.order, self.flags, self.S, self.n_points)
+            self.ws = self.engine.new_workspace(self.device, ws_bytes)
+            T.workspace, T.workspace_bytes = self.ws.data_ptr(), self.ws.numel() * 8
+            if self.latent:
+                T.latent_B, T.latent_y = (t.data_ptr() for t in self.latent_ops)
+            elif self.sym is not None:
+                T.gx, T.jgx, T.n_g = self.sym[0].data_ptr(), self.sym[1].data_ptr(), self.sym[0].shape[1]
+        T.n_problems, T.n_points, T.d, T.order, T.flags, T.inv_count = self.S, self.n_points, self.d, self.order, self.flags, inv_count
         T.q_eff = self.q_eff.data_ptr() if self.q_eff is not None else None
         T.r, T.allow_constant, T.n_params = self.r, int(self.coef.allow_constant), self.n
         T.w_x, T.w_reg, T.l1 = float(w_x), float(w_reg), int(bool(l1))
         T.lr, T.tol_grad, T.tol_change, T.max_iter, T.history = float(lr), float(tol_grad), float(tol_change), int(max_iter), int(history)
         T.threshold, T.tol_update, T.near_band, T.st_freq = float(threshold), float(tol), NEAR_THRESHOLD_BAND, int(st_freq)
-        T.state, T.state_bytes = self.state.data_ptr(), nbytes
+        T.state, T.state_bytes = self.state.data_ptr(), self.state.numel()
         T.log, T.log_test = self.log.data_ptr(), self.log_test.data_ptr()
-        T.log_xi = self.log_xi.data_ptr() if self.detail else None
-        T.log_mask = self.log_mask.data_ptr() if self.detail else None
-        T.log_params = self.log_params.data_ptr() if self.detail else None
-        T.log_epochs = R
-        self.T = T
-        self._Tp = ctypes.byref(T)
-        self.max_iter = int(max_iter)
-        self.threshold = float(threshold)
+        if self.detail:
+            T.log_xi, T.log_mask, T.log_params = self.log_xi.data_ptr(), self.log_mask.data_ptr(), self.log_params.data_ptr()
+        T.log_epochs = self.LOG_RING
+        return T
 
     # -- plumbing -----------------------------------------------------------------------------------------------------
     def _gram_statistics(self, x, dx, reversed_sym, statistics, group):
@@ -175,9 +175,8 @@ class DeviceTrainer:
         return statistics
 
     @staticmethod
-    def _latent_as_pair(z, latent, reversed_sym, group, statistics, w_sindy_z):
-        """The latent operands in the place of a one-element reversed fit -- gx := y, jgx := B, n_g := 1, w_sym := w_pair --
-        so that the update and epoch-end kernels see a pair closure; the closure launch itself is _epoch_latent's."""
+    def _latent_operands(z, latent, reversed_sym, group, statistics, w_sindy_z):
+        """What the latent kind refuses, and its operands (B, y, w_pair) once they match z."""
         if group is not None:
             raise SymodeError("closure='latent' does not take group=... (point shards): the multi-rank latent fit is not implemented")
         if statistics is not None:
@@ -192,7 +191,7 @@ class DeviceTrainer:
         ok = torch.is_tensor(z) and z.dim() == 3 and all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in (B, y))
         if not ok or tuple(y.shape) != tuple(z.shape) or tuple(B.shape) != tuple(z.shape) + (z.shape[-1],):
             raise SymodeError("latent operands do not match z: B (S, N, d, d) and y (S, N, d) as fp32 device tensors")
-        return y.unsqueeze(1), B.unsqueeze(1), float(w_pair)
+        return B, y, float(w_pair)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -227,6 +226,7 @@ class DeviceTrainer:
 
     def _epoch_sharded(self, epoch, test_eval):
         """One epoch with the ranks' partial [loss | grad] summed between closure and update (RCCL / gloo)."""
+        # mirrors symode_trainer_run (the one other statement of the epoch sequence) with a collective between closure and update
         lib, st = self.engine.lib, self._st()
         width = (2 if self.pair else 1) * self.S
         cl = self.state[self._off["cl_loss"]:self._off["cl_grad"] + self.S * self.dp * 4].view(torch.float32)
@@ -246,28 +246,6 @@ class DeviceTrainer:
             self._check(lib.symode_trainer_closure(self._Tp, ctypes.c_void_p(self.log_test[slot].data_ptr()),
                                                    ctypes.c_void_p(tg.data_ptr()), st), "symode_trainer_closure")
             dist.all_reduce(self.log_test[slot], group=self.group)
-
-    def _epoch_latent(self, epoch, test_eval):
-        """One epoch of the latent fit: the descriptor cannot name a third closure kind, so the host enqueues what
-        symode_trainer_run would -- closure, update, ..., epoch end (, the closure at the epoch's final state) -- with
-        symode_loss_grad_latent as the closure, all on the current stream, no wait in between.  The launch's own w_pair is 0:
-        loss2[1] is produced whatever its weight and the gradient is that of the z-term alone, as in the reference (see
-        __init__); the update kernel weighs loss2[1] into the value by the descriptor's w_sym = w_pair."""
-        lib, st, T = self.engine.lib, self._st(), self.T
-        xi, mask = self.field("xi").data_ptr(), self.field("mask").data_ptr()
-
-        def closure(loss, grad):
-            self._check(lib.symode_loss_grad_latent(T.x, T.dx, T.jgx, T.gx, self.S, self.n_points, self.d, self.order, self.flags,
-                                                    xi, mask, T.inv_count, 0.0, loss, grad, T.workspace, T.workspace_bytes, st),
-                        "symode_loss_grad_latent")
-
-        cl_loss, cl_grad = self.field("cl_loss").data_ptr(), self.field("cl_grad").data_ptr()
-        for it in range(self.max_iter):
-            closure(cl_loss, cl_grad)
-            self._check(lib.symode_trainer_update(self._Tp, 2 if it == 0 else 1, st), "symode_trainer_update")
-        self._check(lib.symode_trainer_epoch_end(self._Tp, epoch, st), "symode_trainer_epoch_end")
-        if test_eval:
-            closure(self.log_test[epoch % self.LOG_RING].data_ptr(), self.field("test_grad").data_ptr())
 
     # -- the fit --------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -296,8 +274,6 @@ class DeviceTrainer:
         def enqueue(e):
             if self.distributed:
                 self._epoch_sharded(e, test_eval)
-            elif self.latent:
-                self._epoch_latent(e, test_eval)
             else:
                 self._check(lib.symode_trainer_run(self._Tp, e, 1, 1 if test_eval else 0, self._st()), "symode_trainer_run")
             ev = torch.cuda.Event()

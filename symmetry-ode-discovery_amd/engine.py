@@ -105,7 +105,8 @@ _SIGNATURES = {
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
-ABI_VERSION = 6
+ABI_VERSION = 7
+CLOSURE_STREAM, CLOSURE_GRAM, CLOSURE_LATENT = 0, 1, 2      # SYMODE_CLOSURE_* of include/symode.h
 
 
 class TrainerDesc(ctypes.Structure):
@@ -119,7 +120,8 @@ class TrainerDesc(ctypes.Structure):
                 ("threshold", c_float), ("tol_update", c_float), ("near_band", c_float), ("st_freq", c_int),
                 ("state", c_void_p), ("state_bytes", c_size_t),
                 ("log", c_void_p), ("log_test", c_void_p), ("log_xi", c_void_p), ("log_mask", c_void_p), ("log_params", c_void_p), ("log_epochs", c_int),
-                ("aug_gram", c_void_p), ("rev_gram", c_void_p)]
+                ("aug_gram", c_void_p), ("rev_gram", c_void_p),
+                ("closure", c_int), ("latent_B", c_void_p), ("latent_y", c_void_p)]
 
 
 TRAINER_FIELDS = ("params", "xi", "mask", "cl_loss", "cl_grad", "g", "loss", "act", "n_iter", "d", "t", "old_dirs", "old_stps", "ro",

@@ -173,7 +173,7 @@ def test_fit_matches_the_host_params_route(S, tmp_path, monkeypatch, capsys):
 
 def test_device_trainer_refuses_what_the_latent_closure_does_not_cover(S):
     from symode_amd.device_lbfgs import DeviceTrainer
-    from symode_amd.engine import SymodeError
+    from symode_amd.engine import CLOSURE_LATENT, SymodeError
     z, dz, B, y, _, _ = [t.to(DEV) for t in _problem(2, 2, 0, 1, 64, seed=0)]
     ok = dict(poly_order=2, closure="latent", latent=(B, y, 0.5), w_x=1.0)
     with pytest.raises(SymodeError, match="closure='latent' does not take group"):
@@ -185,7 +185,74 @@ def test_device_trainer_refuses_what_the_latent_closure_does_not_cover(S):
     with pytest.raises(SymodeError, match="latent operands are for closure='latent'"):
         DeviceTrainer(z, dz, 2, latent=(B, y, 0.5))
     tr = DeviceTrainer(z, dz, **ok)                                              # and the covered case is accepted
-    assert tr.latent and tr.pair and tr.T.n_g == 1
+    assert tr.latent and tr.pair and tr.T.closure == CLOSURE_LATENT and tr.T.n_g == 0 and not tr.T.gx
+
+
+def _enqueue_epoch_by_hand(tr, epoch):
+    """The epoch of symode_trainer_run stated entry by entry, with symode_loss_grad_latent called by name on the LATENT
+    descriptor's operands -- the double of the dispatch in symode_trainer_closure: closure (w_pair = 0), BEGIN update,
+    (closure, ACCEPT update) x (max_iter - 1), epoch end, the closure at the epoch's final state into the test line."""
+    import ctypes
+    lib, st, T = tr.engine.lib, tr._st(), tr.T
+    xi, mask = tr.field("xi").data_ptr(), tr.field("mask").data_ptr()
+
+    def closure(loss, grad):
+        rc = lib.symode_loss_grad_latent(T.x, T.dx, T.latent_B, T.latent_y, T.n_problems, T.n_points, T.d, T.order, T.flags, xi, mask,
+                                         T.inv_count, 0.0, ctypes.c_void_p(loss), ctypes.c_void_p(grad), T.workspace,
+                                         T.workspace_bytes, st)
+        assert rc == 0, rc
+
+    for it in range(T.max_iter):
+        closure(tr.field("cl_loss").data_ptr(), tr.field("cl_grad").data_ptr())
+        assert lib.symode_trainer_update(tr._Tp, 2 if it == 0 else 1, st) == 0
+    assert lib.symode_trainer_epoch_end(tr._Tp, epoch, st) == 0
+    closure(tr.log_test[epoch % tr.LOG_RING].data_ptr(), tr.field("test_grad").data_ptr())
+
+
+@pytest.mark.parametrize("constrained", [False, True])
+@pytest.mark.parametrize("n", [513, 65])
+@pytest.mark.parametrize("d, order, flags", only_compiled([(2, 3, 0), (1, 3, 0)]))
+def test_trainer_run_equals_the_hand_enqueued_epoch_bit_for_bit(S, d, order, flags, n, constrained):
+    """symode_trainer_run on a SYMODE_CLOSURE_LATENT descriptor against the same epochs enqueued by hand on a second trainer
+    built from the same inputs: the same kernels with the same arguments in the same order, so the whole state block and
+    every record agree as bytes.  3 problems, max_iter 4 over a ring of 3 curvature pairs (it wraps), st_freq 2 (a
+    period-triggered thresholding with optimiser reset by epoch 2), 5 epochs."""
+    import ctypes
+    from symode_amd.device_lbfgs import EVENT_NAN, EVENT_THRESHOLD_PERIOD, DeviceTrainer
+    from symode_amd.engine import CLOSURE_LATENT
+    epochs, n_problems = 5, 3
+    z, dz, B, y, xi0, mask0 = [t.to(DEV) for t in _problem(d, order, flags, n_problems, n, seed=11)]
+    if d > 1:                                       # _problem zeroes the last row everywhere: keep ONE all-zero row, in problem 1
+        mask0[0, -1], mask0[2, -1] = mask0[0, 0], mask0[2, 0]
+    g = torch.Generator().manual_seed(5)
+    dp = xi0[0].numel()
+    Q = None
+    if constrained:                                 # (d p, 5) with orthonormal columns (d = 1: d p = 4 < 5, orthonormal rows)
+        Q = torch.linalg.qr(torch.randn(max(dp, 5), min(dp, 5), generator=g))[0]
+        Q = (Q if dp >= 5 else Q.T).contiguous()
+    P0 = (0.5 * torch.randn(n_problems, 5 + d, generator=g)).to(DEV) if constrained else xi0.reshape(n_problems, dp).clone()
+    make = lambda: DeviceTrainer(z, dz, order, flags, Q=Q, allow_constant=True, closure="latent", latent=(B, y, 0.37), lr=0.05,  # noqa: E731
+                                 st_freq=2, max_iter=4, history=3, detail=True)
+    a, b = make(), make()
+    assert a.T.closure == CLOSURE_LATENT and (a.q_eff is not None) == constrained
+    a.fit(P0, epochs, mask0=mask0, test_eval=True)
+    assert b.engine.lib.symode_trainer_init(b._Tp, ctypes.c_void_p(P0.data_ptr()), ctypes.c_void_p(mask0.data_ptr()), b._st()) == 0
+    for e in range(epochs):
+        _enqueue_epoch_by_hand(b, e)
+    torch.cuda.synchronize()
+    codes = a.log[:epochs, :, 0]
+    print(f"latent trainer d={d} n={n} constrained={constrained}: event codes per epoch {codes.long().tolist()}")
+    assert torch.equal(a.state, b.state)            # symode_trainer_init zeroes the block: padding compares too
+    for name in ("log", "log_test", "log_xi", "log_mask", "log_params"):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    # (checked when the seeds were chosen: every case thresholds on the period and none runs into NaN)
+    assert bool((codes == EVENT_THRESHOLD_PERIOD).any()) and not bool((codes == EVENT_NAN).any())
+    # the dispatch itself, once, with explicit outputs: the LATENT closure at the trainer's coefficients and mask, w_pair = 0
+    xi, mask = a.field("xi").clone(), a.field("mask").clone()
+    loss, grad = torch.zeros(n_problems, 2, device=DEV), torch.zeros(n_problems, d, dp // d, device=DEV)
+    assert a.engine.lib.symode_trainer_closure(a._Tp, ctypes.c_void_p(loss.data_ptr()), ctypes.c_void_p(grad.data_ptr()), a._st()) == 0
+    want_l, want_g = a.engine.loss_grad_latent(z, dz, B, y, xi, mask, order, flags, w_pair=0.0, inv_count=a.T.inv_count)
+    assert torch.equal(loss, want_l) and torch.equal(grad, want_g)
 
 
 def test_fused_latent_without_use_latent_is_ignored(S, tmp_path, monkeypatch):

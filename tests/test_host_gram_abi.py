@@ -25,8 +25,8 @@ NULL = ctypes.c_void_p(None)
 JUNK = ctypes.c_void_p(0x1000)           # a non-null, aligned pointer that is never dereferenced (validation fails first)
 
 
-def test_abi_version_is_6(lib):
-    assert engine.ABI_VERSION == 6 and lib.symode_abi_version() == 6
+def test_abi_version_is_7(lib):
+    assert engine.ABI_VERSION == 7 and lib.symode_abi_version() == 7
 
 
 def test_reversed_gram_workspace_query(lib):
@@ -81,17 +81,35 @@ def test_quad_closure_argument_validation_needs_no_gpu(lib):
 
 
 def test_trainer_in_gram_mode_needs_no_point_data_but_its_state(lib):
-    """With aug_gram set, x / dx / workspace may be NULL; the state and the records are still required."""
+    """The closure kind alone says what the descriptor needs: with SYMODE_CLOSURE_GRAM x / dx / workspace may be NULL; the
+    state and the records are still required.  Every case fails before a launch."""
     T = engine.TrainerDesc()
-    T.aug_gram = 0x1000
+    call = lambda: lib.symode_trainer_closure(ctypes.byref(T), None, None, NULL)  # noqa: E731
+    T.closure, T.aug_gram = engine.CLOSURE_GRAM, 0x1000
     T.n_problems, T.n_points, T.d, T.order, T.flags = 1, 100, 2, 3, 0
     T.n_params, T.max_iter, T.history, T.log_epochs = 20, 20, 100, 8
     T.state, T.log, T.log_test = None, 0x1000, 0x1000
-    assert lib.symode_trainer_closure(ctypes.byref(T), None, None, NULL) == -2        # no state block
+    assert call() == -2                                                                # no state block
     T.state, T.state_bytes = 0x1000, 0                                                 # state present, too small
-    assert lib.symode_trainer_closure(ctypes.byref(T), None, None, NULL) == -4
-    T.aug_gram = None                                                                  # streaming form: x, dx needed again
-    assert lib.symode_trainer_closure(ctypes.byref(T), None, None, NULL) == -2
+    assert call() == -4
+    T.closure = engine.CLOSURE_STREAM                                                  # streaming form: x, dx needed again
+    assert call() == -2
+    for unknown in (3, -1):
+        T.closure = unknown
+        assert call() == -3
+    T.closure, T.aug_gram = engine.CLOSURE_GRAM, None                                  # the Gram form without its matrix
+    assert call() == -2
+    T.closure, T.x, T.dx, T.workspace = engine.CLOSURE_STREAM, 0x1000, 0x1000, 0x1000
+    assert call() == -4                                                                # the plain closure is complete
+    T.n_g, T.gx = 1, 0x1000                                                            # the reversed one is not: no jgx
+    assert call() == -2
+    T.closure = engine.CLOSURE_LATENT                                                  # gx / jgx / n_g are not this kind's
+    T.latent_B, T.latent_y = None, 0x1000
+    assert call() == -2
+    T.latent_B, T.latent_y = 0x1000, None
+    assert call() == -2
+    T.latent_y = 0x1000                                                                # complete: past the pointer checks
+    assert call() == -4
 
 
 def test_trainer_struct_layout_matches_ctypes():
@@ -99,12 +117,13 @@ def test_trainer_struct_layout_matches_ctypes():
     cc = shutil.which("gcc") or shutil.which("cc")
     if cc is None:
         pytest.skip("no C compiler")
+    names = ["aug_gram", "rev_gram", "log_epochs", "closure", "latent_B", "latent_y"]
     src = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"symode_trainer_layout_{os.getpid()}.c")
     exe = src[:-2]
     with open(src, "w") as f:
         f.write('#include <stdio.h>\n#include <stddef.h>\n#include "symode.h"\n'
-                'int main(void) { printf("%zu %zu %zu %zu\\n", sizeof(symode_trainer), offsetof(symode_trainer, aug_gram), '
-                'offsetof(symode_trainer, rev_gram), offsetof(symode_trainer, log_epochs)); return 0; }\n')
+                'int main(void) { printf("%zu' + ' %zu' * len(names) + '\\n", sizeof(symode_trainer), '
+                + ', '.join(f'offsetof(symode_trainer, {n})' for n in names) + '); return 0; }\n')
     try:
         r = subprocess.run([cc, "-std=c99", f"-I{os.path.join(ROOT, 'include')}", src, "-o", exe], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -114,8 +133,11 @@ def test_trainer_struct_layout_matches_ctypes():
             if os.path.exists(p):
                 os.remove(p)
     D = engine.TrainerDesc
-    assert got == [ctypes.sizeof(D), D.aug_gram.offset, D.rev_gram.offset, D.log_epochs.offset]
-    assert D._fields_[-2:] == [("aug_gram", ctypes.c_void_p), ("rev_gram", ctypes.c_void_p)]
+    assert got == [ctypes.sizeof(D)] + [getattr(D, n).offset for n in names]
+    # the fields appended after aug_gram, rev_gram are exactly these three, in this order
+    assert D._fields_[-5:] == [("aug_gram", ctypes.c_void_p), ("rev_gram", ctypes.c_void_p), ("closure", ctypes.c_int),
+                               ("latent_B", ctypes.c_void_p), ("latent_y", ctypes.c_void_p)]
+    assert (D.aug_gram.offset, D.rev_gram.offset, D.log_epochs.offset) == (224, 232, 216)     # what they were before the append
 
 
 def test_python_layer_names_the_new_entry_points():
