@@ -523,16 +523,18 @@ def precompute_group_jacobians(x, encode, decode, z_mean, gelems):
 
 
 def lbfgs_fit(reg: OracleRegressor, x, dx, num_epochs, lr_sindy, w_sindy_x=1.0, sindy_reg_type="l1",
-              w_sindy_reg=0.0, w_sym_reg=0.0, sym_loss=None, st_freq=100, threshold=0.1, tol=1e-3):
+              w_sindy_reg=0.0, w_sym_reg=0.0, sym_loss=None, st_freq=100, threshold=0.1, tol=1e-3, max_iter=20,
+              history_size=100):
     """Full-batch L-BFGS fit with convergence-triggered / periodic thresholding.
 
     ref: train.py:617-766, non-latent branch.  ``sym_loss`` (optional) is a callable
     ``sym_loss(reg, x) -> scalar tensor`` standing for train.py:667-676.
+    ``max_iter`` / ``history_size`` go to every optimiser made here (torch's defaults, which the reference runs with).
     Returns a history dict: per-epoch loss, events ('conv', 'final', 'freq', 'nan'),
     masks and coefficient snapshots.
     """
     def new_opt():
-        return torch.optim.LBFGS(reg.parameters(), lr=lr_sindy)                        # :630, :717
+        return torch.optim.LBFGS(reg.parameters(), lr=lr_sindy, max_iter=max_iter, history_size=history_size)   # :630, :717
 
     opt = new_opt()
     losses = {}

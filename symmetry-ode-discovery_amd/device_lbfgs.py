@@ -106,7 +106,10 @@ class DeviceTrainer:
         self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self._off = dict(zip(TRAINER_FIELDS, [int(o) for o in offs]))
         self._shape = {"params": (self.S, self.n), "xi": (self.S, self.d, self.p), "mask": (self.S, self.d, self.p),
-                       "cl_loss": (self.S, 2), "cl_grad": (self.S, self.dp), "g": (self.S, self.n), "loss": (self.S,)}
+                       "cl_loss": (self.S, 2), "cl_grad": (self.S, self.dp), "g": (self.S, self.n), "loss": (self.S,),
+                       "d": (self.S, self.n), "prev_g": (self.S, self.n), "prev": (self.S, self.n), "pprev": (self.S, self.n),
+                       "old_dirs": (self.S, int(history), self.n), "old_stps": (self.S, int(history), self.n),
+                       "ro": (self.S, int(history)), "test_grad": (self.S, self.dp)}   # every other array: (S,)
         # --- per-epoch records: pinned host memory the kernels write directly (sharded runs: device memory, copied)
         R = self.LOG_RING
         mk = (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)) if self.distributed else \
