@@ -482,6 +482,9 @@ int symode_trainer_run(const symode_trainer* T, int epoch0, int n_epochs, int te
  *   log     (n_epochs, n_problems, 8): [mean batch MSE over the epoch's steps, mean |params|_1 (as the loss saw it), steps
  *           taken, coefficients with mask set within near_band of the threshold at this epoch's event, 1 = frozen (NaN),
  *           1 = thresholding event, epoch, 0]
+ *           An epoch in which the problem takes no step (every batch padding alone, or the problem frozen) has no mean:
+ *           columns 0 and 1 hold NaN (0 / 0) and column 2 holds 0; the thresholding event of a problem that is not frozen
+ *           still takes place.
  * n_epochs == 0 or n_problems == 0: nothing to do.  n_params and d p are at most 256.
  * replaces: train.py:491-547 (the per-minibatch loop of train_SIGED and its epoch end) plus torch.optim.Adam.step. */
 int symode_adam_epochs(const float* x, const float* dx, long n_src, const int* idx, long n_idx_problems, int n_epochs,
@@ -499,7 +502,8 @@ int symode_adam_epochs(const float* x, const float* dx, long n_src, const int* i
  * A valid entry i of idx reads x[i], dx[i], gx[:, i] and jgx[:, i]; a padding entry (outside [0, n_src)) reads none of the
  * four arrays and does not count.  Every other argument, the state, the freezing rule (applied to MSE + regulariser) and
  * the fixed order of every sum are those of symode_adam_epochs; log column 7 is the mean over the epoch's steps of the batch
- * regulariser (unweighted, the value train.py logs as loss_sym_reg).  n_g == 0 (gx, jgx may be NULL) computes what
+ * regulariser (unweighted, the value train.py logs as loss_sym_reg; NaN like columns 0 and 1 for an epoch without a step
+ * when n_g > 0).  n_g == 0 (gx, jgx may be NULL) computes what
  * symode_adam_epochs computes, bit for bit, and writes 0 into column 7.  The regulariser's gradient is accumulated at
  * weight w_sym / w_x next to the residual's, so n_g > 0 with w_x <= 0 (or NaN) is refused with SYMODE_E_BADSIZE; n_g < 0 too.
  * replaces: train.py:491-547 with loss_sym_reg = symmreg_r (model_utils.py:160-168, the JVP as the explicit matvec on the

@@ -292,7 +292,8 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 if (tid < np) {
                     const float sgn = (float)(p > 0.0f) - (float)(p < 0.0f);
                     const float g = a.l1 ? fmaf(a.w_reg, sgn, a.w_x * g_data) : a.w_x * g_data;
-                    m = fmaf(om1, g - m, m);
+                    // torch's lerp_(g, 1 - b1): from the nearer end, so that a weight of 1 (b1 = 0) gives g itself, not m + (g - m)
+                    m = om1 < 0.5f ? fmaf(om1, g - m, m) : fmaf(-(g - m), a.beta1, g);
                     v = fmaf(om2, g * g, a.beta2 * v);
                     const double bc1 = 1.0 - adam_ipow((double)a.beta1, t), bc2 = 1.0 - adam_ipow((double)a.beta2, t);
                     const float step_size = (float)((double)a.lr / bc1), bc2_sqrt = (float)sqrt(bc2);
@@ -338,7 +339,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                     rec[4] = frozen ? 1.0f : 0.0f;
                     rec[5] = ev ? 1.0f : 0.0f;
                     rec[6] = (float)epoch;
-                    rec[7] = REV ? (float)(sym_sum / (double)steps) : 0.0f;
+                    rec[7] = (REV && a.n_g > 0) ? (float)(sym_sum / (double)steps) : 0.0f;   // no elements: 0 as the plain entry, stepless epochs too
                 }
                 loss_sum = 0.0;
                 l1_sum = 0.0;
