@@ -324,35 +324,29 @@ int symode_lbfgs_direction(const float* g, const float* old_dirs, const float* o
  * permlane-swap / DPP form the L-BFGS kernels use; the two must agree bit for bit (tests/test_gpu_kernels.py). */
 int symode_selftest_wave_sum(const float* in, float* butterfly_out, float* dpp_out, long n_waves, void* stream);
 
-/* One inner iteration of torch.optim.LBFGS.step (no line search) for n_problems problems, up to and including the move
- * x += t d: curvature-pair update of the ring buffers, two-loop recursion, step length (first iteration:
- * min(1, 1/|g|_1) lr), directional-derivative test.  One wavefront per problem, one launch for everything
- * torch/optim/lbfgs.py does between two closure evaluations.  State arrays as in symode_lbfgs_direction plus
- * n_iter (S) int64, d / prev_g (S, n), t / prev_loss (S); act (S) bytes: in = problem is active, out = problem moved
- * (its closure must be re-evaluated).  Inactive problems are left untouched.
+/* One launch for everything torch.optim.LBFGS.step (no line search) does between two closure evaluations, one wavefront
+ * per problem.  The launch takes the closure's new_loss (S) / new_g (S, n) into loss / g (l1 != 0: as the bare data term,
+ * objective w_x * data + w_reg * |params|_1 over the raw parameters, train.py:680-688, gradient w_x * g + w_reg *
+ * sign(params), formed here) and then, by `mode`:
+ *   SYMODE_LBFGS_BEGIN   opens an optimiser step: every problem whose frozen[s] == 0 (frozen == NULL: every problem) runs
+ *                        torch's optimality test max|g| <= tol_grad and, unless it holds, the first iteration; frozen
+ *                        problems get act = 0 and are otherwise left untouched.
+ *   SYMODE_LBFGS_ACCEPT  finishes the running iteration of the problems with act != 0: the three stopping tests of
+ *                        torch/optim/lbfgs.py (max|g| <= tol_grad, max|t d| <= tol_change, |loss - prev_loss| < tol_change);
+ *                        those still active go straight into the next iteration.  frozen is not read.
+ * An iteration is: curvature-pair update of the ring buffers, two-loop recursion, step length (first iteration: min(1,
+ * 1/|g|_1) lr), directional-derivative test, move x += t d.  State arrays as in symode_lbfgs_direction plus n_iter (S)
+ * int64, d / prev_g (S, n), t / prev_loss (S); act (S) bytes out: the problem moved (its closure must be re-evaluated).
+ * An optimiser step of max_iter iterations is  closure, BEGIN, (closure, ACCEPT) x (max_iter - 1).  Any other mode:
+ * SYMODE_E_BADSIZE.
  * replaces: the body of torch.optim.LBFGS.step that train.py:630-695 runs per seed and per inner iteration. */
-int symode_lbfgs_update(float* params, const float* g, const float* loss, unsigned char* act, long* n_iter, float* d,
-                        float* t, float* old_dirs, float* old_stps, float* ro, long* head, long* count, float* h_diag,
-                        float* prev_g, float* prev_loss, long n_problems, int n, int history, float lr,
-                        float tol_change, void* stream);
-
-/* symode_lbfgs_accept (below) followed by symode_lbfgs_update as ONE launch: problems that moved take new_loss / new_g
- * (l1 != 0: as the bare data term, objective w_x * data + w_reg * |params|_1), run the stopping tests, and those still
- * active go straight into the next iteration's update.  Between two closure evaluations the optimiser is one kernel. */
-int symode_lbfgs_accept_update(const float* new_loss, const float* new_g, float tol_grad, int l1, float w_x, float w_reg,
-                               float* params, float* g, float* loss, unsigned char* act, long* n_iter, float* d, float* t,
-                               float* old_dirs, float* old_stps, float* ro, long* head, long* count, float* h_diag,
-                               float* prev_g, float* prev_loss, long n_problems, int n, int history, float lr,
-                               float tol_change, void* stream);
-
-/* Second half of that iteration, after the closure was re-evaluated at the moved parameters: problems with act != 0
- * take new_loss / new_g into loss / g and run the three stopping tests of torch/optim/lbfgs.py (max|g| <= tol_grad,
- * max|t d| <= tol_change, |loss - prev_loss| < tol_change); act: in = moved, out = still active.
- * params != NULL: new_loss / new_g are the bare data term and the objective is w_x * loss + w_reg * |params|_1 (the L1
- * term over the raw parameters, train.py:680-688), gradient w_x * g + w_reg * sign(params), formed here. */
-int symode_lbfgs_accept(const float* new_loss, const float* new_g, float* loss, float* g, unsigned char* act, const float* d,
-                        const float* t, const float* prev_loss, long n_problems, int n, float tol_grad, float tol_change,
-                        const float* params, float w_x, float w_reg, void* stream);
+#define SYMODE_LBFGS_ACCEPT 1
+#define SYMODE_LBFGS_BEGIN 2
+int symode_lbfgs_step(int mode, const float* new_loss, const float* new_g, const unsigned char* frozen, float tol_grad, int l1,
+                      float w_x, float w_reg, float* params, float* g, float* loss, unsigned char* act, long* n_iter, float* d,
+                      float* t, float* old_dirs, float* old_stps, float* ro, long* head, long* count, float* h_diag,
+                      float* prev_g, float* prev_loss, long n_problems, int n, int history, float lr, float tol_change,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Device-resident L-BFGS trainer: train_SIGED_lbfgs for n_problems independent problems with NOTHING on the host between
@@ -362,7 +356,7 @@ int symode_lbfgs_accept(const float* new_loss, const float* new_g, float* loss, 
  *     SYMODE_CLOSURE_STREAM  symode_loss_grad, or symode_loss_grad_reversed when n_g > 0 (one pass over the points),
  *     SYMODE_CLOSURE_GRAM    symode_quad_closure (the quadratic form of matrices built once; no point data),
  *     SYMODE_CLOSURE_LATENT  symode_loss_grad_latent (the latent fit on operands computed once).
- * The update launches are the kernel of symode_lbfgs_accept_update extended by the coefficient map of the equivariance
+ * The update launches are the kernel of symode_lbfgs_step (same two modes) extended by the coefficient map of the equivariance
  * constraint (Xi = reshape(Q beta) + const and its chain rule, sindy.py:169-176, formed inside the launch), and the
  * epoch-end launch is the per-epoch logic of train.py:697-725: NaN guard, the two update norms, convergence- / period-
  * triggered thresholding (strict >, monotone, sindy.py:192-195) with optimiser reset, twice-converged stop.  Every epoch
@@ -450,8 +444,8 @@ size_t symode_trainer_layout(long n_problems, int n_params, int dp, int history,
 int symode_trainer_init(const symode_trainer* T, const float* params0, const float* mask0, void* stream);
 
 /* The three launches of an epoch on their own (a sharded run all-reduces [cl_loss | cl_grad] between closure and update).
- * symode_trainer_closure: loss_out / grad_out NULL = the state's cl_loss / cl_grad.  symode_trainer_update: mode 2 = BEGIN
- * (first iteration of an optimiser step), 1 = ACCEPT (all later ones). */
+ * symode_trainer_closure: loss_out / grad_out NULL = the state's cl_loss / cl_grad.  symode_trainer_update: mode
+ * SYMODE_LBFGS_BEGIN (first iteration of an optimiser step) or SYMODE_LBFGS_ACCEPT (all later ones), as symode_lbfgs_step. */
 int symode_trainer_closure(const symode_trainer* T, float* loss_out, float* grad_out, void* stream);
 int symode_trainer_update(const symode_trainer* T, int mode, void* stream);
 int symode_trainer_epoch_end(const symode_trainer* T, int epoch, void* stream);

@@ -162,7 +162,7 @@ int reversed_closure(bool fused, bool constj, const float* x, const float* dx, c
 
 extern "C" {
 
-int symode_abi_version(void) { return 7; }
+int symode_abi_version(void) { return 8; }
 
 void symode_reload_env(void) { knobs() = read_knobs(); }
 

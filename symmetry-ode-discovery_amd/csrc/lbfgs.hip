@@ -93,7 +93,8 @@ __device__ __forceinline__ float wave_amax(float v) {
 // One inner iteration of torch.optim.LBFGS.step up to (and including) the parameter update, for every problem that is
 // still active -- torch/optim/lbfgs.py "compute gradient descent direction" ... "no line search, simply move with fixed
 // step" -- as ONE launch: curvature-pair update (ring buffer), two-loop recursion, step length, directional-derivative
-// test, x += t d.  act[s] goes in as "active" and comes out as "moved" (the closure has to be re-evaluated there).
+// test, x += t d.  act[s] comes out as "moved" (the closure has to be re-evaluated there); going in it is not read by
+// BEGIN (every problem not `done` is a candidate) and means "moved in the previous launch" to ACCEPT.
 //
 // STAGED: the recursion is 2m dependent steps (dot product -> axpy), and read from global memory every step pays a
 // full memory round trip (measured 42 us per launch at 64 problems, m <= 100, beside a 12 us closure kernel; 19 us now).  The
@@ -106,9 +107,10 @@ __device__ __forceinline__ float wave_amax(float v) {
 // zeroed by selects at fetch time instead of branches around every use, and the m alphas stay in two registers (lane k
 // keeps alpha_k, read back with v_readlane) instead of going through LDS.
 //
-// ACCEPT: the launch first finishes the PREVIOUS iteration (what lbfgs_accept_kernel does: take the re-evaluated loss /
-// gradient, stopping tests) and carries on into this one if the problem is still active -- between two closure
-// evaluations the optimiser is then ONE launch, and the accepted gradient never leaves the registers.
+// Every launch first takes the closure's loss / gradient: ACCEPT finishes the PREVIOUS iteration (the re-evaluated loss /
+// gradient, torch's three stopping tests) and carries on into this one if the problem is still active; BEGIN opens an
+// optimiser step (optimality test only).  Between two closure evaluations the optimiser is then ONE launch, and the
+// accepted gradient never leaves the registers.
 struct AcceptArgs {
     const float* new_loss;   // (S)     closure value at the moved parameters [(S, 2) = (mse, regulariser) with w_pair != 0]
     const float* new_g;      // (S, n)  its gradient [(S, d p) = d/dXi under a coefficient map, see XiMap]
@@ -130,16 +132,16 @@ struct XiMap {
     int r, dp, p, allow_const;
 };
 
-// Trainer-only extras (nullptr in the sweep's tensor-op callers): problems the epoch logic has finished are skipped by
-// the BEGIN launch; the L1 norm of the parameters the last closure was evaluated at is kept for the epoch's log record.
+// Problems the epoch logic has finished (the sweep: `frozen`) are skipped by the BEGIN launch (nullptr: none); the
+// trainer keeps the L1 norm of the parameters the last closure was evaluated at for the epoch's log record.
 struct TrainerHook {
     const unsigned char* done;
     float* l1_last;
 };
 
-constexpr int LB_PLAIN = 0;    // update only: g / loss already hold this iteration's values
-constexpr int LB_ACCEPT = 1;   // finish the previous iteration (take the re-evaluated loss / gradient, stopping tests), then update
-constexpr int LB_BEGIN = 2;    // first iteration of an optimiser step: take the closure's loss / gradient, optimality test, then update
+// the `mode` of symode_lbfgs_step / symode_trainer_update
+constexpr int LB_ACCEPT = SYMODE_LBFGS_ACCEPT;   // finish the previous iteration (take the re-evaluated loss / gradient, stopping tests), then update
+constexpr int LB_BEGIN = SYMODE_LBFGS_BEGIN;     // first iteration of an optimiser step: take the closure's loss / gradient, optimality test, then update
 
 template <int NC, int MODE>
 __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ params, float* __restrict__ g,
@@ -152,7 +154,7 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
                                                             float* __restrict__ prev_loss, int n, int H, float lr,
                                                             float tol_change, AcceptArgs acc, XiMap map, TrainerHook hook) {
     constexpr bool STAGED = NC > 0;
-    constexpr bool ACCEPT = MODE == LB_ACCEPT, BEGIN = MODE == LB_BEGIN;
+    constexpr bool BEGIN = MODE == LB_BEGIN;
     __shared__ float al[LB_MAXH];
     __shared__ float cvt[WAVE * LB_MAXC];                    // coefficient map: d/dXi on the way in, parameters on the way out
     extern __shared__ float staged[];                        // STAGED: pad [n] | Y [H][n] | S [H][n] | ro [H] | 256 floats of padding
@@ -186,7 +188,9 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
     float* const ldsR = ldsS + H * n;
     float gv[LB_MAXC], q[LB_MAXC];
     float loss_s;
-    if constexpr (ACCEPT || BEGIN) {
+    // Take the closure's loss / gradient; optimality / stopping tests.  The braces are deliberate: the block scope ends the
+    // lifetime of its locals, and without it every instantiation gets another register allocation than the one measured.
+    {
         const float tt = BEGIN ? 0.0f : t_in;
         float nl = acc.pair ? fmaf(acc.w_pair, acc.new_loss[2 * s + 1], acc.new_loss[2 * s]) : acc.new_loss[s];
         float gmax = 0.0f, dmax = 0.0f, p_l1 = 0.0f;
@@ -212,9 +216,9 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
                 } else {                                     // const_i: column 0 of equation i (zero when the model does not read it)
                     v = map.allow_const ? cvt[(i - map.r) * map.p] : 0.0f;
                 }
-                if (acc.l1) {
+                if (acc.l1) {                                // train.py:680-688 as the tensor ops do it: products rounded, one add
                     const float pv = params[s * n + i];
-                    const float sg = (float)(pv > 0.0f) - (float)(pv < 0.0f);
+                    const float sg = (float)(pv > 0.0f) - (float)(pv < 0.0f);      // torch.sign: 0 at 0 and at NaN
                     v = __fadd_rn(__fmul_rn(acc.w_x, v), __fmul_rn(acc.w_reg, sg));
                     p_l1 += fabsf(pv);
                 }
@@ -243,13 +247,6 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
             return;
         }
         loss_s = nl;
-    } else {
-#pragma unroll
-        for (int c = 0; c < LB_MAXC; ++c) {
-            const int i = lane + WAVE * c;
-            gv[c] = i < n ? g[s * n + i] : 0.0f;
-        }
-        loss_s = loss[s];
     }
     const long ni = (long)__builtin_amdgcn_readfirstlane((int)ni_in) + 1;          // (scalars: uniform loop bounds below)
     const bool first = ni == 1;
@@ -473,51 +470,6 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
     }
 }
 
-// The part of the iteration after the closure has been re-evaluated: problems that moved take the new loss / gradient
-// and run torch's three stopping tests (optimality, step size, loss change); act[s]: "moved" in, "still active" out.
-//
-// ``params`` != nullptr: the closure handed over the bare data term; the objective is  w_x * loss + w_reg * |params|_1
-// (train.py:680-688: L1 over the raw parameters) and its gradient  w_x * g + w_reg * sign(params)  -- added here, in
-// the arithmetic of the tensor-op form (products rounded, then one add), instead of seven more launches.
-__global__ __launch_bounds__(WAVE) void lbfgs_accept_kernel(const float* __restrict__ new_loss, const float* __restrict__ new_g,
-                                                            float* __restrict__ loss, float* __restrict__ g,
-                                                            unsigned char* __restrict__ act, const float* __restrict__ d,
-                                                            const float* __restrict__ t, const float* __restrict__ prev_loss,
-                                                            int n, float tol_grad, float tol_change,
-                                                            const float* __restrict__ params, float w_x, float w_reg) {
-    const long s = blockIdx.x;
-    const int lane = threadIdx.x;
-    if (!act[s]) return;
-    const float tt = t[s];
-    float nl = new_loss[s];
-    float gmax = 0.0f, dmax = 0.0f, p_l1 = 0.0f;
-#pragma unroll
-    for (int c = 0; c < LB_MAXC; ++c) {
-        const int i = lane + WAVE * c;
-        if (i < n) {
-            float v = new_g[s * n + i];
-            if (params != nullptr) {
-                const float pv = params[s * n + i];
-                const float sg = (float)(pv > 0.0f) - (float)(pv < 0.0f);      // torch.sign: 0 at 0 and at NaN
-                v = __fadd_rn(__fmul_rn(w_x, v), __fmul_rn(w_reg, sg));
-                p_l1 += fabsf(pv);
-            }
-            g[s * n + i] = v;
-            const float av = fabsf(v), ad = fabsf(d[s * n + i] * tt);
-            gmax = (av != av || gmax != gmax) ? __builtin_nanf("") : fmaxf(gmax, av);
-            dmax = (ad != ad || dmax != dmax) ? __builtin_nanf("") : fmaxf(dmax, ad);
-        }
-    }
-    gmax = wave_amax(gmax);
-    dmax = wave_amax(dmax);
-    if (params != nullptr) nl = __fadd_rn(__fmul_rn(w_x, nl), __fmul_rn(w_reg, wave_sum(p_l1)));
-    if (lane == 0) {
-        loss[s] = nl;
-        const bool stop = (gmax <= tol_grad) || (dmax <= tol_change) || (fabsf(nl - prev_loss[s]) < tol_change);
-        act[s] = stop ? 0 : 1;
-    }
-}
-
 }  // namespace symode
 
 extern "C" int symode_lbfgs_direction(const float* g, const float* old_dirs, const float* old_stps, const float* ro,
@@ -558,7 +510,7 @@ inline int launch_lbfgs_update(int mode, float* params, float* g, float* loss, u
                                XiMap map, TrainerHook hook, void* stream) {
     if (n_problems < 1 || n < 1 || n > WAVE * LB_MAXC || history < 1 || history > LB_MAXH) return SYMODE_E_BADSIZE;
     if (!params || !g || !loss || !act || !n_iter || !d || !t || !old_dirs || !old_stps || !ro || !head || !count || !h_diag ||
-        !prev_g || !prev_loss || (mode != LB_PLAIN && (!acc.new_loss || !acc.new_g)))
+        !prev_g || !prev_loss || !acc.new_loss || !acc.new_g)
         return SYMODE_E_NULLPTR;
     if (map.q != nullptr && (!map.xi || map.dp < 1 || map.dp > WAVE * LB_MAXC || map.r < 0 || map.r > n || map.p < 1)) return SYMODE_E_BADSIZE;
     const size_t stage_bytes = (((size_t)2 * n + 1) * history + n + 256) * sizeof(float);
@@ -569,9 +521,8 @@ inline int launch_lbfgs_update(int mode, float* params, float* g, float* loss, u
         tol_change, acc, map, hook)
 #define SYMODE_LBFGS_UPDATE(NC_, BYTES_)                                                                                          \
     do {                                                                                                                          \
-        if (mode == LB_ACCEPT) SYMODE_LBFGS_LAUNCH(NC_, LB_ACCEPT, BYTES_);                                                       \
-        else if (mode == LB_BEGIN) SYMODE_LBFGS_LAUNCH(NC_, LB_BEGIN, BYTES_);                                                    \
-        else SYMODE_LBFGS_LAUNCH(NC_, LB_PLAIN, BYTES_);                                                                          \
+        if (mode == LB_BEGIN) SYMODE_LBFGS_LAUNCH(NC_, LB_BEGIN, BYTES_);                                                         \
+        else SYMODE_LBFGS_LAUNCH(NC_, LB_ACCEPT, BYTES_);                                                                         \
     } while (0)
     switch (nc) {
         case 1: SYMODE_LBFGS_UPDATE(1, stage_bytes); break;
@@ -587,40 +538,17 @@ inline int launch_lbfgs_update(int mode, float* params, float* g, float* loss, u
 }
 }  // namespace symode
 
-extern "C" int symode_lbfgs_update(float* params, const float* g, const float* loss, unsigned char* act, long* n_iter, float* d,
-                                   float* t, float* old_dirs, float* old_stps, float* ro, long* head, long* count,
-                                   float* h_diag, float* prev_g, float* prev_loss, long n_problems, int n, int history,
-                                   float lr, float tol_change, void* stream) {
+extern "C" int symode_lbfgs_step(int mode, const float* new_loss, const float* new_g, const unsigned char* frozen, float tol_grad,
+                                 int l1, float w_x, float w_reg, float* params, float* g, float* loss, unsigned char* act,
+                                 long* n_iter, float* d, float* t, float* old_dirs, float* old_stps, float* ro, long* head,
+                                 long* count, float* h_diag, float* prev_g, float* prev_loss, long n_problems, int n, int history,
+                                 float lr, float tol_change, void* stream) {
     using namespace symode;
-    return launch_lbfgs_update(LB_PLAIN, params, const_cast<float*>(g), const_cast<float*>(loss), act, n_iter, d, t, old_dirs,
-                               old_stps, ro, head, count, h_diag, prev_g, prev_loss, n_problems, n, history, lr, tol_change,
-                               AcceptArgs{nullptr, nullptr, 0.0f, 0, 1.0f, 0.0f, 0, 0.0f}, XiMap{nullptr, nullptr, 0, 0, 1, 0},
-                               TrainerHook{nullptr, nullptr}, stream);
-}
-
-extern "C" int symode_lbfgs_accept_update(const float* new_loss, const float* new_g, float tol_grad, int l1, float w_x, float w_reg,
-                                          float* params, float* g, float* loss, unsigned char* act, long* n_iter, float* d,
-                                          float* t, float* old_dirs, float* old_stps, float* ro, long* head, long* count,
-                                          float* h_diag, float* prev_g, float* prev_loss, long n_problems, int n, int history,
-                                          float lr, float tol_change, void* stream) {
-    using namespace symode;
-    return launch_lbfgs_update(LB_ACCEPT, params, g, loss, act, n_iter, d, t, old_dirs, old_stps, ro, head, count, h_diag, prev_g,
+    if (mode != LB_ACCEPT && mode != LB_BEGIN) return SYMODE_E_BADSIZE;
+    return launch_lbfgs_update(mode, params, g, loss, act, n_iter, d, t, old_dirs, old_stps, ro, head, count, h_diag, prev_g,
                                prev_loss, n_problems, n, history, lr, tol_change,
                                AcceptArgs{new_loss, new_g, tol_grad, l1, w_x, w_reg, 0, 0.0f}, XiMap{nullptr, nullptr, 0, 0, 1, 0},
-                               TrainerHook{nullptr, nullptr}, stream);
-}
-
-extern "C" int symode_lbfgs_accept(const float* new_loss, const float* new_g, float* loss, float* g, unsigned char* act,
-                                   const float* d, const float* t, const float* prev_loss, long n_problems, int n,
-                                   float tol_grad, float tol_change, const float* params, float w_x, float w_reg,
-                                   void* stream) {
-    using namespace symode;
-    if (n_problems < 1 || n < 1 || n > WAVE * LB_MAXC) return SYMODE_E_BADSIZE;
-    if (!new_loss || !new_g || !loss || !g || !act || !d || !t || !prev_loss) return SYMODE_E_NULLPTR;
-    lbfgs_accept_kernel<<<dim3((unsigned)n_problems), dim3(WAVE), 0, (hipStream_t)stream>>>(
-        new_loss, new_g, loss, g, act, d, t, prev_loss, n, tol_grad, tol_change, params, w_x, w_reg);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SYMODE_OK : (int)e;
+                               TrainerHook{frozen, nullptr}, stream);
 }
 
 // =====================================================================================================================

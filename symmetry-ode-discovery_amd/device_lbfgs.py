@@ -16,7 +16,8 @@ import torch
 import torch.distributed as dist
 
 from .coef_map import CoefMap
-from .engine import CLOSURE_GRAM, CLOSURE_LATENT, CLOSURE_STREAM, TRAINER_FIELDS, SymodeError, TrainerDesc, get_engine
+from .engine import (CLOSURE_GRAM, CLOSURE_LATENT, CLOSURE_STREAM, LBFGS_ACCEPT, LBFGS_BEGIN, TRAINER_FIELDS, SymodeError, TrainerDesc,
+                     get_engine)
 from .gram_closure import GramStatistics
 
 NEAR_THRESHOLD_BAND = 1e-4            # sindy.NEAR_THRESHOLD_BAND; repeated here to keep imports light
@@ -241,7 +242,7 @@ class DeviceTrainer:
                 dist.all_reduce(cl[2 * self.S:], group=self.group)
             else:
                 dist.all_reduce(cl, group=self.group)
-            self._check(lib.symode_trainer_update(self._Tp, 2 if it == 0 else 1, st), "symode_trainer_update")
+            self._check(lib.symode_trainer_update(self._Tp, LBFGS_BEGIN if it == 0 else LBFGS_ACCEPT, st), "symode_trainer_update")
         self._check(lib.symode_trainer_epoch_end(self._Tp, epoch, st), "symode_trainer_epoch_end")
         if test_eval:
             slot = epoch % self.LOG_RING

@@ -84,10 +84,8 @@ _SIGNATURES = {
     "symode_lbfgs_direction": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
                                        c_int, c_void_p, c_void_p]),
     "symode_selftest_wave_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
-    "symode_lbfgs_update": (c_int, [c_void_p] * 15 + [c_long, c_int, c_int, c_float, c_float, c_void_p]),
-    "symode_lbfgs_accept_update": (c_int, [c_void_p, c_void_p, c_float, c_int, c_float, c_float] + [c_void_p] * 15
-                                   + [c_long, c_int, c_int, c_float, c_float, c_void_p]),
-    "symode_lbfgs_accept": (c_int, [c_void_p] * 8 + [c_long, c_int, c_float, c_float, c_void_p, c_float, c_float, c_void_p]),
+    "symode_lbfgs_step": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_int, c_float, c_float] + [c_void_p] * 15
+                          + [c_long, c_int, c_int, c_float, c_float, c_void_p]),
     "symode_trainer_layout": (c_size_t, [c_long, c_int, c_int, c_int, c_int, c_void_p]),
     "symode_trainer_init": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_trainer_closure": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -105,7 +103,8 @@ _SIGNATURES = {
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
-ABI_VERSION = 7
+ABI_VERSION = 8
+LBFGS_ACCEPT, LBFGS_BEGIN = 1, 2                            # SYMODE_LBFGS_* of include/symode.h
 CLOSURE_STREAM, CLOSURE_GRAM, CLOSURE_LATENT = 0, 1, 2      # SYMODE_CLOSURE_* of include/symode.h
 
 
@@ -808,56 +807,34 @@ class HipEngine:
                                                     self._stream(g)), "symode_lbfgs_direction")
         return out
 
-    def lbfgs_update(self, params, g, loss, act, st, lr, tol_change):
-        """In place: one L-BFGS inner iteration up to the move x += t d for every active problem (``st``: the
-        optimiser's state tensors, see sweep.BatchedLBFGS); ``act`` (S,) bool: active in, moved out."""
-        S, n = params.shape
-        H = st.old_dirs.shape[1]
-        for name, ten, dt in (("params", params, torch.float32), ("g", g, torch.float32), ("loss", loss, torch.float32),
-                              ("act", act, torch.bool), ("n_iter", st.n_iter, torch.int64), ("d", st.d, torch.float32),
-                              ("t", st.t, torch.float32), ("old_dirs", st.old_dirs, torch.float32),
-                              ("old_stps", st.old_stps, torch.float32), ("ro", st.ro, torch.float32),
-                              ("head", st.head, torch.int64), ("hist", st.hist, torch.int64),
-                              ("H_diag", st.H_diag, torch.float32), ("prev_g", st.prev_g, torch.float32),
-                              ("prev_loss", st.prev_loss, torch.float32)):
-            if not (ten.is_cuda and ten.dtype == dt and ten.is_contiguous()):
-                raise SymodeError(f"lbfgs_update: {name} must be a contiguous {dt} GPU tensor (updated in place)")
-        self._check(self.lib.symode_lbfgs_update(self._ptr(params), self._ptr(g), self._ptr(loss), self._ptr(act),
-                                                 self._ptr(st.n_iter), self._ptr(st.d), self._ptr(st.t), self._ptr(st.old_dirs),
-                                                 self._ptr(st.old_stps), self._ptr(st.ro), self._ptr(st.head), self._ptr(st.hist),
-                                                 self._ptr(st.H_diag), self._ptr(st.prev_g), self._ptr(st.prev_loss), S, n, H,
-                                                 float(lr), float(tol_change), self._stream(params)), "symode_lbfgs_update")
-
-    def lbfgs_accept_update(self, new_loss, new_g, params, g, loss, act, st, lr, tol_grad, tol_change, l1=None):
-        """lbfgs_accept followed by lbfgs_update in ONE launch (state tensors checked by the preceding lbfgs_update call of
-        the same optimiser step).  ``l1 = (w_x, w_reg)``: new_loss / new_g are the bare data term."""
+    def lbfgs_step(self, mode, new_loss, new_g, params, g, loss, act, st, lr, tol_grad, tol_change, l1=None, frozen=None):
+        """In place: ONE launch for everything torch.optim.LBFGS.step does between two closure evaluations (``st``: the
+        optimiser's state tensors, see sweep.BatchedLBFGS).  ``mode`` LBFGS_BEGIN opens an optimiser step (optimality test,
+        first iteration up to the move; ``frozen`` (S,) bool: problems left untouched), LBFGS_ACCEPT finishes the running
+        iteration of the problems with ``act`` set (stopping tests) and starts the next one; ``act`` (S,) bool out: moved.
+        ``l1 = (w_x, w_reg)``: new_loss / new_g are the bare data term, the kernel forms w_x * loss + w_reg * |params|_1
+        and its gradient.  The state tensors are checked in BEGIN, once per optimiser step."""
         S, n = params.shape
         new_loss, new_g = self._dev(new_loss, "new_loss"), self._dev(new_g, "new_g")
+        if mode == LBFGS_BEGIN:
+            for name, ten, dt in (("params", params, torch.float32), ("g", g, torch.float32), ("loss", loss, torch.float32),
+                                  ("act", act, torch.bool), ("n_iter", st.n_iter, torch.int64), ("d", st.d, torch.float32),
+                                  ("t", st.t, torch.float32), ("old_dirs", st.old_dirs, torch.float32),
+                                  ("old_stps", st.old_stps, torch.float32), ("ro", st.ro, torch.float32),
+                                  ("head", st.head, torch.int64), ("hist", st.hist, torch.int64),
+                                  ("H_diag", st.H_diag, torch.float32), ("prev_g", st.prev_g, torch.float32),
+                                  ("prev_loss", st.prev_loss, torch.float32), ("frozen", frozen, torch.bool)):
+                if ten is not None and not (ten.is_cuda and ten.dtype == dt and ten.is_contiguous()):
+                    raise SymodeError(f"lbfgs_step: {name} must be a contiguous {dt} GPU tensor")
+            if new_loss.numel() != S or new_g.numel() != S * n or (frozen is not None and frozen.numel() != S):
+                raise SymodeError("lbfgs_step: new_loss / frozen hold S values and new_g S * n for params (S, n)")
         w_x, w_reg = (1.0, 0.0) if l1 is None else l1
-        self._check(self.lib.symode_lbfgs_accept_update(
-            self._ptr(new_loss), self._ptr(new_g), float(tol_grad), 0 if l1 is None else 1, float(w_x), float(w_reg),
-            self._ptr(params), self._ptr(g), self._ptr(loss), self._ptr(act), self._ptr(st.n_iter), self._ptr(st.d), self._ptr(st.t),
-            self._ptr(st.old_dirs), self._ptr(st.old_stps), self._ptr(st.ro), self._ptr(st.head), self._ptr(st.hist),
+        self._check(self.lib.symode_lbfgs_step(
+            int(mode), self._ptr(new_loss), self._ptr(new_g), self._ptr(frozen), float(tol_grad), 0 if l1 is None else 1, float(w_x),
+            float(w_reg), self._ptr(params), self._ptr(g), self._ptr(loss), self._ptr(act), self._ptr(st.n_iter), self._ptr(st.d),
+            self._ptr(st.t), self._ptr(st.old_dirs), self._ptr(st.old_stps), self._ptr(st.ro), self._ptr(st.head), self._ptr(st.hist),
             self._ptr(st.H_diag), self._ptr(st.prev_g), self._ptr(st.prev_loss), S, n, st.old_dirs.shape[1], float(lr),
-            float(tol_change), self._stream(params)), "symode_lbfgs_accept_update")
-
-    def lbfgs_accept(self, new_loss, new_g, loss, g, act, st, tol_grad, tol_change, l1=None):
-        """In place: moved problems take the re-evaluated loss / gradient and run the stopping tests; ``act``: moved in,
-        still active out.  ``l1 = (params, w_x, w_reg)``: new_loss / new_g are the bare data term, the kernel forms
-        w_x * loss + w_reg * |params|_1 and its gradient."""
-        S, n = g.shape
-        params, w_x, w_reg = (None, 1.0, 0.0) if l1 is None else l1
-        if params is not None and not (params.is_cuda and params.dtype == torch.float32 and params.is_contiguous()
-                                       and params.shape == g.shape):
-            raise SymodeError("lbfgs_accept: params must be a contiguous fp32 GPU tensor shaped like g")
-        new_loss, new_g = self._dev(new_loss, "new_loss"), self._dev(new_g, "new_g")
-        for name, ten, dt in (("loss", loss, torch.float32), ("g", g, torch.float32), ("act", act, torch.bool)):
-            if not (ten.is_cuda and ten.dtype == dt and ten.is_contiguous()):
-                raise SymodeError(f"lbfgs_accept: {name} must be a contiguous {dt} GPU tensor (updated in place)")
-        self._check(self.lib.symode_lbfgs_accept(self._ptr(new_loss), self._ptr(new_g), self._ptr(loss), self._ptr(g),
-                                                 self._ptr(act), self._ptr(st.d), self._ptr(st.t), self._ptr(st.prev_loss), S, n,
-                                                 float(tol_grad), float(tol_change), self._ptr(params), float(w_x),
-                                                 float(w_reg), self._stream(g)), "symode_lbfgs_accept")
+            float(tol_change), self._stream(params)), "symode_lbfgs_step")
 
 
 _ENGINE = None

@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from .coef_map import CoefMap
-from .engine import get_engine, library_flags
+from .engine import LBFGS_ACCEPT, LBFGS_BEGIN, get_engine, library_flags
 from . import lstsq as _lstsq
 from .sindy import NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_solve_from_gram
 
@@ -142,12 +142,19 @@ class BatchedLBFGS:
     stopping tests of torch/optim/lbfgs.py (defaults: max_iter 20, tolerance_grad 1e-7, tolerance_change
     1e-9, history 100).  Problems that stop early simply stop changing.
 
-    Everything is mask arithmetic -- no host synchronisation inside ``step``.  With the variables on the GPU the
-    optimiser side of an inner iteration is TWO kernels, a wavefront per problem: symode_lbfgs_update (curvature
-    memory in ring buffers with per-problem head / count, two-loop recursion, step length, move) and
-    symode_lbfgs_accept (take the re-evaluated loss / gradient, stopping tests); the tensor-op form below is the
-    same arithmetic statement by statement (CPU / gloo runs, ``SYMODE_LBFGS_FUSED=0``) with only the two-loop
-    recursion as a kernel (symode_lbfgs_direction).
+    Everything is mask arithmetic -- no host synchronisation inside ``step``.  Two forms.  The kernel form (variables
+    on the GPU, ``fused``): a step is the device trainer's sequence, closure then ONE optimiser launch per inner
+    iteration (symode_lbfgs_step, a wavefront per problem: BEGIN -- optimality test, first iteration up to the move --
+    then ACCEPT -- take the re-evaluated loss / gradient, stopping tests, next iteration: curvature memory in ring buffers
+    with per-problem head / count, two-loop recursion, step length, move).  It is the launch of symode_trainer_update,
+    which tests/trainer_model.py checks against fp64 (tests/test_gpu_trainer_steps.py ties the two bit for bit).  The
+    tensor-op form is the same arithmetic statement by statement (CPU / gloo runs, ``SYMODE_LBFGS_FUSED=0``) with only
+    the two-loop recursion as a kernel (symode_lbfgs_direction).
+
+    Where the kernel form's bits differ from the tensor-op statement of a step's first iteration: with an L1 weight
+    (``data_term``) the objective value sums |params| by the kernel's wave reduction, as every later iteration does,
+    not by torch's sum (the gradient and the move are the same bits); and a ``frozen`` problem's ``_loss`` / ``_g``
+    are left as they were instead of being refreshed (SeedSweepLBFGS reads neither).
     """
 
     def __init__(self, params, lr, max_iter=20, tolerance_grad=1e-7, tolerance_change=1e-9, history_size=100, engine=None,
@@ -174,12 +181,10 @@ class BatchedLBFGS:
         self._act = torch.zeros(S, dtype=torch.bool, device=dev)
         # HIP-graph replay of the inner iteration: GPU variables + the direction kernel (no host sync inside) only
         self.use_graph = bool(use_graph and params.is_cuda and self.engine is not None)
-        # the whole optimiser side of an iteration as two kernels (symode_lbfgs_update / _accept), a wave per problem
+        # the kernel form: the whole optimiser side of an iteration as one launch (symode_lbfgs_step), a wave per problem
         self.data_term = None          # (closure of the bare data term, w_x, w_reg): objective = w_x * data + w_reg * |P|_1
-        self.merged = False            # accept + next update as one launch (set below)
-        self.fused = bool(self.engine is not None and hasattr(self.engine, 'lbfgs_update') and dt == torch.float32
+        self.fused = bool(self.engine is not None and hasattr(self.engine, 'lbfgs_step') and dt == torch.float32
                           and params.is_contiguous() and os.environ.get('SYMODE_LBFGS_FUSED', '1') != '0')
-        self.merged = bool(self.fused and hasattr(self.engine, 'lbfgs_accept_update') and os.environ.get('SYMODE_LBFGS_MERGED', '1') != '0')
         self._graph, self._graph_closure, self._warm = None, None, 0
 
     def reset(self, which):
@@ -212,19 +217,9 @@ class BatchedLBFGS:
         return r
 
     def _iteration(self, closure, evaluate=True):
-        """One inner iteration of every problem on the persistent buffers (self.P, _loss, _g, _act and the optimiser
-        state): everything is updated in place, so the sequence of launches can be captured once and replayed."""
+        """One inner iteration of every problem in tensor ops on the persistent buffers (self.P, _loss, _g, _act and the
+        optimiser state): everything is updated in place, so the sequence of launches can be captured once and replayed."""
         P, g, loss, act = self.P, self._g, self._loss, self._act
-        if self.fused:                                         # two launches around the closure instead of ~60
-            self.engine.lbfgs_update(P, g, loss, act, self, self.lr, self.tol_c)
-            if evaluate and self.data_term is not None:        # bare data term; scale + L1 term added by the accept kernel
-                raw, w_x, w_reg = self.data_term
-                nl, ng = raw(P)
-                self.engine.lbfgs_accept(nl, ng, loss, g, act, self, self.tol_g, self.tol_c, l1=(P, w_x, w_reg))
-            elif evaluate:
-                nl, ng = closure(P)
-                self.engine.lbfgs_accept(nl, ng, loss, g, act, self, self.tol_g, self.tol_c)
-            return
         self.n_iter.add_(act.long())
         first = act & (self.n_iter == 1)
         upd = act & ~first
@@ -268,9 +263,10 @@ class BatchedLBFGS:
             live = live & ~stop
         act.copy_(live)
 
-    def _evaluate_accept_update(self, closure):
-        """closure at the moved parameters, then ONE optimiser launch: finish the running iteration (accept + stopping
-        tests) and start the next one (update + move) for the problems still active."""
+    def _evaluate_step(self, closure, mode=LBFGS_ACCEPT, frozen=None):
+        """The kernel form's iteration: closure at the current parameters (the bare data term when ``data_term`` is set:
+        scale and L1 term are formed by the launch), then ONE optimiser launch -- BEGIN opens the step, ACCEPT finishes
+        the running iteration and starts the next one for the problems still active."""
         if self.data_term is not None:
             raw, w_x, w_reg = self.data_term
             nl, ng = raw(self.P)
@@ -278,7 +274,8 @@ class BatchedLBFGS:
         else:
             nl, ng = closure(self.P)
             l1 = None
-        self.engine.lbfgs_accept_update(nl, ng, self.P, self._g, self._loss, self._act, self, self.lr, self.tol_g, self.tol_c, l1=l1)
+        self.engine.lbfgs_step(mode, nl, ng, self.P, self._g, self._loss, self._act, self, self.lr, self.tol_g, self.tol_c, l1=l1,
+                               frozen=frozen)
 
     def _replayed(self, body, closure):
         """``body(closure)`` is a handful of launches on persistent buffers: after a few eager runs (lazy initialisations
@@ -300,7 +297,22 @@ class BatchedLBFGS:
 
     @torch.no_grad()
     def step(self, closure, frozen=None):
-        """closure(P) -> (loss (S,), grad (S, n)).  ``frozen`` (S,) bool: problems that must not move."""
+        """closure(P) -> (loss (S,), grad (S, n)).  ``frozen`` (S,) bool: problems that must not move.  Returns the
+        objective (S,) at the last evaluation of each problem; in the kernel form a frozen problem's entry is the value
+        from before it froze (0 if it never took a step), in the tensor-op form the value at its resting parameters."""
+        if self.fused:
+            # (closure, BEGIN), then (closure, ACCEPT) max_iter - 1 times -- symode_trainer_run's sequence: the last launch's
+            # move is the one torch performs without re-evaluating (n_iter == max_iter)
+            for it in range(self.max_iter):
+                if it == 0:
+                    self._evaluate_step(closure, LBFGS_BEGIN, frozen)
+                elif self.use_graph:
+                    self._replayed(self._evaluate_step, closure)
+                else:
+                    self._evaluate_step(closure)
+                if it > 0 and it % 5 == 0 and not bool(self._act.any()):    # the only host sync, every 5th iteration
+                    break
+            return self._loss.clone()
         loss, g = closure(self.P)
         self._loss.copy_(loss)
         self._g.copy_(g)
@@ -310,18 +322,6 @@ class BatchedLBFGS:
         if frozen is not None:
             act = act & ~frozen
         self._act.copy_(act)
-        if self.merged:
-            # iteration 1's update alone, then (closure, accept + next update) max_iter - 1 times: the last update is the
-            # one torch performs without re-evaluating (n_iter == max_iter)
-            self.engine.lbfgs_update(self.P, self._g, self._loss, self._act, self, self.lr, self.tol_c)
-            for it in range(1, self.max_iter):
-                if self.use_graph:
-                    self._replayed(self._evaluate_accept_update, closure)
-                else:
-                    self._evaluate_accept_update(closure)
-                if it % 5 == 0 and not bool(self._act.any()):               # the only host sync, every 5th iteration
-                    break
-            return self._loss.clone()
         for it in range(1, self.max_iter + 1):
             if it == self.max_iter:
                 self._iteration(closure, False)
@@ -416,7 +416,7 @@ class SeedSweepLBFGS:
         if self.statistics is not None:
             return bool(P0.is_cuda and P0.shape[1] <= 256 and c.d * c.p <= 256)
         return bool(P0.is_cuda and eng is not None and hasattr(getattr(eng, 'lib', None), 'symode_trainer_run')
-                    and os.environ.get('SYMODE_LBFGS_FUSED', '1') == '1' and os.environ.get('SYMODE_LBFGS_MERGED', '1') == '1'
+                    and os.environ.get('SYMODE_LBFGS_FUSED', '1') == '1'
                     and P0.shape[1] <= 256 and c.d * c.p <= 256 and getattr(c, 'n_chunks', 1) == 1)
 
     def _fit_native(self, P0, num_epochs, mask0, on_epoch):

@@ -37,7 +37,7 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
 
 
 def test_abi_version_and_error_strings(lib):
-    assert lib.symode_abi_version() == engine.ABI_VERSION
+    assert lib.symode_abi_version() == engine.ABI_VERSION == 8      # 8: the three sweep L-BFGS entries became symode_lbfgs_step
     assert lib.symode_error_string(0) == b"ok"
     for code in (-1, -2, -3, -4, -5):
         assert len(lib.symode_error_string(code)) > 3
@@ -121,34 +121,31 @@ def test_argument_validation_of_the_round2_entries(lib):
 
 
 def test_argument_validation_of_the_lbfgs_iteration_entries(lib):
-    """symode_lbfgs_update / _accept / _accept_update / symode_selftest_wave_sum: sizes and null pointers are refused
-    before any launch (n <= 256 parameters, history <= 128 pairs)."""
+    """symode_lbfgs_step / symode_selftest_wave_sum: an unknown mode, sizes and null pointers are refused before any launch
+    (n <= 256 parameters, history <= 128 pairs); ``frozen`` alone may be NULL."""
     null = ctypes.c_void_p(None)
     buf = (ctypes.c_double * 64)()
     good = ctypes.cast(buf, ctypes.c_void_p)
     st = [good] * 15                     # params, g, loss, act, n_iter, d, t, old_dirs, old_stps, ro, head, count, h_diag, prev_g, prev_loss
-    f = lib.symode_lbfgs_update
-    assert f(*st, 0, 20, 100, 1.0, 1e-9, null) == -3
-    assert f(*st, 4, 257, 100, 1.0, 1e-9, null) == -3
-    assert f(*st, 4, 20, 129, 1.0, 1e-9, null) == -3
-    assert f(*st, 4, 0, 100, 1.0, 1e-9, null) == -3
-    for k in range(15):
-        args = list(st)
-        args[k] = null
-        assert f(*args, 4, 20, 100, 1.0, 1e-9, null) == -2, k
-    f = lib.symode_lbfgs_accept        # new_loss, new_g, loss, g, act, d, t, prev_loss, S, n, tol_grad, tol_change, params, w_x, w_reg, stream
-    assert f(*([good] * 8), 0, 20, 1e-7, 1e-9, null, 1.0, 0.0, null) == -3
-    assert f(*([good] * 8), 4, 300, 1e-7, 1e-9, null, 1.0, 0.0, null) == -3
-    for k in range(8):
-        args = [good] * 8
-        args[k] = null
-        assert f(*args, 4, 20, 1e-7, 1e-9, null, 1.0, 0.0, null) == -2, k
-    f = lib.symode_lbfgs_accept_update  # new_loss, new_g, tol_grad, l1, w_x, w_reg, <15 state pointers>, S, n, history, lr, tol_change, stream
-    assert f(good, good, 1e-7, 0, 1.0, 0.0, *st, 4, 20, 0, 1.0, 1e-9, null) == -3
-    assert f(good, good, 1e-7, 0, 1.0, 0.0, *st, -1, 20, 100, 1.0, 1e-9, null) == -3
-    assert f(null, good, 1e-7, 0, 1.0, 0.0, *st, 4, 20, 100, 1.0, 1e-9, null) == -2
-    assert f(good, null, 1e-7, 0, 1.0, 0.0, *st, 4, 20, 100, 1.0, 1e-9, null) == -2
-    assert f(good, good, 1e-7, 1, 1.0, 0.0, *([null] + st[1:]), 4, 20, 100, 1.0, 1e-9, null) == -2
+    f = lib.symode_lbfgs_step            # mode, new_loss, new_g, frozen, tol_grad, l1, w_x, w_reg, <15 state pointers>, S, n, history, lr, tol_change, stream
+    for mode in (engine.LBFGS_ACCEPT, engine.LBFGS_BEGIN):
+        head = (mode, good, good, null, 1e-7, 0, 1.0, 0.0)
+        assert f(*head, *st, 0, 20, 100, 1.0, 1e-9, null) == -3
+        assert f(*head, *st, -1, 20, 100, 1.0, 1e-9, null) == -3
+        assert f(*head, *st, 4, 257, 100, 1.0, 1e-9, null) == -3
+        assert f(*head, *st, 4, 300, 100, 1.0, 1e-9, null) == -3
+        assert f(*head, *st, 4, 0, 100, 1.0, 1e-9, null) == -3
+        assert f(*head, *st, 4, 20, 129, 1.0, 1e-9, null) == -3
+        assert f(*head, *st, 4, 20, 0, 1.0, 1e-9, null) == -3
+        for k in range(15):
+            args = list(st)
+            args[k] = null
+            assert f(*head, *args, 4, 20, 100, 1.0, 1e-9, null) == -2, (mode, k)
+            assert f(mode, good, good, good, 1e-7, 1, 1.0, 0.0, *args, 4, 20, 100, 1.0, 1e-9, null) == -2, (mode, k)
+        assert f(mode, null, good, null, 1e-7, 0, 1.0, 0.0, *st, 4, 20, 100, 1.0, 1e-9, null) == -2          # new_loss
+        assert f(mode, good, null, null, 1e-7, 0, 1.0, 0.0, *st, 4, 20, 100, 1.0, 1e-9, null) == -2          # new_g
+    for mode in (0, 3, -1):                                                                                  # (0 was the removed update-only form)
+        assert f(mode, good, good, null, 1e-7, 0, 1.0, 0.0, *st, 4, 20, 100, 1.0, 1e-9, null) == -3, mode
     f = lib.symode_selftest_wave_sum
     assert f(good, good, good, 0, null) == -3 and f(null, good, good, 1, null) == -2
 

@@ -351,7 +351,7 @@ def test_lbfgs_direction_kernel_matches_torch_recursion(S):
 
 
 def test_fused_lbfgs_iteration_matches_the_tensor_op_form_and_torch(S, monkeypatch):
-    """symode_lbfgs_update / _accept (the optimiser side of an inner iteration as two launches, a wave per problem) vs the
+    """symode_lbfgs_step (the optimiser side of an inner iteration as one launch, a wave per problem) vs the
     same arithmetic in tensor ops (SYMODE_LBFGS_FUSED=0) and vs torch.optim.LBFGS per problem on the CPU, on convex
     quadratics: sizes that wrap the ring buffer (history 4), leave lanes idle (n = 7), use several components per lane
     (n = 150), problems that stop early (one starts at its optimum, one has a zero gradient direction)."""
@@ -373,17 +373,14 @@ def test_fused_lbfgs_iteration_matches_the_tensor_op_form_and_torch(S, monkeypat
             return 0.5 * (Pm * AP).sum(1) - (bd * Pm).sum(1), AP - bd
 
         runs = {}
-        for mode, fused, merged in (("merged", "1", "1"), ("two", "1", "0"), ("ops", "0", "0")):
+        for mode, fused in (("kernels", "1"), ("ops", "0")):
             monkeypatch.setenv("SYMODE_LBFGS_FUSED", fused)
-            monkeypatch.setenv("SYMODE_LBFGS_MERGED", merged)
             P = P0.to(DEV).clone()
             opt = BatchedLBFGS(P, lr, history_size=H, engine=eng)
-            assert opt.fused == (fused == "1") and opt.merged == (merged == "1")
+            assert opt.fused == (fused == "1")
             losses = [opt.step(batched).cpu() for _ in range(steps)]
             runs[mode] = (P.cpu(), torch.stack(losses), opt.n_iter.cpu(), opt.hist.cpu(), opt.head.cpu())
-        # accept + update as one launch vs as two: the same arithmetic on the same values
-        assert torch.equal(runs["merged"][0], runs["two"][0]) and torch.equal(runs["merged"][2], runs["two"][2]), n
-        Pf, Lf, nf, hf, hdf = runs["merged"]
+        Pf, Lf, nf, hf, hdf = runs["kernels"]
         Pt, Lt, nt, ht, hdt = runs["ops"]
         # (where a problem converges to the last bit the stopping tests fire an iteration or two apart: only the problem
         # that starts at its optimum is pinned on its count)
@@ -407,10 +404,13 @@ def test_fused_lbfgs_iteration_matches_the_tensor_op_form_and_torch(S, monkeypat
 
 
 def test_seed_sweep_with_fused_optimiser_kernels_equals_the_tensor_op_sweep(S, golden, monkeypatch):
-    """SeedSweepLBFGS end to end, optimiser side as symode_lbfgs_update / _accept (scale and L1 term formed by the accept
-    kernel, closure output consumed in place) vs SYMODE_LBFGS_FUSED=0: same masks, epochs and finished flags, coefficients
+    """SeedSweepLBFGS end to end, optimiser side as kernels (scale and L1 term formed by the optimiser launch, closure
+    output consumed in place) vs SYMODE_LBFGS_FUSED=0: same masks, epochs and finished flags, coefficients
     to 2e-3 -- unconstrained with a scaled data term + L1 term, unconstrained unweighted, and the so(2)-constrained recorded run
-    (beta | const layout)."""
+    (beta | const layout).  Arm "1" is the default route, the device trainer (symode_trainer_run); arms "step graph" /
+    "step eager" force the sweep's own kernel form (_native_ok -> False: BatchedLBFGS.step on symode_lbfgs_step with the
+    bare data term, ``frozen`` = the seeds that finished earlier, the (closure, ACCEPT) body replayed from a HIP graph or
+    not) and must give the trainer's bits; arm "0" is the tensor-op form."""
     from symode_amd.batched import BatchedClosure
     from symode_amd.sweep import SeedSweepLBFGS
     g = golden("f4_lbfgs")
@@ -438,11 +438,21 @@ def test_seed_sweep_with_fused_optimiser_kernels_equals_the_tensor_op_sweep(S, g
     ]
     for name, make, P0, epochs in cases:
         out = {}
-        for fused in ("1", "2", "0"):                    # "2": accept and update as separate launches
-            monkeypatch.setenv("SYMODE_LBFGS_FUSED", "0" if fused == "0" else "1")
-            monkeypatch.setenv("SYMODE_LBFGS_MERGED", "1" if fused == "1" else "0")
-            out[fused] = make().fit(P0, epochs)
-        assert torch.equal(out["1"]["mask"], out["2"]["mask"]) and torch.equal(out["1"]["params"], out["2"]["params"]), name
+        for arm, fused, forced, graph in (("1", "1", False, "1"), ("step graph", "1", True, "1"), ("step eager", "1", True, "0"),
+                                          ("0", "0", False, "1")):
+            with monkeypatch.context() as mp:
+                mp.setenv("SYMODE_LBFGS_FUSED", fused)
+                mp.setenv("SYMODE_SWEEP_GRAPH", graph)
+                if forced:
+                    mp.setattr(SeedSweepLBFGS, "_native_ok", lambda self, P0: False)
+                sw = make()
+                out[arm] = sw.fit(P0, epochs)
+                assert hasattr(sw, "trainer") == (arm == "1"), arm
+        for arm in ("step graph", "step eager"):
+            for k in ("mask", "params", "Xi", "epochs", "finished", "nan"):
+                assert torch.equal(out["1"][k], out[arm][k]), (name, arm, k)
+        if name in ("weighted", "plain"):    # seeds finish epochs apart: the later steps of the forced arms ran with frozen problems
+            assert int(out["1"]["epochs"].min()) < int(out["1"]["epochs"].max()), (name, out["1"]["epochs"])
         a, b = out["1"], out["0"]
         assert torch.equal(a["mask"], b["mask"]), name
         assert torch.equal(a["finished"], b["finished"]) and torch.equal(a["nan"], b["nan"]), name

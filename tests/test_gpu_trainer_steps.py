@@ -1,5 +1,6 @@
 """The two kernels under the default fit route, lbfgs_update_kernel (symode_trainer_update, BEGIN / ACCEPT) and
-trainer_epoch_kernel (symode_trainer_epoch_end), one launch at a time against the fp64 model of tests/trainer_model.py.
+trainer_epoch_kernel (symode_trainer_epoch_end), one launch at a time against the fp64 model of tests/trainer_model.py;
+and the sweep's entry to the first of them (symode_lbfgs_step) against the trainer's, byte for byte.
 
 The test plays the closure: it writes cl_loss / cl_grad into the state block, launches, and copies the block to the host
 before and after.  The model is handed the device's state before the launch, so no trajectory drift enters a comparison.
@@ -126,6 +127,69 @@ def test_crafted_update_launches(S, crafted):
     got = C.drive_crafted(crafted, dev, rep)
     assert got == crafted.expect, (crafted.name, got, crafted.expect)       # the model's own outcome is what the case was built for
     _verdict(crafted.name, rep, C.STEP_TOL)
+
+
+# (d, order, flags, history): n = d p = 20 with a memory of 3 pairs (the ring wraps) and of 100 (staged, one component per
+# lane), and the largest unconstrained library of the default build, n = 123: at history 3 staged with two components per
+# lane, at history 100 the unstaged form (no default library has d p = 150; 123 parameters and 100 pairs are past the 60 KB
+# the staged form may use, as 150 are).  Three components per lane need n > 128 (the d = 4 libraries of `make ALL=1` only), four
+# n > 192 (no unconstrained library).  Not filtered by only_compiled: every default build has both libraries, and a row must not
+# drop out silently.
+STEP_ENTRY_CASES = [(2, 3, 0, 3), (2, 3, 0, 100), (3, 4, 3, 3), (3, 4, 3, 100)]
+STATE_ARRAYS = (("params", "P"), ("g", "_g"), ("loss", "_loss"), ("act", "_act"), ("n_iter", "n_iter"), ("d", "d"), ("t", "t"),
+                ("old_dirs", "old_dirs"), ("old_stps", "old_stps"), ("ro", "ro"), ("head", "head"), ("count", "hist"),
+                ("h_diag", "H_diag"), ("prev_g", "prev_g"), ("prev_loss", "prev_loss"))
+
+
+@pytest.mark.parametrize("case", STEP_ENTRY_CASES, ids=lambda c: f"d{c[0]}o{c[1]}f{c[2]}-h{c[3]}")
+def test_the_sweep_entry_is_the_trainer_entry(S, case):
+    """symode_lbfgs_step on plain tensors laid out as sweep.BatchedLBFGS state against symode_trainer_update on a
+    DeviceTrainer state block: the same cl_loss / cl_grad (a convex quadratic's, evaluated on the host at the parameters
+    the launches left) for one BEGIN and four ACCEPT launches of 3 unconstrained problems, one of them frozen / done, L1
+    term on with w_x, w_reg off their defaults.  After every launch all fifteen state arrays hold the same bytes -- no
+    tolerance: the sweep's kernel route is the launch the fp64 model above checks."""
+    from symode_amd.engine import LBFGS_ACCEPT, LBFGS_BEGIN
+    from symode_amd.sweep import BatchedLBFGS
+    d, order, flags, H = case
+    Sn, frozen_one = 3, 1
+    cfg = C.M.make_cfg(lr=0.5, history=H, w_x=0.7, w_reg=0.013, l1=True, d=d)
+    dev = GpuDevice(Sn, d, order, flags, None, True, cfg, False)
+    tr, eng = dev.tr, dev.tr.engine
+    n = tr.n
+    assert n == tr.dp == (20 if d == 2 else 123)
+    gen = torch.Generator().manual_seed(100 * n + H)
+    A = torch.randn(Sn, n, n, generator=gen) / n ** 0.5
+    A = A @ A.transpose(1, 2) + 0.5 * torch.eye(n)
+    b, P0 = torch.randn(Sn, n, generator=gen), torch.randn(Sn, n, generator=gen)
+    dev._launch(eng.lib.symode_trainer_init(tr._Tp, ctypes.c_void_p(P0.data_ptr()), None, tr._st()))
+    frozen = torch.zeros(Sn, dtype=torch.bool)
+    frozen[frozen_one] = True
+    dev.put("done", frozen)
+    P = P0.to(DEV).clone()
+    opt = BatchedLBFGS(P, cfg["lr"], tolerance_grad=cfg["tol_grad"], tolerance_change=cfg["tol_change"], history_size=H, engine=eng)
+    assert opt.fused
+    frozen = frozen.to(DEV)
+    for it in range(5):
+        at = tr.field("params").cpu()
+        AP = torch.einsum("sij,sj->si", A, at)
+        cl_loss, cl_grad = (0.5 * (at * AP).sum(1) - (b * at).sum(1)).to(DEV), (AP - b).to(DEV)
+        tr.field("cl_loss").view(-1)[:Sn] = cl_loss                              # (the plain closure fills the first S floats)
+        dev.put("cl_grad", cl_grad)
+        mode = LBFGS_BEGIN if it == 0 else LBFGS_ACCEPT
+        dev.update(mode)
+        eng.lbfgs_step(mode, cl_loss, cl_grad, P, opt._g, opt._loss, opt._act, opt, cfg["lr"], cfg["tol_grad"], cfg["tol_change"],
+                       l1=(cfg["w_x"], cfg["w_reg"]), frozen=frozen)
+        torch.cuda.synchronize()
+        for field, attr in STATE_ARRAYS:
+            a, b_ = tr.field(field), getattr(opt, attr)
+            assert a.numel() == b_.numel() and a.element_size() == b_.element_size(), (field, a.shape, b_.shape)
+            assert torch.equal(a.reshape(-1).view(torch.uint8), b_.reshape(-1).view(torch.uint8)), (case, it, field)
+    # the launches did what the case is for: the live problems took every iteration and the memory of 3 wrapped
+    live = [s for s in range(Sn) if s != frozen_one]
+    assert opt._act.cpu().tolist() == [s != frozen_one for s in range(Sn)]
+    assert opt.n_iter.cpu().tolist() == [0 if s == frozen_one else 5 for s in range(Sn)]
+    assert opt.hist.cpu()[live].tolist() == [min(4, H)] * 2 and opt.head.cpu()[live].tolist() == [1 if H == 3 else 0] * 2
+    assert torch.equal(P[frozen_one].cpu(), P0[frozen_one])
 
 
 EPOCH_CASES = only_compiled(C.epoch_cases())

@@ -1,5 +1,5 @@
-"""CPU-side checks of the device Adam trainer's surface: symode_adam_epochs is an additive entry (ABI version 7 is the
-L-BFGS trainer descriptor's) whose argument validation returns error codes before any launch, main_sweep accepts the plain
+"""CPU-side checks of the device Adam trainer's surface: symode_adam_epochs is an additive entry (it came with the ABI version of the
+L-BFGS trainer descriptor, 7) whose argument validation returns error codes before any launch, main_sweep accepts the plain
 Adam configuration and keeps its other refusals, train_SIGED(device_adam=True) refuses what it does not cover without
 touching a device, and DeviceBatches.epoch_order() is the permutation __iter__ draws."""
 import ctypes
@@ -34,8 +34,8 @@ def _call(lib, x=JUNK, dx=JUNK, n_src=300, idx=JUNK, n_tab=1, n_epochs=3, n_step
                                   xi, log, NULL)
 
 
-def test_the_entry_is_additive_abi_version_is_the_trainers_7(lib):
-    assert engine.ABI_VERSION == 7 and lib.symode_abi_version() == 7
+def test_the_entry_is_additive_abi_version_is_the_bindings(lib):
+    assert lib.symode_abi_version() == engine.ABI_VERSION            # (the number itself: tests/test_abi.py)
     assert "symode_adam_epochs" in engine._SIGNATURES and hasattr(lib, "symode_adam_epochs")
     header = open(os.path.join(ROOT, "include", "symode.h")).read()
     assert "int symode_adam_epochs(" in header and "torch.optim.Adam.step" in header

@@ -1,5 +1,5 @@
 """CPU-side checks of symode_loss_grad_latent, the closure of the latent L-BFGS fit: the symbol is exported and bound,
-the entry is an addition (ABI version 7 is the trainer descriptor naming it as a closure kind), and bad arguments are refused
+the entry is an addition (it came with ABI version 7, the trainer descriptor naming it as a closure kind), and bad arguments are refused
 before anything is launched (codes: -1 unsupported, -2 null, -3 size, -4 workspace, -5 alignment) in the order of the
 reversed closure's checks."""
 import ctypes
@@ -37,7 +37,7 @@ def test_the_entry_is_exported_bound_and_additive(lib):
     assert hasattr(lib, "symode_loss_grad_latent") and "symode_loss_grad_latent" in engine._SIGNATURES
     res, args = engine._SIGNATURES["symode_loss_grad_latent"]
     assert res is ctypes.c_int and len(args) == len(OK)
-    assert lib.symode_abi_version() == engine.ABI_VERSION == 7
+    assert lib.symode_abi_version() == engine.ABI_VERSION            # (the number itself: tests/test_abi.py)
     assert hasattr(engine.HipEngine, "loss_grad_latent")
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "symode.h")).read()
     decl = header[:header.index("int symode_loss_grad_latent(")]

@@ -90,8 +90,8 @@ def grad_of(g_xi, cfg):
 def update(state, cl_loss, cl_grad, cfg, mode):
     """One ``symode_trainer_update`` launch -- the TRAINER's route only: that entry point always forms
     w_x * data + w_reg * |params|_1 (w_reg = 0 when ``l1`` is off) and always keeps ``l1_last``, and so does this model.  The
-    sweep's entry points (symode_lbfgs_update / symode_lbfgs_accept_update without the L1 term: no w_x, no l1_last) are
-    NOT described here.  ``cl_loss`` (2,) = (mse, regulariser) [the second is ignored without ``pair``],
+    sweep's entry point (symode_lbfgs_step) is the same launch without map, pair and l1_last: with its ``l1`` set it is
+    tied to this one byte for byte (tests/test_gpu_trainer_steps.py); its l1 == 0 call (no w_x) is NOT described here.  ``cl_loss`` (2,) = (mse, regulariser) [the second is ignored without ``pair``],
     ``cl_grad`` (dp,) = d(data term)/dXi.  Returns (state', margins)."""
     st, mg = _copy(state), []
     dt = st["params"].dtype

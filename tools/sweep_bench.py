@@ -1,5 +1,5 @@
-"""Seed-sweep L-BFGS (sweep.SeedSweepLBFGS) wall time: optimiser side as two fused kernels per inner iteration
-(symode_lbfgs_update / _accept) vs the tensor-op form, each eager and replayed from a HIP graph.
+"""Seed-sweep L-BFGS (sweep.SeedSweepLBFGS) wall time: optimiser side as one kernel launch per inner iteration (the
+device trainer where it serves the fit, else symode_lbfgs_step) vs the tensor-op form, each eager and replayed from a HIP graph.
 
     python tools/sweep_bench.py [--shapes 64x50000x3,512x125000x3,1024x125000x5] [--epochs 60]
 """
