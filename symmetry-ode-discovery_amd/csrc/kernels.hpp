@@ -23,7 +23,7 @@ constexpr int MAP_CHUNKS_PER_THREAD = SYMODE_MAP_CHUNKS;   // chunks a thread of
 // for the tests and tuning tools that compare two settings inside one process; no launch path calls getenv.
 struct Knobs {
     long max_grid, min_grid_x, map_grid, gram_grid, gram_valu_grid, small_grid, reduce_grid;
-    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4;
+    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk;
     long gram_m4_grid;
 };
 
@@ -47,6 +47,7 @@ inline Knobs read_knobs() {
     k.row_split = (int)num("SYMODE_ROW_SPLIT", 1);
     k.gram_m4 = on("SYMODE_GRAM_M4");
     k.gram_m4_grid = num("SYMODE_GRAM_M4_GRID", -1);
+    k.closure_pk = on("SYMODE_CLOSURE_PK");
     return k;
 }
 
@@ -415,6 +416,8 @@ __global__ __launch_bounds__(BLOCK) void odeint_kernel(const float* __restrict__
 // ---------------------------------------------------------------------------------------
 constexpr unsigned long long WS_MAGIC = 0x53594d4f44453032ull;      // "SYMODE02"
 constexpr long WS_MAX_PROBLEMS = 65536;                              // tickets in the header (grid.y limit is 65535)
+constexpr int WS_BODY_WORD = 1;                                      // header word the reversed closure leaves its body in:
+constexpr unsigned long long WS_BODY_SCALAR = 1, WS_BODY_PACKED = 2; //   which of its two bit-identical bodies the last launch took
 constexpr long WS_HEADER_DOUBLES = 8 + WS_MAX_PROBLEMS / 2;          // [magic, 7 reserved | uint32 tickets] in front of the partials
 
 struct Finish {
@@ -579,9 +582,14 @@ inline int fused_finalize_mode() { return (int)knobs().fused_finalize; }      //
 //   RING4 = false  everything else: two chunks in flight (D = 3: coalesced tile loads through the wave's LDS slab).
 // Round 1 measured the alternatives on MI355X (profiles/r01_ab_variants.txt; S = 2048 x 125 000 points, d = 2, algorithmic
 // bytes per launch): plain grid-stride loop 4.8 / 5.6 TB/s at order 5 / 3, two chunks per step with non-temporal loads
-// 5.4 / 6.35, a register double buffer 5.55 / 6.45, this ring 5.65 / 6.45; a packed-fp32 form (v_pk_fma_f32 over the two
-// equation rows: same roundings, half the instructions) and an LDS-DMA ring measured within 1 % of it -- gfx950 retires a
-// v_pk_fma_f32 in the time of two v_fma_f32 (profiles/r03_issue_probe.txt) -- and were removed in round 3.
+// 5.4 / 6.35, a register double buffer 5.55 / 6.45, this ring 5.65 / 6.45; a packed-fp32 form of THIS kernel (v_pk_fma_f32
+// over the two equation rows: same roundings, half the instructions) and an LDS-DMA ring measured within 1 % of it and
+// were removed in round 3: at 16 B/point this kernel waits for HBM, not for the vector pipe.  That finding is about this
+// kernel only.  A v_pk_fma_f32 costs 4.6-4.8 cycles per wave-instruction, 2.3-2.4 per FMA, against 2.8-3.15 for the
+// v_fmac_f32 forms these bodies issue (profiles/r03_valu_rate.txt): where a kernel IS issue-bound -- the constant-J
+// reversed closure below, 24 B/point and two libraries per point -- packing halves the instruction count, and that kernel
+// has a packed body of its own (symreg_reversed_kernel, PK).  What it gains is measured, library by library, at
+// launch_symreg_reversed and in profiles/closure_packed.txt: 2 % of the kernel time at order 5, more with exp columns.
 // With the masked Xi in VGPRs the order-5 kernel needs 166 VGPRs (3 waves/SIMD); handing Xi to SGPRs (126 VGPRs,
 // 4 waves) measured 1.5 % slower -- an SGPR operand costs issue time -- and grid widths 4096-16384 measured the same.
 // Why order 5 stops there: 108 VALU ops per point = 422 K wave-instructions per SIMD per launch, and a SIMD with 3
@@ -786,6 +794,26 @@ struct JChunk {
     static_assert(Chunk<D>::PPT * D * D == NV * 4, "Jacobian chunk must be whole 16-byte vectors");
 };
 
+// d = fma(w.SEL broadcast to both halves, t, c) in one v_pk_fma_f32: op_sel / op_sel_hi pick half SEL of the first operand
+// for the low / the high result.  Written out because the compiler, given the same thing as a shuffle of a uniform pair,
+// makes a pair (w, w) of its own for every coefficient -- twice the SGPRs the kernel has.
+template <int SEL, bool SGPR>
+__device__ __forceinline__ float2v pk_fma_bcast(float2v w, float2v t, float2v c) {
+    float2v d;
+    if constexpr (SGPR) {
+        if constexpr (SEL == 0)
+            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "s"(w), "v"(t), "v"(c));
+        else
+            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0]" : "=v"(d) : "s"(w), "v"(t), "v"(c));
+    } else {
+        if constexpr (SEL == 0)
+            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(w), "v"(t), "v"(c));
+        else
+            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0]" : "=v"(d) : "v"(w), "v"(t), "v"(c));
+    }
+    return d;
+}
+
 // MSE = true: the whole closure of the reversed-regulariser runs in ONE pass -- the residual r = h(x) - dx shares
 // Theta(x) and h(x) with the regulariser, x is read once (40 instead of 16 + 32 bytes per point at D = 2, n_g = 1):
 //   sums[0] = sum r^2, sums[1] = sum_g sum u^2,  grad = d( sums[0] + w_sym sums[1] ) / dXi  (both under the same 1/(N D)).
@@ -796,7 +824,14 @@ struct JChunk {
 // MINW: waves per SIMD the register allocation has to leave room for (the launcher asks for 3 in the CJ form of the
 // d = 2 polynomial libraries: left alone, the order-5 closure comes out at 169 VGPRs -- one over the 3-wave limit of 168 --
 // although its ring slot is two vectors shorter; asked, it fits in 148 without scratch).
-template <class Lib, bool MSE, int RING = 2, int XI_SGPR_FROM = 32, bool CJ = false, int MINW = 1>
+// PK (CJ form, D = 2): the packed-fp32 body.  The point's two library evaluations run as ONE on the pairs
+// t[k] = (Theta_k(x), Theta_k(g x)): v_pk_mul_f32 for the monomials, one v_pk_fma_f32 per (j, k) for (h_j(x), h_j(g x)) with
+// the pair (w[0][k], w[1][k]) as the coefficient operand and op_sel choosing j, and the gradient sums as pairs over the two
+// equation rows, acc2[k] = fma((jtu_0, jtu_1), t[k].xx, fma(-(u_0, u_1), t[k].yy, acc2[k])) -- the halves of a full pair
+// picked by op_sel, so no register is half used.  Every product and every sum is the one the scalar body forms, in its
+// order: the results are bit-identical to it (and so to the materialised form).  Per point 19 + 42 + 42 packed
+// instructions instead of 36 + 84 + 84 scalar ones; where that pays is in the launcher's table (launch_symreg_reversed).
+template <class Lib, bool MSE, int RING = 2, int XI_SGPR_FROM = 32, bool CJ = false, int MINW = 1, bool PK = false>
 __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const float* __restrict__ x, const float* __restrict__ dx,
                                                                 const float* __restrict__ gx,
                                                                 const float* __restrict__ jgx, int n_g, long N, bool vec,
@@ -806,6 +841,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
     vec = vec && chunked_stream<Lib>;            // (D = 3 sine / exp libraries: point by point, see chunked_stream)
     constexpr int D = Lib::D, P = Lib::P, NL = MSE ? 2 : 1, NACC = NL + D * P, PPT = Chunk<D>::PPT, NV = Chunk<D>::NV,
                   NVJ = JChunk<D>::NV, SYM0 = NL - 1;
+    static_assert(!PK || (CJ && D == 2), "the packed body pairs the two library evaluations of the constant-J form at d = 2");
     const long s = blockIdx.y;
     const float* xs = x + s * N * D;
     const float* ys = MSE ? dx + s * N * D : nullptr;
@@ -819,6 +855,9 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
 #pragma unroll
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0f;
     const float ws_ = MSE ? w_sym : 1.0f;
+    // (an initialised workspace only: one that never saw symode_workspace_init is left as it was found)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && fin.header[0] == WS_MAGIC)
+        fin.header[WS_BODY_WORD] = PK ? WS_BODY_PACKED : WS_BODY_SCALAR;
     // CJ: the matrix of group element g, wave-uniform (scalar loads; readfirstlane pins the values to SGPRs)
     auto load_cj = [&](int g, float (&J)[D * D]) {
 #pragma unroll
@@ -868,6 +907,67 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
             acc[0] = fmaf(r[j], r[j], acc[0]);
         }
     };
+    // PK: one point against one group element, everything of the point formed here (a further group element forms
+    // Theta(x), h(x) again in the low halves: the same bits); `first`: the group element that carries the residual.
+    // The gradient sums live in acc2 (pair k = rows 0 and 1 of column k) and are unpacked into acc before emit_partials.
+    // The coefficient pair w2[k] = (w[0][k], w[1][k]) is ONE operand (an SGPR pair where load_xi keeps Xi in SGPRs) and the
+    // row is chosen by op_sel (pk_fma_bcast); h0 is the chain's first link, fma(w[j][0], Theta_0 = 1, 0), formed once.
+    constexpr int P2 = PK ? P : 1;
+    constexpr bool W_SGPR = D * P >= XI_SGPR_FROM && D * P <= 80;
+    float2v acc2[P2], w2[P2], h0[D];
+#pragma unroll
+    for (int k = 0; k < P2; ++k) {
+        acc2[k] = float2v{0.0f, 0.0f};
+        w2[k] = PK ? float2v{w[k], w[(D - 1) * P + k]} : acc2[k];
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        const float s0 = fmaf(w[j * P], 1.0f, 0.0f);
+        h0[j] = float2v{s0, s0};
+    }
+    auto one_pk = [&](const float (&xp)[D], const float (&gp)[D], const float (&J)[D * D], const float (&yp)[D], bool first) {
+        float2v xx[D], t[P], hh[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) xx[a] = float2v{xp[a], gp[a]};
+        Lib::eval_pair(xx, t);
+        hh[0] = h0[0];
+        hh[D - 1] = h0[D - 1];
+#pragma unroll
+        for (int k = 1; k < P; ++k) {
+            hh[0] = pk_fma_bcast<0, W_SGPR>(w2[k], t[k], hh[0]);
+            hh[D - 1] = pk_fma_bcast<1, W_SGPR>(w2[k], t[k], hh[D - 1]);
+        }
+        float h[D], r[D], u[D], jtu[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            h[j] = hh[j].x;
+            r[j] = 0.0f;
+        }
+        if constexpr (MSE) {
+            if (first) resid(h, yp, r);
+        }
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            float s_ = -hh[a].y;
+#pragma unroll
+            for (int b = 0; b < D; ++b) s_ = fmaf(J[a * D + b], h[b], s_);
+            u[a] = s_;
+            acc[SYM0] = fmaf(s_, s_, acc[SYM0]);
+        }
+#pragma unroll
+        for (int b = 0; b < D; ++b) {
+            float s_ = 0.0f;
+#pragma unroll
+            for (int a = 0; a < D; ++a) s_ = fmaf(J[a * D + b], u[a], s_);
+            jtu[b] = MSE ? fmaf(ws_, s_, r[b]) : s_;
+        }
+        const float2v ja = float2v{jtu[0], jtu[D - 1]};
+        const float2v ub = MSE ? float2v{-(ws_ * u[0]), -(ws_ * u[D - 1])} : float2v{-u[0], -u[D - 1]};
+#pragma unroll
+        for (int k = 0; k < P2; ++k)
+            acc2[k] = __builtin_elementwise_fma(ja, __builtin_shufflevector(t[k], t[k], 0, 0),
+                                                __builtin_elementwise_fma(ub, __builtin_shufflevector(t[k], t[k], 1, 1), acc2[k]));
+    };
     auto load_j = [&](const float* base, long c, float4 (&v)[NVJ]) {
         typedef float f4v __attribute__((ext_vector_type(4)));
         const f4v* q = reinterpret_cast<const f4v*>(base) + c * NVJ;
@@ -900,6 +1000,20 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
     auto point = [&](long n) {
         float xp[D], th[P], h[D], r[D], zero[D];
         load_point<D>(xs, n, xp);
+        if constexpr (PK) {
+            float yp[D];
+            if constexpr (MSE)
+                load_point<D>(ys, n, yp);
+            else
+                yp[0] = yp[D - 1] = 0.0f;
+            for (int g = 0; g < n_g; ++g) {
+                float gp[D], J[D * D];
+                load_point<D>(gs + (long)g * N * D, n, gp);
+                load_cj(g, J);
+                one_pk(xp, gp, J, yp, g == 0);
+            }
+            return;
+        }
         Lib::eval(xp, th);
         apply_xi<Lib>(w, th, h);
 #pragma unroll
@@ -985,6 +1099,25 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
                     load_j(js + (long)g * N * D * D, c, nj);
                     group(ng, nj, J0, false);
                 }
+            }
+            return;
+        }
+        if constexpr (PK) {
+            float xp[PPT][D], yp[PPT][D], gp[PPT][D];
+            unpack_chunk<D>(vx, xp);
+            if constexpr (MSE)
+                unpack_chunk<D>(vy, yp);
+            else
+                unpack_chunk<D>(vx, yp);               // (not read: one_pk takes the residual's target in the MSE form only)
+            unpack_chunk<D>(vg, gp);
+            each_point<PPT>([&](auto i) { one_pk(xp[i], gp[i], J0, yp[i], true); });
+            for (int g = 1; g < n_g; ++g) {
+                float4 ng[NV];
+                float Jg[D * D];
+                load_chunk_raw<D, true>(gs + (long)g * N * D, c, ng);
+                load_cj(g, Jg);
+                unpack_chunk<D>(ng, gp);
+                each_point<PPT>([&](auto i) { one_pk(xp[i], gp[i], Jg, yp[i], false); });
             }
             return;
         }
@@ -1097,6 +1230,13 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
         if (n < N) point(n);
     } else {
         for (long n = tid; n < N; n += nthreads) point(n);
+    }
+    if constexpr (PK) {
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            acc[NL + k] = acc2[k].x;
+            acc[NL + (D - 1) * P + k] = acc2[k].y;
+        }
     }
     emit_partials<NACC>(acc, ws, fin);
 }
@@ -1699,7 +1839,26 @@ hipError_t launch_symreg_linear(const float* z, long n, const float* xi, const f
     return launch_finalize(fin, part, 1, gx, NACC, st);
 }
 
+// Libraries whose constant-J closure takes the packed body (symreg_reversed_kernel, PK): where it measured faster on the
+// MI355X at the bench shape (8192 x 125 000) in every pass, by more than the arms' own spread, and no slower at 64 x 50 000
+// (tools/micro/closure_ab pk, three interleaved passes, packed / scalar time; profiles/closure_packed.txt has all twenty
+// d = 2 libraries):
+//   order 5           plain 0.980-0.981 / 0.98-1.00   sine 1.012-1.018 / 0.97-0.98   exp 0.897-0.900 / 0.88-0.89   both 0.937-0.944 / 0.90-0.91
+//   order 4           plain 1.03-1.04 / 1.06-1.09     sine 1.05 / 1.05-1.06          exp 0.932-0.944 / 0.92-0.94   both 0.987-0.994 / 0.92-0.93
+//   orders 1-3        0.95-1.14 at the bench shape (plain: 0.99-1.02, they stream at the HBM rate either way), 0.98-1.17 at the small
+//                     one; the two that gain at the bench shape, exp alone at orders 2-3 (0.95-0.96), lose up to 8 % at the small one
+// Sine columns alone lose or stay inside the spread at the bench shape at every order (the two sinf of a pair do not
+// pack and the pair layout only costs); sine + exp at order 4 is inside the arms' 0.85 % spread there: all scalar.
+// The order-5 plain library is the flagship's: its kernel falls from 5.40-5.44 to 5.29-5.33 ms, 2 %, although the
+// vector instructions per point fall from 225 to 128 (counters): a packed instruction costs 4.6-4.8 cycles against 2.85-3.1,
+// both bodies fill the vector pipe, and of the 8 % fewer cycles the kernel then takes 2 % arrive as time.  Below order 4
+// the coefficients sit in VGPRs and the kernels are not issue-bound.
+template <class Lib>
+constexpr bool closure_pk_pays = Lib::D == 2 && ((Lib::ORDER == 5 && (Lib::EXP || !Lib::SINE)) || (Lib::ORDER == 4 && Lib::EXP && !Lib::SINE));
+
 // constj: jgx is the compact (S, n_g, D, D) table of a point-constant Jacobian (the CJ kernels, see symreg_reversed_kernel)
+// SYMODE_CLOSURE_PK=0 keeps the scalar body everywhere.  The body a launch took is left in word 1 of the workspace header
+// (WS_BODY_SCALAR / WS_BODY_PACKED): the bodies are bit-identical, so nothing else tells them apart.
 template <class Lib>
 hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* gxp, const float* jgx, bool constj, int n_g, long S,
                                   long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
@@ -1716,20 +1875,28 @@ hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* 
     const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)gxp % 16 == 0) && (constj || (uintptr_t)jgx % 16 == 0) &&
                      (!mse || (uintptr_t)dx % 16 == 0) && (!multi || ((n * D) % 4 == 0 && (constj || (n * D * D) % 4 == 0)));
     const dim3 grid(gx, (unsigned)S), block(BLOCK);
-    const auto launch = [&](auto cj) {                  // the kernel family: CJ as a compile-time constant
-        constexpr bool CJ = decltype(cj)::value;
+    const auto launch = [&](auto cj, auto pk) {         // the kernel family: CJ and the body as compile-time constants
+        constexpr bool CJ = decltype(cj)::value, PK = decltype(pk)::value;
         constexpr int MINW = (CJ && D == 2 && !Lib::SINE && !Lib::EXP) ? 3 : 1;
         if (mse)
-            symreg_reversed_kernel<Lib, true, 2, 32, CJ, MINW><<<grid, block, 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi, mask, w_sym,
-                                                                                     part, fin);
+            symreg_reversed_kernel<Lib, true, 2, 32, CJ, MINW, PK><<<grid, block, 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi, mask,
+                                                                                         w_sym, part, fin);
         else
-            symreg_reversed_kernel<Lib, false, 2, 32, CJ, MINW><<<grid, block, 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec, xi, mask,
-                                                                                      1.0f, part, fin);
+            symreg_reversed_kernel<Lib, false, 2, 32, CJ, MINW, PK><<<grid, block, 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec, xi,
+                                                                                          mask, 1.0f, part, fin);
     };
-    if (constj)
-        launch(std::true_type{});
-    else
-        launch(std::false_type{});
+    if constexpr (closure_pk_pays<Lib>) {
+        if (constj && knobs().closure_pk)
+            launch(std::true_type{}, std::true_type{});
+        else if (constj)
+            launch(std::true_type{}, std::false_type{});
+        else
+            launch(std::false_type{}, std::false_type{});
+    } else if (constj) {
+        launch(std::true_type{}, std::false_type{});
+    } else {
+        launch(std::false_type{}, std::false_type{});
+    }
     SYMODE_LAUNCH_CHECK();
     return launch_finalize(fin, part, S, gx, nacc, st);
 }

@@ -13,6 +13,8 @@
 
 namespace symode {
 
+typedef float float2v __attribute__((ext_vector_type(2)));   // an aligned VGPR / SGPR pair: operand of the packed-fp32 instructions
+
 constexpr int FLAG_SINE = 1;   // include_sine  (sindy.py:74-75)
 constexpr int FLAG_EXP = 2;    // include_exp   (sindy.py:76-77)
 
@@ -84,6 +86,22 @@ struct Library {
         if constexpr (EXP) {
 #pragma unroll
             for (int i = 0; i < D; ++i) th[EXP0 + i] = expf(x[i]);
+        }
+    }
+
+    // Theta at TWO points at once: pair k holds (Theta_k(a), Theta_k(b)) for x[i] = (a_i, b_i).  The same products in the
+    // same order as eval, elementwise on the pairs (v_pk_mul_f32): each half is bit-identical to eval of its point.
+    static __device__ __forceinline__ void eval_pair(const float2v (&x)[D], float2v (&th)[P]) {
+        th[0] = float2v{1.0f, 1.0f};
+#pragma unroll
+        for (int t = 1; t < NP; ++t) th[t] = th[tab.parent[t]] * x[tab.var[t]];
+        if constexpr (SINE) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) th[SIN0 + i] = float2v{sinf(x[i].x), sinf(x[i].y)};
+        }
+        if constexpr (EXP) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) th[EXP0 + i] = float2v{expf(x[i].x), expf(x[i].y)};
         }
     }
 

@@ -550,6 +550,14 @@ class HipEngine:
                                                       self._stream(jgx)), "symode_jacobian_constant")
         return table, bool(flag.item())
 
+    @staticmethod
+    def closure_body(ws):
+        """Which body the last reversed-closure launch on workspace ``ws`` took: "scalar", "packed" (the packed-fp32 body of the
+        compact-table form, d = 2; SYMODE_CLOSURE_PK=0 turns it off) or None before any.  The kernel leaves it in word 1 of the
+        workspace header (an initialised workspace only, and only its LAST launch is visible): the two bodies return the same
+        bits, so the results cannot tell.  One synchronisation."""
+        return {1: "scalar", 2: "packed"}.get(int(ws.view(torch.int64)[1].item()))
+
     def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None):
         """The closure MSE + w_sym * reversed regulariser in ONE pass (x read once, Theta(x) shared by both terms).
         Shapes as loss_grad / symreg_reversed (jgx may be the compact table of a point-constant Jacobian, as there).

@@ -5,6 +5,9 @@
 // form of the closure measured in profiles/r03_closure_walk.txt lives in commit becc803 only.)
 // `closure_ab constj`: only the ring-depth A/B of the constant-Jacobian form of the fused closure (24 B/point) at the
 // bench's batched shape, beside the materialised form (40 B/point), three interleaved passes.
+// `closure_ab pk`: scalar body against the packed-fp32 body (PK) of the constant-Jacobian fused closure for the d = 2
+// libraries, at the bench's batched shape and at 64 x 50 000, on the launcher's grids, three interleaved passes.  The
+// launcher's table (kernels.hpp, closure_pk_pays) is read off this run.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -I symmetry-ode-discovery_amd/csrc
 //              -o tools/micro/closure_ab tools/micro/closure_ab.hip
 #include <hip/hip_runtime.h>
@@ -146,9 +149,10 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&xi3, S * D * L3::P * 4));
     CK(hipMalloc(&xi5, S * D * L5::P * 4));
     CK(hipMalloc(&loss, S * 2 * 4));
-    CK(hipMalloc(&grad, S * D * L5::P * 4));
+    constexpr int PW = Library<2, 5, 3>::P;       // the widest library any arm launches (`pk`: order 5 with sine and exp columns)
+    CK(hipMalloc(&grad, S * D * PW * 4));
     const long max_rows = 4 * S;                  // partial rows of the widest launch
-    CK(hipMalloc(&ws, (WS_HEADER_DOUBLES + max_rows * (2 + D * L5::P)) * 8));
+    CK(hipMalloc(&ws, (WS_HEADER_DOUBLES + max_rows * (2 + D * PW)) * 8));
     fill<<<4096, 256>>>(x, NT * D, 1u, 0.7f);
     fill<<<4096, 256>>>(dx, NT * D, 2u, 0.5f);
     fill<<<4096, 256>>>(gx, NT * D, 3u, 0.7f);
@@ -177,6 +181,46 @@ int main(int argc, char** argv) {
             CJRUN("constant J, ring 3, 3 waves/SIMD asked", 24.0, 3, 32, true, 3)
             CJRUN("constant J, ring 2, allocator left alone", 24.0, 2, 32, true, 1)
         }
+        CK(hipDeviceSynchronize());
+        return 0;
+    }
+    if (argc > 1 && strcmp(argv[1], "pk") == 0) {
+        float* xiw;                                   // coefficients of the widest library; every library reads a prefix
+        CK(hipMalloc(&xiw, S * D * PW * 4));
+        fill<<<64, 256>>>(xiw, S * D * PW, 6u, 0.3f);
+        CK(hipDeviceSynchronize());
+        printf("# fused closure, constant J (24 B/point), scalar body | packed body: us per launch (min of 3 rounds of 5), three passes\n");
+        const long shapes[2][2] = {{S, NB}, {64, 50000}};
+#define PKRUN(ORDER, FLAGS)                                                                                                        \
+    {                                                                                                                              \
+        using LB = Library<2, ORDER, FLAGS>;                                                                                       \
+        static_assert(LB::P <= PW, "grad, ws and xiw are sized for PW columns");                                                   \
+        constexpr int MW = FLAGS == 0 ? 3 : 1;                                                                                     \
+        const double a_ = time_us([&] { symreg_reversed_kernel<LB, true, 2, 32, true, MW, false><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
+                                            x, dx, gx, jgx, 1, Nx, true, xiw, nullptr, 0.1f, part, fin2); }, 5);                   \
+        const double b_ = time_us([&] { symreg_reversed_kernel<LB, true, 2, 32, true, MW, true><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>(  \
+                                            x, dx, gx, jgx, 1, Nx, true, xiw, nullptr, 0.1f, part, fin2); }, 5);                   \
+        printf("pass %d  %5ld x %6ld  order %d flags %d (p = %2d)  scalar %8.1f us  packed %8.1f us  packed/scalar %.3f\n", pass, Sx, Nx, \
+               ORDER, FLAGS, LB::P, a_, b_, b_ / a_);                                                                              \
+    }
+        for (int pass = 0; pass < 3; ++pass)
+            for (const auto& sh : shapes) {
+                const long Sx = sh[0], Nx = sh[1];
+                const int gxw = grid_x_for(Nx, Sx, 2, 512);
+                if ((long)gxw * Sx > max_rows) {
+                    fprintf(stderr, "grid %d x %ld needs more partial rows than the workspace holds\n", gxw, Sx);
+                    return 1;
+                }
+                PKRUN(1, 0) PKRUN(2, 0) PKRUN(3, 0) PKRUN(4, 0) PKRUN(5, 0)
+                PKRUN(1, 1) PKRUN(2, 1) PKRUN(3, 1) PKRUN(4, 1) PKRUN(5, 1)
+                PKRUN(1, 2) PKRUN(2, 2) PKRUN(3, 2) PKRUN(4, 2) PKRUN(5, 2)
+                PKRUN(1, 3) PKRUN(2, 3) PKRUN(3, 3) PKRUN(4, 3) PKRUN(5, 3)
+                {   // the packed body with three chunks in flight (161 VGPRs, still 3 waves/SIMD): does the freed issue time want a deeper ring?
+                    const double r3 = time_us([&] { symreg_reversed_kernel<L5, true, 3, 32, true, 3, true><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>(
+                                                        x, dx, gx, jgx, 1, Nx, true, xiw, nullptr, 0.1f, part, fin2); }, 5);
+                    printf("pass %d  %5ld x %6ld  order 5 flags 0 (p = 21)  packed, ring 3 %8.1f us\n", pass, Sx, Nx, r3);
+                }
+            }
         CK(hipDeviceSynchronize());
         return 0;
     }
