@@ -4,7 +4,7 @@
 // Jacobian per point whatever the map is.  For a linear or affine group action on the observed coordinates, or a frozen
 // linear autoencoder, every point of a (problem, group element) slab holds the same D x D matrix, and the closure kernels
 // have a form that reads it from a compact (S, n_g, D, D) table instead of streaming 4 D D bytes per point
-// (kernels.hpp, symreg_reversed_kernel<.., CJ = true>).  This pass decides whether that form may be used.
+// (closure_rev.hpp, symreg_reversed_kernel<.., CJ = true>).  This pass decides whether that form may be used.
 //
 // Every word of a slab is compared BITWISE (as 32-bit integers) with the word at the same matrix position of the slab's
 // point 0: -0.0 differs from +0.0 and a NaN payload only matches itself, so anything doubtful keeps the materialised path

@@ -587,9 +587,9 @@ inline int fused_finalize_mode() { return (int)knobs().fused_finalize; }      //
 // were removed in round 3: at 16 B/point this kernel waits for HBM, not for the vector pipe.  That finding is about this
 // kernel only.  A v_pk_fma_f32 costs 4.6-4.8 cycles per wave-instruction, 2.3-2.4 per FMA, against 2.8-3.15 for the
 // v_fmac_f32 forms these bodies issue (profiles/r03_valu_rate.txt): where a kernel IS issue-bound -- the constant-J
-// reversed closure below, 24 B/point and two libraries per point -- packing halves the instruction count, and that kernel
-// has a packed body of its own (symreg_reversed_kernel, PK).  What it gains is measured, library by library, at
-// launch_symreg_reversed and in profiles/closure_packed.txt: 2 % of the kernel time at order 5, more with exp columns.
+// reversed closure, 24 B/point and two libraries per point -- packing halves the instruction count, and that kernel
+// has a packed body of its own (closure_rev.hpp: symreg_reversed_kernel, PK).  What it gains is measured, library by library,
+// at launch_symreg_reversed and in profiles/closure_packed.txt: 2 % of the kernel time at order 5, more with exp columns.
 // With the masked Xi in VGPRs the order-5 kernel needs 166 VGPRs (3 waves/SIMD); handing Xi to SGPRs (126 VGPRs,
 // 4 waves) measured 1.5 % slower -- an SGPR operand costs issue time -- and grid widths 4096-16384 measured the same.
 // Why order 5 stops there: 108 VALU ops per point = 422 K wave-instructions per SIMD per launch, and a SIMD with 3
@@ -776,468 +776,6 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_linear_kernel(const float*
             load_point<D>(z, n, zp);
             one(zp);
         });
-    emit_partials<NACC>(acc, ws, fin);
-}
-
-// ---------------------------------------------------------------------------------------
-// S4: reversed symmetry regulariser with precomputed (g(x), J_g(x))
-//   u = J_g(x) h(x) - h(g(x));  loss = sum_g mean(u^2);
-//   dloss/dXi[j,k] = (2/(N D)) sum ( (J_g^T u)_j th_k(x) - u_j th_k(g x) ).
-// Batched like K1: problem s = blockIdx.y owns x[s] (N, D), gx[s] (n_g, N, D), jgx[s] (n_g, N, D, D), xi[s], mask[s].
-// A pure stream (8 + n_g * 24 bytes per point at D = 2, each read once): every operand arrives as non-temporal
-// 16-byte vectors -- a chunk of PPT points is one vector of x, one of g(x) and PPT*D*D/4 consecutive vectors of J_g --
-// and a step issues the loads of two chunks before the arithmetic of either.
-// ---------------------------------------------------------------------------------------
-template <int D>
-struct JChunk {
-    static constexpr int NV = Chunk<D>::PPT * D * D / 4;              // dwordx4 per chunk of Jacobians
-    static_assert(Chunk<D>::PPT * D * D == NV * 4, "Jacobian chunk must be whole 16-byte vectors");
-};
-
-// d = fma(w.SEL broadcast to both halves, t, c) in one v_pk_fma_f32: op_sel / op_sel_hi pick half SEL of the first operand
-// for the low / the high result.  Written out because the compiler, given the same thing as a shuffle of a uniform pair,
-// makes a pair (w, w) of its own for every coefficient -- twice the SGPRs the kernel has.
-template <int SEL, bool SGPR>
-__device__ __forceinline__ float2v pk_fma_bcast(float2v w, float2v t, float2v c) {
-    float2v d;
-    if constexpr (SGPR) {
-        if constexpr (SEL == 0)
-            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "s"(w), "v"(t), "v"(c));
-        else
-            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0]" : "=v"(d) : "s"(w), "v"(t), "v"(c));
-    } else {
-        if constexpr (SEL == 0)
-            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(w), "v"(t), "v"(c));
-        else
-            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0]" : "=v"(d) : "v"(w), "v"(t), "v"(c));
-    }
-    return d;
-}
-
-// MSE = true: the whole closure of the reversed-regulariser runs in ONE pass -- the residual r = h(x) - dx shares
-// Theta(x) and h(x) with the regulariser, x is read once (40 instead of 16 + 32 bytes per point at D = 2, n_g = 1):
-//   sums[0] = sum r^2, sums[1] = sum_g sum u^2,  grad = d( sums[0] + w_sym sums[1] ) / dXi  (both under the same 1/(N D)).
-// CJ = true: J_g is the same matrix at every point of a (problem, group element) -- a linear or affine action, a frozen
-// linear autoencoder -- and jgx is the compact (S, n_g, D, D) table: the D*D values are wave-uniform and live in SGPRs,
-// nothing of J_g is streamed (24 instead of 40 bytes per point at D = 2, n_g = 1).  Same arithmetic in the same order on
-// the same chunk-to-lane assignment as the materialised form: the results are bit-identical to it.
-// MINW: waves per SIMD the register allocation has to leave room for (the launcher asks for 3 in the CJ form of the
-// d = 2 polynomial libraries: left alone, the order-5 closure comes out at 169 VGPRs -- one over the 3-wave limit of 168 --
-// although its ring slot is two vectors shorter; asked, it fits in 148 without scratch).
-// PK (CJ form, D = 2): the packed-fp32 body.  The point's two library evaluations run as ONE on the pairs
-// t[k] = (Theta_k(x), Theta_k(g x)): v_pk_mul_f32 for the monomials, one v_pk_fma_f32 per (j, k) for (h_j(x), h_j(g x)) with
-// the pair (w[0][k], w[1][k]) as the coefficient operand and op_sel choosing j, and the gradient sums as pairs over the two
-// equation rows, acc2[k] = fma((jtu_0, jtu_1), t[k].xx, fma(-(u_0, u_1), t[k].yy, acc2[k])) -- the halves of a full pair
-// picked by op_sel, so no register is half used.  Every product and every sum is the one the scalar body forms, in its
-// order: the results are bit-identical to it (and so to the materialised form).  Per point 19 + 42 + 42 packed
-// instructions instead of 36 + 84 + 84 scalar ones; where that pays is in the launcher's table (launch_symreg_reversed).
-template <class Lib, bool MSE, int RING = 2, int XI_SGPR_FROM = 32, bool CJ = false, int MINW = 1, bool PK = false>
-__global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const float* __restrict__ x, const float* __restrict__ dx,
-                                                                const float* __restrict__ gx,
-                                                                const float* __restrict__ jgx, int n_g, long N, bool vec,
-                                                                const float* __restrict__ xi,
-                                                                const float* __restrict__ mask, float w_sym,
-                                                                double* __restrict__ ws, Finish fin) {
-    vec = vec && chunked_stream<Lib>;            // (D = 3 sine / exp libraries: point by point, see chunked_stream)
-    constexpr int D = Lib::D, P = Lib::P, NL = MSE ? 2 : 1, NACC = NL + D * P, PPT = Chunk<D>::PPT, NV = Chunk<D>::NV,
-                  NVJ = JChunk<D>::NV, SYM0 = NL - 1;
-    static_assert(!PK || (CJ && D == 2), "the packed body pairs the two library evaluations of the constant-J form at d = 2");
-    const long s = blockIdx.y;
-    const float* xs = x + s * N * D;
-    const float* ys = MSE ? dx + s * N * D : nullptr;
-    const float* gs = gx + s * (long)n_g * N * D;
-    const float* js = jgx + s * (long)n_g * (CJ ? 1 : N) * D * D;
-    float w[D * P];
-    // two libraries per point live here: Xi in SGPRs from d*p = 32 (3 waves/SIMD at order 5) -- and up to 80, the d = 3
-    // order-3 libraries with sine / exp columns (69-78 coefficients would otherwise sit in VGPRs beside 70-79 sums)
-    load_xi<Lib, XI_SGPR_FROM, 80>(xi, mask, s, w);
-    float acc[NACC];
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) acc[k] = 0.0f;
-    const float ws_ = MSE ? w_sym : 1.0f;
-    // (an initialised workspace only: one that never saw symode_workspace_init is left as it was found)
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && fin.header[0] == WS_MAGIC)
-        fin.header[WS_BODY_WORD] = PK ? WS_BODY_PACKED : WS_BODY_SCALAR;
-    // CJ: the matrix of group element g, wave-uniform (scalar loads; readfirstlane pins the values to SGPRs)
-    auto load_cj = [&](int g, float (&J)[D * D]) {
-#pragma unroll
-        for (int e = 0; e < D * D; ++e)
-            J[e] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, js[(long)g * D * D + e])));
-    };
-    float J0[D * D];                                 // (CJ) group element 0, loaded once per workgroup
-#pragma unroll
-    for (int e = 0; e < D * D; ++e) J0[e] = 0.0f;
-    if constexpr (CJ) {
-        if (n_g > 0) load_cj(0, J0);
-    }
-
-    // one point against one group element: th, h belong to x (shared by all group elements of the point);
-    // `extra` (MSE form, first group element only) is the residual r, whose gradient rides on the same Theta(x) products
-    auto one = [&](const float (&th)[P], const float (&h)[D], const float (&gp)[D], const float (&J)[D * D], const float (&extra)[D]) {
-        float thg[P], hg[D], u[D], jtu[D];
-        Lib::eval(gp, thg);
-        apply_xi<Lib>(w, thg, hg);
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            float t = -hg[a];
-#pragma unroll
-            for (int b = 0; b < D; ++b) t = fmaf(J[a * D + b], h[b], t);
-            u[a] = t;
-            acc[SYM0] = fmaf(t, t, acc[SYM0]);
-        }
-#pragma unroll
-        for (int b = 0; b < D; ++b) {
-            float t = 0.0f;
-#pragma unroll
-            for (int a = 0; a < D; ++a) t = fmaf(J[a * D + b], u[a], t);
-            jtu[b] = MSE ? fmaf(ws_, t, extra[b]) : t;
-        }
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            const float uj = MSE ? ws_ * u[j] : u[j];
-#pragma unroll
-            for (int k = 0; k < P; ++k) acc[NL + j * P + k] = fmaf(jtu[j], th[k], fmaf(-uj, thg[k], acc[NL + j * P + k]));
-        }
-    };
-    // residual of one point (MSE form): r = h - dx, sums[0] += r^2; returned for the first group element's `extra`
-    auto resid = [&](const float (&h)[D], const float (&yp)[D], float (&r)[D]) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            r[j] = h[j] - yp[j];
-            acc[0] = fmaf(r[j], r[j], acc[0]);
-        }
-    };
-    // PK: one point against one group element, everything of the point formed here (a further group element forms
-    // Theta(x), h(x) again in the low halves: the same bits); `first`: the group element that carries the residual.
-    // The gradient sums live in acc2 (pair k = rows 0 and 1 of column k) and are unpacked into acc before emit_partials.
-    // The coefficient pair w2[k] = (w[0][k], w[1][k]) is ONE operand (an SGPR pair where load_xi keeps Xi in SGPRs) and the
-    // row is chosen by op_sel (pk_fma_bcast); h0 is the chain's first link, fma(w[j][0], Theta_0 = 1, 0), formed once.
-    constexpr int P2 = PK ? P : 1;
-    constexpr bool W_SGPR = D * P >= XI_SGPR_FROM && D * P <= 80;
-    float2v acc2[P2], w2[P2], h0[D];
-#pragma unroll
-    for (int k = 0; k < P2; ++k) {
-        acc2[k] = float2v{0.0f, 0.0f};
-        w2[k] = PK ? float2v{w[k], w[(D - 1) * P + k]} : acc2[k];
-    }
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        const float s0 = fmaf(w[j * P], 1.0f, 0.0f);
-        h0[j] = float2v{s0, s0};
-    }
-    auto one_pk = [&](const float (&xp)[D], const float (&gp)[D], const float (&J)[D * D], const float (&yp)[D], bool first) {
-        float2v xx[D], t[P], hh[D];
-#pragma unroll
-        for (int a = 0; a < D; ++a) xx[a] = float2v{xp[a], gp[a]};
-        Lib::eval_pair(xx, t);
-        hh[0] = h0[0];
-        hh[D - 1] = h0[D - 1];
-#pragma unroll
-        for (int k = 1; k < P; ++k) {
-            hh[0] = pk_fma_bcast<0, W_SGPR>(w2[k], t[k], hh[0]);
-            hh[D - 1] = pk_fma_bcast<1, W_SGPR>(w2[k], t[k], hh[D - 1]);
-        }
-        float h[D], r[D], u[D], jtu[D];
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            h[j] = hh[j].x;
-            r[j] = 0.0f;
-        }
-        if constexpr (MSE) {
-            if (first) resid(h, yp, r);
-        }
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            float s_ = -hh[a].y;
-#pragma unroll
-            for (int b = 0; b < D; ++b) s_ = fmaf(J[a * D + b], h[b], s_);
-            u[a] = s_;
-            acc[SYM0] = fmaf(s_, s_, acc[SYM0]);
-        }
-#pragma unroll
-        for (int b = 0; b < D; ++b) {
-            float s_ = 0.0f;
-#pragma unroll
-            for (int a = 0; a < D; ++a) s_ = fmaf(J[a * D + b], u[a], s_);
-            jtu[b] = MSE ? fmaf(ws_, s_, r[b]) : s_;
-        }
-        const float2v ja = float2v{jtu[0], jtu[D - 1]};
-        const float2v ub = MSE ? float2v{-(ws_ * u[0]), -(ws_ * u[D - 1])} : float2v{-u[0], -u[D - 1]};
-#pragma unroll
-        for (int k = 0; k < P2; ++k)
-            acc2[k] = __builtin_elementwise_fma(ja, __builtin_shufflevector(t[k], t[k], 0, 0),
-                                                __builtin_elementwise_fma(ub, __builtin_shufflevector(t[k], t[k], 1, 1), acc2[k]));
-    };
-    auto load_j = [&](const float* base, long c, float4 (&v)[NVJ]) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        const f4v* q = reinterpret_cast<const f4v*>(base) + c * NVJ;
-#pragma unroll
-        for (int i = 0; i < NVJ; ++i) {
-            const f4v t = __builtin_nontemporal_load(q + i);
-            v[i] = make_float4(t.x, t.y, t.z, t.w);
-        }
-    };
-    // the chunk's points against group element g, operands already in registers
-    auto chunk_g = [&](float (&th)[PPT][P], float (&h)[PPT][D], const float4 (&vg)[NV], const float4 (&vj)[NVJ],
-                       const float (&Jc)[D * D], float (&extra)[PPT][D]) {
-        float gp[PPT][D], jf[NVJ * 4], J[PPT][D * D];
-        unpack_chunk<D>(vg, gp);
-        if constexpr (CJ) {
-            each_point<PPT>([&](auto i) { one(th[i], h[i], gp[i], Jc, extra[i]); });
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < NVJ; ++i) {
-            jf[4 * i + 0] = vj[i].x;
-            jf[4 * i + 1] = vj[i].y;
-            jf[4 * i + 2] = vj[i].z;
-            jf[4 * i + 3] = vj[i].w;
-        }
-#pragma unroll
-        for (int e = 0; e < PPT * D * D; ++e) J[e / (D * D)][e % (D * D)] = jf[e];
-        each_point<PPT>([&](auto i) { one(th[i], h[i], gp[i], J[i], extra[i]); });
-    };
-    auto point = [&](long n) {
-        float xp[D], th[P], h[D], r[D], zero[D];
-        load_point<D>(xs, n, xp);
-        if constexpr (PK) {
-            float yp[D];
-            if constexpr (MSE)
-                load_point<D>(ys, n, yp);
-            else
-                yp[0] = yp[D - 1] = 0.0f;
-            for (int g = 0; g < n_g; ++g) {
-                float gp[D], J[D * D];
-                load_point<D>(gs + (long)g * N * D, n, gp);
-                load_cj(g, J);
-                one_pk(xp, gp, J, yp, g == 0);
-            }
-            return;
-        }
-        Lib::eval(xp, th);
-        apply_xi<Lib>(w, th, h);
-#pragma unroll
-        for (int j = 0; j < D; ++j) r[j] = zero[j] = 0.0f;
-        if constexpr (MSE) {
-            float yp[D];
-            load_point<D>(ys, n, yp);
-            resid(h, yp, r);
-        }
-        for (int g = 0; g < n_g; ++g) {
-            float gp[D], J[D * D];
-            load_point<D>(gs + (long)g * N * D, n, gp);
-            if constexpr (CJ) {
-                load_cj(g, J);
-            } else {
-                const float* Jp = js + ((long)g * N + n) * D * D;
-#pragma unroll
-                for (int e = 0; e < D * D; ++e) J[e] = Jp[e];
-            }
-            if (g == 0)
-                one(th, h, gp, J, r);
-            else
-                one(th, h, gp, J, zero);
-        }
-    };
-    auto eval_x = [&](const float4 (&vx)[NV], float (&th)[PPT][P], float (&h)[PPT][D]) {
-        float xp[PPT][D];
-        unpack_chunk<D>(vx, xp);
-        each_point<PPT>([&](auto i) {
-            Lib::eval(xp[i], th[i]);
-            apply_xi<Lib>(w, th[i], h[i]);
-        });
-    };
-
-    const long tid = (long)blockIdx.x * BLOCK + threadIdx.x, nthreads = (long)gridDim.x * BLOCK;
-    // one chunk: its points' Theta(x), h(x) are formed once and live only while this chunk's group elements are visited
-    auto chunk_all = [&](long c, const float4 (&vx)[NV], const float4 (&vy)[NV], const float4 (&vg)[NV], const float4 (&vj)[NVJ]) {
-        if constexpr (D == 3) {
-            // four points per chunk: Theta(x), h(x) of ALL of them (4 P + 12 registers) do not fit beside the sums -- point by
-            // point instead, Theta(x) re-evaluated for every further group element (same values, same order of every sum)
-            float xp[PPT][D], yp[PPT][D];
-            unpack_chunk<D>(vx, xp);
-            if constexpr (MSE) unpack_chunk<D>(vy, yp);
-            auto group = [&](const float4 (&ug)[NV], const float4 (&uj)[NVJ], const float (&Jc)[D * D], bool first) {
-                float gp[PPT][D], jf[NVJ * 4], J[PPT][D * D];
-                unpack_chunk<D>(ug, gp);
-                if constexpr (!CJ) {
-#pragma unroll
-                    for (int i = 0; i < NVJ; ++i) {
-                        jf[4 * i + 0] = uj[i].x;
-                        jf[4 * i + 1] = uj[i].y;
-                        jf[4 * i + 2] = uj[i].z;
-                        jf[4 * i + 3] = uj[i].w;
-                    }
-#pragma unroll
-                    for (int e = 0; e < PPT * D * D; ++e) J[e / (D * D)][e % (D * D)] = jf[e];
-                }
-                auto body = [&](auto i) {
-                    float th[P], h[D], r[D];
-                    Lib::eval(xp[i], th);
-                    apply_xi<Lib>(w, th, h);
-#pragma unroll
-                    for (int j = 0; j < D; ++j) r[j] = 0.0f;
-                    if constexpr (MSE) {
-                        if (first) resid(h, yp[i], r);
-                    }
-                    if constexpr (CJ)
-                        one(th, h, gp[i], Jc, r);
-                    else
-                        one(th, h, gp[i], J[i], r);
-                };
-                each_point<PPT>(body);
-            };
-            group(vg, vj, J0, true);
-            for (int g = 1; g < n_g; ++g) {
-                float4 ng[NV], nj[NVJ];
-                float Jg[D * D];
-                load_chunk_raw<D, true>(gs + (long)g * N * D, c, ng);
-                if constexpr (CJ) {
-                    load_cj(g, Jg);
-                    group(ng, nj, Jg, false);
-                } else {
-                    load_j(js + (long)g * N * D * D, c, nj);
-                    group(ng, nj, J0, false);
-                }
-            }
-            return;
-        }
-        if constexpr (PK) {
-            float xp[PPT][D], yp[PPT][D], gp[PPT][D];
-            unpack_chunk<D>(vx, xp);
-            if constexpr (MSE)
-                unpack_chunk<D>(vy, yp);
-            else
-                unpack_chunk<D>(vx, yp);               // (not read: one_pk takes the residual's target in the MSE form only)
-            unpack_chunk<D>(vg, gp);
-            each_point<PPT>([&](auto i) { one_pk(xp[i], gp[i], J0, yp[i], true); });
-            for (int g = 1; g < n_g; ++g) {
-                float4 ng[NV];
-                float Jg[D * D];
-                load_chunk_raw<D, true>(gs + (long)g * N * D, c, ng);
-                load_cj(g, Jg);
-                unpack_chunk<D>(ng, gp);
-                each_point<PPT>([&](auto i) { one_pk(xp[i], gp[i], Jg, yp[i], false); });
-            }
-            return;
-        }
-        float th[PPT][P], h[PPT][D], r[PPT][D], zero[PPT][D];
-        eval_x(vx, th, h);
-#pragma unroll
-        for (int i = 0; i < PPT; ++i)
-#pragma unroll
-            for (int j = 0; j < D; ++j) r[i][j] = zero[i][j] = 0.0f;
-        if constexpr (MSE) {
-            float yp[PPT][D];
-            unpack_chunk<D>(vy, yp);
-            each_point<PPT>([&](auto i) { resid(h[i], yp[i], r[i]); });
-        }
-        chunk_g(th, h, vg, vj, J0, r);
-        for (int g = 1; g < n_g; ++g) {
-            float4 ng[NV], nj[NVJ];
-            float Jg[D * D];
-            load_chunk_raw<D, true>(gs + (long)g * N * D, c, ng);
-            if constexpr (CJ) {
-                load_cj(g, Jg);
-                chunk_g(th, h, ng, nj, Jg, zero);
-            } else {
-                load_j(js + (long)g * N * D * D, c, nj);
-                chunk_g(th, h, ng, nj, J0, zero);
-            }
-        }
-    };
-    if constexpr (D == 3) {
-        // 12-byte points and 36-byte Jacobians: whole waves fetch their tiles coalesced and redistribute through a
-        // wave-private LDS slab (points.hpp, exchange_tile); ragged waves and the tail keep the per-lane loads
-        if (vec && n_g > 0) {
-            __shared__ float4 slab3[BLOCK / WAVE][(CJ ? NV : NVJ) * WAVE];
-            const int lane = threadIdx.x & (WAVE - 1);
-            float4* slab = slab3[threadIdx.x / WAVE];
-            const long nchunks = N / PPT;
-            for (long c = tid;; c += nthreads) {
-                const bool in = c < nchunks;
-                const unsigned long long live = __builtin_amdgcn_ballot_w64(in);
-                if (live == 0ull) break;
-                float4 ax[NV], ay[NV], ag[NV], aj[NVJ];
-                if (live == ~0ull) {
-                    const long c0 = c - lane;
-                    float4 tx[NV], ty[NV], tg[NV], tj[NVJ];
-                    load_tile_raw<NV, true>(xs, c0, lane, tx);
-                    if constexpr (MSE) load_tile_raw<NV, true>(ys, c0, lane, ty);
-                    load_tile_raw<NV, true>(gs, c0, lane, tg);
-                    if constexpr (!CJ) load_tile_raw<NVJ, true>(js, c0, lane, tj);
-                    exchange_tile<NV>(tx, ax, slab, lane);
-                    if constexpr (MSE) exchange_tile<NV>(ty, ay, slab, lane);
-                    exchange_tile<NV>(tg, ag, slab, lane);
-                    if constexpr (!CJ) exchange_tile<NVJ>(tj, aj, slab, lane);
-                } else if (in) {
-                    load_chunk_raw<D, true>(xs, c, ax);
-                    if constexpr (MSE) load_chunk_raw<D, true>(ys, c, ay);
-                    load_chunk_raw<D, true>(gs, c, ag);
-                    if constexpr (!CJ) load_j(js, c, aj);
-                }
-                if (in) chunk_all(c, ax, ay, ag, aj);
-            }
-            const long n = nchunks * PPT + tid;
-            if (n < N) point(n);
-        } else {
-            for (long n = tid; n < N; n += nthreads) point(n);
-        }
-    } else if (vec && n_g > 0) {
-        // register ring: RING chunks of x, (dx,) g(x), J_g of the first group element in flight per lane, a slot refilled
-        // as soon as its chunk has been consumed (closure_ab: one 2^26-point problem 334 -> 325 us at order 3, the fused
-        // closure at order 5 470 -> 442 us; the batched bench shape is VALU / HBM co-limited either way)
-        constexpr int NVT = (MSE ? 3 : 2) * NV + (CJ ? 0 : NVJ), OY = NV, OG = (MSE ? 2 : 1) * NV, OJ = OG + NV;
-        const long nchunks = N / PPT;
-        chunk_ring<RING, NVT>(
-            nchunks, tid, nthreads,
-            [&](long q, float4 (&slot)[NVT]) {
-                float4 tx[NV], tg[NV], tj[NVJ];
-                load_chunk_raw<D, true>(xs, q, tx);
-                load_chunk_raw<D, true>(gs, q, tg);
-                if constexpr (!CJ) load_j(js, q, tj);
-#pragma unroll
-                for (int i = 0; i < NV; ++i) {
-                    slot[i] = tx[i];
-                    slot[OG + i] = tg[i];
-                }
-                if constexpr (!CJ) {
-#pragma unroll
-                    for (int i = 0; i < NVJ; ++i) slot[OJ + i] = tj[i];
-                }
-                if constexpr (MSE) {
-                    float4 ty[NV];
-                    load_chunk_raw<D, true>(ys, q, ty);
-#pragma unroll
-                    for (int i = 0; i < NV; ++i) slot[OY + i] = ty[i];
-                }
-            },
-            [&](long c, const float4 (&slot)[NVT]) {
-                float4 ax[NV], ay[NV], ag[NV], aj[NVJ];
-#pragma unroll
-                for (int i = 0; i < NV; ++i) {
-                    ax[i] = slot[i];
-                    ay[i] = MSE ? slot[OY + i] : slot[i];
-                    ag[i] = slot[OG + i];
-                }
-                if constexpr (!CJ) {
-#pragma unroll
-                    for (int i = 0; i < NVJ; ++i) aj[i] = slot[OJ + i];
-                }
-                chunk_all(c, ax, ay, ag, aj);
-            });
-        const long n = nchunks * PPT + tid;
-        if (n < N) point(n);
-    } else {
-        for (long n = tid; n < N; n += nthreads) point(n);
-    }
-    if constexpr (PK) {
-#pragma unroll
-        for (int k = 0; k < P; ++k) {
-            acc[NL + k] = acc2[k].x;
-            acc[NL + (D - 1) * P + k] = acc2[k].y;
-        }
-    }
     emit_partials<NACC>(acc, ws, fin);
 }
 
@@ -1837,68 +1375,6 @@ hipError_t launch_symreg_linear(const float* z, long n, const float* xi, const f
                                                                   part, fin);
     SYMODE_LAUNCH_CHECK();
     return launch_finalize(fin, part, 1, gx, NACC, st);
-}
-
-// Libraries whose constant-J closure takes the packed body (symreg_reversed_kernel, PK): where it measured faster on the
-// MI355X at the bench shape (8192 x 125 000) in every pass, by more than the arms' own spread, and no slower at 64 x 50 000
-// (tools/micro/closure_ab pk, three interleaved passes, packed / scalar time; profiles/closure_packed.txt has all twenty
-// d = 2 libraries):
-//   order 5           plain 0.980-0.981 / 0.98-1.00   sine 1.012-1.018 / 0.97-0.98   exp 0.897-0.900 / 0.88-0.89   both 0.937-0.944 / 0.90-0.91
-//   order 4           plain 1.03-1.04 / 1.06-1.09     sine 1.05 / 1.05-1.06          exp 0.932-0.944 / 0.92-0.94   both 0.987-0.994 / 0.92-0.93
-//   orders 1-3        0.95-1.14 at the bench shape (plain: 0.99-1.02, they stream at the HBM rate either way), 0.98-1.17 at the small
-//                     one; the two that gain at the bench shape, exp alone at orders 2-3 (0.95-0.96), lose up to 8 % at the small one
-// Sine columns alone lose or stay inside the spread at the bench shape at every order (the two sinf of a pair do not
-// pack and the pair layout only costs); sine + exp at order 4 is inside the arms' 0.85 % spread there: all scalar.
-// The order-5 plain library is the flagship's: its kernel falls from 5.40-5.44 to 5.29-5.33 ms, 2 %, although the
-// vector instructions per point fall from 225 to 128 (counters): a packed instruction costs 4.6-4.8 cycles against 2.85-3.1,
-// both bodies fill the vector pipe, and of the 8 % fewer cycles the kernel then takes 2 % arrive as time.  Below order 4
-// the coefficients sit in VGPRs and the kernels are not issue-bound.
-template <class Lib>
-constexpr bool closure_pk_pays = Lib::D == 2 && ((Lib::ORDER == 5 && (Lib::EXP || !Lib::SINE)) || (Lib::ORDER == 4 && Lib::EXP && !Lib::SINE));
-
-// constj: jgx is the compact (S, n_g, D, D) table of a point-constant Jacobian (the CJ kernels, see symreg_reversed_kernel)
-// SYMODE_CLOSURE_PK=0 keeps the scalar body everywhere.  The body a launch took is left in word 1 of the workspace header
-// (WS_BODY_SCALAR / WS_BODY_PACKED): the bodies are bit-identical, so nothing else tells them apart.
-template <class Lib>
-hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* gxp, const float* jgx, bool constj, int n_g, long S,
-                                  long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
-                                  float* grad, double* ws, int gx, hipStream_t st) {
-    constexpr int D = Lib::D;
-    const bool mse = dx != nullptr;
-    const int nacc = (mse ? 2 : 1) + D * Lib::P;
-    double* part = ws + WS_HEADER_DOUBLES;
-    Finish fin = make_finish(ws, mask, inv_count, 2.0f * inv_count, loss, grad);
-    fin.n_loss = mse ? 2 : 1;
-    // 16-byte vectors need every slab (problem, group element) to start on a 16-byte boundary
-    // (the compact table of the CJ form is read by scalar loads: it takes no part in this)
-    const bool multi = S > 1 || n_g > 1;
-    const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)gxp % 16 == 0) && (constj || (uintptr_t)jgx % 16 == 0) &&
-                     (!mse || (uintptr_t)dx % 16 == 0) && (!multi || ((n * D) % 4 == 0 && (constj || (n * D * D) % 4 == 0)));
-    const dim3 grid(gx, (unsigned)S), block(BLOCK);
-    const auto launch = [&](auto cj, auto pk) {         // the kernel family: CJ and the body as compile-time constants
-        constexpr bool CJ = decltype(cj)::value, PK = decltype(pk)::value;
-        constexpr int MINW = (CJ && D == 2 && !Lib::SINE && !Lib::EXP) ? 3 : 1;
-        if (mse)
-            symreg_reversed_kernel<Lib, true, 2, 32, CJ, MINW, PK><<<grid, block, 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi, mask,
-                                                                                         w_sym, part, fin);
-        else
-            symreg_reversed_kernel<Lib, false, 2, 32, CJ, MINW, PK><<<grid, block, 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec, xi,
-                                                                                          mask, 1.0f, part, fin);
-    };
-    if constexpr (closure_pk_pays<Lib>) {
-        if (constj && knobs().closure_pk)
-            launch(std::true_type{}, std::true_type{});
-        else if (constj)
-            launch(std::true_type{}, std::false_type{});
-        else
-            launch(std::false_type{}, std::false_type{});
-    } else if (constj) {
-        launch(std::true_type{}, std::false_type{});
-    } else {
-        launch(std::false_type{}, std::false_type{});
-    }
-    SYMODE_LAUNCH_CHECK();
-    return launch_finalize(fin, part, S, gx, nacc, st);
 }
 
 template <class Lib>

@@ -6,9 +6,10 @@
 //   r_z = h - dz,   r_x = B h - y:
 //   sums[0] = sum r_z^2,  sums[1] = sum r_x^2,  grad = d( sums[0] + w_pair sums[1] ) / dXi  (both under the same 1/(N D)),
 //   dsums/dXi[j,k] = 2 sum_n ( r_z + w_pair B^T r_x )_j th_k(z_n).
-// The same shape of work as the J_g(x) h(x) half of symreg_reversed_kernel (kernels.hpp) with one library evaluation per
+// The same shape of work as the J_g(x) h(x) half of symreg_reversed_kernel (closure_rev.hpp) with one library evaluation per
 // point instead of two, and the same traffic at D = 2: z 8, dz 8, B 16, y 8 bytes per point, each read once.
 #pragma once
+#include "closure_rev.hpp"
 #include "kernels.hpp"
 
 namespace symode {

@@ -1,6 +1,7 @@
 // One translation unit per state dimension D instantiates every kernel for its libraries.
 #pragma once
 #include "adam.hpp"
+#include "closure_rev.hpp"
 #include "gram.hpp"
 #include "gram_rev.hpp"
 #include "gram_valu.hpp"

@@ -1,13 +1,13 @@
 // A/B harness for the closure kernels (tuning runs, not product code): loss_grad and the fused residual + reversed
-// regulariser closure straight from csrc/kernels.hpp, one big problem (S = 1, 2^26 points) and the bench's batched shape
-// (8192 x 125 000 points), over launch widths and ring depths -- one process, so variants see the same box.  (The run
+// regulariser closure straight from csrc/kernels.hpp and csrc/closure_rev.hpp, one big problem (S = 1, 2^26 points) and the
+// bench's batched shape (8192 x 125 000 points), over launch widths and ring depths -- one process, so variants see the same box.  (The run
 // kept as profiles/r03_closure_ab.txt also held the two-chunk form the ring replaced: ring=0 there; the problem-walking
 // form of the closure measured in profiles/r03_closure_walk.txt lives in commit becc803 only.)
 // `closure_ab constj`: only the ring-depth A/B of the constant-Jacobian form of the fused closure (24 B/point) at the
 // bench's batched shape, beside the materialised form (40 B/point), three interleaved passes.
 // `closure_ab pk`: scalar body against the packed-fp32 body (PK) of the constant-Jacobian fused closure for the d = 2
 // libraries, at the bench's batched shape and at 64 x 50 000, on the launcher's grids, three interleaved passes.  The
-// launcher's table (kernels.hpp, closure_pk_pays) is read off this run.
+// launcher's table (closure_rev.hpp, closure_pk_pays) is read off this run.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -I symmetry-ode-discovery_amd/csrc
 //              -o tools/micro/closure_ab tools/micro/closure_ab.hip
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@
 #include <cstring>
 #include <vector>
 
+#include "closure_rev.hpp"
 #include "kernels.hpp"
 using namespace symode;
 using L3 = Library<2, 3, 0>;

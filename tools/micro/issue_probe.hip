@@ -1,12 +1,12 @@
 // Which pipe should carry the closure's per-point arithmetic on gfx950?  A synthetic point loop with the shape of the
 // fused closure at order 5 (d = 2, p = 21): two "apply" products h = W th, hg = W thg (W wave-uniform) and the gradient
 // accumulation acc[j][k] += a_j th_k - u_j thg_k, in four forms:
-//   S   scalar fp32 VALU: 84 v_fmac with an SGPR coefficient + 84 with VGPR operands          (what kernels.hpp issues)
+//   S   scalar fp32 VALU: 84 v_fmac with an SGPR coefficient + 84 with VGPR operands          (what closure_rev.hpp issues)
 //   P   packed over the two equation rows: 42 + 42 v_pk_fma_f32 (same roundings, same order)
 //   M   the applies as 42 v_mfma_f32_4x4x1_16b_f32 (A = column k of W in lanes l%4 < 2, B = th_k: row i of block b of the
 //       result lands in lane 4b + j -- the lane's own point), gradient scalar
 //   MP  applies on the matrix pipe, gradient packed
-//   X   packed over the point's two library evaluations, the layout kernels.hpp ships for the constant-J closure: terms as
+//   X   packed over the point's two library evaluations, the layout closure_rev.hpp ships for the constant-J closure: terms as
 //       pairs t[k] = (th_k, thg_k), (h_j, hg_j) = sum_k W[j][k] t[k] with the SGPR pair (W[0][k], W[1][k]) as the operand and
 //       op_sel choosing j, gradient sums as pairs over j with both halves of t[k] picked by op_sel: 42 + 42 v_pk_fma_f32,
 //       no half-used register pair
@@ -34,7 +34,7 @@ constexpr int P = 21;
 __device__ __forceinline__ f2 splat(float a) { return f2{a, a}; }
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-// d = fma(w.SEL in both halves, t, c): the coefficient pair stays one SGPR pair (csrc/kernels.hpp, pk_fma_bcast)
+// d = fma(w.SEL in both halves, t, c): the coefficient pair stays one SGPR pair (csrc/closure_rev.hpp, pk_fma_bcast)
 template <int SEL>
 __device__ __forceinline__ f2 fma2_bcast(f2 w, f2 t, f2 c) {
     f2 d;
