@@ -509,6 +509,44 @@ int symode_adam_epochs_reversed(const float* x, const float* dx, const float* gx
                                 float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
                                 int* step, float* mask, float* xi_out, float* log, void* stream);
 
+/* symode_adam_epochs on the --use_latent branch of train_SIGED under a frozen autoencoder (the optimiser steps the SINDy
+ * coefficients alone, so the autoencoder is data): per-row operands computed once per fit (model_utils.latent_operands),
+ * shared by all problems and gathered by the row numbers of idx,
+ *   z, dz   (n_src, d)      z = enc(x), dz = J_enc(x) dx
+ *   B       (n_src, d, d)   the decoder's Jacobian at z reduced by a thin QR, J_dec(z_b) = Q_b B_b
+ *   y       (n_src, d)      Q_b^T dx_b
+ *   e       (n_src)         |dx_b - Q_b y_b|^2; read only when D_obs > d (D_obs == d: every e_b is 0, e may be NULL)
+ *   L       (n_gen, d, d)   the generators L_g (v[:d, :d] of generator.get_full_basis_list()), read uniformly
+ * With W = Xi * mask, rows = the valid entries of the batch and, per valid row b, theta = Theta(z_b), h = W theta:
+ *   r_z = h - dz_b,   r_x = B_b h - y_b,   and for every generator   dtheta = J_Theta(z_b)(L_g z_b),   u = W dtheta - L_g h
+ *   mse_z = sum_b |r_z|^2 / (rows d)
+ *   mse_x = (sum_b |r_x|^2 + sum_b e_b) / (rows D_obs)
+ *   sym   = sum_g sum_b |u|^2                       NOT divided by rows (torch.norm(..)**2)
+ *   loss  = w_z mse_z + w_x mse_x + w_sym sym + w_reg |params|_1
+ *   dloss/dXi = mask * [ (2 w_z / (rows d)) sum_b r_z theta^T + 2 w_sym sum_g sum_b ( u dtheta^T - (L_g^T u) theta^T ) ]
+ *               (+ the L1 sign term on params)
+ * mse_x contributes NO gradient: compute_dx is a functional jvp without create_graph, so train.py adds and logs the term but
+ * it is cut from the graph (the same fact as SYMODE_CLOSURE_LATENT).  The Adam step, the coefficient map, padding entries
+ * (none of the five arrays is read, the entry does not count), a batch of padding alone, thresholding, the near count, the
+ * freezing rule -- applied to w_z mse_z + w_x mse_x + w_sym sym -- and the fixed order of every sum are those of
+ * symode_adam_epochs.  With n_gen == 0, B = I, y = dz and D_obs == d the entry leaves in params, m, v and mask what
+ * symode_adam_epochs leaves on (z, dz) with its w_x = w_z, bit for bit.
+ *   log     (n_epochs, n_problems, SYMODE_ADAM_LOG_LATENT = 10): columns 0-6 as symode_adam_epochs with column 0 = mean mse_x,
+ *           7 = mean sym, 8 = mean mse_z (all unweighted; NaN for an epoch without a step), 9 = 0
+ * Refused with SYMODE_E_BADSIZE beyond the checks of symode_adam_epochs: n_gen < 0, w_z <= 0 or NaN (the regulariser's
+ * gradient is accumulated at weight w_sym / w_z, and without w_z no data term reaches the coefficients), D_obs < d,
+ * e == NULL with D_obs > d, L == NULL with n_gen > 0.
+ * replaces: train.py:491-508, 522-547 (the use_latent branch of the per-minibatch loop: encoder pass, compute_dz, compute_dx,
+ * the linear-latent regulariser and the epoch end) plus torch.optim.Adam.step. */
+#define SYMODE_ADAM_LOG_LATENT 10
+int symode_adam_epochs_latent(const float* z, const float* dz, const float* B, const float* y, const float* e, int D_obs,
+                              const float* L, int n_gen, long n_src, const int* idx, long n_idx_problems, int n_epochs,
+                              int n_steps, int batch, long n_problems, int d, int order, int flags, const float* q_eff, int r,
+                              int allow_constant, int n_params, float lr, float beta1, float beta2, float eps, float w_z,
+                              float w_x, float w_reg, float w_sym, int l1, float threshold, int st_freq, int epoch0,
+                              float near_band, float* params, float* m, float* v, int* step, float* mask, float* xi_out,
+                              float* log, void* stream);
+
 /* HOST function (no GPU work): least squares on the normal equations G = A^T A (n, n), C = A^T b (n, k), fp64
  * row-major host arrays; A had m_rows rows.  driver 0 = LAPACK gelsy semantics (pivoted QR rank rule with
  * rcond < 0 -> torch's default eps_fp32 * max(m_rows, n), minimum-norm solution), driver 1 = gels (full rank).

@@ -3,6 +3,8 @@
 // set_threshold every st_freq epochs -- as ONE launch for n_epochs whole epochs of n_problems independent problems.
 // symode_adam_epochs_reversed is the same launch with the reversed symmetry regulariser (model_utils.py:160-168 of the
 // reference, the JVP as the explicit matvec on precomputed g(x), J_g(x)) added to every minibatch loss.
+// symode_adam_epochs_latent is the use_latent branch of the same loop (train.py:491-508, 522-547) under a frozen autoencoder:
+// mse_z, mse_x and the linear-latent regulariser on per-row operands z, dz, B, y, e computed once per fit.
 #pragma once
 #include <cfloat>
 
@@ -12,6 +14,10 @@ namespace symode {
 
 constexpr int ADAM_BLOCK = 256;       // four wave64: thread j owns parameter j and coefficient j, row b of a batch goes to thread b % 256
 constexpr int ADAM_LOG = 8;           // floats per (epoch, problem) log row, see include/symode.h
+constexpr int ADAM_LOG_LATENT = 10;   // the latent entry's row (SYMODE_ADAM_LOG_LATENT)
+
+// the three forms of the epoch kernel: they share the cursor, the step and the epoch end
+enum AdamKind { ADAM_PLAIN = 0, ADAM_REVERSED = 1, ADAM_LATENT = 2 };
 
 struct AdamArgs {
     const float* x;
@@ -31,11 +37,18 @@ struct AdamArgs {
     float *params, *m, *v;
     int* step;
     float *mask, *xi_out, *log;
-    // the reversed variant alone (adam_epochs_kernel<Lib, true>); the plain kernel reads none of these
+    // the reversed variant alone (adam_epochs_kernel<Lib, ADAM_REVERSED>); the plain kernel reads none of these
     const float* gx;                  // (n_g, n_src, d)
     const float* jgx;                 // (n_g, n_src, d, d)
     int n_g;
     float w_ratio;                    // w_sym / w_x (0 with n_g == 0): the C entry refuses w_x <= 0 with n_g > 0
+    // the latent variant alone (adam_epochs_kernel<Lib, ADAM_LATENT>): x, dx are z, dz, w_x is w_z and w_ratio is w_sym / w_z
+    const float* lat_b;               // (n_src, d, d)
+    const float* lat_y;               // (n_src, d)
+    const float* lat_e;               // (n_src) or nullptr (D_obs == d: every e_b is 0)
+    const float* gen_l;               // (n_gen, d, d)
+    int n_gen, d_obs;
+    float w_obs, w_sym;               // the weights of mse_x and sym in the value the freezing rule tests
 };
 
 // b^n for an integer n >= 0 by squaring: a function of (b, n) alone, so a fit cut into several launches meets the same
@@ -71,10 +84,22 @@ __device__ __forceinline__ double adam_ipow(double b, int n) {
 // optimiser multiplies the sum by w_x as before.  The MSE sums are untouched, so with n_g == 0 every value of the plain
 // kernel is reproduced bit for bit.  sum |r|^2 (unscaled) is one more reduced value; a batch is non-finite when
 // MSE + regulariser is.
-template <class Lib, bool REV = false>
+//
+// LAT is the --use_latent branch (symode_adam_epochs_latent): x, dx are z, dz, and a valid row also gathers B_b (d x d), y_b
+// and e_b by its row number, one chunk ahead like z and dz.  The residual above is r_z; r_x = B_b h - y_b adds |r_x|^2 + e_b to
+// a sum of its own (logged, no gradient).  The generators L_g are read uniformly inside the row, as symreg_linear_kernel
+// reads them: u = W J_Theta(z)(L_g z) - L_g h, sum |u|^2 NOT divided by the rows, and  u dth^T - (L_g^T u) th^T  goes into a
+// SECOND set of d p accumulators, because its divisor (none) differs from r_z's (rows d) and rows is known only after the
+// reduction: there the two meet as  tot_z + (w_sym / w_z) rows d tot_s,  and the optimiser multiplies by 2 w_z / (rows d)
+// as before.  With n_gen == 0 the second set is neither reduced nor added, so params, m, v and mask are those of the plain
+// kernel on (z, dz) with w_x = w_z bit for bit.  A batch is non-finite when w_z mse_z + w_x mse_x + w_sym sym is.
+template <class Lib, int KIND = ADAM_PLAIN>
 __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs a) {
-    constexpr int D = Lib::D, P = Lib::P, DP = D * P, NV = DP + 2 + (REV ? 1 : 0), NW = ADAM_BLOCK / WAVE,
-                  SLOTS = (NV + WAVE - 1) / WAVE;
+    constexpr bool REV = KIND == ADAM_REVERSED, LAT = KIND == ADAM_LATENT;
+    // reduced values: [0, DP) the gradient sums, DP sum r^2, DP + 1 the valid rows, DP + 2 sum |r|^2 (REV) / sum |u|^2 (LAT),
+    // LAT: DP + 3 sum (|r_x|^2 + e), then the regulariser's DP gradient sums
+    constexpr int D = Lib::D, P = Lib::P, DP = D * P, NV1 = DP + 2 + (REV ? 1 : 0) + (LAT ? 2 : 0), NV = NV1 + (LAT ? DP : 0),
+                  NW = ADAM_BLOCK / WAVE, SLOTS = (NV + WAVE - 1) / WAVE, LOGW = LAT ? ADAM_LOG_LATENT : ADAM_LOG;
     static_assert(DP <= ADAM_BLOCK, "thread j owns coefficient j");
     __shared__ float w_s[DP];
     __shared__ float part[NW][NV];
@@ -160,12 +185,24 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
         for (int c = 0; c < D * D; ++c) jr[c] = ok ? a.jgx[at * (D * D) + c] : 0.0f;
     };
 
+    // B_b, y_b, e_b of row i: the validity predicate of fetch_row
+    auto fetch_lat = [&](int i, float (&br)[D * D], float (&yr)[D], float& er) __attribute__((always_inline)) {
+        const bool ok = i >= 0 && (long)i < a.n_src;
+#pragma unroll
+        for (int c = 0; c < D * D; ++c) br[c] = ok ? a.lat_b[(long)i * (D * D) + c] : 0.0f;
+#pragma unroll
+        for (int c = 0; c < D; ++c) yr[c] = ok ? a.lat_y[(long)i * D + c] : 0.0f;
+        er = (ok && a.lat_e) ? a.lat_e[i] : 0.0f;
+    };
+
     Cursor c{0, 0, 0}, c2{0, 0, 0};
     float cx[D], cdx[D];
     int cidx = fetch_idx(c2);
     bool cok = fetch_row(cidx, cx, cdx);
     float cg[D], cj[D * D];
     if constexpr (REV) fetch_sym(0, cidx, cg, cj);
+    float cb[D * D], cy[D], ce = 0.0f;
+    if constexpr (LAT) fetch_lat(cidx, cb, cy, ce);
     advance(c2);
     int nidx = fetch_idx(c2);
     advance(c2);
@@ -173,13 +210,19 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
     float acc[DP], ss = 0.0f, cnt = 0.0f, sr = 0.0f;
 #pragma unroll
     for (int j = 0; j < DP; ++j) acc[j] = 0.0f;
+    float accs[LAT ? DP : 1], sx = 0.0f;                      // LAT: the regulariser's gradient sums, sum (|r_x|^2 + e)
+#pragma unroll
+    for (int j = 0; j < (LAT ? DP : 1); ++j) accs[j] = 0.0f;
     double loss_sum = 0.0, l1_sum = 0.0, sym_sum = 0.0;       // the epoch's running sums (train.py:541-543), uniform over the block
+    double msez_sum = 0.0;                                    // LAT: loss_sum holds mse_x, this one mse_z
     int steps = 0;
     const float om1 = (float)(1.0 - (double)a.beta1), om2 = (float)(1.0 - (double)a.beta2);
 
     while (c.e < a.n_epochs) {
         float nx[D], ndx[D];
         const bool nok = fetch_row(nidx, nx, ndx);
+        float nb[D * D], ny[D], ne = 0.0f;
+        if constexpr (LAT) fetch_lat(nidx, nb, ny, ne);
         const int nnidx = fetch_idx(c2);
 
         const bool eval = cok && !frozen;
@@ -233,15 +276,70 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 for (int i = 0; i < D * D; ++i) cj[i] = nj[i];
             }
         }
+        if constexpr (LAT) {
+            if (eval) {
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    float f = -cy[i];                         // r_x = B h - y
+#pragma unroll
+                    for (int j = 0; j < D; ++j) f = fmaf(cb[i * D + j], hx[j], f);
+                    sx = fmaf(f, f, sx);
+                }
+                sx += ce;
+                for (int g = 0; g < a.n_gen; ++g) {
+                    float L[D][D], lz[D];
+#pragma unroll
+                    for (int i = 0; i < D; ++i)
+#pragma unroll
+                        for (int j = 0; j < D; ++j) L[i][j] = a.gen_l[(g * D + i) * D + j];
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        float f = 0.0f;
+#pragma unroll
+                        for (int j = 0; j < D; ++j) f = fmaf(L[i][j], cx[j], f);
+                        lz[i] = f;
+                    }
+                    float tz[P], dth[P], u[D];
+                    Lib::eval_jvp(cx, lz, tz, dth);           // tz = th again
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        float f = 0.0f;                       // u = W dth - L h
+#pragma unroll
+                        for (int k = 0; k < P; ++k) f = fmaf(dth[k], w_s[i * P + k], f);
+#pragma unroll
+                        for (int j = 0; j < D; ++j) f = fmaf(-L[i][j], hx[j], f);
+                        u[i] = f;
+                        sr = fmaf(f, f, sr);
+                    }
+#pragma unroll
+                    for (int i = 0; i < D; ++i) {
+                        float ltu = 0.0f;                     // (L^T u)_i
+#pragma unroll
+                        for (int j = 0; j < D; ++j) ltu = fmaf(L[j][i], u[j], ltu);
+#pragma unroll
+                        for (int k = 0; k < P; ++k) accs[i * P + k] = fmaf(u[i], dth[k], fmaf(-ltu, th[k], accs[i * P + k]));
+                    }
+                }
+            }
+        }
 
         if (c.k == n_chunks - 1) {                            // the batch is complete: one optimiser step
             float keep[SLOTS];
 #pragma unroll
             for (int q = 0; q < SLOTS; ++q) keep[q] = 0.0f;
 #pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                const float tot = wave_sum_dpp(j < DP ? acc[j < DP ? j : 0] : (j == DP ? ss : (j == DP + 1 ? cnt : sr)));
+            for (int j = 0; j < NV1; ++j) {
+                const float tot = wave_sum_dpp(j < DP ? acc[j < DP ? j : 0] : (j == DP ? ss : (j == DP + 1 ? cnt : (j == DP + 2 ? sr : sx))));
                 if (lane == (j & (WAVE - 1))) keep[j / WAVE] = tot;
+            }
+            if constexpr (LAT) {
+                if (a.n_gen > 0) {
+#pragma unroll
+                    for (int j = NV1; j < NV; ++j) {
+                        const float tot = wave_sum_dpp(accs[j - NV1]);
+                        if (lane == (j & (WAVE - 1))) keep[j / WAVE] = tot;
+                    }
+                }
             }
 #pragma unroll
             for (int q = 0; q < SLOTS; ++q)
@@ -265,7 +363,19 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 for (int w = 1; w < NW; ++w) sr_t += part[w][DP + 2];
                 reg = sr_t / (cnt_t * (float)D);
             }
-            const bool bad = live && !(fabsf(REV ? loss + reg : loss) <= FLT_MAX);
+            float loss_x = 0.0f;
+            if constexpr (LAT) {
+                float sr_t = part[0][DP + 2], sx_t = part[0][DP + 3];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) {
+                    sr_t += part[w][DP + 2];
+                    sx_t += part[w][DP + 3];
+                }
+                reg = sr_t;                                   // torch.norm(..)**2 over the batch: no divisor
+                loss_x = sx_t / (cnt_t * (float)a.d_obs);
+            }
+            const float tested = LAT ? fmaf(a.w_x, loss, fmaf(a.w_obs, loss_x, a.w_sym * reg)) : (REV ? loss + reg : loss);
+            const bool bad = live && !(fabsf(tested) <= FLT_MAX);
             if (bad) frozen = true;                           // NaN / inf: the problem keeps its state from here on
             const bool upd = live && !bad;
             const float scale = 2.0f / (cnt_t * (float)D);
@@ -274,6 +384,14 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 float tot = part[0][tid];
 #pragma unroll
                 for (int w = 1; w < NW; ++w) tot += part[w][tid];
+                if constexpr (LAT) {
+                    if (a.n_gen > 0) {
+                        float tot_s = part[0][NV1 + tid];
+#pragma unroll
+                        for (int w = 1; w < NW; ++w) tot_s += part[w][NV1 + tid];
+                        tot = fmaf(a.w_ratio * (cnt_t * (float)D), tot_s, tot);
+                    }
+                }
                 g_xi = scale * tot * mk;                      // d mse / d Xi: the model reads Xi * mask
             }
             float g_data = g_xi;
@@ -302,9 +420,10 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 float l1_t = l1_s[0];
 #pragma unroll
                 for (int w = 1; w < NW; ++w) l1_t += l1_s[w];
-                loss_sum += (double)loss;
+                loss_sum += (double)(LAT ? loss_x : loss);
                 l1_sum += (double)l1_t;
-                if constexpr (REV) sym_sum += (double)reg;
+                if constexpr (REV || LAT) sym_sum += (double)reg;
+                if constexpr (LAT) msez_sum += (double)loss;
                 ++steps;
                 coefficient();
             }
@@ -313,6 +432,11 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
             ss = 0.0f;
             cnt = 0.0f;
             sr = 0.0f;
+            if constexpr (LAT) {
+#pragma unroll
+                for (int j = 0; j < DP; ++j) accs[j] = 0.0f;
+                sx = 0.0f;
+            }
             __syncthreads();
 
             if (c.s == a.n_steps - 1) {                       // the epoch is complete (train.py:545-546, sindy.py:192-194)
@@ -331,7 +455,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 if (tid == 0) {
                     int near_t = 0;
                     for (int w = 0; w < NW; ++w) near_t += near_s[w];
-                    float* rec = a.log + ((long)c.e * a.n_problems + s) * ADAM_LOG;
+                    float* rec = a.log + ((long)c.e * a.n_problems + s) * LOGW;
                     rec[0] = (float)(loss_sum / (double)steps);               // 0 / 0 = NaN: an epoch without a step
                     rec[1] = (float)(l1_sum / (double)steps);
                     rec[2] = (float)steps;
@@ -339,8 +463,15 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                     rec[4] = frozen ? 1.0f : 0.0f;
                     rec[5] = ev ? 1.0f : 0.0f;
                     rec[6] = (float)epoch;
-                    rec[7] = (REV && a.n_g > 0) ? (float)(sym_sum / (double)steps) : 0.0f;   // no elements: 0 as the plain entry, stepless epochs too
+                    if constexpr (LAT) {
+                        rec[7] = (float)(sym_sum / (double)steps);            // 0 with n_gen == 0, NaN for an epoch without a step
+                        rec[8] = (float)(msez_sum / (double)steps);
+                        rec[9] = 0.0f;
+                    } else {
+                        rec[7] = (REV && a.n_g > 0) ? (float)(sym_sum / (double)steps) : 0.0f;   // no elements: 0 as the plain entry, stepless epochs too
+                    }
                 }
+                msez_sum = 0.0;
                 loss_sum = 0.0;
                 l1_sum = 0.0;
                 sym_sum = 0.0;
@@ -354,6 +485,13 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
         for (int i = 0; i < D; ++i) {
             cx[i] = nx[i];
             cdx[i] = ndx[i];
+        }
+        if constexpr (LAT) {
+#pragma unroll
+            for (int i = 0; i < D * D; ++i) cb[i] = nb[i];
+#pragma unroll
+            for (int i = 0; i < D; ++i) cy[i] = ny[i];
+            ce = ne;
         }
         nidx = nnidx;
         advance(c);
@@ -383,7 +521,15 @@ hipError_t launch_adam_epochs(const AdamArgs& a, hipStream_t st) {
 template <class Lib>
 hipError_t launch_adam_epochs_reversed(const AdamArgs& a, hipStream_t st) {
     if (a.n_problems == 0 || a.n_epochs == 0) return hipSuccess;
-    adam_epochs_kernel<Lib, true><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
+    adam_epochs_kernel<Lib, ADAM_REVERSED><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
+    SYMODE_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+template <class Lib>
+hipError_t launch_adam_epochs_latent(const AdamArgs& a, hipStream_t st) {
+    if (a.n_problems == 0 || a.n_epochs == 0) return hipSuccess;
+    adam_epochs_kernel<Lib, ADAM_LATENT><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
     SYMODE_LAUNCH_CHECK();
     return hipSuccess;
 }

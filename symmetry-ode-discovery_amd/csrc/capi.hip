@@ -536,18 +536,29 @@ int symode_euler_jvp_vjp(const float* x, const float* v, const float* g_x, const
 
 namespace {
 
-// symode_adam_epochs (gx_, jgx null, n_g 0, reversed false) and symode_adam_epochs_reversed: one set of argument checks
-int adam_epochs(bool reversed, const float* x, const float* dx, const float* gx_, const float* jgx, int n_g, long n_src,
-                const int* idx, long n_idx_problems, int n_epochs, int n_steps, int batch, long n_problems, int d, int order,
-                int flags, const float* q_eff, int r, int allow_constant, int n_params, float lr, float beta1, float beta2,
-                float eps, float w_x, float w_reg, float w_sym, int l1, float threshold, int st_freq, int epoch0,
+// the operands symode_adam_epochs_latent has beyond z, dz
+struct AdamLatent {
+    const float *B, *y, *e, *L;
+    int d_obs, n_gen;
+    float w_obs, w_sym;
+};
+
+// symode_adam_epochs (gx_, jgx null, n_g 0, kind ADAM_PLAIN), symode_adam_epochs_reversed and symode_adam_epochs_latent (lat
+// set; x, dx are z, dz and w_x is w_z): one set of argument checks
+int adam_epochs(AdamKind kind, const AdamLatent* lat, const float* x, const float* dx, const float* gx_, const float* jgx, int n_g,
+                long n_src, const int* idx, long n_idx_problems, int n_epochs, int n_steps, int batch, long n_problems, int d,
+                int order, int flags, const float* q_eff, int r, int allow_constant, int n_params, float lr, float beta1,
+                float beta2, float eps, float w_x, float w_reg, float w_sym, int l1, float threshold, int st_freq, int epoch0,
                 float near_band, float* params, float* m, float* v, int* step, float* mask, float* xi_out, float* log,
                 void* stream) {
     SYMODE_GET_OPS();
-    if (n_epochs < 0 || n_problems < 0 || n_g < 0) return SYMODE_E_BADSIZE;
+    if (n_epochs < 0 || n_problems < 0 || n_g < 0 || (lat && lat->n_gen < 0)) return SYMODE_E_BADSIZE;
     if (n_epochs == 0 || n_problems == 0) return SYMODE_OK;
     // the regulariser's gradient is accumulated at weight w_sym / w_x next to the residual's (adam.hpp): it needs w_x > 0
     if (n_g > 0 && !(w_x > 0.0f)) return SYMODE_E_BADSIZE;
+    // latent: the same for w_sym / w_z, and without w_z no data term reaches the coefficients at all (mse_x has no gradient)
+    if (lat && (!(w_x > 0.0f) || lat->d_obs < d || (!lat->e && lat->d_obs > d) || (!lat->L && lat->n_gen > 0)))
+        return SYMODE_E_BADSIZE;
     if (n_problems > 2147483647L || n_src < 1 || n_src > 2147483647L || n_steps < 1 || batch < 1 || epoch0 < 0)
         return SYMODE_E_BADSIZE;
     if (n_idx_problems != 1 && n_idx_problems != n_problems) return SYMODE_E_BADSIZE;
@@ -556,15 +567,31 @@ int adam_epochs(bool reversed, const float* x, const float* dx, const float* gx_
     if (n_params > ADAM_BLOCK || d * ops->p > ADAM_BLOCK) return SYMODE_E_BADSIZE;
     if (!x || !dx || !idx || !params || !m || !v || !step || !mask || !xi_out || !log) return SYMODE_E_NULLPTR;
     if (n_g > 0 && (!gx_ || !jgx)) return SYMODE_E_NULLPTR;
+    if (lat && (!lat->B || !lat->y)) return SYMODE_E_NULLPTR;
     if (misaligned(x, 4) || misaligned(dx, 4) || misaligned(idx, 4) || misaligned(q_eff, 4) || misaligned(params, 4) ||
         misaligned(m, 4) || misaligned(v, 4) || misaligned(step, 4) || misaligned(mask, 4) || misaligned(xi_out, 4) ||
         misaligned(log, 4) || (n_g > 0 && (misaligned(gx_, 4) || misaligned(jgx, 4))))
         return SYMODE_E_ALIGN;
-    const AdamArgs a{x, dx, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, q_eff, q_eff ? r : 0,
-                     allow_constant != 0, n_params, lr, beta1, beta2, eps, w_x, w_reg, l1, threshold, st_freq, epoch0,
-                     near_band, params, m, v, step, mask, xi_out, log, n_g > 0 ? gx_ : nullptr, n_g > 0 ? jgx : nullptr, n_g,
-                     n_g > 0 ? w_sym / w_x : 0.0f};
-    return (int)(reversed ? ops->adam_epochs_reversed(a, (hipStream_t)stream) : ops->adam_epochs(a, (hipStream_t)stream));
+    if (lat && (misaligned(lat->B, 4) || misaligned(lat->y, 4) || (lat->d_obs > d && misaligned(lat->e, 4)) ||
+                (lat->n_gen > 0 && misaligned(lat->L, 4))))
+        return SYMODE_E_ALIGN;
+    AdamArgs a{x, dx, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, q_eff, q_eff ? r : 0,
+               allow_constant != 0, n_params, lr, beta1, beta2, eps, w_x, w_reg, l1, threshold, st_freq, epoch0,
+               near_band, params, m, v, step, mask, xi_out, log, n_g > 0 ? gx_ : nullptr, n_g > 0 ? jgx : nullptr, n_g,
+               n_g > 0 ? w_sym / w_x : 0.0f};
+    if (lat) {
+        a.lat_b = lat->B;
+        a.lat_y = lat->y;
+        a.lat_e = lat->d_obs > d ? lat->e : nullptr;          // D_obs == d: every e_b is 0, the array is not read
+        a.gen_l = lat->n_gen > 0 ? lat->L : nullptr;
+        a.n_gen = lat->n_gen;
+        a.d_obs = lat->d_obs;
+        a.w_obs = lat->w_obs;
+        a.w_sym = lat->w_sym;
+        a.w_ratio = lat->n_gen > 0 ? lat->w_sym / w_x : 0.0f;
+        return (int)ops->adam_epochs_latent(a, (hipStream_t)stream);
+    }
+    return (int)(kind == ADAM_REVERSED ? ops->adam_epochs_reversed(a, (hipStream_t)stream) : ops->adam_epochs(a, (hipStream_t)stream));
 }
 
 }  // namespace
@@ -576,7 +603,7 @@ int symode_adam_epochs(const float* x, const float* dx, long n_src, const int* i
                        int allow_constant, int n_params, float lr, float beta1, float beta2, float eps, float w_x, float w_reg,
                        int l1, float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
                        int* step, float* mask, float* xi_out, float* log, void* stream) {
-    return adam_epochs(false, x, dx, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d,
+    return adam_epochs(ADAM_PLAIN, nullptr, x, dx, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d,
                        order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, 0.0f, l1, threshold,
                        st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
 }
@@ -587,9 +614,22 @@ int symode_adam_epochs_reversed(const float* x, const float* dx, const float* gx
                                 float lr, float beta1, float beta2, float eps, float w_x, float w_reg, float w_sym, int l1,
                                 float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
                                 int* step, float* mask, float* xi_out, float* log, void* stream) {
-    return adam_epochs(true, x, dx, gx, jgx, n_g, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d, order,
+    return adam_epochs(ADAM_REVERSED, nullptr, x, dx, gx, jgx, n_g, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d, order,
                        flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, w_sym, l1, threshold,
                        st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+}
+
+int symode_adam_epochs_latent(const float* z, const float* dz, const float* B, const float* y, const float* e, int D_obs,
+                              const float* L, int n_gen, long n_src, const int* idx, long n_idx_problems, int n_epochs,
+                              int n_steps, int batch, long n_problems, int d, int order, int flags, const float* q_eff, int r,
+                              int allow_constant, int n_params, float lr, float beta1, float beta2, float eps, float w_z,
+                              float w_x, float w_reg, float w_sym, int l1, float threshold, int st_freq, int epoch0,
+                              float near_band, float* params, float* m, float* v, int* step, float* mask, float* xi_out,
+                              float* log, void* stream) {
+    const AdamLatent lat{B, y, e, L, D_obs, n_gen, w_x, w_sym};
+    return adam_epochs(ADAM_LATENT, &lat, z, dz, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch,
+                       n_problems, d, order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_z, w_reg, 0.0f, l1,
+                       threshold, st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
 }
 
 }  // extern "C"

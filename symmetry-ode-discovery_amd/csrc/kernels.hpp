@@ -131,6 +131,9 @@ struct LibOps {
     hipError_t (*latent_closure)(const float* z, const float* dz, const float* B, const float* y, long S, long n, const float* xi,
                                  const float* mask, float inv_count, float w_pair, float* loss2, float* grad, double* ws, int gx,
                                  hipStream_t st);
+    // adam_epochs on the latent branch: a.x, a.dx are z, dz; a.lat_b, a.lat_y, a.lat_e, a.gen_l, a.n_gen (adam.hpp).  Last in
+    // the table: an additive entry
+    hipError_t (*adam_epochs_latent)(const AdamArgs& a, hipStream_t st);
 };
 
 // ---------------------------------------------------------------------------------------

@@ -38,7 +38,8 @@ constexpr LibOps make_ops() {
                   &launch_rollout_error<Lib>,
                   &launch_adam_epochs<Lib>,
                   &launch_adam_epochs_reversed<Lib>,
-                  &launch_latent_closure<Lib>};
+                  &launch_latent_closure<Lib>,
+                  &launch_adam_epochs_latent<Lib>};
 }
 
 #define SYMODE_OPS_ALL_FLAGS(D, O) make_ops<D, O, 0>(), make_ops<D, O, 1>(), make_ops<D, O, 2>(), make_ops<D, O, 3>()

@@ -6,8 +6,11 @@ problem, nothing on the host inside a launch.
 Covered: the observed-space fit, unconstrained or under the equivariance constraint (any ``CoefMap``), L1 regulariser, and
 the reversed symmetry regulariser on operands g(x), J_g(x) computed once for the data set (``reversed_sym``,
 symode_adam_epochs_reversed: ``+ w_sym * sum_g mean |J_g(x) h(x) - h(g x)|^2`` per minibatch).
-Not covered (the callers refuse them): the latent branch (its L-BFGS fit has a fused route of its own, train._train_latent_on_device), the i / f symmetry regularisers (they run the autoencoder on
-Xi-dependent inputs), several ranks.
+The ``--use_latent`` branch under a frozen autoencoder (``latent``, symode_adam_epochs_latent): x, dx are then z, dz, and
+every minibatch loss is ``w_z * mse_z + w_x * mse_x + w_sym * (linear-latent regulariser, not divided by the rows)`` on the
+per-row operands of ``model_utils.latent_operands``; mse_x is logged and added but has no gradient, as in train_SIGED.
+Not covered (the callers refuse them): the i / f symmetry regularisers (they run the autoencoder on Xi-dependent inputs), a
+latent fit whose autoencoder trains, several ranks.
 """
 from __future__ import annotations
 
@@ -25,13 +28,17 @@ TABLE_BYTES = 256 << 20
 LOG_COLUMNS = ('loss_sindy_x', 'loss_sindy_reg', 'steps', 'near', 'nan', 'event', 'epoch')
 # records of a trainer with ``reversed_sym``: column 7 is the epoch mean of the batch regulariser (unweighted)
 LOG_COLUMNS_REVERSED = LOG_COLUMNS + ('loss_sym_reg',)
+# records of a trainer with ``latent``: ten columns, the three loss terms unweighted
+LOG_COLUMNS_LATENT = LOG_COLUMNS + ('loss_sym_reg', 'loss_sindy_z', 'unused')
 
 
 class DeviceAdam:
     def __init__(self, x, dx, poly_order, include_sine, include_exp, coef, lr, w_sindy_x, w_sindy_reg, threshold, st_freq,
-                 batch_size, betas=(0.9, 0.999), eps=1e-8, engine=None, reversed_sym=None):
+                 batch_size, betas=(0.9, 0.999), eps=1e-8, engine=None, reversed_sym=None, latent=None):
         """x, dx (n, d) fp32 on the device, shared by all problems; ``coef``: the CoefMap of the parametrisation;
-        ``reversed_sym``: (gx (n_g, n, d), jgx (n_g, n, d, d), w_sym) on the device of x, or None."""
+        ``reversed_sym``: (gx (n_g, n, d), jgx (n_g, n, d, d), w_sym) on the device of x, or None;
+        ``latent``: (B (n, d, d), y (n, d), e (n,) or None with D_obs == d, D_obs, L (n_gen, d, d) or None, w_z, w_sym) on the
+        device of x, or None -- with it x, dx are z, dz and ``w_sindy_x`` weighs mse_x."""
         self.engine = engine or get_engine()
         self.x, self.dx = x.contiguous(), dx.contiguous()
         self.n, self.d = self.x.shape
@@ -64,7 +71,33 @@ class DeviceAdam:
             if gx.shape[0] > 0 and not self.w_x > 0:
                 raise ValueError(f'reversed_sym needs w_sindy_x > 0 (the regulariser is weighed against it), got {self.w_x}')
             self.reversed_sym = (gx.contiguous(), jgx.contiguous(), float(w_sym))
-        self.log_columns = LOG_COLUMNS if self.reversed_sym is None else LOG_COLUMNS_REVERSED
+        self.latent = None
+        if latent is not None:
+            if reversed_sym is not None:
+                raise ValueError('reversed_sym and latent are two different losses: give one of them')
+            B, y, e, D_obs, L, w_z, w_sym = latent
+            D_obs = int(D_obs)
+            if D_obs < self.d:
+                raise ValueError(f'latent D_obs is {D_obs}, below the latent dimension {self.d} of x {tuple(self.x.shape)}')
+            if e is None and D_obs > self.d:
+                raise ValueError(f'latent e must be (n,) with D_obs {D_obs} > d {self.d}, got None')
+            for name, t, shape in (('B', B, (self.n, self.d, self.d)), ('y', y, (self.n, self.d)), ('e', e, (self.n,)),
+                                   ('L', L, (self.d, self.d))):
+                if t is None and name in 'eL':
+                    continue
+                lead = 1 if name == 'L' else 0
+                if not isinstance(t, torch.Tensor) or t.dim() != len(shape) + lead or tuple(t.shape[lead:]) != shape:
+                    raise ValueError(f'latent {name} must be ({"n_gen, " if lead else ""}{", ".join(map(str, shape))}) like x '
+                                     f'{tuple(self.x.shape)}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}')
+                if t.device != self.x.device or t.dtype != torch.float32:
+                    raise ValueError(f'latent {name} must be fp32 on {self.x.device}, got {t.dtype} on {t.device}')
+            if not float(w_z) > 0:
+                raise ValueError(f'latent needs w_sindy_z > 0 (mse_x has no gradient and the regulariser is weighed against '
+                                 f'mse_z), got {w_z}')
+            cont = lambda t: None if t is None else t.contiguous()  # noqa: E731
+            self.latent = (B.contiguous(), y.contiguous(), cont(e), D_obs, cont(L), float(w_z), float(w_sym))
+        self.log_columns = (LOG_COLUMNS_LATENT if self.latent is not None
+                            else LOG_COLUMNS if self.reversed_sym is None else LOG_COLUMNS_REVERSED)
 
     def table(self, order):
         """One epoch's (S or 1, n) permutation cut into (S or 1, steps, batch) int32 row numbers, the short last batch
@@ -81,10 +114,10 @@ class DeviceAdam:
             state=None):
         """``params0`` (S, n_params); ``orders`` yields one (S or 1, n) integer permutation on the device per epoch, drawn
         in epoch order.  ``on_epoch(epoch, record)`` is called for every epoch after its launch was read back, with that
-        epoch's own record: the LOG_COLUMNS (with ``reversed_sym``: LOG_COLUMNS_REVERSED) as (S,) numpy arrays, and ``record['state']`` = {params, mask, Xi} (device
+        epoch's own record: the LOG_COLUMNS (with ``reversed_sym``: LOG_COLUMNS_REVERSED, with ``latent``: LOG_COLUMNS_LATENT) as (S,) numpy arrays, and ``record['state']`` = {params, mask, Xi} (device
         tensors, valid until the next launch) when the epoch is the last of its launch, else None.  ``boundary(epoch)``
         true ends the launch after that epoch (a caller that needs the state there).  ``state``: (m, v, step) of an
-        earlier fit to continue.  Returns Xi, mask, params (device), log (n_epochs, S, 8) numpy, nan (S,) bool and m, v,
+        earlier fit to continue.  Returns Xi, mask, params (device), log (n_epochs, S, 8; with ``latent`` 10) numpy, nan (S,) bool and m, v,
         step."""
         dev = self.x.device
         params = params0.detach().to(dev, torch.float32).clone().contiguous()
@@ -116,7 +149,11 @@ class DeviceAdam:
             kw = dict(lr=self.lr, betas=self.betas, eps=self.eps, w_x=self.w_x, w_reg=self.w_reg, l1=True,
                       threshold=self.threshold, st_freq=self.st_freq, epoch0=epoch0 + done, near_band=NEAR_THRESHOLD_BAND,
                       q_eff=self.q_eff, allow_constant=self.coef.allow_constant)
-            if self.reversed_sym is None:
+            if self.latent is not None:
+                B, y, e, D_obs, L, w_z, w_sym = self.latent
+                xi, log = self.engine.adam_epochs_latent(self.x, self.dx, B, y, e, D_obs, L, idx, params, m, v, step, mask,
+                                                         self.order, self.flags, w_z=w_z, w_sym=w_sym, **kw)
+            elif self.reversed_sym is None:
                 xi, log = self.engine.adam_epochs(self.x, self.dx, idx, params, m, v, step, mask, self.order, self.flags, **kw)
             else:
                 gx, jgx, w_sym = self.reversed_sym
@@ -130,5 +167,5 @@ class DeviceAdam:
                     rec['state'] = {'params': params, 'mask': mask, 'Xi': xi} if k == len(tables) - 1 else None
                     on_epoch(epoch0 + done + k, rec)
             done += len(tables)
-        log = np.concatenate(logs) if logs else np.zeros((0, S, 8), dtype=np.float32)
+        log = np.concatenate(logs) if logs else np.zeros((0, S, 8 if self.latent is None else 10), dtype=np.float32)
         return {'Xi': xi, 'mask': mask, 'params': params, 'log': log, 'nan': step < 0, 'm': m, 'v': v, 'step': step}

@@ -98,6 +98,9 @@ _SIGNATURES = {
     "symode_adam_epochs_reversed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_long, c_int, c_int,
                                             c_int, c_long, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_float] * 7
                                     + [c_int, c_float, c_int, c_int, c_float] + [c_void_p] * 8),
+    "symode_adam_epochs_latent": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_long, c_void_p, c_long, c_int, c_int, c_int,
+                                          c_long, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_float] * 8
+                                  + [c_int, c_float, c_int, c_int, c_float] + [c_void_p] * 8),
     "symode_host_stlsq_sweep": (c_int, [c_void_p, c_int, c_int, c_int, c_long, ctypes.c_double, ctypes.c_double, c_int, c_int,
                                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
@@ -287,7 +290,7 @@ class HipEngine:
 
     def adam_epochs(self, x, dx, idx, params, m, v, step, mask, order, flags=0, *, lr, betas=(0.9, 0.999), eps=1e-8, w_x=1.0,
                     w_reg=0.0, l1=True, threshold=0.0, st_freq=0, epoch0=0, near_band=1e-4, q_eff=None, allow_constant=True,
-                    _reversed=None):
+                    _reversed=None, _latent=None):
         """``idx.shape[0]`` whole epochs of minibatch Adam steps for S problems in ONE launch (symode_adam_epochs).
         x, dx (n_src, d) fp32; idx (n_epochs, S or 1, n_steps, batch) int32 row numbers; params, m, v (S, n_params) fp32,
         step (S,) int32 and mask (S, d, p) fp32 are the state, UPDATED IN PLACE (so they must be contiguous); q_eff
@@ -330,7 +333,17 @@ class HipEngine:
         if n_params != (r + d if q_eff is not None else d * p):
             raise SymodeError(f"params has {n_params} columns, expected {r + d if q_eff is not None else d * p}")
         xi = torch.empty(S, d, p, dtype=torch.float32, device=x.device)
-        log = torch.empty(n_epochs, S, 8, dtype=torch.float32, device=x.device)
+        log = torch.empty(n_epochs, S, 10 if _latent is not None else 8, dtype=torch.float32, device=x.device)
+        if _latent is not None:
+            B, y, e, D_obs, L, n_gen, w_z, w_sym = _latent
+            self._check(self.lib.symode_adam_epochs_latent(
+                self._ptr(x), self._ptr(dx), self._ptr(B), self._ptr(y), self._ptr(e), D_obs, self._ptr(L), n_gen, n_src,
+                self._ptr(idx), n_tab, n_epochs, n_steps, batch, S, d, order, flags, self._ptr(q_eff), r,
+                int(bool(allow_constant)), n_params, float(lr), float(betas[0]), float(betas[1]), float(eps), float(w_z),
+                float(w_x), float(w_reg), float(w_sym), int(bool(l1)), float(threshold), int(st_freq), int(epoch0),
+                float(near_band), self._ptr(params), self._ptr(m), self._ptr(v), self._ptr(step), self._ptr(mask),
+                self._ptr(xi), self._ptr(log), self._stream(x)), "symode_adam_epochs_latent")
+            return xi, log
         if _reversed is not None:
             gx, jgx, n_g, w_sym = _reversed
             self._check(self.lib.symode_adam_epochs_reversed(
@@ -374,6 +387,43 @@ class HipEngine:
         if n_g == 0:
             gx = jgx = None
         return self.adam_epochs(x, dx, idx, params, m, v, step, mask, order, flags, _reversed=(gx, jgx, n_g, w_sym), **kw)
+
+    def adam_epochs_latent(self, z, dz, B, y, e, D_obs, L, idx, params, m, v, step, mask, order, flags=0, *, w_z, w_sym, **kw):
+        """``adam_epochs`` on the latent branch (symode_adam_epochs_latent): per minibatch
+        ``w_z * mse_z + w_x * mse_x + w_sym * sum_g sum_b |W J_Theta(z)(L_g z) - L_g W Theta(z)|^2 + w_reg * |params|_1`` on the
+        per-row operands of ``model_utils.latent_operands``: z, dz, y (n_src, d), B (n_src, d, d), e (n_src,) or None when
+        D_obs == d, and the generators L (n_gen, d, d) or None (n_gen = 0), all fp32.  mse_x is logged and added but has no
+        gradient; the regulariser is not divided by the rows.  The other arguments are those of ``adam_epochs``; returns
+        (xi (S, d, p), log (n_epochs, S, 10)): columns 0-6 as ``adam_epochs`` with 0 = mean mse_x, 7 = mean regulariser,
+        8 = mean mse_z, 9 = 0.  Needs w_z > 0."""
+        z = self._dev(z, "z")
+        if z.dim() != 2:
+            raise SymodeError(f"z must be (n_src, d), got {tuple(z.shape)}")
+        n_src, d = z.shape
+        B, y = self._dev(B, "B"), self._dev(y, "y")
+        if B.shape != (n_src, d, d) or y.shape != (n_src, d):
+            raise SymodeError(f"B must be ({n_src}, {d}, {d}) and y ({n_src}, {d}), got {tuple(B.shape)} and {tuple(y.shape)}")
+        D_obs = int(D_obs)
+        if D_obs < d:
+            raise SymodeError(f"D_obs is {D_obs}, below the latent dimension {d}")
+        if e is None and D_obs > d:
+            raise SymodeError(f"e (n_src,) is needed with D_obs {D_obs} > d {d}")
+        if e is not None:
+            e = self._dev(e, "e")
+            if e.shape != (n_src,):
+                raise SymodeError(f"e must be ({n_src},), got {tuple(e.shape)}")
+        n_gen = 0
+        if L is not None:
+            L = self._dev(L, "L")
+            if L.dim() != 3 or L.shape[1:] != (d, d):
+                raise SymodeError(f"L must be (n_gen, {d}, {d}), got {tuple(L.shape)}")
+            n_gen = L.shape[0]
+        if n_gen == 0:
+            L = None
+        for name, t in (("B", B), ("y", y), ("e", e), ("L", L)):
+            if t is not None and t.device != z.device:
+                raise SymodeError(f"{name} is on {t.device}, z on {z.device}: all tensors of one launch live on one device")
+        return self.adam_epochs(z, dz, idx, params, m, v, step, mask, order, flags, _latent=(B, y, e, D_obs, L, n_gen, w_z, w_sym), **kw)
 
     def _check_coef(self, xi, mask, d, order, flags, n_problems=1):
         p = self.lib_size(d, order, flags)

@@ -563,7 +563,7 @@ def reversed_operands(x, autoencoder, generator, chunk=None):
     return gx, jgx
 
 
-def latent_operands(x, dx, autoencoder, chunk=PRECOMPUTE_CHUNK):
+def latent_operands(x, dx, autoencoder, chunk=PRECOMPUTE_CHUNK, per_row=False):
     """The data of the latent closure (train.py:647-661) under a frozen autoencoder in eval mode, computed once per fit:
     ``(z, dz, B, y, e0, D)`` with z = enc(x), dz = J_enc(x) dx (compute_dz) as the reference computes them, and the decoder's
     Jacobian A_n = J_dec(z_n) (D, d) -- d JVPs of the decoder along the unit vectors, no per-sample Jacobian call -- reduced by
@@ -572,10 +572,12 @@ def latent_operands(x, dx, autoencoder, chunk=PRECOMPUTE_CHUNK):
     D = d: B = A, y = dx, e0 = 0, no QR.  The QR runs in fp64 on x's device; B and y are rounded to x's dtype once.
     ``n_comps`` is flattened into the point axis as the regressor does (N = batch * n_comps); rows go through the
     autoencoder in chunks of ``chunk`` (pointwise in eval mode).  With loss2 of ``symode_loss_grad_latent`` on these operands
-    the reference's logged terms are  loss_sindy_z = loss2[0],  loss_sindy_x = loss2[1] * d / D + e0 / (N * D)."""
+    the reference's logged terms are  loss_sindy_z = loss2[0],  loss_sindy_x = loss2[1] * d / D + e0 / (N * D).
+    ``per_row=True`` (the minibatch trainers, whose batches are subsets of the rows): in e0's place the terms of that sum,
+    e (N,) in x's dtype with e_n = |dx_n - Q_n y_n|^2 computed in fp64 and rounded once; zeros with D = d."""
     if autoencoder.training:
         raise ValueError('latent_operands needs the autoencoder in eval mode (batch norm must be pointwise)')
-    zs, dzs, Bs, ys, e0 = [], [], [], [], 0.0
+    zs, dzs, Bs, ys, es, e0 = [], [], [], [], [], 0.0
     with torch.no_grad():
         for a in range(0, x.shape[0], chunk):
             xc, dxc = x[a:a + chunk], dx[a:a + chunk]
@@ -591,10 +593,16 @@ def latent_operands(x, dx, autoencoder, chunk=PRECOMPUTE_CHUNK):
             dxf = dxc.reshape(-1, D)
             if D == d:
                 B, y = A, dxf
+                if per_row:
+                    es.append(dxf.new_zeros(dxf.shape[0]))
             else:
                 Q, R = torch.linalg.qr(A.double(), mode='reduced')              # Q (N, D, k), R (N, k, d), k = min(D, d)
                 qty = torch.einsum('nij,ni->nj', Q, dxf.double())
-                e0 += float((dxf.double() - torch.einsum('nij,nj->ni', Q, qty)).square().sum())
+                e_sq = (dxf.double() - torch.einsum('nij,nj->ni', Q, qty)).square()
+                if per_row:
+                    es.append(e_sq.sum(1).to(x.dtype))
+                else:
+                    e0 += float(e_sq.sum())
                 k = R.shape[-2]
                 B, y = R.new_zeros(R.shape[0], d, d), R.new_zeros(R.shape[0], d)   # (D < d: the rows beyond D stay zero)
                 B[:, :k], y[:, :k] = R, qty
@@ -603,7 +611,7 @@ def latent_operands(x, dx, autoencoder, chunk=PRECOMPUTE_CHUNK):
             Bs.append(B.to(x.dtype))
             ys.append(y.to(x.dtype))
     cat = lambda parts: torch.cat(parts).contiguous()  # noqa: E731
-    return cat(zs), cat(dzs), cat(Bs), cat(ys), e0, x.shape[-1]
+    return cat(zs), cat(dzs), cat(Bs), cat(ys), cat(es) if per_row else e0, x.shape[-1]
 
 
 class _ReversedFused(torch.autograd.Function):

@@ -60,8 +60,9 @@ _MAIN_ARGS = [
 # Flags of this project beyond the reference's surface and the three above, kept apart from _MAIN_ARGS (whose length is
 # pinned against the reference parser): --gram_closure runs the device trainer's closure as the quadratic form of the
 # batch's fp64 Gram matrices, built in one pass over the data (one all-reduce when sharded) instead of streaming the points
-# per evaluation (gram_closure.py).  --device_adam runs the plain minibatch Adam fit (--sindy_optimizer adam, no latent space;
-# a symmetry regulariser only as --sym_reg_type r with --fix_laligan) as whole epochs per launch on the device
+# per evaluation (gram_closure.py).  --device_adam runs the minibatch Adam fit (--sindy_optimizer adam; the plain branch with
+# a symmetry regulariser only as --sym_reg_type r with --fix_laligan; with --use_latent the latent branch under a frozen
+# autoencoder and w_sindy_z > 0, its linear-latent regulariser included) as whole epochs per launch on the device
 # (device_adam.py) instead of one Python iteration per batch.
 # --fused_latent (with --use_latent and the L-BFGS optimiser; ignored without --use_latent) runs the latent fit with one fused
 # closure kernel and the device trainer (train._train_latent_on_device) instead of autograd through the autoencoder per closure.

@@ -762,15 +762,18 @@ def _test_loss_line(epoch, regressor, test_loader, device):
 
 def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir, regressor,
                           use_latent, lr_sindy, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg, st_freq, threshold,
-                          print_eq, sym_reg_type=None, autoencoder=None, generator=None):
+                          print_eq, sym_reg_type=None, autoencoder=None, generator=None, w_sindy_z=0.0):
     """train_SIGED's plain branch on DeviceAdam: the same shuffles (one ``randperm`` per epoch from the global generator, as
     the loader draws them), prints, wandb records, test loss and checkpoints at the same epochs, produced from the
     launch's log and from the state adopted into the regressor at those epochs and at the end.  ``w_sym_reg > 0`` with
     ``sym_reg_type 'r'`` and a frozen autoencoder and generator adds ``w_sym_reg * symmreg_r`` to every minibatch loss:
-    g(x), J_g(x) are computed once over the loader's rows."""
+    g(x), J_g(x) are computed once over the loader's rows.
+    ``use_latent`` runs the latent branch (_train_adam_latent_on_device)."""
     from .dataset import DeviceBatches
     if use_latent:
-        raise ValueError('device_adam covers the observed-space fit only: use_latent is set')
+        return _train_adam_latent_on_device(train_loader, num_epochs, log_interval, save_interval, save_dir, regressor, lr_sindy,
+                                            w_sindy_z, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg, st_freq, threshold,
+                                            print_eq, autoencoder, generator)
     if w_sym_reg < 0:
         raise ValueError(f'w_sym_reg is {w_sym_reg}: a weight is not negative')
     sym = w_sym_reg > 0
@@ -818,6 +821,73 @@ def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_int
     coef.adopt(regressor, out['params'][0], out['mask'][0])
 
 
+def _train_adam_latent_on_device(train_loader, num_epochs, log_interval, save_interval, save_dir, regressor, lr_sindy, w_sindy_z,
+                                 w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg, st_freq, threshold, print_eq, autoencoder,
+                                 generator):
+    """train_SIGED's ``use_latent`` branch on DeviceAdam(latent=...): the optimiser steps the SINDy coefficients alone, so the
+    autoencoder is data -- z, dz, the QR-reduced decoder Jacobian and the per-row constant of loss_sindy_x are computed once
+    over the loader's rows (model_utils.latent_operands), the generators are read once, and every epoch is part of one
+    launch.  Same shuffles, prints, records and checkpoints as the tensor-op branch; no test line, as there.
+    ``sym_reg_type`` is not read, as there: the regulariser of this branch is the linear-latent one whenever w_sym_reg > 0."""
+    from .dataset import DeviceBatches
+    if not w_sindy_z > 0:
+        raise ValueError(f'device_adam with use_latent needs w_sindy_z > 0 (here {w_sindy_z}): loss_sindy_x has no gradient '
+                         '(compute_dx cuts it from the graph), so without it no data term reaches the coefficients')
+    # training mode matters where a layer depends on it: batch norm on batch statistics is not pointwise, and it moves
+    mode_layers = (torch.nn.modules.batchnorm._BatchNorm, torch.nn.modules.dropout._DropoutNd)
+    in_training = autoencoder.training and any(isinstance(layer, mode_layers) for layer in autoencoder.modules())
+    if any(q.requires_grad for q in autoencoder.parameters()) or in_training:
+        raise ValueError('device_adam with use_latent needs a frozen autoencoder in eval mode (no parameter requires grad, '
+                         'batch norm pointwise): z, dz and the decoder Jacobian are computed once')
+    arrays = getattr(train_loader, 'arrays', None)                   # (a loader without arrays is refused below, by its type)
+    if arrays is not None and arrays[0].dim() != 2:
+        raise ValueError(f'device_adam with use_latent needs one latent point per row: the items are {tuple(arrays[0].shape[1:])}, '
+                         'not single (D,) points (n_comps > 1)')
+    if sindy_reg_type != 'l1':
+        raise ValueError(f"device_adam covers sindy_reg_type 'l1', not '{sindy_reg_type}'")
+    if not isinstance(train_loader, DeviceBatches):
+        raise ValueError(f'device_adam needs train_loader to be a DeviceBatches, got {type(train_loader).__name__}')
+    if train_loader.window != 0:
+        raise ValueError(f'device_adam needs single-row items: train_loader.window is {train_loader.window}, not 0')
+    x, dx = train_loader.arrays
+    if not (x.is_cuda and dx.is_cuda):
+        raise ValueError('device_adam needs the data set resident on the device (DeviceBatches kept it in host memory)')
+    was_training = autoencoder.training                      # (only without a layer that reads the flag, see above)
+    autoencoder.eval()
+    try:
+        z, dz, B, y, e, D = latent_operands(x, dx, autoencoder, per_row=True)
+    finally:
+        autoencoder.train(was_training)
+    if z.shape != (x.shape[0], regressor.latent_dim):
+        raise ValueError(f'device_adam with use_latent needs one latent point per row: the {x.shape[0]} rows encode to z '
+                         f'{tuple(z.shape)}, not ({x.shape[0]}, {regressor.latent_dim}) (n_comps > 1)')
+    from .device_adam import DeviceAdam
+    coef = regressor.coef
+    d = z.shape[1]
+    L = None
+    if w_sym_reg > 0:
+        L = torch.stack([v[:d, :d] for v in generator.get_full_basis_list()]).detach().to(z.device).float().contiguous()
+    trainer = DeviceAdam(z.float(), dz.float(), regressor.poly_order, regressor.include_sine, regressor.include_exp, coef, lr_sindy,
+                         w_sindy_x, w_sindy_reg, threshold, st_freq, train_loader.bs, engine=regressor.engine,
+                         latent=(B.float(), y.float(), e.float() if D > d else None, D, L, w_sindy_z, w_sym_reg if L is not None else 0.0))
+    last_mask = [regressor.mask.detach().clone()]
+    report = _EpochReport(regressor, log_interval, save_interval, save_dir, print_eq)
+
+    def on_epoch(epoch, rec):
+        wandb_log = {k: float(rec[k][0]) for k in ('loss_sindy_x', 'loss_sindy_z', 'loss_sindy_reg', 'loss_sym_reg')}
+        state = rec['state']
+        if _at(epoch, st_freq) and not rec['nan'][0]:                                  # train.py:545-546
+            regressor.note_near_threshold(state['Xi'][0], last_mask[0], threshold, 'set_threshold (device Adam)')
+            last_mask[0] = state['mask'][0].clone()
+        report(epoch, wandb_log, adopt=partial(coef.adopt, regressor, state['params'][0], state['mask'][0]), test=None)
+
+    regressor.train()
+    out = trainer.fit(coef.pack(regressor)[None], num_epochs, (train_loader.epoch_order()[None] for _ in range(num_epochs)),
+                      mask0=regressor.mask[None], on_epoch=on_epoch,
+                      boundary=lambda epoch: any(_at(epoch, every) for every in (log_interval, save_interval, st_freq)))
+    coef.adopt(regressor, out['params'][0], out['mask'][0])
+
+
 def train_SIGED(
     train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir,  # global
     autoencoder, discriminator, generator,  # symmetry discovery model
@@ -829,13 +899,14 @@ def train_SIGED(
 ):
     """Mini-batch Adam variant                                                       (train.py:382-614).
     ``device_adam=True`` (--device_adam): the plain branch runs whole epochs per launch on the device (device_adam.py),
-    with ``sym_reg_type='r'`` and a frozen LaLiGAN also under the reversed symmetry regulariser; any other configuration is
-    refused, not silently run the usual way."""
+    with ``sym_reg_type='r'`` and a frozen LaLiGAN also under the reversed symmetry regulariser; the ``use_latent`` branch
+    runs there too under a frozen autoencoder in eval mode with ``w_sindy_z > 0`` (the linear-latent regulariser included);
+    any other configuration is refused, not silently run the usual way."""
     if kwargs.get('device_adam'):
         return _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir,
                                      regressor, use_latent, lr_sindy, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg,
                                      st_freq, threshold, kwargs.get('print_eq'), sym_reg_type=kwargs.get('sym_reg_type'),
-                                     autoencoder=autoencoder, generator=generator)
+                                     autoencoder=autoencoder, generator=generator, w_sindy_z=w_sindy_z)
     optimizer_sindy = torch.optim.Adam(regressor.parameters(), lr=lr_sindy)
     symm_loss = make_symmreg_pttrain(autoencoder, generator)
     report = _EpochReport(regressor, log_interval, save_interval, save_dir, kwargs.get('print_eq'))
