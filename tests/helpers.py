@@ -1,4 +1,6 @@
 """Shared test helpers (test infrastructure, not product code)."""
+import os
+
 import numpy as np
 import torch
 
@@ -197,3 +199,28 @@ def make_config2(S, dev):
     for p in list(ae.parameters()) + list(gen.parameters()):
         p.requires_grad = False
     return x, dx, ae, gen
+
+
+class _env:
+    """SYMODE_* variables for the duration of a block (the library reads them once: engine.reload_env reads them again)."""
+
+    def __init__(self, **kv):
+        self.kv = kv
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kv}
+        os.environ.update({k: str(v) for k, v in self.kv.items()})
+        _reload_env()                                  # the library reads its SYMODE_* variables once; re-read on request
+
+    def __exit__(self, *exc):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        _reload_env()
+
+
+def _reload_env():
+    import symode_amd
+    symode_amd.engine.reload_env()

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from oracle import sindy_oracle as O
-from tests.helpers import TinyAE, only_compiled, t
+from tests.helpers import TinyAE, _env, only_compiled, t
 
 pytestmark = pytest.mark.gpu
 
@@ -404,29 +404,6 @@ def test_plain_c_caller_of_the_abi_runs(tmp_path):
 
 
 # ------------------------------------------------------------- one-launch finalisation (tickets)
-class _env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        os.environ.update({k: str(v) for k, v in self.kv.items()})
-        _reload_env()                                  # the library reads its SYMODE_* variables once; re-read on request
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        _reload_env()
-
-
-def _reload_env():
-    import symode_amd
-    symode_amd.engine.reload_env()
-
-
 @pytest.mark.parametrize("S,n,d,order", [(1, 125000, 2, 5), (1, 999, 2, 3), (7, 4097, 2, 3), (1, 50000, 3, 2), (64, 20000, 2, 2),
                                          (1, 1 << 22, 2, 3)])
 def test_fused_finalize_bit_identical_to_two_launches(eng, S, n, d, order):
