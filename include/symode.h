@@ -547,6 +547,58 @@ int symode_adam_epochs_latent(const float* z, const float* dz, const float* B, c
                               float near_band, float* params, float* m, float* v, int* step, float* mask, float* xi_out,
                               float* log, void* stream);
 
+/* The three entries above WITHOUT an index table: the launch computes the row of every batch slot from an order seed, so
+ * nothing runs between two launches of a fit and no index memory exists.  Each takes its sibling's arguments with
+ * (idx, n_idx_problems, n_steps) replaced by
+ *   order_seeds   (n_order_seeds) int64 ON THE DEVICE; n_order_seeds = 1: all problems walk the same order (as
+ *                 n_idx_problems = 1), else n_order_seeds = n_problems
+ *   shuffle       0: the loader with shuffle=False, see below
+ * n_steps is implied: ceil(n_src / batch).  Batch slot b of step s in epoch e (global number epoch0 + e) is position
+ * pos = s * batch + b of that epoch's order; its row is
+ *   pos >= n_src                 -1, the canonical pad of the short last batch: not read, not counted
+ *   shuffle == 0                 pos
+ *   otherwise                    pi(pos), pi the permutation of [0, n_src) keyed by (order seed, epoch0 + e): an unbalanced
+ *                                Feistel network over ceil(log2 n_src) bits, cycle-walked into [0, n_src); round keys from
+ *                                the seed's 64-bit mix and the epoch number through the counter hash of
+ *                                symode_seeded_subsamples (csrc/adam_order.hpp; device_adam.epoch_order is its numpy twin)
+ * The order is a function of (order seed, global epoch, n_src) alone -- not of n_problems, batch, the launch cut or the
+ * device -- so a fit cut into launches (epoch0 carried) agrees bit for bit with the fit in one launch, and each keyed entry
+ * leaves bit for bit what its sibling leaves on the table symode_adam_order_table writes for the same arguments.  It is an
+ * equivalent draw of the loader's shuffle, not a replay of torch's generator.
+ * Refused beyond the sibling's checks: order_seeds == NULL (SYMODE_E_NULLPTR), n_order_seeds not in {1, n_problems},
+ * n_src < 1 or n_src >= 2^31, batch < 1 (SYMODE_E_BADSIZE).  n_epochs == 0 or n_problems == 0: nothing to do.
+ * replaces: train.py:491-547 (as the siblings) plus the per-epoch shuffle of DataLoader(train_dataset, batch_size,
+ * shuffle=True) (main.py:36-38) that the table entries leave to the caller. */
+int symode_adam_epochs_keyed(const float* x, const float* dx, long n_src, const long long* order_seeds, long n_order_seeds,
+                             int shuffle, int n_epochs, int batch, long n_problems, int d, int order, int flags,
+                             const float* q_eff, int r, int allow_constant, int n_params, float lr, float beta1, float beta2,
+                             float eps, float w_x, float w_reg, int l1, float threshold, int st_freq, int epoch0,
+                             float near_band, float* params, float* m, float* v, int* step, float* mask, float* xi_out,
+                             float* log, void* stream);
+int symode_adam_epochs_reversed_keyed(const float* x, const float* dx, const float* gx, const float* jgx, int n_g, long n_src,
+                                      const long long* order_seeds, long n_order_seeds, int shuffle, int n_epochs, int batch,
+                                      long n_problems, int d, int order, int flags, const float* q_eff, int r,
+                                      int allow_constant, int n_params, float lr, float beta1, float beta2, float eps,
+                                      float w_x, float w_reg, float w_sym, int l1, float threshold, int st_freq, int epoch0,
+                                      float near_band, float* params, float* m, float* v, int* step, float* mask,
+                                      float* xi_out, float* log, void* stream);
+int symode_adam_epochs_latent_keyed(const float* z, const float* dz, const float* B, const float* y, const float* e, int D_obs,
+                                    const float* L, int n_gen, long n_src, const long long* order_seeds, long n_order_seeds,
+                                    int shuffle, int n_epochs, int batch, long n_problems, int d, int order, int flags,
+                                    const float* q_eff, int r, int allow_constant, int n_params, float lr, float beta1,
+                                    float beta2, float eps, float w_z, float w_x, float w_reg, float w_sym, int l1,
+                                    float threshold, int st_freq, int epoch0, float near_band, float* params, float* m,
+                                    float* v, int* step, float* mask, float* xi_out, float* log, void* stream);
+
+/* The table the keyed entries walk, written out through the same device function: idx_out (n_epochs, n_order_seeds,
+ * n_steps = ceil(n_src / batch), batch) int32, entry [e, s, step, b] the row of position step * batch + b in epoch
+ * epoch0 + e under order_seeds[s] (device int64), -1 beyond n_src.  It is what idx of the table entries would have to hold
+ * for the same fit: which rows a step saw, and the handle by which device and twin are compared.
+ * Refused: order_seeds or idx_out NULL (SYMODE_E_NULLPTR); n_src < 1, n_src >= 2^31, batch < 1, n_order_seeds < 1,
+ * n_epochs < 0, epoch0 < 0 (SYMODE_E_BADSIZE).  n_epochs == 0: nothing to do. */
+int symode_adam_order_table(long n_src, int batch, const long long* order_seeds, long n_order_seeds, int shuffle, int epoch0,
+                            int n_epochs, int* idx_out, void* stream);
+
 /* HOST function (no GPU work): least squares on the normal equations G = A^T A (n, n), C = A^T b (n, k), fp64
  * row-major host arrays; A had m_rows rows.  driver 0 = LAPACK gelsy semantics (pivoted QR rank rule with
  * rcond < 0 -> torch's default eps_fp32 * max(m_rows, n), minimum-norm solution), driver 1 = gels (full rank).

@@ -8,6 +8,7 @@
 #pragma once
 #include <cfloat>
 
+#include "adam_order.hpp"
 #include "kernels.hpp"
 
 namespace symode {
@@ -23,7 +24,7 @@ struct AdamArgs {
     const float* x;
     const float* dx;
     long n_src;
-    const int* idx;                   // (n_epochs, n_idx_problems, n_steps, batch)
+    const int* idx;                   // (n_epochs, n_idx_problems, n_steps, batch), or nullptr: the keyed entries, rows from order_seeds
     long n_idx_problems;
     int n_epochs, n_steps, batch;
     long n_problems;
@@ -49,6 +50,10 @@ struct AdamArgs {
     const float* gen_l;               // (n_gen, d, d)
     int n_gen, d_obs;
     float w_obs, w_sym;               // the weights of mse_x and sym in the value the freezing rule tests
+    // the keyed entries alone (idx == nullptr): no table, n_steps = ceil(n_src / batch)
+    const long long* order_seeds;     // (n_order_seeds): 1 (every problem walks the same order) or n_problems
+    long n_order_seeds;
+    int shuffle;                      // 0: position pos is row pos (the loader with shuffle=False)
 };
 
 // b^n for an integer n >= 0 by squaring: a function of (b, n) alone, so a fit cut into several launches meets the same
@@ -73,6 +78,11 @@ __device__ __forceinline__ double adam_ipow(double b, int n) {
 // constraint, Xi = reshape(Q beta) + const.  Two barriers per step (four under the constraint).
 // The gathers do not depend on the parameters, so they run ahead of the chain of steps: the index of chunk c + 2 and the
 // rows of chunk c + 1 are in flight while chunk c is evaluated, across step and epoch boundaries of the launch.
+// Without a table (a.idx == nullptr, the keyed entries) that index is COMPUTED in the same slot, two chunks ahead: batch
+// slot b of step s in epoch e is position pos = s batch + b, its row adam_order_row(key(order seed, epoch0 + e), n_src, pos)
+// for pos < n_src and the pad -1 beyond (adam_order.hpp).  The branch is uniform over the launch; everything downstream of
+// the index is the same code.  The slot keeps the rows' latency where it was, but with one wave per SIMD the integer
+// arithmetic itself is on the step's path: 0.2-0.3 us per chunk at 125 000 rows (profiles/adam_device_shuffle.txt).
 //
 // REV adds  w_sym * sum_g sum_b |r|^2 / (valid rows * d),  r = J_g(x_b) h(x_b) - h(g x_b),  h = Theta(.) (Xi * mask)^T,  to the
 // loss of every batch.  A valid row gathers gx[g, i, :] and jgx[g, i, :, :] with the row number i of x and dx (padding reads
@@ -145,6 +155,11 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
 
     const int n_chunks = (a.batch + ADAM_BLOCK - 1) / ADAM_BLOCK;
     const long sp = a.n_idx_problems == 1 ? 0 : s;
+    const bool keyed = a.idx == nullptr;
+    unsigned long long seed_w = 0;
+    if (keyed && a.shuffle) seed_w = seed_words((unsigned long long)a.order_seeds[a.n_order_seeds == 1 ? 0 : s]);
+    AdamOrderKey okey{};                                      // the round keys of epoch okey_e: derived once per epoch, not per chunk
+    int okey_e = -1;
     struct Cursor { int e, s, k; };
     auto advance = [&](Cursor& c) __attribute__((always_inline)) {
         if (++c.k == n_chunks) {
@@ -158,7 +173,18 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
     auto fetch_idx = [&](const Cursor& c) __attribute__((always_inline)) {
         const int b = c.k * ADAM_BLOCK + tid;
         int i = -1;
-        if (c.e < a.n_epochs && b < a.batch) i = a.idx[(((long)c.e * a.n_idx_problems + sp) * a.n_steps + c.s) * a.batch + b];
+        if (c.e < a.n_epochs && b < a.batch) {
+            if (!keyed) {
+                i = a.idx[(((long)c.e * a.n_idx_problems + sp) * a.n_steps + c.s) * a.batch + b];
+            } else {
+                const long pos = (long)c.s * a.batch + b;    // n_src < 2^31: a position that is a row fits an int
+                if (a.shuffle && c.e != okey_e) {             // uniform over the workgroup
+                    okey = adam_order_key(seed_w, a.epoch0 + c.e);
+                    okey_e = c.e;
+                }
+                if (pos < a.n_src) i = a.shuffle ? adam_order_row(okey, (int)a.n_src, (int)pos) : (int)pos;
+            }
+        }
         return i;
     };
     auto fetch_row = [&](int i, float (&xr)[D], float (&dr)[D]) __attribute__((always_inline)) {

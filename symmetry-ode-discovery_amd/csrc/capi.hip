@@ -536,6 +536,23 @@ int symode_euler_jvp_vjp(const float* x, const float* v, const float* g_x, const
 
 namespace {
 
+// symode_adam_order_table: the (n_epochs, n_seeds, per) rows the keyed epoch kernels compute in their index slot, per =
+// n_steps * batch positions of which those from n_src on are the pad.  blockIdx.y strides over the (epoch, seed) tables,
+// blockIdx.x over the positions of one.
+__global__ __launch_bounds__(ADAM_BLOCK) void adam_order_table_kernel(int n_src, long per, const long long* __restrict__ seeds,
+                                                                      long n_seeds, int shuffle, int epoch0, long tables,
+                                                                      int* __restrict__ out) {
+    for (long t = blockIdx.y; t < tables; t += gridDim.y) {
+        const long e = t / n_seeds, sp = t % n_seeds;
+        const AdamOrderKey key = adam_order_key(seed_words((unsigned long long)seeds[sp]), epoch0 + (int)e);
+        for (long pos = (long)blockIdx.x * ADAM_BLOCK + threadIdx.x; pos < per; pos += (long)gridDim.x * ADAM_BLOCK) {
+            int i = -1;
+            if (pos < n_src) i = shuffle ? adam_order_row(key, n_src, (int)pos) : (int)pos;
+            out[t * per + pos] = i;
+        }
+    }
+}
+
 // the operands symode_adam_epochs_latent has beyond z, dz
 struct AdamLatent {
     const float *B, *y, *e, *L;
@@ -543,9 +560,17 @@ struct AdamLatent {
     float w_obs, w_sym;
 };
 
+// what the keyed entries take in place of (idx, n_idx_problems, n_steps)
+struct AdamOrder {
+    const long long* seeds;
+    long n_seeds;
+    int shuffle;
+};
+
 // symode_adam_epochs (gx_, jgx null, n_g 0, kind ADAM_PLAIN), symode_adam_epochs_reversed and symode_adam_epochs_latent (lat
-// set; x, dx are z, dz and w_x is w_z): one set of argument checks
-int adam_epochs(AdamKind kind, const AdamLatent* lat, const float* x, const float* dx, const float* gx_, const float* jgx, int n_g,
+// set; x, dx are z, dz and w_x is w_z): one set of argument checks.  The keyed entries pass ord (idx null, n_idx_problems and
+// n_steps unused: the order seeds take the table's place and n_steps is ceil(n_src / batch)).
+int adam_epochs(AdamKind kind, const AdamLatent* lat, const AdamOrder* ord, const float* x, const float* dx, const float* gx_, const float* jgx, int n_g,
                 long n_src, const int* idx, long n_idx_problems, int n_epochs, int n_steps, int batch, long n_problems, int d,
                 int order, int flags, const float* q_eff, int r, int allow_constant, int n_params, float lr, float beta1,
                 float beta2, float eps, float w_x, float w_reg, float w_sym, int l1, float threshold, int st_freq, int epoch0,
@@ -559,13 +584,18 @@ int adam_epochs(AdamKind kind, const AdamLatent* lat, const float* x, const floa
     // latent: the same for w_sym / w_z, and without w_z no data term reaches the coefficients at all (mse_x has no gradient)
     if (lat && (!(w_x > 0.0f) || lat->d_obs < d || (!lat->e && lat->d_obs > d) || (!lat->L && lat->n_gen > 0)))
         return SYMODE_E_BADSIZE;
+    if (ord) {
+        if (n_src < 1 || n_src > 2147483647L || batch < 1) return SYMODE_E_BADSIZE;
+        n_idx_problems = ord->n_seeds;
+        n_steps = (int)((n_src + batch - 1) / batch);
+    }
     if (n_problems > 2147483647L || n_src < 1 || n_src > 2147483647L || n_steps < 1 || batch < 1 || epoch0 < 0)
         return SYMODE_E_BADSIZE;
     if (n_idx_problems != 1 && n_idx_problems != n_problems) return SYMODE_E_BADSIZE;
     // thread j of the problem's workgroup owns parameter j: [beta | const] under the constraint, Xi without
     if (q_eff ? (r < 1 || n_params != r + d) : (n_params != d * ops->p)) return SYMODE_E_BADSIZE;
     if (n_params > ADAM_BLOCK || d * ops->p > ADAM_BLOCK) return SYMODE_E_BADSIZE;
-    if (!x || !dx || !idx || !params || !m || !v || !step || !mask || !xi_out || !log) return SYMODE_E_NULLPTR;
+    if (!x || !dx || (ord ? !ord->seeds : !idx) || !params || !m || !v || !step || !mask || !xi_out || !log) return SYMODE_E_NULLPTR;
     if (n_g > 0 && (!gx_ || !jgx)) return SYMODE_E_NULLPTR;
     if (lat && (!lat->B || !lat->y)) return SYMODE_E_NULLPTR;
     if (misaligned(x, 4) || misaligned(dx, 4) || misaligned(idx, 4) || misaligned(q_eff, 4) || misaligned(params, 4) ||
@@ -575,10 +605,16 @@ int adam_epochs(AdamKind kind, const AdamLatent* lat, const float* x, const floa
     if (lat && (misaligned(lat->B, 4) || misaligned(lat->y, 4) || (lat->d_obs > d && misaligned(lat->e, 4)) ||
                 (lat->n_gen > 0 && misaligned(lat->L, 4))))
         return SYMODE_E_ALIGN;
-    AdamArgs a{x, dx, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, q_eff, q_eff ? r : 0,
+    if (ord && misaligned(ord->seeds, 8)) return SYMODE_E_ALIGN;
+    AdamArgs a{x, dx, n_src, ord ? nullptr : idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, q_eff, q_eff ? r : 0,
                allow_constant != 0, n_params, lr, beta1, beta2, eps, w_x, w_reg, l1, threshold, st_freq, epoch0,
                near_band, params, m, v, step, mask, xi_out, log, n_g > 0 ? gx_ : nullptr, n_g > 0 ? jgx : nullptr, n_g,
                n_g > 0 ? w_sym / w_x : 0.0f};
+    if (ord) {
+        a.order_seeds = ord->seeds;
+        a.n_order_seeds = ord->n_seeds;
+        a.shuffle = ord->shuffle != 0;
+    }
     if (lat) {
         a.lat_b = lat->B;
         a.lat_y = lat->y;
@@ -603,7 +639,7 @@ int symode_adam_epochs(const float* x, const float* dx, long n_src, const int* i
                        int allow_constant, int n_params, float lr, float beta1, float beta2, float eps, float w_x, float w_reg,
                        int l1, float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
                        int* step, float* mask, float* xi_out, float* log, void* stream) {
-    return adam_epochs(ADAM_PLAIN, nullptr, x, dx, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d,
+    return adam_epochs(ADAM_PLAIN, nullptr, nullptr, x, dx, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d,
                        order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, 0.0f, l1, threshold,
                        st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
 }
@@ -614,7 +650,7 @@ int symode_adam_epochs_reversed(const float* x, const float* dx, const float* gx
                                 float lr, float beta1, float beta2, float eps, float w_x, float w_reg, float w_sym, int l1,
                                 float threshold, int st_freq, int epoch0, float near_band, float* params, float* m, float* v,
                                 int* step, float* mask, float* xi_out, float* log, void* stream) {
-    return adam_epochs(ADAM_REVERSED, nullptr, x, dx, gx, jgx, n_g, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d, order,
+    return adam_epochs(ADAM_REVERSED, nullptr, nullptr, x, dx, gx, jgx, n_g, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d, order,
                        flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, w_sym, l1, threshold,
                        st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
 }
@@ -627,9 +663,64 @@ int symode_adam_epochs_latent(const float* z, const float* dz, const float* B, c
                               float near_band, float* params, float* m, float* v, int* step, float* mask, float* xi_out,
                               float* log, void* stream) {
     const AdamLatent lat{B, y, e, L, D_obs, n_gen, w_x, w_sym};
-    return adam_epochs(ADAM_LATENT, &lat, z, dz, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch,
+    return adam_epochs(ADAM_LATENT, &lat, nullptr, z, dz, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch,
                        n_problems, d, order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_z, w_reg, 0.0f, l1,
                        threshold, st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+}
+
+int symode_adam_epochs_keyed(const float* x, const float* dx, long n_src, const long long* order_seeds, long n_order_seeds,
+                             int shuffle, int n_epochs, int batch, long n_problems, int d, int order, int flags,
+                             const float* q_eff, int r, int allow_constant, int n_params, float lr, float beta1, float beta2,
+                             float eps, float w_x, float w_reg, int l1, float threshold, int st_freq, int epoch0,
+                             float near_band, float* params, float* m, float* v, int* step, float* mask, float* xi_out,
+                             float* log, void* stream) {
+    const AdamOrder ord{order_seeds, n_order_seeds, shuffle};
+    return adam_epochs(ADAM_PLAIN, nullptr, &ord, x, dx, nullptr, nullptr, 0, n_src, nullptr, 0, n_epochs, 0, batch, n_problems, d,
+                       order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, 0.0f, l1, threshold,
+                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+}
+
+int symode_adam_epochs_reversed_keyed(const float* x, const float* dx, const float* gx, const float* jgx, int n_g, long n_src,
+                                      const long long* order_seeds, long n_order_seeds, int shuffle, int n_epochs, int batch,
+                                      long n_problems, int d, int order, int flags, const float* q_eff, int r,
+                                      int allow_constant, int n_params, float lr, float beta1, float beta2, float eps,
+                                      float w_x, float w_reg, float w_sym, int l1, float threshold, int st_freq, int epoch0,
+                                      float near_band, float* params, float* m, float* v, int* step, float* mask,
+                                      float* xi_out, float* log, void* stream) {
+    const AdamOrder ord{order_seeds, n_order_seeds, shuffle};
+    return adam_epochs(ADAM_REVERSED, nullptr, &ord, x, dx, gx, jgx, n_g, n_src, nullptr, 0, n_epochs, 0, batch, n_problems, d, order,
+                       flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, w_sym, l1, threshold,
+                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+}
+
+int symode_adam_epochs_latent_keyed(const float* z, const float* dz, const float* B, const float* y, const float* e, int D_obs,
+                                    const float* L, int n_gen, long n_src, const long long* order_seeds, long n_order_seeds,
+                                    int shuffle, int n_epochs, int batch, long n_problems, int d, int order, int flags,
+                                    const float* q_eff, int r, int allow_constant, int n_params, float lr, float beta1,
+                                    float beta2, float eps, float w_z, float w_x, float w_reg, float w_sym, int l1,
+                                    float threshold, int st_freq, int epoch0, float near_band, float* params, float* m,
+                                    float* v, int* step, float* mask, float* xi_out, float* log, void* stream) {
+    const AdamLatent lat{B, y, e, L, D_obs, n_gen, w_x, w_sym};
+    const AdamOrder ord{order_seeds, n_order_seeds, shuffle};
+    return adam_epochs(ADAM_LATENT, &lat, &ord, z, dz, nullptr, nullptr, 0, n_src, nullptr, 0, n_epochs, 0, batch, n_problems, d,
+                       order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_z, w_reg, 0.0f, l1, threshold,
+                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+}
+
+int symode_adam_order_table(long n_src, int batch, const long long* order_seeds, long n_order_seeds, int shuffle, int epoch0,
+                            int n_epochs, int* idx_out, void* stream) {
+    if (n_src < 1 || n_src > 2147483647L || batch < 1 || n_order_seeds < 1 || n_order_seeds > 2147483647L || n_epochs < 0 ||
+        epoch0 < 0)
+        return SYMODE_E_BADSIZE;
+    if (n_epochs == 0) return SYMODE_OK;
+    if (!order_seeds || !idx_out) return SYMODE_E_NULLPTR;
+    if (misaligned(order_seeds, 8) || misaligned(idx_out, 4)) return SYMODE_E_ALIGN;
+    const long per = (n_src + batch - 1) / batch * (long)batch, tables = (long)n_epochs * n_order_seeds;
+    const long bx = (per + ADAM_BLOCK - 1) / ADAM_BLOCK;
+    adam_order_table_kernel<<<dim3((unsigned)(bx < 65535 ? bx : 65535), (unsigned)(tables < 65535 ? tables : 65535)),
+                              dim3(ADAM_BLOCK), 0, (hipStream_t)stream>>>((int)n_src, per, order_seeds, n_order_seeds,
+                                                                          shuffle != 0, epoch0, tables, idx_out);
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

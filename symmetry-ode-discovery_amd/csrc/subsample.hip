@@ -11,34 +11,15 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/symode.h"
+#include "adam_order.hpp"
 
 namespace {
 
 constexpr int SB = 1024;                                  // threads per workgroup: 16 waves
 
-// key(seed, row) = fmix32((row ^ a) * 0x9E3779B1 + b), (a, b) = the two halves of a 64-bit mix of the seed: three 32-bit
-// multiplies per row (the kernel recomputes every key in each of its four passes; a 64-bit mixer per row -- twelve
-// quarter-rate multiplies -- made the hash most of its time: 103 us for 64 seeds of 10^5 rows).  Every step is a bijection
-// of the 32-bit word, so for n <= 2^32 rows no two rows of a seed share a key.
-__device__ __forceinline__ unsigned long long seed_words(unsigned long long seed) {
-    unsigned long long z = seed * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull;
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-__device__ __forceinline__ unsigned subsample_key(unsigned a, unsigned b, unsigned row) {
-    unsigned h = (row ^ a) * 0x9E3779B1u + b;
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    h ^= h >> 16;
-    return h;
-}
+// key(seed, row): seed_words and subsample_key of adam_order.hpp, which the device Adam trainer's epoch order draws from too
+using symode::seed_words;
+using symode::subsample_key;
 
 __global__ __launch_bounds__(SB) void seeded_subsample_kernel(long n, long m, const long long* __restrict__ seeds,
                                                               int* __restrict__ out) {

@@ -9,6 +9,9 @@ symode_adam_epochs_reversed: ``+ w_sym * sum_g mean |J_g(x) h(x) - h(g x)|^2`` p
 The ``--use_latent`` branch under a frozen autoencoder (``latent``, symode_adam_epochs_latent): x, dx are then z, dz, and
 every minibatch loss is ``w_z * mse_z + w_x * mse_x + w_sym * (linear-latent regulariser, not divided by the rows)`` on the
 per-row operands of ``model_utils.latent_operands``; mse_x is logged and added but has no gradient, as in train_SIGED.
+The rows of a step come from an index table built from the caller's shuffles, or -- ``fit(order_seeds=...)``, the device
+shuffle -- from the launch itself, which computes them from (order seed, epoch, position) by ``epoch_order``'s function
+(symode_adam_epochs*_keyed): no table, nothing between two launches, an equivalent draw of the shuffle rather than a replay.
 Not covered (the callers refuse them): the i / f symmetry regularisers (they run the autoencoder on Xi-dependent inputs), a
 latent fit whose autoencoder trains, several ranks.
 """
@@ -30,6 +33,83 @@ LOG_COLUMNS = ('loss_sindy_x', 'loss_sindy_reg', 'steps', 'near', 'nan', 'event'
 LOG_COLUMNS_REVERSED = LOG_COLUMNS + ('loss_sym_reg',)
 # records of a trainer with ``latent``: ten columns, the three loss terms unweighted
 LOG_COLUMNS_LATENT = LOG_COLUMNS + ('loss_sym_reg', 'loss_sindy_z', 'unused')
+
+
+ORDER_ROUNDS = 2          # ADAM_ORDER_ROUNDS of csrc/adam_order.hpp
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _seed_words(seed):
+    """``seed_words`` of csrc/adam_order.hpp: the 64-bit mix of a seed, as (low word, high word)."""
+    m64 = (1 << 64) - 1
+    z = ((int(seed) & m64) * 0x9E3779B97F4A7C15 + 0x632BE59BD9B4E019) & m64
+    z ^= z >> 30
+    z = (z * 0xBF58476D1CE4E5B9) & m64
+    z ^= z >> 27
+    z = (z * 0x94D049BB133111EB) & m64
+    z ^= z >> 31
+    return z & 0xFFFFFFFF, z >> 32
+
+
+def _subsample_key(a, b, row):
+    """``subsample_key``: fmix32((row ^ a) * 0x9E3779B1 + b) on Python integers."""
+    m32 = 0xFFFFFFFF
+    h = (((row ^ a) & m32) * 0x9E3779B1 + b) & m32
+    h ^= h >> 16
+    h = (h * 0x85EBCA6B) & m32
+    h ^= h >> 13
+    h = (h * 0xC2B2AE35) & m32
+    h ^= h >> 16
+    return h
+
+
+def _order_mix(k, half):
+    """``adam_order_mix``: uint64 arrays that hold 32-bit words, every step reduced mod 2^32."""
+    h = (np.uint64(k) + ((half + np.uint64(1)) & np.uint64(0xFFFFFF)) * np.uint64(0x9E3779)) & _M32
+    for down, up in ((15, 3), (11, 7), (13, 5)):
+        h ^= h >> np.uint64(down)
+        h = (h + (h << np.uint64(up))) & _M32
+    h ^= h >> np.uint64(16)
+    return h
+
+
+def epoch_order(seed, epoch, n, rounds=ORDER_ROUNDS):
+    """The row order of epoch ``epoch`` (the GLOBAL epoch number of the fit) under order seed ``seed``: a permutation of
+    range(n) as int32, entry for entry what ``adam_order_row`` (csrc/adam_order.hpp) computes inside the keyed epoch
+    launches.  A function of (seed, epoch, n) alone.  ``rounds`` is for the uniformity study only; the kernels use
+    ORDER_ROUNDS.
+
+    n == 1: the identity.  Otherwise bits = ceil(log2 n), and a position is a word (hi | lo) of ``bits`` bits whose low part
+    has lb bits.  Round r = 0 .. ORDER_ROUNDS - 1 maps
+        (hi | lo) -> (lo | (hi ^ F(k_r, lo)) mod 2^(bits - lb)),   lb <- bits - lb,
+    starting from lb = bits - bits // 2 (an alternating unbalanced Feistel network, a bijection of [0, 2^bits), 2^bits < 2 n).
+    Round key k_r = subsample_key(a, b, (epoch * ORDER_ROUNDS + r) mod 2^32), (a, b) the low and high word of
+    seed_words(seed).  F(k, lo), all mod 2^32:
+        h = k + (lo + 1) * 0x9E3779          (lo < 2^16: a 24-bit multiply)
+        h ^= h >> 15;  h += h << 3;  h ^= h >> 11;  h += h << 7;  h ^= h >> 13;  h += h << 5;  h ^= h >> 16
+    The network is applied again to every value that is still >= n (cycle walking): the walk follows the cycle of a
+    permutation that started below n, so it ends."""
+    n = int(n)
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f'n must be in [1, 2^31), got {n}')
+    if n == 1:
+        return np.zeros(1, dtype=np.int32)
+    a, b = _seed_words(seed)
+    keys = [_subsample_key(a, b, (int(epoch) * rounds + r) & 0xFFFFFFFF) for r in range(rounds)]
+    bits = (n - 1).bit_length()
+    x = np.arange(n, dtype=np.uint64)
+    walk = np.arange(n)                                   # the entries still on their walk
+    while walk.size:
+        y = x[walk]
+        lb = bits - bits // 2
+        for k in keys:
+            hb = bits - lb
+            lo, hi = y & np.uint64((1 << lb) - 1), y >> np.uint64(lb)
+            y = (lo << np.uint64(hb)) | ((hi ^ _order_mix(k, lo)) & np.uint64((1 << hb) - 1))
+            lb = hb
+        x[walk] = y
+        walk = walk[y >= n]
+    return x.astype(np.int32)
 
 
 class DeviceAdam:
@@ -110,10 +190,15 @@ class DeviceAdam:
             t = torch.cat([t, torch.full((t.shape[0], pad), -1, dtype=torch.int32, device=t.device)], dim=1)
         return t.view(t.shape[0], self.steps, self.batch)
 
-    def fit(self, params0, n_epochs, orders, mask0=None, on_epoch=None, epochs_per_launch=16, boundary=None, epoch0=0,
-            state=None):
+    def fit(self, params0, n_epochs, orders=None, mask0=None, on_epoch=None, epochs_per_launch=16, boundary=None, epoch0=0,
+            state=None, order_seeds=None, shuffle=True):
         """``params0`` (S, n_params); ``orders`` yields one (S or 1, n) integer permutation on the device per epoch, drawn
-        in epoch order.  ``on_epoch(epoch, record)`` is called for every epoch after its launch was read back, with that
+        in epoch order.  ``order_seeds`` (1 or S integers, with ``orders`` None) is the device shuffle instead: no table is
+        built and nothing is drawn, epoch e of problem s walks ``epoch_order(order_seeds[s or 0], e, n)`` -- e the global epoch
+        number, so ``epoch0`` continues a fit and the cut into launches (``epochs_per_launch`` and ``boundary`` alone,
+        TABLE_BYTES does not apply) changes no result -- computed inside the launch (symode_adam_epochs*_keyed);
+        ``shuffle=False`` walks the rows in order.  It is an equivalent draw, not a replay of a torch generator.
+        ``on_epoch(epoch, record)`` is called for every epoch after its launch was read back, with that
         epoch's own record: the LOG_COLUMNS (with ``reversed_sym``: LOG_COLUMNS_REVERSED, with ``latent``: LOG_COLUMNS_LATENT) as (S,) numpy arrays, and ``record['state']`` = {params, mask, Xi} (device
         tensors, valid until the next launch) when the epoch is the last of its launch, else None.  ``boundary(epoch)``
         true ends the launch after that epoch (a caller that needs the state there).  ``state``: (m, v, step) of an
@@ -131,24 +216,35 @@ class DeviceAdam:
         else:
             m, v, step = (t.detach().to(dev).clone().contiguous() for t in state)
         xi = self.coef.xi(*self.coef.split(params)).reshape(S, self.d, self.coef.p) if n_epochs == 0 else None
-        orders = iter(orders)
+        if (orders is None) == (order_seeds is None):
+            raise ValueError('give the epoch orders or order_seeds (the device shuffle), one of them')
+        if order_seeds is not None:
+            order_seeds = self.engine._order_seeds(order_seeds, dev)
+            if order_seeds.numel() not in (1, S):
+                raise ValueError(f'order_seeds must hold 1 or {S} seeds, got {order_seeds.numel()}')
+        else:
+            orders = iter(orders)
         logs = []
         done = 0
         while done < n_epochs:
             tables = []
             while done + len(tables) < n_epochs:
-                t = self.table(next(orders))
-                if t.shape[0] not in (1, S) or (tables and t.shape[0] != tables[0].shape[0]):
+                t = None if orders is None else self.table(next(orders))
+                if t is not None and (t.shape[0] not in (1, S) or (tables and t.shape[0] != tables[0].shape[0])):
                     raise ValueError(f'an epoch order must have 1 or {S} rows, all epochs alike; got {t.shape[0]}')
                 tables.append(t)
                 epoch = epoch0 + done + len(tables) - 1
-                full = len(tables) >= max(1, int(epochs_per_launch)) or (len(tables) + 1) * t.numel() * 4 > TABLE_BYTES
+                full = len(tables) >= max(1, int(epochs_per_launch)) or (
+                    t is not None and (len(tables) + 1) * t.numel() * 4 > TABLE_BYTES)
                 if full or (boundary is not None and boundary(epoch)):
                     break
-            idx = torch.stack(tables).contiguous()
+            if orders is None:
+                idx, keyed = None, dict(_keyed=(order_seeds, len(tables), self.batch, shuffle))
+            else:
+                idx, keyed = torch.stack(tables).contiguous(), {}
             kw = dict(lr=self.lr, betas=self.betas, eps=self.eps, w_x=self.w_x, w_reg=self.w_reg, l1=True,
                       threshold=self.threshold, st_freq=self.st_freq, epoch0=epoch0 + done, near_band=NEAR_THRESHOLD_BAND,
-                      q_eff=self.q_eff, allow_constant=self.coef.allow_constant)
+                      q_eff=self.q_eff, allow_constant=self.coef.allow_constant, **keyed)
             if self.latent is not None:
                 B, y, e, D_obs, L, w_z, w_sym = self.latent
                 xi, log = self.engine.adam_epochs_latent(self.x, self.dx, B, y, e, D_obs, L, idx, params, m, v, step, mask,

@@ -101,6 +101,17 @@ _SIGNATURES = {
     "symode_adam_epochs_latent": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_long, c_void_p, c_long, c_int, c_int, c_int,
                                           c_long, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int] + [c_float] * 8
                                   + [c_int, c_float, c_int, c_int, c_float] + [c_void_p] * 8),
+    # the keyed siblings: (idx, n_idx_problems, n_epochs, n_steps, batch) -> (order_seeds, n_order_seeds, shuffle, n_epochs, batch)
+    "symode_adam_epochs_keyed": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_long, c_int, c_int,
+                                         c_int, c_void_p, c_int, c_int, c_int] + [c_float] * 6
+                                 + [c_int, c_float, c_int, c_int, c_float] + [c_void_p] * 8),
+    "symode_adam_epochs_reversed_keyed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_long, c_int,
+                                                  c_int, c_int, c_long, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int]
+                                          + [c_float] * 7 + [c_int, c_float, c_int, c_int, c_float] + [c_void_p] * 8),
+    "symode_adam_epochs_latent_keyed": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_int, c_long, c_void_p, c_long, c_int, c_int,
+                                                c_int, c_long, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int]
+                                        + [c_float] * 8 + [c_int, c_float, c_int, c_int, c_float] + [c_void_p] * 8),
+    "symode_adam_order_table": (c_int, [c_long, c_int, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
     "symode_host_stlsq_sweep": (c_int, [c_void_p, c_int, c_int, c_int, c_long, ctypes.c_double, ctypes.c_double, c_int, c_int,
                                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
@@ -290,7 +301,7 @@ class HipEngine:
 
     def adam_epochs(self, x, dx, idx, params, m, v, step, mask, order, flags=0, *, lr, betas=(0.9, 0.999), eps=1e-8, w_x=1.0,
                     w_reg=0.0, l1=True, threshold=0.0, st_freq=0, epoch0=0, near_band=1e-4, q_eff=None, allow_constant=True,
-                    _reversed=None, _latent=None):
+                    _reversed=None, _latent=None, _keyed=None):
         """``idx.shape[0]`` whole epochs of minibatch Adam steps for S problems in ONE launch (symode_adam_epochs).
         x, dx (n_src, d) fp32; idx (n_epochs, S or 1, n_steps, batch) int32 row numbers; params, m, v (S, n_params) fp32,
         step (S,) int32 and mask (S, d, p) fp32 are the state, UPDATED IN PLACE (so they must be contiguous); q_eff
@@ -303,9 +314,17 @@ class HipEngine:
             raise SymodeError(f"x and dx must both be (n_src, d), got {tuple(x.shape)} and {tuple(dx.shape)}")
         n_src, d = x.shape
         p = self.lib_size(d, order, flags)
-        if not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 4 or not idx.is_contiguous():
+        seeds = None
+        if _keyed is not None:                               # the *_keyed entries: no table, see adam_epochs_keyed
+            if idx is not None:
+                raise SymodeError("a keyed launch takes order seeds in place of idx, not both")
+            seeds, n_epochs, batch, shuffle = _keyed
+            seeds, n_epochs, batch = self._order_seeds(seeds, x.device), int(n_epochs), int(batch)
+            if n_epochs < 0 or batch < 1:
+                raise SymodeError(f"a keyed launch needs n_epochs >= 0 and batch >= 1, got {n_epochs} and {batch}")
+        elif not isinstance(idx, torch.Tensor) or not idx.is_cuda or idx.dtype != torch.int32 or idx.dim() != 4 or not idx.is_contiguous():
             raise SymodeError("idx must be a contiguous (n_epochs, S or 1, n_steps, batch) int32 CUDA/HIP tensor")
-        for name, t in (("dx", dx), ("idx", idx), ("params", params), ("m", m), ("v", v), ("step", step), ("mask", mask), ("q_eff", q_eff)):
+        for name, t in (("dx", dx), ("idx", idx), ("order_seeds", seeds), ("params", params), ("m", m), ("v", v), ("step", step), ("mask", mask), ("q_eff", q_eff)):
             if isinstance(t, torch.Tensor) and t.device != x.device:
                 raise SymodeError(f"{name} is on {t.device}, x on {x.device}: all tensors of one launch live on one device")
         state = {"params": params, "m": m, "v": v, "mask": mask}
@@ -321,9 +340,15 @@ class HipEngine:
             raise SymodeError(f"step must be ({S},), got {tuple(step.shape)}")
         if mask.numel() != S * d * p:
             raise SymodeError(f"mask has {mask.numel()} elements, expected {S}x{d}x{p}")
-        n_epochs, n_tab, n_steps, batch = idx.shape
-        if n_tab not in (1, S):
-            raise SymodeError(f"idx holds {n_tab} tables, expected 1 or {S}")
+        if seeds is None:
+            n_epochs, n_tab, n_steps, batch = idx.shape
+            if n_tab not in (1, S):
+                raise SymodeError(f"idx holds {n_tab} tables, expected 1 or {S}")
+            suffix, table = "", (self._ptr(idx), n_tab, n_epochs, n_steps, batch)
+        else:
+            if seeds.numel() not in (1, S):
+                raise SymodeError(f"order_seeds holds {seeds.numel()} seeds, expected 1 or {S}")
+            suffix, table = "_keyed", (self._ptr(seeds), seeds.numel(), int(bool(shuffle)), n_epochs, batch)
         r = 0
         if q_eff is not None:
             q_eff = self._dev(q_eff, "q_eff")
@@ -336,30 +361,77 @@ class HipEngine:
         log = torch.empty(n_epochs, S, 10 if _latent is not None else 8, dtype=torch.float32, device=x.device)
         if _latent is not None:
             B, y, e, D_obs, L, n_gen, w_z, w_sym = _latent
-            self._check(self.lib.symode_adam_epochs_latent(
+            self._check(getattr(self.lib, "symode_adam_epochs_latent" + suffix)(
                 self._ptr(x), self._ptr(dx), self._ptr(B), self._ptr(y), self._ptr(e), D_obs, self._ptr(L), n_gen, n_src,
-                self._ptr(idx), n_tab, n_epochs, n_steps, batch, S, d, order, flags, self._ptr(q_eff), r,
+                *table, S, d, order, flags, self._ptr(q_eff), r,
                 int(bool(allow_constant)), n_params, float(lr), float(betas[0]), float(betas[1]), float(eps), float(w_z),
                 float(w_x), float(w_reg), float(w_sym), int(bool(l1)), float(threshold), int(st_freq), int(epoch0),
                 float(near_band), self._ptr(params), self._ptr(m), self._ptr(v), self._ptr(step), self._ptr(mask),
-                self._ptr(xi), self._ptr(log), self._stream(x)), "symode_adam_epochs_latent")
+                self._ptr(xi), self._ptr(log), self._stream(x)), "symode_adam_epochs_latent" + suffix)
             return xi, log
         if _reversed is not None:
             gx, jgx, n_g, w_sym = _reversed
-            self._check(self.lib.symode_adam_epochs_reversed(
-                self._ptr(x), self._ptr(dx), self._ptr(gx), self._ptr(jgx), n_g, n_src, self._ptr(idx), n_tab, n_epochs, n_steps,
-                batch, S, d, order, flags, self._ptr(q_eff), r, int(bool(allow_constant)), n_params, float(lr), float(betas[0]),
+            self._check(getattr(self.lib, "symode_adam_epochs_reversed" + suffix)(
+                self._ptr(x), self._ptr(dx), self._ptr(gx), self._ptr(jgx), n_g, n_src, *table, S, d, order, flags, self._ptr(q_eff), r, int(bool(allow_constant)), n_params, float(lr), float(betas[0]),
                 float(betas[1]), float(eps), float(w_x), float(w_reg), float(w_sym), int(bool(l1)), float(threshold),
                 int(st_freq), int(epoch0), float(near_band), self._ptr(params), self._ptr(m), self._ptr(v), self._ptr(step),
-                self._ptr(mask), self._ptr(xi), self._ptr(log), self._stream(x)), "symode_adam_epochs_reversed")
+                self._ptr(mask), self._ptr(xi), self._ptr(log), self._stream(x)), "symode_adam_epochs_reversed" + suffix)
             return xi, log
-        self._check(self.lib.symode_adam_epochs(
-            self._ptr(x), self._ptr(dx), n_src, self._ptr(idx), n_tab, n_epochs, n_steps, batch, S, d, order, flags,
+        self._check(getattr(self.lib, "symode_adam_epochs" + suffix)(
+            self._ptr(x), self._ptr(dx), n_src, *table, S, d, order, flags,
             self._ptr(q_eff), r, int(bool(allow_constant)), n_params, float(lr), float(betas[0]), float(betas[1]), float(eps),
             float(w_x), float(w_reg), int(bool(l1)), float(threshold), int(st_freq), int(epoch0), float(near_band),
             self._ptr(params), self._ptr(m), self._ptr(v), self._ptr(step), self._ptr(mask), self._ptr(xi), self._ptr(log),
-            self._stream(x)), "symode_adam_epochs")
+            self._stream(x)), "symode_adam_epochs" + suffix)
         return xi, log
+
+    def _order_seeds(self, seeds, device):
+        """Order seeds as the keyed entries read them: a contiguous int64 device tensor (a sequence of Python integers of any
+        size is taken modulo 2^64, as the subsample seeds are)."""
+        if isinstance(seeds, torch.Tensor):
+            if not seeds.is_cuda or seeds.dtype != torch.int64 or seeds.dim() != 1 or not seeds.is_contiguous():
+                raise SymodeError("order_seeds must be a contiguous 1-D int64 CUDA/HIP tensor or a sequence of integers")
+            return seeds
+        words = [((int(s) & 0xFFFFFFFFFFFFFFFF) ^ (1 << 63)) - (1 << 63) for s in seeds]
+        return torch.tensor(words, dtype=torch.int64, device=device)
+
+    def adam_epochs_keyed(self, x, dx, order_seeds, n_epochs, batch, params, m, v, step, mask, order, flags=0, *, shuffle=True,
+                          **kw):
+        """``adam_epochs`` without an index table (symode_adam_epochs_keyed): batch slot b of step s in epoch e reads the row
+        at position s * batch + b of the order ``device_adam.epoch_order(order seed, epoch0 + e, n_src)``, computed inside
+        the launch (``shuffle=False``: the row is the position).  ``order_seeds``: one integer (every problem walks the
+        same order) or S of them, a sequence or an int64 device tensor.  The other arguments and the return value are those
+        of ``adam_epochs``; the state it leaves is, bit for bit, that of ``adam_epochs`` on ``adam_order_table``."""
+        return self.adam_epochs(x, dx, None, params, m, v, step, mask, order, flags,
+                                _keyed=(order_seeds, n_epochs, batch, shuffle), **kw)
+
+    def adam_epochs_reversed_keyed(self, x, dx, gx, jgx, order_seeds, n_epochs, batch, params, m, v, step, mask, order, flags=0,
+                                   *, shuffle=True, **kw):
+        """``adam_epochs_reversed`` on the computed order of ``adam_epochs_keyed`` (symode_adam_epochs_reversed_keyed)."""
+        return self.adam_epochs_reversed(x, dx, gx, jgx, None, params, m, v, step, mask, order, flags,
+                                         _keyed=(order_seeds, n_epochs, batch, shuffle), **kw)
+
+    def adam_epochs_latent_keyed(self, z, dz, B, y, e, D_obs, L, order_seeds, n_epochs, batch, params, m, v, step, mask, order,
+                                 flags=0, *, shuffle=True, **kw):
+        """``adam_epochs_latent`` on the computed order of ``adam_epochs_keyed`` (symode_adam_epochs_latent_keyed)."""
+        return self.adam_epochs_latent(z, dz, B, y, e, D_obs, L, None, params, m, v, step, mask, order, flags,
+                                       _keyed=(order_seeds, n_epochs, batch, shuffle), **kw)
+
+    def adam_order_table(self, n_src, batch, order_seeds, n_epochs, epoch0=0, shuffle=True, device=None):
+        """The (n_epochs, len(order_seeds), ceil(n_src / batch), batch) int32 table the keyed launches walk, written by the
+        device function they use (symode_adam_order_table): rows of epochs epoch0 .. epoch0 + n_epochs - 1, -1 beyond
+        n_src.  ``device``: where a sequence of seeds goes (default: the current device)."""
+        seeds = self._order_seeds(order_seeds, torch.device('cuda', torch.cuda.current_device()) if device is None else device)
+        n_src, batch, n_epochs = int(n_src), int(batch), int(n_epochs)
+        if n_src < 1 or batch < 1 or n_epochs < 0 or seeds.numel() < 1:
+            raise SymodeError(f"adam_order_table needs n_src >= 1, batch >= 1, n_epochs >= 0 and a seed, got {n_src}, {batch}, "
+                              f"{n_epochs}, {seeds.numel()}")
+        idx = torch.empty(n_epochs, seeds.numel(), (n_src + batch - 1) // batch, batch, dtype=torch.int32, device=seeds.device)
+        with torch.cuda.device(seeds.device):
+            self._check(self.lib.symode_adam_order_table(n_src, batch, self._ptr(seeds), seeds.numel(), int(bool(shuffle)),
+                                                         int(epoch0), n_epochs, self._ptr(idx), self._stream(seeds)),
+                        "symode_adam_order_table")
+        return idx
 
     def adam_epochs_reversed(self, x, dx, gx, jgx, idx, params, m, v, step, mask, order, flags=0, *, w_sym, **kw):
         """``adam_epochs`` with the reversed symmetry regulariser in every minibatch loss (symode_adam_epochs_reversed):

@@ -34,6 +34,9 @@ def main(argv=None, backend='nccl', one_gpu=False):
     rehearsal with every rank on cuda:0 (tests)."""
     args = get_args(argv=argv)
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
+    if args.device_shuffle and not (args.device_adam and args.sindy_optimizer == 'adam' and not args.mt_data):
+        raise SystemExit('--device_shuffle draws the epoch order of the device Adam fit inside its launch: it needs '
+                         '--device_adam with --sindy_optimizer adam')
     T.wandb.init(project='anonym', entity='anonym', name=args.wandb_name, config=args)
     seed = args.seed
     torch.manual_seed(seed)

@@ -8,6 +8,7 @@
     python -m symode_amd.main_sweep --config dosc/noise20_sindy.cfg --n_seeds 50 --eval_ltp --ltp_bound_rel 0.1
     python -m symode_amd.main_sweep --config lv/noise99_eq_rsymreg.cfg --n_seeds 50 [--gram_closure]
     python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --batch_size 256 --num_epochs 1000 --n_seeds 64
+    python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --device_shuffle --batch_size 256 --n_seeds 64
 
 plan:   ``_refusal`` decides from the arguments alone whether the sweep runs, before a process group, a data file or a
         device is touched; what it refuses it answers with the per-seed command to run instead.
@@ -23,7 +24,10 @@ decisions.
 A sweep's seed n does NOT reproduce ``python -m symode_amd.main --seed n`` row for row: the sweep draws each seed's
 subsample with the counter hash (seeded_subsamples) -- under Adam each seed's shuffles from its own generator, where main
 shuffles with the global one after drawing the model -- and its initial coefficients from its own torch.Generator(seed), as
-the plain sweep always has; the success rate over seeds is what the two estimate alike.
+the plain sweep always has; the success rate over seeds is what the two estimate alike.  Under ``--device_shuffle`` the
+Adam sweep draws no shuffle at all: every epoch launch computes its rows from (seed, epoch) (device_adam.epoch_order), so
+the rows of a step differ from the tensor-op shuffle's as well -- an equivalent draw, not a replay -- and nothing runs on
+the host or the device between two launches.
 """
 from __future__ import annotations
 
@@ -103,6 +107,9 @@ def _refusal(args, method='lbfgs', world=1, engine=None):
         return '--method stlsq sweeps the plain least-squares fit (use --method lbfgs with the symmetry regulariser)'
     if method == 'stlsq' and args.get('eq_constraint'):
         return '--method stlsq sweeps the unconstrained library (use --method lbfgs for EquivSINDy-c)'
+    if args.get('device_shuffle') and (method == 'stlsq' or not adam):
+        return ('--device_shuffle draws the epoch order of the minibatch Adam fit inside its launch: it needs '
+                '--sindy_optimizer adam (with the default --method lbfgs), L-BFGS and STLSQ fits have no epoch order')
     return None
 
 
@@ -191,7 +198,9 @@ def _fit_adam(ctx):
     """--sindy_optimizer adam: the minibatch Adam fit of train_SIGED's plain branch on device_adam.DeviceAdam, one workgroup
     per seed, whole epochs per launch.  Every epoch of every seed is a pass over the WHOLE data set in batches of
     --batch_size (--lbfgs_subsample does not apply, as in main.py); seed s shuffles with its own device generator seeded
-    with s, so a seed's fit depends on the seed alone, not on --n_seeds or --seed."""
+    with s, so a seed's fit depends on the seed alone, not on --n_seeds or --seed.  --device_shuffle: no generator, no keys
+    and no argsort -- seed s is the order seed of problem s, the launch computes every row (DeviceAdam.fit(order_seeds=...));
+    the fit is still a function of s alone, with other rows per step than the generator's shuffle gives."""
     from .device_adam import DeviceAdam
     args, dev, seeds = ctx.args, ctx.dev, ctx.seeds
     template, P0, _ = _template(ctx)
@@ -199,6 +208,9 @@ def _fit_adam(ctx):
     n_all, n_seeds = ctx.x_all.shape[0], len(seeds)
     trainer = DeviceAdam(ctx.x_all, ctx.dx_all, *lib, template.coef, args['lr_sindy'], args['w_sindy_x'], args['w_sindy_reg'],
                          args['threshold'], args['st_freq'], args['batch_size'], engine=ctx.engine)
+    if args.get('device_shuffle'):
+        out = trainer.fit(P0, args['num_epochs'], order_seeds=seeds)
+        return _adam_result(out, trainer, args, seeds, lib)
     gens = [torch.Generator(device=dev).manual_seed(s) for s in seeds]
     keys = torch.empty(n_seeds, n_all, device=dev)
 
@@ -208,7 +220,11 @@ def _fit_adam(ctx):
                 torch.rand(n_all, generator=g, out=keys[k])
             yield torch.argsort(keys, dim=1, stable=True)
 
-    out = trainer.fit(P0, args['num_epochs'], orders())
+    return _adam_result(trainer.fit(P0, args['num_epochs'], orders()), trainer, args, seeds, lib)
+
+
+def _adam_result(out, trainer, args, seeds, lib):
+    n_seeds = len(seeds)
     near = out['log'][:, :, 3].sum(axis=0) if len(out['log']) else np.zeros(n_seeds)
     lines = [f'{n_seeds} seeds, {args["num_epochs"]} epochs x {trainer.steps} Adam steps of {trainer.batch} rows, '
              f'NaN {int(out["nan"].sum())}, '

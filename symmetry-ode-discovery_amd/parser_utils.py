@@ -63,10 +63,14 @@ _MAIN_ARGS = [
 # per evaluation (gram_closure.py).  --device_adam runs the minibatch Adam fit (--sindy_optimizer adam; the plain branch with
 # a symmetry regulariser only as --sym_reg_type r with --fix_laligan; with --use_latent the latent branch under a frozen
 # autoencoder and w_sindy_z > 0, its linear-latent regulariser included) as whole epochs per launch on the device
-# (device_adam.py) instead of one Python iteration per batch.
+# (device_adam.py) instead of one Python iteration per batch.  --device_shuffle (with --device_adam in main, with
+# --sindy_optimizer adam in main_sweep) has those launches compute every epoch's row order from (seed, epoch) themselves
+# (device_adam.epoch_order) instead of reading shuffles drawn with tensor ops between the launches: an equivalent draw, not
+# a replay -- the rows of a step differ from the tensor-op loop's.
 # --fused_latent (with --use_latent and the L-BFGS optimiser; ignored without --use_latent) runs the latent fit with one fused
 # closure kernel and the device trainer (train._train_latent_on_device) instead of autograd through the autoencoder per closure.
-_EXTRA_ARGS = [("gram_closure", _FLAG, None), ("device_adam", _FLAG, None), ("fused_latent", _FLAG, None)]
+_EXTRA_ARGS = [("gram_closure", _FLAG, None), ("device_adam", _FLAG, None), ("fused_latent", _FLAG, None),
+               ("device_shuffle", _FLAG, None)]
 
 # parser_utils.py:122-171
 _SINDY_ARGS = [

@@ -760,11 +760,19 @@ def _test_loss_line(epoch, regressor, test_loader, device):
     return out
 
 
+def _epoch_orders(train_loader, num_epochs, order_seed):
+    """How DeviceAdam.fit gets its rows: the loader's own shuffles as one table per epoch, or the order seed alone."""
+    if order_seed is not None:
+        return dict(order_seeds=[int(order_seed)], shuffle=train_loader.shuffle)
+    return dict(orders=(train_loader.epoch_order()[None] for _ in range(num_epochs)))
+
+
 def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir, regressor,
                           use_latent, lr_sindy, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg, st_freq, threshold,
-                          print_eq, sym_reg_type=None, autoencoder=None, generator=None, w_sindy_z=0.0):
+                          print_eq, sym_reg_type=None, autoencoder=None, generator=None, w_sindy_z=0.0, order_seed=None):
     """train_SIGED's plain branch on DeviceAdam: the same shuffles (one ``randperm`` per epoch from the global generator, as
-    the loader draws them), prints, wandb records, test loss and checkpoints at the same epochs, produced from the
+    the loader draws them; with ``order_seed`` -- --device_shuffle -- none is drawn: the launch computes epoch e's rows from
+    (order_seed, e), device_adam.epoch_order, an equivalent draw with other rows per step, not a replay), prints, wandb records, test loss and checkpoints at the same epochs, produced from the
     launch's log and from the state adopted into the regressor at those epochs and at the end.  ``w_sym_reg > 0`` with
     ``sym_reg_type 'r'`` and a frozen autoencoder and generator adds ``w_sym_reg * symmreg_r`` to every minibatch loss:
     g(x), J_g(x) are computed once over the loader's rows.
@@ -773,7 +781,7 @@ def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_int
     if use_latent:
         return _train_adam_latent_on_device(train_loader, num_epochs, log_interval, save_interval, save_dir, regressor, lr_sindy,
                                             w_sindy_z, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg, st_freq, threshold,
-                                            print_eq, autoencoder, generator)
+                                            print_eq, autoencoder, generator, order_seed)
     if w_sym_reg < 0:
         raise ValueError(f'w_sym_reg is {w_sym_reg}: a weight is not negative')
     sym = w_sym_reg > 0
@@ -815,7 +823,7 @@ def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_int
                test=partial(_test_loss_line, regressor=regressor, test_loader=test_loader, device=device))
 
     regressor.train()
-    out = trainer.fit(coef.pack(regressor)[None], num_epochs, (train_loader.epoch_order()[None] for _ in range(num_epochs)),
+    out = trainer.fit(coef.pack(regressor)[None], num_epochs, **_epoch_orders(train_loader, num_epochs, order_seed),
                       mask0=regressor.mask[None], on_epoch=on_epoch,
                       boundary=lambda epoch: any(_at(epoch, every) for every in (log_interval, save_interval, st_freq)))
     coef.adopt(regressor, out['params'][0], out['mask'][0])
@@ -823,7 +831,7 @@ def _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_int
 
 def _train_adam_latent_on_device(train_loader, num_epochs, log_interval, save_interval, save_dir, regressor, lr_sindy, w_sindy_z,
                                  w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg, st_freq, threshold, print_eq, autoencoder,
-                                 generator):
+                                 generator, order_seed=None):
     """train_SIGED's ``use_latent`` branch on DeviceAdam(latent=...): the optimiser steps the SINDy coefficients alone, so the
     autoencoder is data -- z, dz, the QR-reduced decoder Jacobian and the per-row constant of loss_sindy_x are computed once
     over the loader's rows (model_utils.latent_operands), the generators are read once, and every epoch is part of one
@@ -882,7 +890,7 @@ def _train_adam_latent_on_device(train_loader, num_epochs, log_interval, save_in
         report(epoch, wandb_log, adopt=partial(coef.adopt, regressor, state['params'][0], state['mask'][0]), test=None)
 
     regressor.train()
-    out = trainer.fit(coef.pack(regressor)[None], num_epochs, (train_loader.epoch_order()[None] for _ in range(num_epochs)),
+    out = trainer.fit(coef.pack(regressor)[None], num_epochs, **_epoch_orders(train_loader, num_epochs, order_seed),
                       mask0=regressor.mask[None], on_epoch=on_epoch,
                       boundary=lambda epoch: any(_at(epoch, every) for every in (log_interval, save_interval, st_freq)))
     coef.adopt(regressor, out['params'][0], out['mask'][0])
@@ -901,12 +909,16 @@ def train_SIGED(
     ``device_adam=True`` (--device_adam): the plain branch runs whole epochs per launch on the device (device_adam.py),
     with ``sym_reg_type='r'`` and a frozen LaLiGAN also under the reversed symmetry regulariser; the ``use_latent`` branch
     runs there too under a frozen autoencoder in eval mode with ``w_sindy_z > 0`` (the linear-latent regulariser included);
-    any other configuration is refused, not silently run the usual way."""
+    any other configuration is refused, not silently run the usual way.  ``device_shuffle=True`` (--device_shuffle, with
+    device_adam only): the epoch launches compute their rows from (``seed``, epoch) instead of reading the loader's shuffles."""
+    if kwargs.get('device_shuffle') and not kwargs.get('device_adam'):
+        raise ValueError('device_shuffle is the epoch order of the device Adam fit: it needs device_adam (--device_adam)')
     if kwargs.get('device_adam'):
         return _train_adam_on_device(train_loader, test_loader, num_epochs, device, log_interval, save_interval, save_dir,
                                      regressor, use_latent, lr_sindy, w_sindy_x, sindy_reg_type, w_sindy_reg, w_sym_reg,
                                      st_freq, threshold, kwargs.get('print_eq'), sym_reg_type=kwargs.get('sym_reg_type'),
-                                     autoencoder=autoencoder, generator=generator, w_sindy_z=w_sindy_z)
+                                     autoencoder=autoencoder, generator=generator, w_sindy_z=w_sindy_z,
+                                     order_seed=kwargs.get('seed', 0) if kwargs.get('device_shuffle') else None)
     optimizer_sindy = torch.optim.Adam(regressor.parameters(), lr=lr_sindy)
     symm_loss = make_symmreg_pttrain(autoencoder, generator)
     report = _EpochReport(regressor, log_interval, save_interval, save_dir, kwargs.get('print_eq'))
