@@ -599,6 +599,82 @@ int symode_adam_epochs_latent_keyed(const float* z, const float* dz, const float
 int symode_adam_order_table(long n_src, int batch, const long long* order_seeds, long n_order_seeds, int shuffle, int epoch0,
                             int n_epochs, int* idx_out, void* stream);
 
+/* The six epoch entries above as ONE descriptor entry, and with it a hyper-parameter grid in one launch: every problem may
+ * have its own learning rate, L1 weight, threshold and regulariser weight.  `kind` names the loss (SYMODE_ADAM_*), exactly
+ * one of idx / order_seeds non-NULL names the order: the table of symode_adam_epochs (idx, n_idx_problems, n_steps) or the
+ * computed order of symode_adam_epochs_keyed (order_seeds, n_order_seeds, shuffle; n_steps is not read).  Every field has
+ * the meaning of the argument of the same name in those entries; under SYMODE_ADAM_LATENT x, dx are z, dz, w_x is the weight
+ * of mse_z (the latent entries' w_z) and w_obs the weight of mse_x (their w_x).  Pointers and counts that belong to another
+ * kind are never read.
+ *   hyper   NULL: the scalars lr, w_reg, threshold, w_sym apply and the entry leaves, bit for bit, what the entry of that
+ *           kind and order leaves.
+ *           else (n_problems, SYMODE_ADAM_HYPER = 4) fp32 row-major on the device, row s = [lr, w_reg, threshold, w_sym] of
+ *           problem s; the four scalar fields are not read.  Workgroup s reads its row once, before its first step, and
+ *           uses it wherever the scalar stands otherwise: the step size, the L1 term of the gradient, the thresholding
+ *           event and its near count, the weight of the regulariser's gradient w_sym / w_x (REVERSED, LATENT: formed on
+ *           the device as one fp32 division, 0 without a group element / generator) and w_sym in the value LATENT's
+ *           freezing rule tests.  PLAIN does not read column 3.  Problem s of the launch leaves, bit for bit, what the
+ *           scalar entry leaves for that problem alone with row s's four values.
+ *           beta1, beta2, eps, w_x, w_obs, l1, st_freq and near_band are launch-wide.
+ * Refused beyond the checks of the entry the descriptor names: J == NULL (SYMODE_E_NULLPTR); kind not one of the three,
+ * idx and order_seeds both NULL or both given (SYMODE_E_BADSIZE; checked before everything else, the nothing-to-do cases
+ * included); hyper not 4-byte aligned (SYMODE_E_ALIGN).
+ * replaces: train.py:491-547 (as symode_adam_epochs and its siblings), per hyper-parameter point: one process
+ * `python main.py --lr_sindy .. --w_sindy_reg .. --threshold .. --w_sym_reg ..` per candidate value. */
+#define SYMODE_ADAM_PLAIN 0    /* symode_adam_epochs / _keyed */
+#define SYMODE_ADAM_REVERSED 1 /* symode_adam_epochs_reversed / _reversed_keyed: gx, jgx, n_g, w_sym */
+#define SYMODE_ADAM_LATENT 2   /* symode_adam_epochs_latent / _latent_keyed: lat_B, lat_y, lat_e, lat_L, D_obs, n_gen, w_obs, w_sym */
+#define SYMODE_ADAM_HYPER 4    /* columns of hyper: lr, w_reg, threshold, w_sym */
+typedef struct symode_adam_job {
+    int kind;                  /* SYMODE_ADAM_* */
+    /* data, read only, shared by all problems */
+    const float* x;            /* (n_src, d); LATENT: z */
+    const float* dx;           /* (n_src, d); LATENT: dz */
+    long n_src;
+    const float* gx;           /* REVERSED: (n_g, n_src, d) */
+    const float* jgx;          /* REVERSED: (n_g, n_src, d, d) */
+    int n_g;
+    int D_obs;                 /* LATENT */
+    const float* lat_B;        /* LATENT: (n_src, d, d) */
+    const float* lat_y;        /* LATENT: (n_src, d) */
+    const float* lat_e;        /* LATENT: (n_src), or NULL with D_obs == d */
+    const float* lat_L;        /* LATENT: (n_gen, d, d), or NULL with n_gen == 0 */
+    int n_gen;
+    /* the order of the rows: the table ... */
+    int n_steps;
+    const int* idx;            /* (n_epochs, n_idx_problems, n_steps, batch) int32, or NULL */
+    long n_idx_problems;       /* 1 or n_problems */
+    /* ... or the order seeds */
+    const long long* order_seeds; /* (n_order_seeds) int64 on the device, or NULL */
+    long n_order_seeds;        /* 1 or n_problems */
+    int shuffle;
+    /* sizes and the coefficient map */
+    int n_epochs, batch;
+    long n_problems;
+    int d, order, flags;
+    const float* q_eff;        /* (d p, r), or NULL (the parameters are Xi) */
+    int r, allow_constant, n_params;
+    /* scalars; lr, w_reg, threshold and w_sym are not read when hyper is given */
+    float lr, beta1, beta2, eps;
+    float w_x;                 /* weight of the term with a gradient: mse, under LATENT mse_z */
+    float w_obs;               /* LATENT: weight of mse_x */
+    float w_reg, w_sym;
+    int l1;
+    float threshold;
+    int st_freq, epoch0;
+    float near_band;
+    /* state (read and written back), Xi after the launch, the epoch records */
+    float* params;             /* (n_problems, n_params) */
+    float* m;
+    float* v;
+    int* step;                 /* (n_problems) */
+    float* mask;               /* (n_problems, d p) */
+    float* xi_out;             /* (n_problems, d p) */
+    float* log;                /* (n_epochs, n_problems, 8; LATENT: SYMODE_ADAM_LOG_LATENT) */
+    const float* hyper;        /* (n_problems, SYMODE_ADAM_HYPER), or NULL */
+} symode_adam_job;
+int symode_adam_run(const symode_adam_job* J, void* stream);
+
 /* HOST function (no GPU work): least squares on the normal equations G = A^T A (n, n), C = A^T b (n, k), fp64
  * row-major host arrays; A had m_rows rows.  driver 0 = LAPACK gelsy semantics (pivoted QR rank rule with
  * rcond < 0 -> torch's default eps_fp32 * max(m_rows, n), minimum-norm solution), driver 1 = gels (full rank).

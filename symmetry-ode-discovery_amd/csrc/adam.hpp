@@ -16,9 +16,11 @@ namespace symode {
 constexpr int ADAM_BLOCK = 256;       // four wave64: thread j owns parameter j and coefficient j, row b of a batch goes to thread b % 256
 constexpr int ADAM_LOG = 8;           // floats per (epoch, problem) log row, see include/symode.h
 constexpr int ADAM_LOG_LATENT = 10;   // the latent entry's row (SYMODE_ADAM_LOG_LATENT)
+constexpr int ADAM_HYPER = 4;         // columns of a problem's hyper-parameter row (SYMODE_ADAM_HYPER)
 
 // the three forms of the epoch kernel: they share the cursor, the step and the epoch end
 enum AdamKind { ADAM_PLAIN = 0, ADAM_REVERSED = 1, ADAM_LATENT = 2 };
+constexpr int ADAM_PER_PROBLEM = 4;   // or-ed to a kind: the instantiation that reads a.hyper
 
 struct AdamArgs {
     const float* x;
@@ -54,6 +56,8 @@ struct AdamArgs {
     const long long* order_seeds;     // (n_order_seeds): 1 (every problem walks the same order) or n_problems
     long n_order_seeds;
     int shuffle;                      // 0: position pos is row pos (the loader with shuffle=False)
+    // symode_adam_run alone: (n_problems, ADAM_HYPER) rows [lr, w_reg, threshold, w_sym], or nullptr (the scalars above apply)
+    const float* hyper;
 };
 
 // b^n for an integer n >= 0 by squaring: a function of (b, n) alone, so a fit cut into several launches meets the same
@@ -103,9 +107,19 @@ __device__ __forceinline__ double adam_ipow(double b, int n) {
 // reduction: there the two meet as  tot_z + (w_sym / w_z) rows d tot_s,  and the optimiser multiplies by 2 w_z / (rows d)
 // as before.  With n_gen == 0 the second set is neither reduced nor added, so params, m, v and mask are those of the plain
 // kernel on (z, dz) with w_x = w_z bit for bit.  A batch is non-finite when w_z mse_z + w_x mse_x + w_sym sym is.
+//
+// a.hyper (symode_adam_run) gives every problem its own lr, w_reg, threshold and w_sym: workgroup s reads row s ONCE, before
+// the step loop, and uses it wherever the launch-wide scalars stand otherwise -- the step size, the L1 term, the thresholding
+// event with its near count, w_ratio = w_sym / w_x (REV, LAT; one fp32 division, rounded as the host's) and w_sym in LAT's
+// tested value.  PLAIN does not read column 3.  The row is uniform over the workgroup (the address depends on blockIdx
+// alone), so it costs no memory traffic and no barrier per step.  The table is a bit of the template parameter
+// (KIND | ADAM_PER_PROBLEM), not a test of the pointer: the kernel is bound by its scalar registers (the compiler already
+// spills some into vector lanes), and the launches without a table keep the instantiations -- name and code -- they had
+// before the table existed.
 template <class Lib, int KIND = ADAM_PLAIN>
 __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs a) {
-    constexpr bool REV = KIND == ADAM_REVERSED, LAT = KIND == ADAM_LATENT;
+    constexpr bool HYPER = (KIND & ADAM_PER_PROBLEM) != 0;
+    constexpr bool REV = (KIND & ~ADAM_PER_PROBLEM) == ADAM_REVERSED, LAT = (KIND & ~ADAM_PER_PROBLEM) == ADAM_LATENT;
     // reduced values: [0, DP) the gradient sums, DP sum r^2, DP + 1 the valid rows, DP + 2 sum |r|^2 (REV) / sum |u|^2 (LAT),
     // LAT: DP + 3 sum (|r_x|^2 + e), then the regulariser's DP gradient sums
     constexpr int D = Lib::D, P = Lib::P, DP = D * P, NV1 = DP + 2 + (REV ? 1 : 0) + (LAT ? 2 : 0), NV = NV1 + (LAT ? DP : 0),
@@ -122,6 +136,20 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
     const int tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE;
     const int np = a.n_params, r = a.r;
     const bool con = a.q != nullptr;
+
+    float lr = a.lr, w_reg = a.w_reg, threshold = a.threshold, w_ratio = a.w_ratio, w_sym = a.w_sym;
+    if constexpr (HYPER) {
+        const float* row = a.hyper + s * ADAM_HYPER;
+        lr = row[0];
+        w_reg = row[1];
+        threshold = row[2];
+        if constexpr (REV) w_ratio = a.n_g > 0 ? row[3] / a.w_x : 0.0f;
+        if constexpr (LAT) {
+            w_sym = row[3];
+            w_ratio = a.n_gen > 0 ? row[3] / a.w_x : 0.0f;
+        }
+    }
+    (void)w_sym;
 
     float p = 0.0f, m = 0.0f, v = 0.0f, mk = 0.0f, xi = 0.0f;
     if (tid < np) {
@@ -285,7 +313,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                         for (int j = 0; j < D; ++j) jh = fmaf(cj[i * D + j], hx[j], jh);
                         const float rr = jh - hg;
                         sr = fmaf(rr, rr, sr);
-                        rs[i] = a.w_ratio * rr;
+                        rs[i] = w_ratio * rr;
                     }
 #pragma unroll
                     for (int i = 0; i < D; ++i) {
@@ -400,7 +428,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 reg = sr_t;                                   // torch.norm(..)**2 over the batch: no divisor
                 loss_x = sx_t / (cnt_t * (float)a.d_obs);
             }
-            const float tested = LAT ? fmaf(a.w_x, loss, fmaf(a.w_obs, loss_x, a.w_sym * reg)) : (REV ? loss + reg : loss);
+            const float tested = LAT ? fmaf(a.w_x, loss, fmaf(a.w_obs, loss_x, w_sym * reg)) : (REV ? loss + reg : loss);
             const bool bad = live && !(fabsf(tested) <= FLT_MAX);
             if (bad) frozen = true;                           // NaN / inf: the problem keeps its state from here on
             const bool upd = live && !bad;
@@ -415,7 +443,7 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                         float tot_s = part[0][NV1 + tid];
 #pragma unroll
                         for (int w = 1; w < NW; ++w) tot_s += part[w][NV1 + tid];
-                        tot = fmaf(a.w_ratio * (cnt_t * (float)D), tot_s, tot);
+                        tot = fmaf(w_ratio * (cnt_t * (float)D), tot_s, tot);
                     }
                 }
                 g_xi = scale * tot * mk;                      // d mse / d Xi: the model reads Xi * mask
@@ -435,12 +463,12 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 ++t;
                 if (tid < np) {
                     const float sgn = (float)(p > 0.0f) - (float)(p < 0.0f);
-                    const float g = a.l1 ? fmaf(a.w_reg, sgn, a.w_x * g_data) : a.w_x * g_data;
+                    const float g = a.l1 ? fmaf(w_reg, sgn, a.w_x * g_data) : a.w_x * g_data;
                     // torch's lerp_(g, 1 - b1): from the nearer end, so that a weight of 1 (b1 = 0) gives g itself, not m + (g - m)
                     m = om1 < 0.5f ? fmaf(om1, g - m, m) : fmaf(-(g - m), a.beta1, g);
                     v = fmaf(om2, g * g, a.beta2 * v);
                     const double bc1 = 1.0 - adam_ipow((double)a.beta1, t), bc2 = 1.0 - adam_ipow((double)a.beta2, t);
-                    const float step_size = (float)((double)a.lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+                    const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
                     p -= step_size * (m / (sqrtf(v) / bc2_sqrt + a.eps));
                 }
                 float l1_t = l1_s[0];
@@ -471,8 +499,8 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
                 bool near = false;
                 if (ev && tid < DP) {
                     const float av = fabsf(xi);
-                    near = fabsf(av - a.threshold) < a.near_band && mk > 0.0f;
-                    mk = (av > a.threshold && mk > 0.0f) ? 1.0f : 0.0f;       // strict >, monotone
+                    near = fabsf(av - threshold) < a.near_band && mk > 0.0f;
+                    mk = (av > threshold && mk > 0.0f) ? 1.0f : 0.0f;       // strict >, monotone
                     w_s[tid] = xi * mk;
                 }
                 const int near_w = __popcll(__ballot(near));
@@ -536,28 +564,31 @@ __global__ __launch_bounds__(ADAM_BLOCK) void adam_epochs_kernel(const AdamArgs 
     if (tid == 0) a.step[s] = frozen ? -t - 1 : t;
 }
 
-template <class Lib>
-hipError_t launch_adam_epochs(const AdamArgs& a, hipStream_t st) {
+// a.hyper picks the instantiation that reads the per-problem rows
+template <class Lib, int KIND>
+hipError_t launch_adam_kind(const AdamArgs& a, hipStream_t st) {
     if (a.n_problems == 0 || a.n_epochs == 0) return hipSuccess;
-    adam_epochs_kernel<Lib><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
+    if (a.hyper)
+        adam_epochs_kernel<Lib, KIND | ADAM_PER_PROBLEM><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
+    else
+        adam_epochs_kernel<Lib, KIND><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
     SYMODE_LAUNCH_CHECK();
     return hipSuccess;
+}
+
+template <class Lib>
+hipError_t launch_adam_epochs(const AdamArgs& a, hipStream_t st) {
+    return launch_adam_kind<Lib, ADAM_PLAIN>(a, st);
 }
 
 template <class Lib>
 hipError_t launch_adam_epochs_reversed(const AdamArgs& a, hipStream_t st) {
-    if (a.n_problems == 0 || a.n_epochs == 0) return hipSuccess;
-    adam_epochs_kernel<Lib, ADAM_REVERSED><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
-    SYMODE_LAUNCH_CHECK();
-    return hipSuccess;
+    return launch_adam_kind<Lib, ADAM_REVERSED>(a, st);
 }
 
 template <class Lib>
 hipError_t launch_adam_epochs_latent(const AdamArgs& a, hipStream_t st) {
-    if (a.n_problems == 0 || a.n_epochs == 0) return hipSuccess;
-    adam_epochs_kernel<Lib, ADAM_LATENT><<<dim3((unsigned)a.n_problems), dim3(ADAM_BLOCK), 0, st>>>(a);
-    SYMODE_LAUNCH_CHECK();
-    return hipSuccess;
+    return launch_adam_kind<Lib, ADAM_LATENT>(a, st);
 }
 
 }  // namespace symode

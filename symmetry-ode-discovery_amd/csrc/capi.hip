@@ -569,13 +569,14 @@ struct AdamOrder {
 
 // symode_adam_epochs (gx_, jgx null, n_g 0, kind ADAM_PLAIN), symode_adam_epochs_reversed and symode_adam_epochs_latent (lat
 // set; x, dx are z, dz and w_x is w_z): one set of argument checks.  The keyed entries pass ord (idx null, n_idx_problems and
-// n_steps unused: the order seeds take the table's place and n_steps is ceil(n_src / batch)).
+// n_steps unused: the order seeds take the table's place and n_steps is ceil(n_src / batch)).  symode_adam_run alone passes
+// hyper, the per-problem (n_problems, 4) table that takes the place of lr, w_reg, threshold and w_sym (adam.hpp).
 int adam_epochs(AdamKind kind, const AdamLatent* lat, const AdamOrder* ord, const float* x, const float* dx, const float* gx_, const float* jgx, int n_g,
                 long n_src, const int* idx, long n_idx_problems, int n_epochs, int n_steps, int batch, long n_problems, int d,
                 int order, int flags, const float* q_eff, int r, int allow_constant, int n_params, float lr, float beta1,
                 float beta2, float eps, float w_x, float w_reg, float w_sym, int l1, float threshold, int st_freq, int epoch0,
                 float near_band, float* params, float* m, float* v, int* step, float* mask, float* xi_out, float* log,
-                void* stream) {
+                const float* hyper, void* stream) {
     SYMODE_GET_OPS();
     if (n_epochs < 0 || n_problems < 0 || n_g < 0 || (lat && lat->n_gen < 0)) return SYMODE_E_BADSIZE;
     if (n_epochs == 0 || n_problems == 0) return SYMODE_OK;
@@ -606,10 +607,12 @@ int adam_epochs(AdamKind kind, const AdamLatent* lat, const AdamOrder* ord, cons
                 (lat->n_gen > 0 && misaligned(lat->L, 4))))
         return SYMODE_E_ALIGN;
     if (ord && misaligned(ord->seeds, 8)) return SYMODE_E_ALIGN;
+    if (misaligned(hyper, 4)) return SYMODE_E_ALIGN;
     AdamArgs a{x, dx, n_src, ord ? nullptr : idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, q_eff, q_eff ? r : 0,
                allow_constant != 0, n_params, lr, beta1, beta2, eps, w_x, w_reg, l1, threshold, st_freq, epoch0,
                near_band, params, m, v, step, mask, xi_out, log, n_g > 0 ? gx_ : nullptr, n_g > 0 ? jgx : nullptr, n_g,
                n_g > 0 ? w_sym / w_x : 0.0f};
+    a.hyper = hyper;
     if (ord) {
         a.order_seeds = ord->seeds;
         a.n_order_seeds = ord->n_seeds;
@@ -641,7 +644,7 @@ int symode_adam_epochs(const float* x, const float* dx, long n_src, const int* i
                        int* step, float* mask, float* xi_out, float* log, void* stream) {
     return adam_epochs(ADAM_PLAIN, nullptr, nullptr, x, dx, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d,
                        order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, 0.0f, l1, threshold,
-                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, nullptr, stream);
 }
 
 int symode_adam_epochs_reversed(const float* x, const float* dx, const float* gx, const float* jgx, int n_g, long n_src,
@@ -652,7 +655,7 @@ int symode_adam_epochs_reversed(const float* x, const float* dx, const float* gx
                                 int* step, float* mask, float* xi_out, float* log, void* stream) {
     return adam_epochs(ADAM_REVERSED, nullptr, nullptr, x, dx, gx, jgx, n_g, n_src, idx, n_idx_problems, n_epochs, n_steps, batch, n_problems, d, order,
                        flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, w_sym, l1, threshold,
-                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, nullptr, stream);
 }
 
 int symode_adam_epochs_latent(const float* z, const float* dz, const float* B, const float* y, const float* e, int D_obs,
@@ -665,7 +668,7 @@ int symode_adam_epochs_latent(const float* z, const float* dz, const float* B, c
     const AdamLatent lat{B, y, e, L, D_obs, n_gen, w_x, w_sym};
     return adam_epochs(ADAM_LATENT, &lat, nullptr, z, dz, nullptr, nullptr, 0, n_src, idx, n_idx_problems, n_epochs, n_steps, batch,
                        n_problems, d, order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_z, w_reg, 0.0f, l1,
-                       threshold, st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+                       threshold, st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, nullptr, stream);
 }
 
 int symode_adam_epochs_keyed(const float* x, const float* dx, long n_src, const long long* order_seeds, long n_order_seeds,
@@ -677,7 +680,7 @@ int symode_adam_epochs_keyed(const float* x, const float* dx, long n_src, const 
     const AdamOrder ord{order_seeds, n_order_seeds, shuffle};
     return adam_epochs(ADAM_PLAIN, nullptr, &ord, x, dx, nullptr, nullptr, 0, n_src, nullptr, 0, n_epochs, 0, batch, n_problems, d,
                        order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, 0.0f, l1, threshold,
-                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, nullptr, stream);
 }
 
 int symode_adam_epochs_reversed_keyed(const float* x, const float* dx, const float* gx, const float* jgx, int n_g, long n_src,
@@ -690,7 +693,7 @@ int symode_adam_epochs_reversed_keyed(const float* x, const float* dx, const flo
     const AdamOrder ord{order_seeds, n_order_seeds, shuffle};
     return adam_epochs(ADAM_REVERSED, nullptr, &ord, x, dx, gx, jgx, n_g, n_src, nullptr, 0, n_epochs, 0, batch, n_problems, d, order,
                        flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_x, w_reg, w_sym, l1, threshold,
-                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, nullptr, stream);
 }
 
 int symode_adam_epochs_latent_keyed(const float* z, const float* dz, const float* B, const float* y, const float* e, int D_obs,
@@ -704,7 +707,23 @@ int symode_adam_epochs_latent_keyed(const float* z, const float* dz, const float
     const AdamOrder ord{order_seeds, n_order_seeds, shuffle};
     return adam_epochs(ADAM_LATENT, &lat, &ord, z, dz, nullptr, nullptr, 0, n_src, nullptr, 0, n_epochs, 0, batch, n_problems, d,
                        order, flags, q_eff, r, allow_constant, n_params, lr, beta1, beta2, eps, w_z, w_reg, 0.0f, l1, threshold,
-                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, stream);
+                       st_freq, epoch0, near_band, params, m, v, step, mask, xi_out, log, nullptr, stream);
+}
+
+int symode_adam_run(const symode_adam_job* J, void* stream) {
+    if (!J) return SYMODE_E_NULLPTR;
+    if (J->kind != SYMODE_ADAM_PLAIN && J->kind != SYMODE_ADAM_REVERSED && J->kind != SYMODE_ADAM_LATENT) return SYMODE_E_BADSIZE;
+    if ((J->idx != nullptr) == (J->order_seeds != nullptr)) return SYMODE_E_BADSIZE;      // the table or the order seeds: one of them
+    const bool rev = J->kind == SYMODE_ADAM_REVERSED, latent = J->kind == SYMODE_ADAM_LATENT, per_problem = J->hyper != nullptr;
+    // pointers and counts of another kind are never read; with the table the four scalars it replaces are not either
+    const AdamLatent lat{J->lat_B, J->lat_y, J->lat_e, J->lat_L, J->D_obs, J->n_gen, J->w_obs, per_problem ? 0.0f : J->w_sym};
+    const AdamOrder ord{J->order_seeds, J->n_order_seeds, J->shuffle};
+    return adam_epochs((AdamKind)J->kind, latent ? &lat : nullptr, J->order_seeds ? &ord : nullptr, J->x, J->dx, rev ? J->gx : nullptr,
+                       rev ? J->jgx : nullptr, rev ? J->n_g : 0, J->n_src, J->idx, J->n_idx_problems, J->n_epochs, J->n_steps, J->batch,
+                       J->n_problems, J->d, J->order, J->flags, J->q_eff, J->r, J->allow_constant, J->n_params,
+                       per_problem ? 0.0f : J->lr, J->beta1, J->beta2, J->eps, J->w_x, per_problem ? 0.0f : J->w_reg,
+                       rev && !per_problem ? J->w_sym : 0.0f, J->l1, per_problem ? 0.0f : J->threshold, J->st_freq, J->epoch0, J->near_band,
+                       J->params, J->m, J->v, J->step, J->mask, J->xi_out, J->log, J->hyper, stream);
 }
 
 int symode_adam_order_table(long n_src, int batch, const long long* order_seeds, long n_order_seeds, int shuffle, int epoch0,

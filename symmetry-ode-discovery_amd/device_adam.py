@@ -12,6 +12,8 @@ per-row operands of ``model_utils.latent_operands``; mse_x is logged and added b
 The rows of a step come from an index table built from the caller's shuffles, or -- ``fit(order_seeds=...)``, the device
 shuffle -- from the launch itself, which computes them from (order seed, epoch, position) by ``epoch_order``'s function
 (symode_adam_epochs*_keyed): no table, nothing between two launches, an equivalent draw of the shuffle rather than a replay.
+``fit(hyper=...)`` gives every problem its own lr, w_reg, threshold and w_sym -- a hyper-parameter grid over common seeds in
+one launch (symode_adam_run): problem s is, bit for bit, the fit of a trainer built with problem s's scalars.
 Not covered (the callers refuse them): the i / f symmetry regularisers (they run the autoencoder on Xi-dependent inputs), a
 latent fit whose autoencoder trains, several ranks.
 """
@@ -33,6 +35,8 @@ LOG_COLUMNS = ('loss_sindy_x', 'loss_sindy_reg', 'steps', 'near', 'nan', 'event'
 LOG_COLUMNS_REVERSED = LOG_COLUMNS + ('loss_sym_reg',)
 # records of a trainer with ``latent``: ten columns, the three loss terms unweighted
 LOG_COLUMNS_LATENT = LOG_COLUMNS + ('loss_sym_reg', 'loss_sindy_z', 'unused')
+# the columns of a problem's hyper-parameter row (SYMODE_ADAM_HYPER of include/symode.h), by the names ``fit(hyper=...)`` takes
+HYPER_COLUMNS = ('lr', 'w_reg', 'threshold', 'w_sym')
 
 
 ORDER_ROUNDS = 2          # ADAM_ORDER_ROUNDS of csrc/adam_order.hpp
@@ -190,8 +194,30 @@ class DeviceAdam:
             t = torch.cat([t, torch.full((t.shape[0], pad), -1, dtype=torch.int32, device=t.device)], dim=1)
         return t.view(t.shape[0], self.steps, self.batch)
 
+    def hyper_table(self, hyper, S):
+        """The (S, 4) fp32 device table [lr, w_reg, threshold, w_sym] of ``fit(hyper=...)``: every given key a length-S sequence
+        or tensor, every missing column the trainer's own scalar."""
+        if not isinstance(hyper, dict):
+            raise ValueError(f'hyper must be a dict with keys among {HYPER_COLUMNS}, got {type(hyper).__name__}')
+        unknown = sorted(set(hyper) - set(HYPER_COLUMNS))
+        if unknown:
+            raise ValueError(f'hyper has unknown keys {unknown}: the per-problem values are {HYPER_COLUMNS}')
+        w_sym = self.latent[6] if self.latent is not None else self.reversed_sym[2] if self.reversed_sym is not None else 0.0
+        if 'w_sym' in hyper and self.latent is None and self.reversed_sym is None:
+            raise ValueError('hyper w_sym needs a trainer with reversed_sym or latent: the plain loss has no symmetry regulariser')
+        table = torch.empty(S, len(HYPER_COLUMNS), dtype=torch.float32)
+        for c, (name, scalar) in enumerate(zip(HYPER_COLUMNS, (self.lr, self.w_reg, self.threshold, w_sym))):
+            if name not in hyper:
+                table[:, c] = scalar
+                continue
+            col = torch.as_tensor(hyper[name]).detach().to('cpu', torch.float32)
+            if col.shape != (S,):
+                raise ValueError(f'hyper {name} must hold one value per problem ({S}), got shape {tuple(col.shape)}')
+            table[:, c] = col
+        return table.to(self.x.device).contiguous()
+
     def fit(self, params0, n_epochs, orders=None, mask0=None, on_epoch=None, epochs_per_launch=16, boundary=None, epoch0=0,
-            state=None, order_seeds=None, shuffle=True):
+            state=None, order_seeds=None, shuffle=True, hyper=None):
         """``params0`` (S, n_params); ``orders`` yields one (S or 1, n) integer permutation on the device per epoch, drawn
         in epoch order.  ``order_seeds`` (1 or S integers, with ``orders`` None) is the device shuffle instead: no table is
         built and nothing is drawn, epoch e of problem s walks ``epoch_order(order_seeds[s or 0], e, n)`` -- e the global epoch
@@ -202,7 +228,10 @@ class DeviceAdam:
         epoch's own record: the LOG_COLUMNS (with ``reversed_sym``: LOG_COLUMNS_REVERSED, with ``latent``: LOG_COLUMNS_LATENT) as (S,) numpy arrays, and ``record['state']`` = {params, mask, Xi} (device
         tensors, valid until the next launch) when the epoch is the last of its launch, else None.  ``boundary(epoch)``
         true ends the launch after that epoch (a caller that needs the state there).  ``state``: (m, v, step) of an
-        earlier fit to continue.  Returns Xi, mask, params (device), log (n_epochs, S, 8; with ``latent`` 10) numpy, nan (S,) bool and m, v,
+        earlier fit to continue.  ``hyper``: a dict with any of the keys ``lr``, ``w_reg``, ``threshold``, ``w_sym`` (the last with
+        ``reversed_sym`` or ``latent`` only), each a length-S sequence or tensor: problem s's own value in place of the
+        trainer's scalar; missing keys are filled from the scalars.  The (S, 4) table is built once and read by every launch
+        of the fit (symode_adam_run), under the epoch orders and under ``order_seeds`` alike.  Returns Xi, mask, params (device), log (n_epochs, S, 8; with ``latent`` 10) numpy, nan (S,) bool and m, v,
         step."""
         dev = self.x.device
         params = params0.detach().to(dev, torch.float32).clone().contiguous()
@@ -216,6 +245,7 @@ class DeviceAdam:
         else:
             m, v, step = (t.detach().to(dev).clone().contiguous() for t in state)
         xi = self.coef.xi(*self.coef.split(params)).reshape(S, self.d, self.coef.p) if n_epochs == 0 else None
+        per_problem = {} if hyper is None else {'hyper': self.hyper_table(hyper, S)}
         if (orders is None) == (order_seeds is None):
             raise ValueError('give the epoch orders or order_seeds (the device shuffle), one of them')
         if order_seeds is not None:
@@ -244,7 +274,7 @@ class DeviceAdam:
                 idx, keyed = torch.stack(tables).contiguous(), {}
             kw = dict(lr=self.lr, betas=self.betas, eps=self.eps, w_x=self.w_x, w_reg=self.w_reg, l1=True,
                       threshold=self.threshold, st_freq=self.st_freq, epoch0=epoch0 + done, near_band=NEAR_THRESHOLD_BAND,
-                      q_eff=self.q_eff, allow_constant=self.coef.allow_constant, **keyed)
+                      q_eff=self.q_eff, allow_constant=self.coef.allow_constant, **keyed, **per_problem)
             if self.latent is not None:
                 B, y, e, D_obs, L, w_z, w_sym = self.latent
                 xi, log = self.engine.adam_epochs_latent(self.x, self.dx, B, y, e, D_obs, L, idx, params, m, v, step, mask,

@@ -112,6 +112,7 @@ _SIGNATURES = {
                                                 c_int, c_long, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int]
                                         + [c_float] * 8 + [c_int, c_float, c_int, c_int, c_float] + [c_void_p] * 8),
     "symode_adam_order_table": (c_int, [c_long, c_int, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "symode_adam_run": (c_int, [c_void_p, c_void_p]),
     "symode_host_stlsq_sweep": (c_int, [c_void_p, c_int, c_int, c_int, c_long, ctypes.c_double, ctypes.c_double, c_int, c_int,
                                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
@@ -135,6 +136,26 @@ class TrainerDesc(ctypes.Structure):
                 ("log", c_void_p), ("log_test", c_void_p), ("log_xi", c_void_p), ("log_mask", c_void_p), ("log_params", c_void_p), ("log_epochs", c_int),
                 ("aug_gram", c_void_p), ("rev_gram", c_void_p),
                 ("closure", c_int), ("latent_B", c_void_p), ("latent_y", c_void_p)]
+
+
+ADAM_PLAIN, ADAM_REVERSED, ADAM_LATENT = 0, 1, 2              # SYMODE_ADAM_* of include/symode.h
+ADAM_HYPER = 4                                              # columns of a hyper row: lr, w_reg, threshold, w_sym
+
+
+class AdamJob(ctypes.Structure):
+    """``symode_adam_job`` of include/symode.h, field for field."""
+    _fields_ = [("kind", c_int), ("x", c_void_p), ("dx", c_void_p), ("n_src", c_long),
+                ("gx", c_void_p), ("jgx", c_void_p), ("n_g", c_int), ("D_obs", c_int),
+                ("lat_B", c_void_p), ("lat_y", c_void_p), ("lat_e", c_void_p), ("lat_L", c_void_p), ("n_gen", c_int),
+                ("n_steps", c_int), ("idx", c_void_p), ("n_idx_problems", c_long),
+                ("order_seeds", c_void_p), ("n_order_seeds", c_long), ("shuffle", c_int),
+                ("n_epochs", c_int), ("batch", c_int), ("n_problems", c_long), ("d", c_int), ("order", c_int), ("flags", c_int),
+                ("q_eff", c_void_p), ("r", c_int), ("allow_constant", c_int), ("n_params", c_int),
+                ("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("w_x", c_float), ("w_obs", c_float),
+                ("w_reg", c_float), ("w_sym", c_float), ("l1", c_int), ("threshold", c_float), ("st_freq", c_int), ("epoch0", c_int),
+                ("near_band", c_float),
+                ("params", c_void_p), ("m", c_void_p), ("v", c_void_p), ("step", c_void_p), ("mask", c_void_p), ("xi_out", c_void_p),
+                ("log", c_void_p), ("hyper", c_void_p)]
 
 
 TRAINER_FIELDS = ("params", "xi", "mask", "cl_loss", "cl_grad", "g", "loss", "act", "n_iter", "d", "t", "old_dirs", "old_stps", "ro",
@@ -301,14 +322,18 @@ class HipEngine:
 
     def adam_epochs(self, x, dx, idx, params, m, v, step, mask, order, flags=0, *, lr, betas=(0.9, 0.999), eps=1e-8, w_x=1.0,
                     w_reg=0.0, l1=True, threshold=0.0, st_freq=0, epoch0=0, near_band=1e-4, q_eff=None, allow_constant=True,
-                    _reversed=None, _latent=None, _keyed=None):
+                    hyper=None, _reversed=None, _latent=None, _keyed=None):
         """``idx.shape[0]`` whole epochs of minibatch Adam steps for S problems in ONE launch (symode_adam_epochs).
         x, dx (n_src, d) fp32; idx (n_epochs, S or 1, n_steps, batch) int32 row numbers; params, m, v (S, n_params) fp32,
         step (S,) int32 and mask (S, d, p) fp32 are the state, UPDATED IN PLACE (so they must be contiguous); q_eff
         (d p, r) fp32 or None (the parameters are Xi).  ``idx`` is NOT range-checked here: the kernel treats every entry
         outside [0, n_src) as padding -- not read, not counted in the batch's divisor (-1 is the canonical pad).
         Returns (xi (S, d, p), log (n_epochs, S, 8)); log columns: mean batch MSE, mean |params|_1, steps taken,
-        near-threshold coefficients at the epoch's event, frozen-after-NaN flag, thresholding event, epoch, 0."""
+        near-threshold coefficients at the epoch's event, frozen-after-NaN flag, thresholding event, epoch, 0.
+        ``hyper``: None, or a contiguous (S, 4) fp32 tensor on the device of x whose row s is problem s's own
+        [lr, w_reg, threshold, w_sym] (symode_adam_run): the launch then reads none of the scalars ``lr``, ``w_reg``,
+        ``threshold``, ``w_sym``, and problem s is bit for bit the scalar launch on problem s alone with row s's values.  The
+        reversed, latent and keyed wrappers hand it through."""
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.dim() != 2 or dx.shape != x.shape:
             raise SymodeError(f"x and dx must both be (n_src, d), got {tuple(x.shape)} and {tuple(dx.shape)}")
@@ -359,6 +384,32 @@ class HipEngine:
             raise SymodeError(f"params has {n_params} columns, expected {r + d if q_eff is not None else d * p}")
         xi = torch.empty(S, d, p, dtype=torch.float32, device=x.device)
         log = torch.empty(n_epochs, S, 10 if _latent is not None else 8, dtype=torch.float32, device=x.device)
+        if hyper is not None:
+            if (not isinstance(hyper, torch.Tensor) or not hyper.is_cuda or hyper.dtype != torch.float32
+                    or tuple(hyper.shape) != (S, ADAM_HYPER) or not hyper.is_contiguous() or hyper.device != x.device):
+                raise SymodeError(f"hyper must be a contiguous ({S}, {ADAM_HYPER}) fp32 tensor on {x.device}: one row "
+                                  "[lr, w_reg, threshold, w_sym] per problem")
+            J = AdamJob(kind=ADAM_PLAIN, x=x.data_ptr(), dx=dx.data_ptr(), n_src=n_src, n_epochs=n_epochs, batch=batch, n_problems=S,
+                        d=d, order=order, flags=flags, q_eff=None if q_eff is None else q_eff.data_ptr(), r=r,
+                        allow_constant=int(bool(allow_constant)), n_params=n_params, lr=float(lr), beta1=float(betas[0]),
+                        beta2=float(betas[1]), eps=float(eps), w_x=float(w_x), w_reg=float(w_reg), l1=int(bool(l1)),
+                        threshold=float(threshold), st_freq=int(st_freq), epoch0=int(epoch0), near_band=float(near_band),
+                        params=params.data_ptr(), m=m.data_ptr(), v=v.data_ptr(), step=step.data_ptr(), mask=mask.data_ptr(),
+                        xi_out=xi.data_ptr(), log=log.data_ptr(), hyper=hyper.data_ptr())
+            if seeds is None:
+                J.idx, J.n_idx_problems, J.n_steps = idx.data_ptr(), n_tab, n_steps
+            else:
+                J.order_seeds, J.n_order_seeds, J.shuffle = seeds.data_ptr(), seeds.numel(), int(bool(shuffle))
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            if _latent is not None:
+                B, y, e, D_obs, L, n_gen, w_z, w_sym = _latent
+                J.kind, J.lat_B, J.lat_y, J.lat_e, J.lat_L, J.D_obs, J.n_gen = ADAM_LATENT, ptr(B), ptr(y), ptr(e), ptr(L), D_obs, n_gen
+                J.w_x, J.w_obs, J.w_sym = float(w_z), float(w_x), float(w_sym)
+            elif _reversed is not None:
+                gx, jgx, n_g, w_sym = _reversed
+                J.kind, J.gx, J.jgx, J.n_g, J.w_sym = ADAM_REVERSED, ptr(gx), ptr(jgx), n_g, float(w_sym)
+            self._check(self.lib.symode_adam_run(ctypes.byref(J), self._stream(x)), "symode_adam_run")
+            return xi, log
         if _latent is not None:
             B, y, e, D_obs, L, n_gen, w_z, w_sym = _latent
             self._check(getattr(self.lib, "symode_adam_epochs_latent" + suffix)(

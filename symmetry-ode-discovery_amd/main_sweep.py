@@ -9,6 +9,8 @@
     python -m symode_amd.main_sweep --config lv/noise99_eq_rsymreg.cfg --n_seeds 50 [--gram_closure]
     python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --batch_size 256 --num_epochs 1000 --n_seeds 64
     python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --device_shuffle --batch_size 256 --n_seeds 64
+    python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --n_seeds 64 --eval_ltp \
+        --grid threshold=0.01,0.05,0.075,0.15 --grid lr_sindy=0.1,1.0     # 8 grid points x 64 seeds in every epoch launch
 
 plan:   ``_refusal`` decides from the arguments alone whether the sweep runs, before a process group, a data file or a
         device is touched; what it refuses it answers with the per-seed command to run instead.
@@ -28,9 +30,17 @@ the plain sweep always has; the success rate over seeds is what the two estimate
 Adam sweep draws no shuffle at all: every epoch launch computes its rows from (seed, epoch) (device_adam.epoch_order), so
 the rows of a step differ from the tensor-op shuffle's as well -- an equivalent draw, not a replay -- and nothing runs on
 the host or the device between two launches.
+
+``--grid name=v1,v2,...`` (repeatable; names lr_sindy, w_sindy_reg, threshold; Adam only) fits the Cartesian product of the
+value lists, the first axis given slowest, over COMMON seeds in the same launches: problem g * n_seeds + k is grid point g on
+seed k, with seed k's initial coefficients and epoch orders at every point, so the fit of (g, k) is exactly the fit main_sweep
+with that point's scalar flags gives seed k.  The results go to ``eval_results/<save_dir>/grid{g}/seed{n}.npz`` and
+``eval_results/<save_dir>/grid.json``; ``main`` returns {g: aggregate}.
 """
 from __future__ import annotations
 
+import itertools
+import json
 import os
 import sys
 from types import SimpleNamespace
@@ -59,6 +69,16 @@ def _pop(argv, flag, default, cast):
     return default
 
 
+def _pop_all(argv, flag):
+    """Every value of a repeatable flag, in the order given."""
+    values = []
+    while flag in argv:
+        i = argv.index(flag)
+        values.append(argv[i + 1] if i + 1 < len(argv) else '')
+        del argv[i:i + 2]
+    return values
+
+
 def _pop_flag(argv, flag):
     if flag in argv:
         argv.remove(flag)
@@ -67,11 +87,43 @@ def _pop_flag(argv, flag):
 
 
 # ---- plan --------------------------------------------------------------------------------------------------------------------
-def _refusal(args, method='lbfgs', world=1, engine=None):
+GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold'}      # --grid name -> DeviceAdam.fit(hyper=) key
+
+
+def _parse_grid(specs):
+    """``--grid name=v1,v2,...`` strings -> ([(name, [values])] in the order given, None), or (None, why not)."""
+    axes = []
+    for spec in specs:
+        name, eq, values = str(spec).partition('=')
+        if name not in GRID_NAMES:
+            return None, f"--grid {spec}: unknown name '{name}', the grid axes are {', '.join(GRID_NAMES)} (name=v1,v2,...)"
+        if name in [a[0] for a in axes]:
+            return None, f'--grid {name} is given twice: one value list per name'
+        try:
+            axis = [float(v) for v in values.split(',')] if eq else []
+        except ValueError:
+            axis = []
+        if not axis or not all(np.isfinite(axis)):
+            return None, f"--grid {spec}: the values of {name} must be a non-empty comma-separated list of numbers"
+        axes.append((name, axis))
+    return axes, None
+
+
+def _grid_points(axes):
+    """The Cartesian product of the axes, the first axis slowest: one {name: value} per grid point."""
+    return [dict(zip([a[0] for a in axes], values)) for values in itertools.product(*[a[1] for a in axes])]
+
+
+def _grid_problem(problem, n_seeds):
+    """Problem ``g * n_seeds + k`` of a grid launch is grid point g on seed k: (g, k)."""
+    return divmod(problem, n_seeds)
+
+
+def _refusal(args, method='lbfgs', world=1, engine=None, grid=None):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
-    apply to the default method."""
+    apply to the default method.  ``grid``: the ``--grid`` strings, if any; their rules come after all others."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
     cfg = args.get('config')
@@ -110,6 +162,11 @@ def _refusal(args, method='lbfgs', world=1, engine=None):
     if args.get('device_shuffle') and (method == 'stlsq' or not adam):
         return ('--device_shuffle draws the epoch order of the minibatch Adam fit inside its launch: it needs '
                 '--sindy_optimizer adam (with the default --method lbfgs), L-BFGS and STLSQ fits have no epoch order')
+    if grid:
+        if method == 'stlsq' or not adam:
+            return ('--grid gives every problem of the minibatch Adam launch its own hyper-parameters: it needs '
+                    '--sindy_optimizer adam (with the default --method lbfgs); the L-BFGS and STLSQ sweeps take one value each')
+        return _parse_grid(grid)[1]
     return None
 
 
@@ -200,7 +257,9 @@ def _fit_adam(ctx):
     --batch_size (--lbfgs_subsample does not apply, as in main.py); seed s shuffles with its own device generator seeded
     with s, so a seed's fit depends on the seed alone, not on --n_seeds or --seed.  --device_shuffle: no generator, no keys
     and no argsort -- seed s is the order seed of problem s, the launch computes every row (DeviceAdam.fit(order_seeds=...));
-    the fit is still a function of s alone, with other rows per step than the generator's shuffle gives."""
+    the fit is still a function of s alone, with other rows per step than the generator's shuffle gives.  --grid: the seeds'
+    initial coefficients, order seeds or epoch orders repeated once per grid point, and the points' values as the per-problem
+    table of DeviceAdam.fit(hyper=...); TABLE_BYTES then cuts the launches of the table path shorter."""
     from .device_adam import DeviceAdam
     args, dev, seeds = ctx.args, ctx.dev, ctx.seeds
     template, P0, _ = _template(ctx)
@@ -208,9 +267,15 @@ def _fit_adam(ctx):
     n_all, n_seeds = ctx.x_all.shape[0], len(seeds)
     trainer = DeviceAdam(ctx.x_all, ctx.dx_all, *lib, template.coef, args['lr_sindy'], args['w_sindy_x'], args['w_sindy_reg'],
                          args['threshold'], args['st_freq'], args['batch_size'], engine=ctx.engine)
+    # --grid: G points on common seeds, problem g * n_seeds + k = point g on seed k with seed k's start and orders
+    points = getattr(ctx, 'grid', None)
+    G, grid = (1, {}) if points is None else (len(points), dict(hyper={
+        GRID_NAMES[name]: [point[name] for point in points for _ in seeds] for name in points[0]}))
+    if G > 1:
+        P0 = P0.repeat(G, 1)
     if args.get('device_shuffle'):
-        out = trainer.fit(P0, args['num_epochs'], order_seeds=seeds)
-        return _adam_result(out, trainer, args, seeds, lib)
+        out = trainer.fit(P0, args['num_epochs'], order_seeds=seeds * G, **grid)
+        return _adam_result(out, trainer, args, seeds, lib, points and G)
     gens = [torch.Generator(device=dev).manual_seed(s) for s in seeds]
     keys = torch.empty(n_seeds, n_all, device=dev)
 
@@ -218,17 +283,23 @@ def _fit_adam(ctx):
         for _ in range(args['num_epochs']):
             for k, g in enumerate(gens):                            # row k is a function of seed k alone
                 torch.rand(n_all, generator=g, out=keys[k])
-            yield torch.argsort(keys, dim=1, stable=True)
+            order = torch.argsort(keys, dim=1, stable=True)
+            yield order if G == 1 else order.repeat(G, 1)           # the seeds' orders at every grid point
 
-    return _adam_result(trainer.fit(P0, args['num_epochs'], orders()), trainer, args, seeds, lib)
+    return _adam_result(trainer.fit(P0, args['num_epochs'], orders(), **grid), trainer, args, seeds, lib, points and G)
 
 
-def _adam_result(out, trainer, args, seeds, lib):
+def _adam_result(out, trainer, args, seeds, lib, G=None):
+    """``G``: the number of grid points (problem g * n_seeds + k is point g on seed k), None without --grid."""
     n_seeds = len(seeds)
-    near = out['log'][:, :, 3].sum(axis=0) if len(out['log']) else np.zeros(n_seeds)
-    lines = [f'{n_seeds} seeds, {args["num_epochs"]} epochs x {trainer.steps} Adam steps of {trainer.batch} rows, '
-             f'NaN {int(out["nan"].sum())}, '
-             f'seeds with near-threshold coefficients {[seeds[i] for i in np.nonzero(near)[0].tolist()] or "none"}']
+    near = out['log'][:, :, 3].sum(axis=0) if len(out['log']) else np.zeros((G or 1) * n_seeds)
+    lines = []
+    for g in range(G or 1):
+        at = slice(g * n_seeds, (g + 1) * n_seeds)
+        lines.append(('' if G is None else f'grid {g}: ') +
+                     f'{n_seeds} seeds, {args["num_epochs"]} epochs x {trainer.steps} Adam steps of {trainer.batch} rows, '
+                     f'NaN {int(out["nan"][at].sum())}, '
+                     f'seeds with near-threshold coefficients {[seeds[i] for i in np.nonzero(near[at])[0].tolist()] or "none"}')
     return SimpleNamespace(Xi=out['Xi'], mask=out['mask'], lib=lib, lines=lines)
 
 
@@ -291,6 +362,53 @@ def _report(ctx, result, val_dataset, eval_ltp, ltp_bound_rel):
     return aggregate_results(args['save_dir'], min_seed=seeds[0], max_seed=seeds[-1] + 1)
 
 
+def _report_grid(ctx, result, val_dataset, eval_ltp, ltp_bound_rel):
+    """--grid: ``_report`` per grid point into eval_results/<save_dir>/grid{g}/ (every seed file also holds the point's
+    lr_sindy, w_sindy_reg and threshold), the table of the points -- values, success rate = mean correct_form_all and, with
+    --eval_ltp, the median over seeds of the per-seed median roll-out error and of val_mse -- on stdout and in
+    eval_results/<save_dir>/grid.json, and {g: aggregate}."""
+    if ctx.rank != 0:
+        return None
+    args, seeds, points = ctx.args, ctx.seeds, ctx.grid
+    n_seeds = len(seeds)
+    scores = None
+    if eval_ltp:                                                     # all G x S models in the one roll-out launch
+        scores = _score_on_validation(val_dataset, result.Xi.to(ctx.dev), result.mask.to(ctx.dev), result.lib, args['task'],
+                                      ltp_bound_rel, ctx.dev, ctx.kw)
+    Xi, mask = result.Xi.cpu().numpy(), result.mask.cpu().numpy().astype(bool)
+    truth = truth_table(args['task'], mask.shape[-1], *result.lib[1:])
+    for line in result.lines:
+        print(line)
+    table, out = [], {}
+    for g, point in enumerate(points):
+        at = slice(g * n_seeds, (g + 1) * n_seeds)
+        values = {name: float(point.get(name, args[name])) for name in GRID_NAMES}
+        extra = {name: np.full(n_seeds, v) for name, v in values.items()}
+        if scores is not None:
+            extra.update({name: np.asarray(v)[at] for name, v in scores.items()})
+        sub = dict(args, save_dir=f'{args["save_dir"]}/grid{g}')
+        forms = _write_results(sub, seeds, Xi[at], mask[at], truth, extra)
+        row = dict(grid=g, **values, success_rate=float(np.mean(forms)))
+        if scores is not None:
+            med = np.median(extra['ltp_mean_error'], axis=1)
+            row['ltp_median_error'] = float(np.median(np.where(np.isfinite(med), med, np.inf)))
+            row['val_mse'] = float(np.median(extra['val_mse']))
+        table.append(row)
+        out[g] = aggregate_results(sub['save_dir'], min_seed=seeds[0], max_seed=seeds[-1] + 1)
+    with open(f'eval_results/{args["save_dir"]}/grid.json', 'w') as f:                  # null: every seed diverged / NaN
+        finite = [{k: v if not isinstance(v, float) or np.isfinite(v) else None for k, v in row.items()} for row in table]
+        json.dump({'axes': [[name, axis] for name, axis in ctx.grid_axes], 'n_seeds': n_seeds, 'seed0': seeds[0], 'points': finite},
+                  f, indent=1, allow_nan=False)
+    print(f'grid of {len(points)} points x {n_seeds} seeds (' + ', '.join(table[0]) + '):')
+    for row in table:
+        print('  ' + ', '.join(f'{v:.6g}' if isinstance(v, float) else str(v) for v in row.values()))
+    if scores is not None:
+        best = min(table, key=lambda row: row['ltp_median_error'])          # the first of equals; inf = diverged
+        print(f'best by validation roll-out error: grid {best["grid"]} (' +
+              ' '.join(f'{name}={best[name]:g}' for name in GRID_NAMES) + ')')
+    return out
+
+
 def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     """``engine`` / ``backend`` exist for the CPU rehearsal of the multi-rank path in tests (gloo + the test engine);
     ``one_gpu``: every rank uses cuda:0 (rehearsal of the HIP path with several ranks on a one-GPU box, gloo collectives)."""
@@ -299,9 +417,10 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     method = _pop(argv, '--method', 'lbfgs', str)
     eval_ltp = _pop_flag(argv, '--eval_ltp')
     ltp_bound_rel = _pop(argv, '--ltp_bound_rel', None, float)
+    grid = _pop_all(argv, '--grid')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
-    why = _refusal(args, method, world, engine)
+    why = _refusal(args, method, world, engine, grid=grid or None)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -320,9 +439,13 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     m = int(x_all.shape[0] * args['lbfgs_subsample'])
     ctx = SimpleNamespace(args=args, seeds=list(range(args['seed'], args['seed'] + n_seeds)), dev=dev, group=group, rank=rank,
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
-                          engine=engine, kw={} if engine is None else {'engine': engine})
+                          engine=engine, kw={} if engine is None else {'engine': engine}, grid=None)
+    if grid:
+        ctx.grid_axes = _parse_grid(grid)[0]
+        ctx.grid = _grid_points(ctx.grid_axes)
     fit = {('stlsq', 'lbfgs'): _fit_stlsq, ('lbfgs', 'lbfgs'): _fit_lbfgs, ('lbfgs', 'adam'): _fit_adam}
-    return _report(ctx, fit[method, args['sindy_optimizer']](ctx), val_dataset, eval_ltp, ltp_bound_rel)
+    report = _report if ctx.grid is None else _report_grid
+    return report(ctx, fit[method, args['sindy_optimizer']](ctx), val_dataset, eval_ltp, ltp_bound_rel)
 
 
 if __name__ == '__main__':
