@@ -146,8 +146,8 @@ int symode_symreg_linear(const float* z, long n, int d, int order, int flags, co
                          const float* L, int n_gen, float* loss_out, float* grad_out, void* workspace,
                          size_t workspace_bytes, void* stream);
 
-/* The five entries of the reversed symmetry closure (this one, _batched, symode_loss_grad_reversed and the two _constj
- * forms) are ONE implementation behind five signatures: the same argument checks in the same order, one grid rule, one
+/* The entries of the reversed symmetry closure (this one, _batched, symode_loss_grad_reversed, the two _constj forms and
+ * their _live forms) are ONE implementation behind seven signatures: the same argument checks in the same order, one grid rule, one
  * launcher.  They differ only in whether dx joins (the fused closure, which also keeps more workgroups on one large
  * problem), whether jgx is the compact table (_constj), and in n_g = 0, which the materialised regulariser alone accepts.
  *
@@ -222,6 +222,28 @@ int symode_loss_grad_reversed_constj(const float* x, const float* dx, const floa
                                      long n, int d, int order, int flags, const float* xi, const float* mask, float inv_count,
                                      float w_sym, float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes,
                                      void* stream);
+
+/* The two _constj entries for coefficients whose zero columns are known beforehand: live_columns is a set of library
+ * columns, bit k set = column k may hold a coefficient in some equation row (p > 64: pass all ones).  An equivariance
+ * constraint keeps whole columns of xi at zero for the length of a fit -- for the planar rotations every even degree --
+ * up to the round-off of its basis Q; the caller that knows the set (CoefMap.live_columns) says so here.  Contract:
+ *   - coefficients in columns outside the set are treated as zero, whatever xi holds there;
+ *   - the gradient in those columns is returned as zero;
+ *   - every other result is, on an xi that IS zero outside the set, bit-identical to the plain _constj entry;
+ *   - a set the library has no kernel for (anything not inside "constant column + odd degrees" of the d = 2 plain
+ *     polynomial libraries of order 4-5; all ones; SYMODE_CLOSURE_LIVE=0) runs the dense kernel on xi as it is: the
+ *     results of the plain _constj entry.
+ * The kernels for a set leave out the per-point work of the dead columns (order 5: 13 of 21 columns stay).
+ * Arguments, checks and workspace as in the plain entries; added to ABI version 8 (nothing existing changed). */
+int symode_symreg_reversed_batched_constj_live(const float* x, const float* gx, const float* jgx, int n_g, long n_problems,
+                                               long n, int d, int order, int flags, const float* xi, const float* mask,
+                                               unsigned long long live_columns, float inv_count, float* loss_out,
+                                               float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
+int symode_loss_grad_reversed_constj_live(const float* x, const float* dx, const float* gx, const float* jgx, int n_g,
+                                          long n_problems, long n, int d, int order, int flags, const float* xi,
+                                          const float* mask, unsigned long long live_columns, float inv_count, float w_sym,
+                                          float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes,
+                                          void* stream);
 
 /* Gram matrix of the reversed regulariser: for S problems (layouts as in symode_symreg_reversed_batched, n_g >= 1)
  *     gram_out[s] (d p, d p) fp64 = sum_g sum_n B^T B,   B[i, (j, a)] = J_g(x_n)[i, j] theta_a(x_n) - delta_ij theta_a(g x_n),

@@ -61,7 +61,7 @@ def allreduce_sums(sums, params, group):
 class BatchedClosure:
     def __init__(self, x, dx, poly_order, include_sine=False, include_exp=False, Q=None, use_kron_product=True,
                  allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True, coef=None,
-                 const_jacobian=None):
+                 const_jacobian=None, live_columns=True):
         """``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from Q / use_kron_product / allow_constant).
         ``reversed_sym = (gx (S, n_g, N_local, d), jgx (S, n_g, N_local, d, d), weight)`` adds  weight * the reversed
         symmetry regulariser (model_utils.py:126-170 on precomputed (g(x), J_g(x))) to every problem's loss and gradient:
@@ -73,7 +73,12 @@ class BatchedClosure:
         (bit-identical results); False -- always the materialised (S, n_g, N, d, d) form (A/B, tests).
         The verdict is remembered with jgx's in-place version counter and data pointer and the pass runs again when either
         differs at the next evaluation.  What that cannot see: jgx refilled through a raw pointer or another view of its
-        storage made outside torch's version tracking (a foreign kernel writing into it) -- rebuild the closure then."""
+        storage made outside torch's version tracking (a foreign kernel writing into it) -- rebuild the closure then.
+        ``live_columns``: True (default) -- ``evaluate``, where Xi is known to come from the map, tells the compact-table
+        closures which library columns the map can fill (``CoefMap.live_mask``, read once here): the columns the
+        constraint keeps at zero up to the round-off of Q count as exactly zero and cost nothing per point where the
+        library has a kernel for the set; False -- the dense launch (A/B, tests).  ``loss_grad_xi`` called directly is
+        dense unless it is given a set."""
         assert x.dim() == 3 and x.shape == dx.shape, "x, dx must be (S, N_local, d)"
         self.engine = engine or get_engine()
         self.x, self.dx = x.contiguous(), dx.contiguous()
@@ -114,6 +119,10 @@ class BatchedClosure:
         self._cj_seen, self._cj_table = None, None
         if self._cj_detect:
             self._jacobian_for_launch()
+        self._live = None                                    # the map's column set, where it names a dead column at all
+        if live_columns and self._cj_detect:
+            live = self.coef.live_mask()
+            self._live = None if live == 0xFFFFFFFFFFFFFFFF else live
 
     def _jacobian_for_launch(self):
         """What the closures get as J_g: the compact table when the detection pass found every slab constant, else the
@@ -135,10 +144,13 @@ class BatchedClosure:
         return self.coef.grad(grad_xi)
 
     # -- the hot path -------------------------------------------------------------------------
-    def loss_grad_xi(self, Xi, mask=None, alias=False):
+    def loss_grad_xi(self, Xi, mask=None, alias=False, live_columns=None):
         """loss (S,), dloss/dXi (S, d, p) summed over all ranks' shards.  ``alias=True``: with a single chunk the results
-        are returned as views of the packed buffer the kernel wrote (no copies; overwritten by the next evaluation)."""
+        are returned as views of the packed buffer the kernel wrote (no copies; overwritten by the next evaluation).
+        ``live_columns``: the library columns Xi can be non-zero in (an int, bit k = column k), for the symmetry launches
+        (engine.loss_grad_reversed); None: every column."""
         works = []
+        live_kw = {} if live_columns is None else {'live_columns': live_columns}
         fused = self.sym is not None and self.fuse_sym and hasattr(self.engine, 'loss_grad_reversed')
         jg = self._jacobian_for_launch() if self.sym is not None else None      # (S, n_g, d, d) table or the (S, n_g, N, d, d) tensor
         for ci, ((a, b), buf) in enumerate(zip(self.chunks, self.buffers)):
@@ -153,7 +165,7 @@ class BatchedClosure:
                 l2 = sb[:2 * n].view(n, 2)
                 self.engine.loss_grad_reversed(self.x[a:b], self.dx[a:b], gx[a:b], jg[a:b], Xi[a:b],
                                                None if mask is None else mask[a:b], self.order, self.flags, w_sym=weight,
-                                               inv_count=self.inv_count, out=(l2, grad), **self._ws_kw)
+                                               inv_count=self.inv_count, out=(l2, grad), **live_kw, **self._ws_kw)
                 torch.add(l2[:, 0], l2[:, 1], alpha=weight, out=loss)
                 if self.distributed:
                     works.append(dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
@@ -168,7 +180,8 @@ class BatchedClosure:
                 sb = self.sym_buffers[ci]
                 sl, sg = sb[:n], sb[n:].view(n, self.d, self.p)
                 l2, g2 = self.engine.symreg_reversed(self.x[a:b], gx[a:b], jg[a:b], Xi[a:b], None if mask is None else mask[a:b],
-                                                     self.order, self.flags, out=(sl, sg), inv_count=self.inv_count, **self._ws_kw)
+                                                     self.order, self.flags, out=(sl, sg), inv_count=self.inv_count, **live_kw,
+                                                     **self._ws_kw)
                 if l2.data_ptr() != sl.data_ptr():
                     sl.copy_(l2)
                     sg.copy_(g2)
@@ -187,7 +200,7 @@ class BatchedClosure:
     def evaluate(self, beta, const=None, mask=None, alias=False):
         """Closure of all S problems: (loss (S,), d/dbeta [or d/dXi when unconstrained], d/dconst)."""
         Xi = self.xi_from(beta, const)
-        loss, grad = self.loss_grad_xi(Xi, mask, alias=alias)
+        loss, grad = self.loss_grad_xi(Xi, mask, alias=alias, live_columns=self._live)
         g_beta, g_const = self.grads_to(grad)
         return loss, g_beta, g_const
 

@@ -129,3 +129,27 @@ class CoefMap:
             return Q
         rows = (np.arange(self.p)[None, :] * self.d + np.arange(self.d)[:, None]).reshape(-1)
         return np.ascontiguousarray(Q[rows])
+
+    def live_columns(self):
+        """(d, p) bool: the entries of Xi the map can make non-zero.  The constraint keeps whole entries of Xi at zero (for
+        the planar rotations every even degree), but the rows of Q that say so are not zero: its basis comes out of an SVD
+        and all but one of them carry round-off, 1e-7 against 0.2-0.4 in the live rows -- a test for ``== 0`` finds
+        nothing.  An entry counts as live when its row of ``effective_Q`` has max |.| above 64 eps_fp32 max|Q| (7.6e-6
+        max|Q|: ten times the largest dead row seen, four orders under the smallest live one); whatever lies between
+        counts as live, the threshold may only err towards doing the work.  Column 0 is live in every row when the model
+        reads ``const``; without Q everything is."""
+        if self.Q is None or self.r == 0:
+            return np.ones((self.d, self.p), dtype=bool)
+        rows =np.abs(self.effective_Q()).max(axis=1)
+        live = (rows > 64.0 * np.finfo(np.float32).eps * rows.max()).reshape(self.d, self.p)
+        if self.allow_constant:
+            live[:, 0] = True
+        return live
+
+    def live_mask(self):
+        """``live_columns`` as the launches take it: an int with bit k set when column k is live in any row -- all 64 bits
+        when nothing is dead or the library has more than 64 columns."""
+        cols = self.live_columns().any(axis=0)
+        if self.p > 64 or cols.all():
+            return 0xFFFFFFFFFFFFFFFF
+        return sum(1 << k for k in np.flatnonzero(cols).tolist())

@@ -126,14 +126,17 @@ size_t workspace_doubles(const LibOps* ops, long S, long n) {
     if (!workspace || misaligned(workspace, 8)) return SYMODE_E_WORKSPACE;                   \
     if (workspace_bytes < workspace_doubles(ops, (S_), (n_)) * sizeof(double)) return SYMODE_E_WORKSPACE;
 
-// The reversed-symmetry closure: the one path from its five C entries to LibOps::symreg_reversed.
+// The reversed-symmetry closure: the one path from its seven C entries to LibOps::symreg_reversed.
 //   fused   MSE + w_sym * regulariser on (x, dx), loss (S, 2); else the regulariser alone, loss (S) (dx, w_sym unused)
 //   constj  jgx is the compact (S, n_g, d, d) table of a point-constant Jacobian (symode_jacobian_constant), not the
 //           materialised (S, n_g, n, d, d) tensor: the same grids and workspace, the same partial rows summed in the same order
+//   live    the library columns that may hold a coefficient (the _live entries; all ones from every other entry): handed to the
+//           launcher, which owns the choice of kernel
 // The forms differ in the three places marked (1)-(3), and nowhere else.
 int reversed_closure(bool fused, bool constj, const float* x, const float* dx, const float* gx_, const float* jgx, int n_g,
                      long n_problems, long n, int d, int order, int flags, const float* xi, const float* mask, float inv_count,
-                     float w_sym, float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
+                     float w_sym, float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream,
+                     unsigned long long live = ~0ull) {
     SYMODE_GET_OPS();
     // (1) no group element at all (the regulariser is 0) is a call only the materialised regulariser accepts
     const int min_n_g = (fused || constj) ? 1 : 0;
@@ -154,8 +157,8 @@ int reversed_closure(bool fused, bool constj, const float* x, const float* dx, c
         if (cap > 0 && gx > cap) gx = cap;
     }
     // (3) without dx there is no second term to weigh the regulariser against: its weight is 1
-    return (int)ops->symreg_reversed(x, dx, gx_, jgx, constj, n_g, n_problems, n, xi, mask, inv_count, fused ? w_sym : 1.0f,
-                                     loss_out, grad_out, (double*)workspace, gx, (hipStream_t)stream);
+    return (int)ops->symreg_reversed(x, dx, gx_, jgx, constj, n_g, n_problems, n, xi, mask, live, inv_count,
+                                     fused ? w_sym : 1.0f, loss_out, grad_out, (double*)workspace, gx, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -313,8 +316,8 @@ int symode_symreg_linear(const float* z, long n, int d, int order, int flags, co
                                    (hipStream_t)stream);
 }
 
-// The five entries of the reversed-symmetry closure are forwards to reversed_closure() above: batched or not, with or
-// without dx, jgx materialised or the compact (S, n_g, d, d) table (_constj).
+// The seven entries of the reversed-symmetry closure are forwards to reversed_closure() above: batched or not, with or
+// without dx, jgx materialised or the compact (S, n_g, d, d) table (_constj), the latter with a set of live columns (_live).
 int symode_symreg_reversed_batched(const float* x, const float* gx_, const float* jgx, int n_g, long n_problems, long n, int d,
                                    int order, int flags, const float* xi, const float* mask, float inv_count,
                                    float* loss_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -363,6 +366,23 @@ int symode_loss_grad_reversed_constj(const float* x, const float* dx, const floa
                                      void* stream) {
     return reversed_closure(true, true, x, dx, gx_, jgx, n_g, n_problems, n, d, order, flags, xi, mask, inv_count, w_sym,
                             loss2_out, grad_out, workspace, workspace_bytes, stream);
+}
+
+int symode_symreg_reversed_batched_constj_live(const float* x, const float* gx_, const float* jgx, int n_g, long n_problems,
+                                               long n, int d, int order, int flags, const float* xi, const float* mask,
+                                               unsigned long long live_columns, float inv_count, float* loss_out,
+                                               float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return reversed_closure(false, true, x, nullptr, gx_, jgx, n_g, n_problems, n, d, order, flags, xi, mask, inv_count, 1.0f,
+                            loss_out, grad_out, workspace, workspace_bytes, stream, live_columns);
+}
+
+int symode_loss_grad_reversed_constj_live(const float* x, const float* dx, const float* gx_, const float* jgx, int n_g,
+                                          long n_problems, long n, int d, int order, int flags, const float* xi,
+                                          const float* mask, unsigned long long live_columns, float inv_count, float w_sym,
+                                          float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+    return reversed_closure(true, true, x, dx, gx_, jgx, n_g, n_problems, n, d, order, flags, xi, mask, inv_count, w_sym,
+                            loss2_out, grad_out, workspace, workspace_bytes, stream, live_columns);
 }
 
 int symode_jacobian_constant(const float* jgx, int n_g, long n_problems, long n, int d, float* table_out, int* flag_out,

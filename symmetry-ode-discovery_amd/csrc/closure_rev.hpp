@@ -104,17 +104,29 @@ __device__ __forceinline__ void sym_uv(const float (&J)[D * D], const float (&h)
 // picked by op_sel, so no register is half used.  Every product and every sum is the one the scalar body forms, in its
 // order: the results are bit-identical to it (and so to the materialised form).  Per point 19 + 42 + 42 packed
 // instructions instead of 36 + 84 + 84 scalar ones; where that pays is in the launcher's table (launch_symreg_reversed).
-template <class Lib, bool MSE, int RING = 2, int XI_SGPR_FROM = 32, bool CJ = false, int MINW = 1, bool PK = false>
+// LIVE (CJ form): the library columns that may hold a coefficient, a compile-time set (col_live).  A column outside it costs
+// nothing per point: its coefficients are not read, its two links of the h(x) / h(g x) chains, its gradient sums and its
+// slots of acc2 / w2 are not formed -- the monomials stay, an even degree feeds the next odd one, and the compiler drops
+// those nothing reads.  What a dead column contributes with a zero coefficient is fma(0, t, s) = s, so on coefficients
+// that ARE zero there every live sum is the one the dense kernel forms, in its order, on its chunk-to-lane assignment:
+// bit-identical.  The dead slots of acc stay zero; partial rows and finalise keep their layout.  `live` is the caller's
+// own set, a subset of LIVE: the columns of LIVE outside it are read as zero and their gradient sums cleared, once per
+// thread, so that the result depends on the caller's set alone and not on which instantiation served it.
+template <class Lib, bool MSE, int RING = 2, int XI_SGPR_FROM = 32, bool CJ = false, int MINW = 1, bool PK = false,
+          unsigned long long LIVE = ~0ull>
 __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const float* __restrict__ x, const float* __restrict__ dx,
                                                                 const float* __restrict__ gx,
                                                                 const float* __restrict__ jgx, int n_g, long N, bool vec,
                                                                 const float* __restrict__ xi,
                                                                 const float* __restrict__ mask, float w_sym,
-                                                                double* __restrict__ ws, Finish fin) {
+                                                                double* __restrict__ ws, Finish fin,
+                                                                unsigned long long live = ~0ull) {
     vec = vec && chunked_stream<Lib>;            // (D = 3 sine / exp libraries: point by point, see chunked_stream)
     constexpr int D = Lib::D, P = Lib::P, NL = MSE ? 2 : 1, NACC = NL + D * P, PPT = Chunk<D>::PPT, NV = Chunk<D>::NV,
                   NVJ = JChunk<D>::NV, SYM0 = NL - 1;
+    constexpr bool SPARSE = LIVE != ~0ull;
     static_assert(!PK || (CJ && D == 2), "the packed body pairs the two library evaluations of the constant-J form at d = 2");
+    static_assert(!SPARSE || (CJ && P <= 64), "a column set is honoured in the constant-J forms, for libraries of up to 64 columns");
     const long s = blockIdx.y;
     const float* xs = x + s * N * D;
     const float* ys = MSE ? dx + s * N * D : nullptr;
@@ -123,14 +135,14 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
     float w[D * P];
     // two libraries per point live here: Xi in SGPRs from d*p = 32 (3 waves/SIMD at order 5) -- and up to 80, the d = 3
     // order-3 libraries with sine / exp columns (69-78 coefficients would otherwise sit in VGPRs beside 70-79 sums)
-    load_xi<Lib, XI_SGPR_FROM, 80>(xi, mask, s, w);
+    load_xi<Lib, XI_SGPR_FROM, 80, LIVE>(xi, mask, s, w, SPARSE ? live : ~0ull);
     float acc[NACC];
 #pragma unroll
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0f;
     const float ws_ = MSE ? w_sym : 1.0f;
     // (an initialised workspace only: one that never saw symode_workspace_init is left as it was found)
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && fin.header[0] == WS_MAGIC)
-        fin.header[WS_BODY_WORD] = PK ? WS_BODY_PACKED : WS_BODY_SCALAR;
+        fin.header[WS_BODY_WORD] = (PK ? WS_BODY_PACKED : WS_BODY_SCALAR) | (SPARSE ? WS_BODY_LIVE : 0ull);
     // CJ: the matrix of group element g, wave-uniform (scalar loads; readfirstlane pins the values to SGPRs)
     auto load_cj = [&](int g, float (&J)[D * D]) {
 #pragma unroll
@@ -149,13 +161,14 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
     auto one = [&](const float (&th)[P], const float (&h)[D], const float (&gp)[D], const float (&J)[D * D], const float (&extra)[D]) {
         float thg[P], hg[D], u[D], jtu[D];
         Lib::eval(gp, thg);
-        apply_xi<Lib>(w, thg, hg);
+        apply_xi<Lib, LIVE>(w, thg, hg);
         sym_uv<D, MSE>(J, h, hg, extra, ws_, acc[SYM0], u, jtu);
 #pragma unroll
         for (int j = 0; j < D; ++j) {
             const float uj = MSE ? ws_ * u[j] : u[j];
 #pragma unroll
-            for (int k = 0; k < P; ++k) acc[NL + j * P + k] = fmaf(jtu[j], th[k], fmaf(-uj, thg[k], acc[NL + j * P + k]));
+            for (int k = 0; k < P; ++k)
+                if (col_live<LIVE>(k)) acc[NL + j * P + k] = fmaf(jtu[j], th[k], fmaf(-uj, thg[k], acc[NL + j * P + k]));
         }
     };
     // residual of one point (MSE form): r = h - dx, sums[0] += r^2; returned for the first group element's `extra`
@@ -192,10 +205,11 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
         hh[0] = h0[0];
         hh[D - 1] = h0[D - 1];
 #pragma unroll
-        for (int k = 1; k < P; ++k) {
-            hh[0] = pk_fma_bcast<0, W_SGPR>(w2[k], t[k], hh[0]);
-            hh[D - 1] = pk_fma_bcast<1, W_SGPR>(w2[k], t[k], hh[D - 1]);
-        }
+        for (int k = 1; k < P; ++k)
+            if (col_live<LIVE>(k)) {
+                hh[0] = pk_fma_bcast<0, W_SGPR>(w2[k], t[k], hh[0]);
+                hh[D - 1] = pk_fma_bcast<1, W_SGPR>(w2[k], t[k], hh[D - 1]);
+            }
         float h[D], hg[D], r[D], u[D], jtu[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) {
@@ -211,8 +225,9 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
         const float2v ub = MSE ? float2v{-(ws_ * u[0]), -(ws_ * u[D - 1])} : float2v{-u[0], -u[D - 1]};
 #pragma unroll
         for (int k = 0; k < P2; ++k)
-            acc2[k] = __builtin_elementwise_fma(ja, __builtin_shufflevector(t[k], t[k], 0, 0),
-                                                __builtin_elementwise_fma(ub, __builtin_shufflevector(t[k], t[k], 1, 1), acc2[k]));
+            if (col_live<LIVE>(k))
+                acc2[k] = __builtin_elementwise_fma(ja, __builtin_shufflevector(t[k], t[k], 0, 0),
+                                                    __builtin_elementwise_fma(ub, __builtin_shufflevector(t[k], t[k], 1, 1), acc2[k]));
     };
     // A point against its group elements.  What is kept of the point from one group element to the next is the visitor's form,
     // fixed at compile time:
@@ -227,7 +242,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
     auto prep = [&](auto keep, const Pt& p) {
         if constexpr (decltype(keep)::value == CACHED) {
             Lib::eval(p.x, p.th);
-            apply_xi<Lib>(w, p.th, p.h);
+            apply_xi<Lib, LIVE>(w, p.th, p.h);
         }
     };
     // (MSE form) the residual's target y: consumed at once where r is kept, kept itself where r is formed per group element
@@ -246,7 +261,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
         } else {
             float th[P], h[D], r[D];
             Lib::eval(p.x, th);
-            apply_xi<Lib>(w, th, h);
+            apply_xi<Lib, LIVE>(w, th, h);
 #pragma unroll
             for (int j = 0; j < D; ++j) r[j] = 0.0f;
             if constexpr (MSE) {
@@ -444,6 +459,11 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
             acc[NL + (D - 1) * P + k] = acc2[k].y;
         }
     }
+    if constexpr (SPARSE) {
+#pragma unroll
+        for (int i = 0; i < D * P; ++i)
+            if (col_live<LIVE>(i % P) && ((live >> (i % P)) & 1ull) == 0) acc[NL + i] = 0.0f;
+    }
     emit_partials<NACC>(acc, ws, fin);
 }
 
@@ -464,13 +484,41 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_reversed_kernel(const floa
 template <class Lib>
 constexpr bool closure_pk_pays = Lib::D == 2 && ((Lib::ORDER == 5 && (Lib::EXP || !Lib::SINE)) || (Lib::ORDER == 4 && Lib::EXP && !Lib::SINE));
 
+// The column set the sparse closures are instantiated for: the constant column and the whole odd degrees.  A planar field
+// that commutes with the rotations has odd degrees only, so the constraint's Q holds nothing but SVD round-off (1e-7 against
+// 0.2-0.4 in the live rows) in the even ones: degree 2 (columns 3-5), degree 4 (10-14) -- at order 5 the set is
+// {0, 1, 2, 6-9, 15-20}, 13 of 21 columns.  A closed family, picked by the launcher: a run-time branch per column would put
+// every two to four FMAs into a basic block of their own.
+template <class Lib>
+constexpr unsigned long long odd_degree_columns() {
+    unsigned long long m = 1ull;
+    for (int deg = 1; deg <= Lib::ORDER; deg += 2)
+        for (int k = poly_terms(Lib::D, deg - 1); k < poly_terms(Lib::D, deg); ++k) m |= 1ull << k;
+    return m;
+}
+// Libraries with a sparse instantiation: the d = 2 plain polynomial ones where the dense closure is bound by vector issue and
+// not by the stream.  tools/micro/closure_ab live on the MI355X, fused closure, three interleaved passes, ms per launch at the
+// bench shape (8192 x 125 000), and sparse / dense at 64 x 50 000 (profiles/closure_live.txt):
+//   order 5   dense packed 5.37-5.39, dense scalar 5.48-5.52   sparse scalar 4.30-4.32   sparse packed 4.37-4.43   small 0.87-0.93
+//   order 4   dense scalar 4.34-4.35, dense packed 4.50-4.52   sparse scalar 3.87-3.88   sparse packed 3.88-3.89   small 0.79-0.85
+//   orders 1-3  dense 3.88-3.94, sparse 3.86-3.95: the stream floor either way -- no instantiation
+// With the even degrees gone the SCALAR body is the faster one at order 5 in every pass (fewer instructions left to pack,
+// and it needs no SGPR pairs), and no slower at order 4: the sparse launch always takes it.  Order 4 then sits on the
+// stream floor of the orders 1-3; order 5 stays 10 % above it.
+template <class Lib>
+constexpr bool closure_live_pays = Lib::D == 2 && !Lib::SINE && !Lib::EXP && (Lib::ORDER == 4 || Lib::ORDER == 5);
+
 // constj: jgx is the compact (S, n_g, D, D) table of a point-constant Jacobian (the CJ kernels, see symreg_reversed_kernel)
-// SYMODE_CLOSURE_PK=0 keeps the scalar body everywhere.  The body a launch took is left in word 1 of the workspace header
-// (WS_BODY_SCALAR / WS_BODY_PACKED): the bodies are bit-identical, so nothing else tells them apart.
+// live: the library columns that may hold a coefficient (bit k = column k, all ones: nothing known).  Where the set lies
+// inside odd_degree_columns and the library has the instantiation, the constant-J launch takes the kernel that leaves the
+// other columns out: their coefficients count as zero, their gradient comes back zero.  Any other set runs the dense kernel.
+// SYMODE_CLOSURE_PK=0 keeps the scalar body everywhere, SYMODE_CLOSURE_LIVE=0 the dense kernels.  What a launch took is left
+// in word 1 of the workspace header (WS_BODY_SCALAR / WS_BODY_PACKED, + WS_BODY_LIVE): the bodies are bit-identical, so
+// nothing else tells them apart.
 template <class Lib>
 hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* gxp, const float* jgx, bool constj, int n_g, long S,
-                                  long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
-                                  float* grad, double* ws, int gx, hipStream_t st) {
+                                  long n, const float* xi, const float* mask, unsigned long long live, float inv_count,
+                                  float w_sym, float* loss, float* grad, double* ws, int gx, hipStream_t st) {
     constexpr int D = Lib::D;
     const bool mse = dx != nullptr;
     const int nacc = (mse ? 2 : 1) + D * Lib::P;
@@ -483,23 +531,32 @@ hipError_t launch_symreg_reversed(const float* x, const float* dx, const float* 
     const bool vec = ((uintptr_t)x % 16 == 0) && ((uintptr_t)gxp % 16 == 0) && (constj || (uintptr_t)jgx % 16 == 0) &&
                      (!mse || (uintptr_t)dx % 16 == 0) && (!multi || ((n * D) % 4 == 0 && (constj || (n * D * D) % 4 == 0)));
     const dim3 grid(gx, (unsigned)S), block(BLOCK);
-    const auto launch = [&](auto cj, auto pk) {         // the kernel family: CJ and the body as compile-time constants
+    // the kernel family: CJ, the body and the column set as compile-time constants
+    const auto launch = [&](auto cj, auto pk, auto sparse) {
         constexpr bool CJ = decltype(cj)::value, PK = decltype(pk)::value;
         constexpr int MINW = (CJ && D == 2 && !Lib::SINE && !Lib::EXP) ? 3 : 1;
+        constexpr unsigned long long LIVE = decltype(sparse)::value ? odd_degree_columns<Lib>() : ~0ull;
         if (mse)
-            symreg_reversed_kernel<Lib, true, 2, 32, CJ, MINW, PK><<<grid, block, 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi, mask,
-                                                                                         w_sym, part, fin);
+            symreg_reversed_kernel<Lib, true, 2, 32, CJ, MINW, PK, LIVE><<<grid, block, 0, st>>>(x, dx, gxp, jgx, n_g, n, vec, xi, mask,
+                                                                                               w_sym, part, fin, live);
         else
-            symreg_reversed_kernel<Lib, false, 2, 32, CJ, MINW, PK><<<grid, block, 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec, xi,
-                                                                                          mask, 1.0f, part, fin);
+            symreg_reversed_kernel<Lib, false, 2, 32, CJ, MINW, PK, LIVE><<<grid, block, 0, st>>>(x, nullptr, gxp, jgx, n_g, n, vec, xi,
+                                                                                                mask, 1.0f, part, fin, live);
     };
     const bool pk = closure_pk_pays<Lib> && constj && knobs().closure_pk;
-    if (pk) {
-        if constexpr (closure_pk_pays<Lib>) launch(std::true_type{}, std::true_type{});
+    bool sparse = false;
+    if constexpr (closure_live_pays<Lib>) {
+        constexpr unsigned long long columns = Lib::P >= 64 ? ~0ull : (1ull << Lib::P) - 1;
+        sparse = constj && knobs().closure_live && (live & columns & ~odd_degree_columns<Lib>()) == 0;
+    }
+    if (sparse) {
+        if constexpr (closure_live_pays<Lib>) launch(std::true_type{}, std::false_type{}, std::true_type{});
+    } else if (pk) {
+        if constexpr (closure_pk_pays<Lib>) launch(std::true_type{}, std::true_type{}, std::false_type{});
     } else if (constj) {
-        launch(std::true_type{}, std::false_type{});
+        launch(std::true_type{}, std::false_type{}, std::false_type{});
     } else {
-        launch(std::false_type{}, std::false_type{});
+        launch(std::false_type{}, std::false_type{}, std::false_type{});
     }
     SYMODE_LAUNCH_CHECK();
     return launch_finalize(fin, part, S, gx, nacc, st);

@@ -23,7 +23,7 @@ constexpr int MAP_CHUNKS_PER_THREAD = SYMODE_MAP_CHUNKS;   // chunks a thread of
 // for the tests and tuning tools that compare two settings inside one process; no launch path calls getenv.
 struct Knobs {
     long max_grid, min_grid_x, map_grid, gram_grid, gram_valu_grid, small_grid, reduce_grid;
-    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk;
+    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live;
     long gram_m4_grid;
 };
 
@@ -48,6 +48,7 @@ inline Knobs read_knobs() {
     k.gram_m4 = on("SYMODE_GRAM_M4");
     k.gram_m4_grid = num("SYMODE_GRAM_M4_GRID", -1);
     k.closure_pk = on("SYMODE_CLOSURE_PK");
+    k.closure_live = on("SYMODE_CLOSURE_LIVE");
     return k;
 }
 
@@ -95,9 +96,10 @@ struct LibOps {
                                 float* loss, float* grad, double* ws, int gx, hipStream_t st);
     // dx == nullptr: the regulariser alone (loss (S)); else the fused closure MSE + w_sym * regulariser (loss (S, 2))
     // constj: the Jacobian is constant over the points of a (problem, group element) and jgx its (S, n_g, d, d) table
+    // live: bit k set = library column k may hold a coefficient (all ones: nothing is known), see launch_symreg_reversed
     hipError_t (*symreg_reversed)(const float* x, const float* dx, const float* gx_, const float* jgx, bool constj, int n_g, long S,
-                                  long n, const float* xi, const float* mask, float inv_count, float w_sym, float* loss,
-                                  float* grad, double* ws, int gx, hipStream_t st);
+                                  long n, const float* xi, const float* mask, unsigned long long live, float inv_count, float w_sym,
+                                  float* loss, float* grad, double* ws, int gx, hipStream_t st);
     hipError_t (*aug_gram)(const float* x, const float* dx, long S, long n, const int* idx, double* gram, double* ws,
                            int gx_mfma, int gx_valu, int gx_m4, hipStream_t st);
     hipError_t (*vjp)(const float* x, const float* g, long n, const float* xi, const float* mask, float* grad_x,
@@ -203,18 +205,33 @@ constexpr bool chunked_stream = !((Lib::D == 3) && (Lib::SINE || Lib::EXP));
 constexpr int VGPR_XI_MAX = 48;     // up to here the masked coefficients simply stay in VGPRs (see load_xi)
 constexpr int SGPR_XI_MAX = 64;     // VGPR_XI_MAX < D*P <= this: Xi in SGPRs (the wave has ~100 of them: d = 3 order 3, d = 4 order 2)
 
+// A compile-time set of library columns as a 64-bit mask (bit k = column k; columns from 64 on are always in it): the
+// columns a kernel instantiated for the set reads and forms sums for.  All ones: every column, the kernels as they were.
+template <unsigned long long LIVE>
+constexpr bool col_live(int k) {
+    return k >= 64 || ((LIVE >> k) & 1ull) != 0;
+}
+
 // Masked coefficients of problem s into registers (uniform across the block -> scalar loads).
-template <class Lib, int SGPR_FROM = VGPR_XI_MAX + 1, int SGPR_TO = SGPR_XI_MAX>
+// LIVE: columns outside the set are not read, their coefficients are zero; `live`: a run-time subset of LIVE (wave-uniform),
+// the columns of LIVE outside it are zero as well.
+template <class Lib, int SGPR_FROM = VGPR_XI_MAX + 1, int SGPR_TO = SGPR_XI_MAX, unsigned long long LIVE = ~0ull>
 __device__ __forceinline__ void load_xi(const float* __restrict__ xi, const float* __restrict__ mask, long s,
-                                        float (&w)[Lib::D * Lib::P]) {
+                                        float (&w)[Lib::D * Lib::P], unsigned long long live = ~0ull) {
     constexpr int DP = Lib::D * Lib::P;
     const float* a = xi + s * DP;
 #pragma unroll
-    for (int i = 0; i < DP; ++i) w[i] = a[i];
+    for (int i = 0; i < DP; ++i) w[i] = col_live<LIVE>(i % Lib::P) ? a[i] : 0.0f;
+    if constexpr (LIVE != ~0ull) {
+#pragma unroll
+        for (int i = 0; i < DP; ++i)
+            if (col_live<LIVE>(i % Lib::P) && ((live >> (i % Lib::P)) & 1ull) == 0) w[i] = 0.0f;
+    }
     if (mask != nullptr) {
         const float* m = mask + s * DP;
 #pragma unroll
-        for (int i = 0; i < DP; ++i) w[i] *= m[i];
+        for (int i = 0; i < DP; ++i)
+            if (col_live<LIVE>(i % Lib::P)) w[i] *= m[i];
     }
     // The masked product is a VALU result and stays in VGPRs for small libraries: an SGPR operand costs issue time
     // (constant-bus read; measured with the register-ring kernel: Xi in VGPRs +1.5 % at d = 2 order 5, +4.5 % at order 3).
@@ -224,19 +241,22 @@ __device__ __forceinline__ void load_xi(const float* __restrict__ xi, const floa
     if constexpr (DP >= SGPR_FROM && DP <= SGPR_TO) {
 #pragma unroll
         for (int i = 0; i < DP; ++i)
-            w[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w[i])));
+            if (col_live<LIVE>(i % Lib::P))
+                w[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w[i])));
     }
 }
 
 // h = Theta . Xi_m^T for one point (fp32 fma chain over the library columns).
-template <class Lib>
+// LIVE: the chain's links of the columns outside the set are left out (their coefficient is zero: fma(0, t, s) = s).
+template <class Lib, unsigned long long LIVE = ~0ull>
 __device__ __forceinline__ void apply_xi(const float (&w)[Lib::D * Lib::P], const float (&th)[Lib::P],
                                          float (&h)[Lib::D]) {
 #pragma unroll
     for (int j = 0; j < Lib::D; ++j) {
         float s = 0.0f;
 #pragma unroll
-        for (int k = 0; k < Lib::P; ++k) s = fmaf(w[j * Lib::P + k], th[k], s);
+        for (int k = 0; k < Lib::P; ++k)
+            if (col_live<LIVE>(k)) s = fmaf(w[j * Lib::P + k], th[k], s);
         h[j] = s;
     }
 }
@@ -420,7 +440,8 @@ __global__ __launch_bounds__(BLOCK) void odeint_kernel(const float* __restrict__
 constexpr unsigned long long WS_MAGIC = 0x53594d4f44453032ull;      // "SYMODE02"
 constexpr long WS_MAX_PROBLEMS = 65536;                              // tickets in the header (grid.y limit is 65535)
 constexpr int WS_BODY_WORD = 1;                                      // header word the reversed closure leaves its body in:
-constexpr unsigned long long WS_BODY_SCALAR = 1, WS_BODY_PACKED = 2; //   which of its two bit-identical bodies the last launch took
+constexpr unsigned long long WS_BODY_SCALAR = 1, WS_BODY_PACKED = 2; //   which of its two bit-identical bodies the last launch took,
+constexpr unsigned long long WS_BODY_LIVE = 4;                       //   + this where it was the form that leaves out dead columns
 constexpr long WS_HEADER_DOUBLES = 8 + WS_MAX_PROBLEMS / 2;          // [magic, 7 reserved | uint32 tickets] in front of the partials
 
 struct Finish {

@@ -58,6 +58,12 @@ _SIGNATURES = {
     "symode_loss_grad_reversed_constj": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int,
                                                  c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
                                                  c_void_p]),
+    "symode_symreg_reversed_batched_constj_live": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int,
+                                                           c_void_p, c_void_p, ctypes.c_ulonglong, c_float, c_void_p, c_void_p,
+                                                           c_void_p, c_size_t, c_void_p]),
+    "symode_loss_grad_reversed_constj_live": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int,
+                                                      c_int, c_void_p, c_void_p, ctypes.c_ulonglong, c_float, c_float, c_void_p,
+                                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_loss_grad_latent": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
                                         c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
@@ -607,11 +613,13 @@ class HipEngine:
             raise SymodeError("private workspace too small for this call")
         return loss, grad, ws, 1.0 / (n * d) if inv_count is None else float(inv_count)
 
-    def _closure_call(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, stream):
+    def _closure_call(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, stream, live=None):
         """One closure launch, ready to go: (entry name, its argument tuple, the tensors the arguments point into, what
         the caller gets back).  ``dx`` None: the regulariser alone; ``rev`` None: the MSE alone, else what
-        _reversed_operands returned.  The ONE statement of the closures' C signatures: the eager methods call
-        ``getattr(lib, name)(*args)``, bind_closure converts ``args`` once and keeps the call."""
+        _reversed_operands returned; ``live``: the set of library columns that may hold a coefficient (an int, bit k =
+        column k), honoured by the compact-table forms (their _live entries) and without effect elsewhere.  The ONE
+        statement of the closures' C signatures: the eager methods call ``getattr(lib, name)(*args)``, bind_closure
+        converts ``args`` once and keeps the call."""
         batched, S, n, d = self._problems(x)
         xi, mask, p = self._coef(xi, mask, d, order, flags, S, pinned_ok=True)
         fused = dx is not None and rev is not None
@@ -619,19 +627,23 @@ class HipEngine:
         head = (self._ptr(x),) if dx is None else (self._ptr(x), self._ptr(dx))
         keep = (x, dx, xi, mask, loss, grad, ws)
         name = "symode_loss_grad"
+        live_arg = ()
         if rev is not None:
             gx, jgx, n_g, constj = rev
             head += (self._ptr(gx), self._ptr(jgx), n_g)
             keep += (gx, jgx)
             name = ("symode_loss_grad_reversed" if fused else "symode_symreg_reversed_batched") + ("_constj" if constj else "")
-        args = head + (S, n, d, order, flags, self._ptr(xi), self._ptr(mask), inv) + ((float(w_sym),) if fused else ()) \
+            if constj and live is not None:
+                name, live_arg = name + "_live", (int(live) & 0xFFFFFFFFFFFFFFFF,)
+        args = head + (S, n, d, order, flags, self._ptr(xi), self._ptr(mask)) + live_arg + (inv,) + ((float(w_sym),) if fused else ()) \
             + (self._ptr(loss), self._ptr(grad), self._ptr(ws), ws.numel() * 8, stream)
         # the outputs in the caller's form: the batch axis is there only if x had one
         loss, grad = loss.reshape(S, 2) if fused else loss.reshape(S), grad.reshape(S, d, p)
         return name, args, keep, (loss, grad) if batched else (loss[0], grad[0])
 
-    def _closure(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws):
-        name, args, _, result = self._closure_call(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, self._stream(x))
+    def _closure(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live=None):
+        name, args, _, result = self._closure_call(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, self._stream(x),
+                                                   live)
         self._check(getattr(self.lib, name)(*args), name)
         return result
 
@@ -695,16 +707,17 @@ class HipEngine:
                                                   self._ptr(ws), ws.numel() * 8, self._stream(z)), "symode_symreg_linear")
         return loss[0], grad
 
-    def symreg_reversed(self, x, gx, jgx, xi, mask, order, flags=0, out=None, ws=None, inv_count=None):
+    def symreg_reversed(self, x, gx, jgx, xi, mask, order, flags=0, out=None, ws=None, inv_count=None, live_columns=None):
         """Reversed symmetry regulariser on precomputed (g(x), J_g(x)).
         One problem: x (N, d), gx (n_g, N, d), jgx (n_g, N, d, d), xi / mask (d, p) -> (loss scalar, grad (d, p)).
         S problems in one launch: x (S, N, d), gx (S, n_g, N, d), jgx (S, n_g, N, d, d), xi / mask (S, d, p) -> ((S,), (S, d, p)).
         ``xi`` / ``out`` may be pinned host tensors for the one-problem form; ``inv_count`` as in loss_grad.
         A point-constant Jacobian may be given as its compact table, jgx (n_g, d, d) / (S, n_g, d, d) (``jacobian_constant``):
-        the shape alone selects the kernel form that streams nothing of J_g; the results are bit-identical."""
+        the shape alone selects the kernel form that streams nothing of J_g; the results are bit-identical.
+        ``live_columns`` as in loss_grad_reversed."""
         x = self._dev(x, "x")
         rev = self._reversed_operands(x, gx, jgx, min_n_g=0, compact_ok=True)
-        return self._closure(x, None, rev, xi, mask, order, flags, None, inv_count, out, ws)
+        return self._closure(x, None, rev, xi, mask, order, flags, None, inv_count, out, ws, live_columns)
 
     def jacobian_constant(self, jgx):
         """Is J_g the same matrix at every point of each (problem, group element)?  jgx (S, n_g, N, d, d) or (n_g, N, d, d)
@@ -726,21 +739,26 @@ class HipEngine:
     @staticmethod
     def closure_body(ws):
         """Which body the last reversed-closure launch on workspace ``ws`` took: "scalar", "packed" (the packed-fp32 body of the
-        compact-table form, d = 2; SYMODE_CLOSURE_PK=0 turns it off) or None before any.  The kernel leaves it in word 1 of the
+        compact-table form, d = 2; SYMODE_CLOSURE_PK=0 turns it off), either with "-live" where it was the kernel that leaves out
+        the columns outside ``live_columns`` (SYMODE_CLOSURE_LIVE=0 turns that off), or None before any.  The kernel leaves it in word 1 of the
         workspace header (an initialised workspace only, and only its LAST launch is visible): the two bodies return the same
         bits, so the results cannot tell.  One synchronisation."""
-        return {1: "scalar", 2: "packed"}.get(int(ws.view(torch.int64)[1].item()))
+        return {1: "scalar", 2: "packed", 5: "scalar-live", 6: "packed-live"}.get(int(ws.view(torch.int64)[1].item()))
 
-    def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None):
+    def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None,
+                           live_columns=None):
         """The closure MSE + w_sym * reversed regulariser in ONE pass (x read once, Theta(x) shared by both terms).
         Shapes as loss_grad / symreg_reversed (jgx may be the compact table of a point-constant Jacobian, as there).
         Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mse, regulariser), grad = d(mse + w_sym * regulariser)/dXi
-        (S, d, p) [or (d, p)]."""
+        (S, d, p) [or (d, p)].
+        ``live_columns``: an int, bit k set = library column k may hold a coefficient (``CoefMap.live_mask``); with the compact
+        table the call goes to the _live entry (symode.h): columns outside the set count as zero, their gradient is zero,
+        and where the library has a kernel for the set it leaves their per-point work out.  None: every column."""
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
         rev = self._reversed_operands(x, gx, jgx, compact_ok=True)
-        return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws)
+        return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live_columns)
 
     def loss_grad_latent(self, z, dz, B, y, xi, mask, order, flags=0, w_pair=1.0, inv_count=None, out=None, ws=None):
         """The closure of the latent fit in ONE pass (symode_loss_grad_latent): z, dz, y (S, N, d) or (N, d), B (S, N, d, d)

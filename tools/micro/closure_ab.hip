@@ -8,6 +8,8 @@
 // `closure_ab pk`: scalar body against the packed-fp32 body (PK) of the constant-Jacobian fused closure for the d = 2
 // libraries, at the bench's batched shape and at 64 x 50 000, on the launcher's grids, three interleaved passes.  The
 // launcher's table (closure_rev.hpp, closure_pk_pays) is read off this run.
+// `closure_ab live`: every column against the constant + odd-degree column set (LIVE) of the constant-Jacobian fused closure
+// for the d = 2 plain libraries, both bodies at orders 4-5, same shapes and passes.  closure_live_pays is read off this run.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -I symmetry-ode-discovery_amd/csrc
 //              -o tools/micro/closure_ab tools/micro/closure_ab.hip
 #include <hip/hip_runtime.h>
@@ -221,6 +223,34 @@ int main(int argc, char** argv) {
                                                         x, dx, gx, jgx, 1, Nx, true, xiw, nullptr, 0.1f, part, fin2); }, 5);
                     printf("pass %d  %5ld x %6ld  order 5 flags 0 (p = 21)  packed, ring 3 %8.1f us\n", pass, Sx, Nx, r3);
                 }
+            }
+        CK(hipDeviceSynchronize());
+        return 0;
+    }
+    if (argc > 1 && strcmp(argv[1], "live") == 0) {
+        printf("# fused closure, constant J (24 B/point), every column | constant + odd degrees only: us per launch (min of 3 rounds of 5), three passes\n");
+        const long shapes[2][2] = {{S, NB}, {64, 50000}};
+#define LVRUN(ORDER, PKB)                                                                                                          \
+    {                                                                                                                              \
+        using LB = Library<2, ORDER, 0>;                                                                                           \
+        constexpr unsigned long long LV = odd_degree_columns<LB>();                                                                \
+        const double a_ = time_us([&] { symreg_reversed_kernel<LB, true, 2, 32, true, 3, PKB><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
+                                            x, dx, gx, jgx, 1, Nx, true, xi5, nullptr, 0.1f, part, fin2); }, 5);                   \
+        const double b_ = time_us([&] { symreg_reversed_kernel<LB, true, 2, 32, true, 3, PKB, LV><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
+                                            x, dx, gx, jgx, 1, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5);               \
+        printf("pass %d  %5ld x %6ld  order %d (p = %2d) %s  dense %8.1f us  sparse %8.1f us  sparse/dense %.3f\n", pass, Sx, Nx,   \
+               ORDER, LB::P, PKB ? "packed" : "scalar", a_, b_, b_ / a_);                                                          \
+    }
+        for (int pass = 0; pass < 3; ++pass)
+            for (const auto& sh : shapes) {
+                const long Sx = sh[0], Nx = sh[1];
+                const int gxw = grid_x_for(Nx, Sx, 2, 512);
+                if ((long)gxw * Sx > max_rows) {
+                    fprintf(stderr, "grid %d x %ld needs more partial rows than the workspace holds\n", gxw, Sx);
+                    return 1;
+                }
+                LVRUN(1, false) LVRUN(2, false) LVRUN(3, false) LVRUN(4, false) LVRUN(5, false)
+                LVRUN(4, true) LVRUN(5, true)
             }
         CK(hipDeviceSynchronize());
         return 0;
