@@ -476,6 +476,41 @@ int symode_trainer_epoch_end(const symode_trainer* T, int epoch, void* stream);
  * log_test.  Problems that finished earlier cost empty launches only. */
 int symode_trainer_run(const symode_trainer* T, int epoch0, int n_epochs, int test_eval, void* stream);
 
+/* A hyper-parameter grid on shared Gram matrices: the Gram-form trainer with a per-problem table.  A grid point changes only
+ * four numbers around the fixed matrices of symode_quad_closure -- step size, L1 weight, threshold, weight of R against G --
+ * so n_problems = grid points x seeds problems fit from n_sets = seeds sets of matrices: problem s reads set s % n_sets and
+ * row s of hyper wherever the launch-wide scalar of symode_trainer stood (lr: the step length, first iteration included;
+ * w_reg: L1 value and gradient, 0 for every problem when base.l1 == 0; threshold: thresholding event and near count, near_band
+ * stays launch-wide; w_sym: the pair's weight in loss value and gradient, not read without rev_gram).  One wave per problem
+ * in every launch and no arithmetic shared between problems: problem s is bit for bit the one-problem scalar trainer on set
+ * s % n_sets at row s's values.  State block, symode_trainer_layout and symode_trainer_init are the scalar trainer's, on
+ * &G->base.  The four entries are symode_trainer_closure / _update / _epoch_end / _run with the table; each refuses, before
+ * anything is launched: G, hyper or aug_gram NULL (SYMODE_E_NULLPTR); base.closure != SYMODE_CLOSURE_GRAM, n_sets < 1 or
+ * n_problems % n_sets != 0 (SYMODE_E_BADSIZE); hyper not 16-byte aligned (SYMODE_E_ALIGN); then whatever the scalar entry
+ * refuses, with its code.
+ * replaces: one sweep of a run script per value of --lr_sindy / --w_sindy_reg / --threshold / --w_sym_reg (new: the
+ * reference has no hyper-parameter search; every value is a loop of per-seed processes). */
+#define SYMODE_TRAINER_HYPER 4          /* columns of hyper: lr, w_reg, threshold, w_sym */
+typedef struct symode_trainer_grid {
+    symode_trainer base;   /* closure must be SYMODE_CLOSURE_GRAM; n_problems counts ALL problems (grid points x seeds);
+                              its lr, w_reg, threshold and w_sym are not read */
+    const float* hyper;    /* (n_problems, SYMODE_TRAINER_HYPER) fp32, device memory, 16-byte aligned */
+    long n_sets;           /* aug_gram is (n_sets, p+d, p+d), rev_gram (n_sets, d p, d p) or NULL;
+                              problem s reads set s % n_sets */
+} symode_trainer_grid;
+int symode_trainer_grid_closure(const symode_trainer_grid* G, float* loss_out, float* grad_out, void* stream);
+int symode_trainer_grid_update(const symode_trainer_grid* G, int mode, void* stream);
+int symode_trainer_grid_epoch_end(const symode_trainer_grid* G, int epoch, void* stream);
+int symode_trainer_grid_run(const symode_trainer_grid* G, int epoch0, int n_epochs, int test_eval, void* stream);
+
+/* symode_quad_closure for n_problems problems on n_sets sets of matrices (n_problems % n_sets == 0, else SYMODE_E_BADSIZE):
+ * problem s reads aug_gram[s % n_sets] (and rev_gram[s % n_sets]) and, with rev_gram, takes w_sym from column 3 of row s of
+ * hyper (n_problems, SYMODE_TRAINER_HYPER) fp32; without rev_gram the table is not read.  Outputs as symode_quad_closure.
+ * replaces: the closure of symode_quad_closure, once per grid point. */
+int symode_quad_closure_grid(const double* aug_gram, const double* rev_gram, long n_sets, long n_problems, int d, int p,
+                             const float* xi, const float* mask, double inv_count, const float* hyper /* (n_problems, 4) */,
+                             float* loss_out, float* grad_out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Device-resident minibatch Adam trainer: n_epochs whole epochs of train_SIGED's plain branch (no latent space, no symmetry
  * regulariser) for n_problems independent problems in ONE launch, one workgroup per problem, nothing on the host inside.

@@ -443,6 +443,19 @@ int symode_quad_closure(const double* aug_gram, const double* rev_gram, long n_p
                                     (hipStream_t)stream);
 }
 
+int symode_quad_closure_grid(const double* aug_gram, const double* rev_gram, long n_sets, long n_problems, int d, int p,
+                             const float* xi, const float* mask, double inv_count, const float* hyper, float* loss_out,
+                             float* grad_out, void* stream) {
+    if (n_problems < 1 || n_problems > 2147483647L || d < 1 || p < 1 || d * p > QUAD_MAX_DP) return SYMODE_E_BADSIZE;
+    if (n_sets < 1 || n_problems % n_sets != 0) return SYMODE_E_BADSIZE;
+    if (!aug_gram || !xi || !hyper || !loss_out || !grad_out) return SYMODE_E_NULLPTR;
+    if (misaligned(aug_gram, 8) || misaligned(rev_gram, 8) || misaligned(xi, 4) || misaligned(mask, 4) || misaligned(hyper, 4) ||
+        misaligned(loss_out, 4) || misaligned(grad_out, 4))
+        return SYMODE_E_ALIGN;
+    return (int)launch_quad_closure_grid(aug_gram, rev_gram, (int)n_sets, n_problems, d, p, xi, mask, inv_count, hyper, loss_out,
+                                         grad_out, (hipStream_t)stream);
+}
+
 int symode_symreg_reversed(const float* x, const float* gx_, const float* jgx, int n_g, long n, int d, int order,
                            int flags, const float* xi, const float* mask, float* loss_out, float* grad_out,
                            void* workspace, size_t workspace_bytes, void* stream) {

@@ -116,10 +116,17 @@ struct AcceptArgs {
     const float* new_g;      // (S, n)  its gradient [(S, d p) = d/dXi under a coefficient map, see XiMap]
     float tol_grad;
     int l1;                  // != 0: new_loss / new_g are the bare data term, objective = w_x * data + w_reg * |params|_1
-    float w_x, w_reg;
+    float w_x, w_reg;        // (per-problem table: w_reg only gates the table's column -- 0 switches the L1 term off for all)
     int pair;                // != 0: new_loss holds (mse, regulariser) per problem, data term = mse + w_pair * regulariser
     float w_pair;
 };
+
+// The per-problem table of a grid trainer (symode_trainer_grid): row s = [lr, w_reg, threshold, w_sym] takes the place of the
+// launch-wide scalars of problem s.  Whether a kernel reads it is a template bit (LB_PER_PROBLEM or-ed to the mode, a bool
+// elsewhere), not a test of the pointer: the scalar instantiations keep the code, and the register allocation, they had.
+constexpr int LB_HYPER = SYMODE_TRAINER_HYPER;
+constexpr int LB_PER_PROBLEM = 4;
+static_assert(LB_HYPER == 4, "a row of the table is read as one 16-byte load");
 
 // The trainer's parametrisation of the coefficients (sindy.py:169-176): under the equivariance constraint the
 // optimisation variables are [beta (r) | const (d)] and Xi (d, p) = reshape(Q beta) (+ const in column 0); q holds Q with
@@ -152,9 +159,11 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
                                                             long* __restrict__ head, long* __restrict__ count,
                                                             float* __restrict__ h_diag, float* __restrict__ prev_g,
                                                             float* __restrict__ prev_loss, int n, int H, float lr,
-                                                            float tol_change, AcceptArgs acc, XiMap map, TrainerHook hook) {
+                                                            float tol_change, AcceptArgs acc, XiMap map, TrainerHook hook,
+                                                            const float* __restrict__ hyper) {
     constexpr bool STAGED = NC > 0;
-    constexpr bool BEGIN = MODE == LB_BEGIN;
+    constexpr bool HYPER = (MODE & LB_PER_PROBLEM) != 0;
+    constexpr bool BEGIN = (MODE & ~LB_PER_PROBLEM) == LB_BEGIN;
     __shared__ float al[LB_MAXH];
     __shared__ float cvt[WAVE * LB_MAXC];                    // coefficient map: d/dXi on the way in, parameters on the way out
     extern __shared__ float staged[];                        // STAGED: pad [n] | Y [H][n] | S [H][n] | ro [H] | 256 floats of padding
@@ -168,6 +177,8 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
     const unsigned char act_in = BEGIN ? (unsigned char)1 : act[s];
     const float t_in = t[s], hd_in = h_diag[s], prev_loss_in = prev_loss[s];
     const long ni_in = n_iter[s], count_in = count[s], head_in = head[s];
+    float4 row = {0.0f, 0.0f, 0.0f, 0.0f};                   // HYPER: this problem's [lr, w_reg, threshold, w_sym], one load of the batch
+    if constexpr (HYPER) row = *reinterpret_cast<const float4*>(hyper + s * LB_HYPER);
     float d_in[LB_MAXC], pg_in[LB_MAXC];
 #pragma unroll
     for (int c = 0; c < LB_MAXC; ++c) {
@@ -192,7 +203,8 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
     // lifetime of its locals, and without it every instantiation gets another register allocation than the one measured.
     {
         const float tt = BEGIN ? 0.0f : t_in;
-        float nl = acc.pair ? fmaf(acc.w_pair, acc.new_loss[2 * s + 1], acc.new_loss[2 * s]) : acc.new_loss[s];
+        const float w_pair = HYPER ? row.w : acc.w_pair, w_reg = HYPER ? (acc.w_reg != 0.0f ? row.y : 0.0f) : acc.w_reg;
+        float nl = acc.pair ? fmaf(w_pair, acc.new_loss[2 * s + 1], acc.new_loss[2 * s]) : acc.new_loss[s];
         float gmax = 0.0f, dmax = 0.0f, p_l1 = 0.0f;
         if (map.q != nullptr) {                              // d/dXi (d p) -> LDS; each lane then forms its parameter's gradient
 #pragma unroll
@@ -219,7 +231,7 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
                 if (acc.l1) {                                // train.py:680-688 as the tensor ops do it: products rounded, one add
                     const float pv = params[s * n + i];
                     const float sg = (float)(pv > 0.0f) - (float)(pv < 0.0f);      // torch.sign: 0 at 0 and at NaN
-                    v = __fadd_rn(__fmul_rn(acc.w_x, v), __fmul_rn(acc.w_reg, sg));
+                    v = __fadd_rn(__fmul_rn(acc.w_x, v), __fmul_rn(w_reg, sg));
                     p_l1 += fabsf(pv);
                 }
                 g[s * n + i] = v;
@@ -233,7 +245,7 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
         dmax = wave_amax(dmax);
         if (acc.l1) {
             const float l1 = wave_sum(p_l1);
-            nl = __fadd_rn(__fmul_rn(acc.w_x, nl), __fmul_rn(acc.w_reg, l1));
+            nl = __fadd_rn(__fmul_rn(acc.w_x, nl), __fmul_rn(w_reg, l1));
             if (hook.l1_last != nullptr && lane == 0) hook.l1_last[s] = l1;
         }
         // BEGIN: torch's "optimal condition" at the top of step() -- `if flat_grad.abs().max() <= tolerance_grad: return`,
@@ -429,7 +441,8 @@ __global__ __launch_bounds__(WAVE) void lbfgs_update_kernel(float* __restrict__ 
         p_abs += fabsf(gv[c]);
         p_gtd = fmaf(gv[c], q[c], p_gtd);
     }
-    const float tn = first ? fminf(1.0f, 1.0f / wave_sum_dpp_uniform(p_abs)) * lr : lr;
+    const float lr_s = HYPER ? row.x : lr;
+    const float tn = first ? fminf(1.0f, 1.0f / wave_sum_dpp_uniform(p_abs)) * lr_s : lr_s;
     const float gtd = wave_sum_dpp_uniform(p_gtd);
     const bool live = !(gtd > -tol_change);
     if (map.q != nullptr && live) __syncthreads();           // (cvt still holds d/dXi of this launch's first half)
@@ -507,7 +520,7 @@ namespace symode {
 inline int launch_lbfgs_update(int mode, float* params, float* g, float* loss, unsigned char* act, long* n_iter, float* d, float* t,
                                float* old_dirs, float* old_stps, float* ro, long* head, long* count, float* h_diag, float* prev_g,
                                float* prev_loss, long n_problems, int n, int history, float lr, float tol_change, AcceptArgs acc,
-                               XiMap map, TrainerHook hook, void* stream) {
+                               XiMap map, TrainerHook hook, void* stream, const float* hyper = nullptr) {
     if (n_problems < 1 || n < 1 || n > WAVE * LB_MAXC || history < 1 || history > LB_MAXH) return SYMODE_E_BADSIZE;
     if (!params || !g || !loss || !act || !n_iter || !d || !t || !old_dirs || !old_stps || !ro || !head || !count || !h_diag ||
         !prev_g || !prev_loss || !acc.new_loss || !acc.new_g)
@@ -518,10 +531,13 @@ inline int launch_lbfgs_update(int mode, float* params, float* g, float* loss, u
 #define SYMODE_LBFGS_LAUNCH(NC_, MODE_, BYTES_)                                                                                   \
     lbfgs_update_kernel<NC_, MODE_><<<dim3((unsigned)n_problems), dim3(WAVE), BYTES_, (hipStream_t)stream>>>(                     \
         params, g, loss, act, n_iter, d, t, old_dirs, old_stps, ro, head, count, h_diag, prev_g, prev_loss, n, history, lr,       \
-        tol_change, acc, map, hook)
+        tol_change, acc, map, hook, hyper)
+    // hyper picks the instantiations that read the per-problem rows
 #define SYMODE_LBFGS_UPDATE(NC_, BYTES_)                                                                                          \
     do {                                                                                                                          \
-        if (mode == LB_BEGIN) SYMODE_LBFGS_LAUNCH(NC_, LB_BEGIN, BYTES_);                                                         \
+        if (hyper != nullptr && mode == LB_BEGIN) SYMODE_LBFGS_LAUNCH(NC_, LB_BEGIN | LB_PER_PROBLEM, BYTES_);                    \
+        else if (hyper != nullptr) SYMODE_LBFGS_LAUNCH(NC_, LB_ACCEPT | LB_PER_PROBLEM, BYTES_);                                  \
+        else if (mode == LB_BEGIN) SYMODE_LBFGS_LAUNCH(NC_, LB_BEGIN, BYTES_);                                                    \
         else SYMODE_LBFGS_LAUNCH(NC_, LB_ACCEPT, BYTES_);                                                                         \
     } while (0)
     switch (nc) {
@@ -691,13 +707,17 @@ struct EpochArgs {
     float *log, *log_xi, *log_mask, *log_params;
     int n, r, dp, pair, st_freq, epoch, slot;
     float threshold, tol_update, near_band;
+    const float* hyper;      // HYPER: (S, LB_HYPER), column 2 is the problem's threshold
 };
 
 // The per-epoch logic of train.py:697-725 for one problem per wavefront (statement numbers of the reference in comments).
+template <bool HYPER>
 __global__ __launch_bounds__(WAVE) void trainer_epoch_kernel(EpochArgs a) {
     const long s = blockIdx.x;
     const long S = gridDim.x;
     const int lane = threadIdx.x;
+    float thr = a.threshold;                                 // HYPER: the problem's own, requested before the first wait
+    if constexpr (HYPER) thr = a.hyper[s * LB_HYPER + 2];
     float* rec = a.log + ((long)a.slot * S + s) * 8;
     if (__builtin_amdgcn_readfirstlane((int)a.done[s])) {
         if (lane == 0) { rec[0] = -1.0f; rec[7] = (float)a.epoch; }
@@ -736,8 +756,8 @@ __global__ __launch_bounds__(WAVE) void trainer_epoch_kernel(EpochArgs a) {
             const int j = lane + WAVE * c;
             if (j < a.dp) {
                 const float av = fabsf(a.xi[s * a.dp + j]), m = a.mask[s * a.dp + j];
-                near_here += (fabsf(av - a.threshold) < a.near_band) && (m > 0.0f);
-                a.mask[s * a.dp + j] = (av > a.threshold && m > 0.0f) ? 1.0f : 0.0f;     // strict >, monotone
+                near_here += (fabsf(av - thr) < a.near_band) && (m > 0.0f);
+                a.mask[s * a.dp + j] = (av > thr && m > 0.0f) ? 1.0f : 0.0f;             // strict >, monotone
             }
         }
         near_here = (int)wave_sum((float)near_here);
@@ -815,8 +835,29 @@ extern "C" int symode_trainer_init(const symode_trainer* T, const float* params0
     return e == hipSuccess ? SYMODE_OK : (int)e;
 }
 
-extern "C" int symode_trainer_closure(const symode_trainer* T, float* loss_out, float* grad_out, void* stream) {
-    using namespace symode;
+namespace symode {
+
+// A trainer as its launches see it: the descriptor, and a grid trainer's table and number of matrix sets (hyper == nullptr:
+// the scalar trainer, whose launches are the ones they were).  The four functions below are the trainer; the symode_trainer_*
+// and symode_trainer_grid_* entries differ only in how they make the view.
+struct TrainerView {
+    const symode_trainer* T;
+    const float* hyper;
+    long n_sets;
+};
+
+// what a grid trainer refuses on top of trainer_state, before anything is launched (symode.h)
+inline int trainer_grid_view(const symode_trainer_grid* G, TrainerView& v) {
+    if (!G || !G->hyper || !G->base.aug_gram) return SYMODE_E_NULLPTR;
+    if (G->base.closure != SYMODE_CLOSURE_GRAM) return SYMODE_E_BADSIZE;
+    if (G->n_sets < 1 || G->base.n_problems % G->n_sets != 0) return SYMODE_E_BADSIZE;
+    if (((uintptr_t)G->hyper % 16) != 0) return SYMODE_E_ALIGN;
+    v = TrainerView{&G->base, G->hyper, G->n_sets};
+    return SYMODE_OK;
+}
+
+inline int trainer_closure(const TrainerView& v, float* loss_out, float* grad_out, void* stream) {
+    const symode_trainer* T = v.T;
     TrainerState st;
     int dp;
     if (int rc = trainer_state(T, st, dp)) return rc;
@@ -824,6 +865,9 @@ extern "C" int symode_trainer_closure(const symode_trainer* T, float* loss_out, 
     float* go = grad_out ? grad_out : st.cl_grad;
     switch (st.closure.kind) {
         case SYMODE_CLOSURE_GRAM:
+            if (v.hyper != nullptr)
+                return symode_quad_closure_grid(T->aug_gram, T->rev_gram, v.n_sets, T->n_problems, T->d, dp / T->d, st.xi, st.mask,
+                                                (double)T->inv_count, v.hyper, lo, go, stream);
             return symode_quad_closure(T->aug_gram, T->rev_gram, T->n_problems, T->d, dp / T->d, st.xi, st.mask, (double)T->inv_count,
                                        T->w_sym, lo, go, stream);
         case SYMODE_CLOSURE_LATENT:                          // w_pair = 0: the gradient is the z-term's alone (symode.h)
@@ -840,20 +884,22 @@ extern "C" int symode_trainer_closure(const symode_trainer* T, float* loss_out, 
     }
 }
 
-extern "C" int symode_trainer_update(const symode_trainer* T, int mode, void* stream) {
-    using namespace symode;
+inline int trainer_update(const TrainerView& v, int mode, void* stream) {
+    const symode_trainer* T = v.T;
     TrainerState st;
     int dp;
     if (int rc = trainer_state(T, st, dp)) return rc;
     if (mode != LB_ACCEPT && mode != LB_BEGIN) return SYMODE_E_BADSIZE;
+    // (with the table, w_reg only gates the table's column: AcceptArgs)
+    const float w_reg = v.hyper != nullptr ? (T->l1 ? 1.0f : 0.0f) : (T->l1 ? T->w_reg : 0.0f);
     return launch_lbfgs_update(mode, st.params, st.g, st.loss, st.act, st.n_iter, st.d, st.t, st.old_dirs, st.old_stps, st.ro, st.head,
                                st.count, st.h_diag, st.prev_g, st.prev_loss, T->n_problems, T->n_params, T->history, T->lr, T->tol_change,
-                               AcceptArgs{st.cl_loss, st.cl_grad, T->tol_grad, 1, T->w_x, T->l1 ? T->w_reg : 0.0f, st.closure.pair, T->w_sym},
-                               trainer_map(T, st, dp), TrainerHook{st.done, st.l1_last}, stream);
+                               AcceptArgs{st.cl_loss, st.cl_grad, T->tol_grad, 1, T->w_x, w_reg, st.closure.pair, T->w_sym},
+                               trainer_map(T, st, dp), TrainerHook{st.done, st.l1_last}, stream, v.hyper);
 }
 
-extern "C" int symode_trainer_epoch_end(const symode_trainer* T, int epoch, void* stream) {
-    using namespace symode;
+inline int trainer_epoch_end(const TrainerView& v, int epoch, void* stream) {
+    const symode_trainer* T = v.T;
     TrainerState st;
     int dp;
     if (int rc = trainer_state(T, st, dp)) return rc;
@@ -862,28 +908,75 @@ extern "C" int symode_trainer_epoch_end(const symode_trainer* T, int epoch, void
     EpochArgs a{st.params, st.prev, st.pprev, st.xi, st.mask, st.n_iter, st.head, st.count, st.h_diag, st.n_iters, st.done, st.nan,
                 st.finished, st.epochs, st.near, st.cl_loss, st.l1_last, T->log, T->log_xi, T->log_mask, T->log_params, T->n_params,
                 T->q_eff ? T->r : 0, dp, st.closure.pair, T->st_freq, epoch, epoch % T->log_epochs, T->threshold, T->tol_update,
-                T->near_band};
-    trainer_epoch_kernel<<<dim3((unsigned)T->n_problems), dim3(WAVE), 0, (hipStream_t)stream>>>(a);
+                T->near_band, v.hyper};
+    if (v.hyper != nullptr)
+        trainer_epoch_kernel<true><<<dim3((unsigned)T->n_problems), dim3(WAVE), 0, (hipStream_t)stream>>>(a);
+    else
+        trainer_epoch_kernel<false><<<dim3((unsigned)T->n_problems), dim3(WAVE), 0, (hipStream_t)stream>>>(a);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? SYMODE_OK : (int)e;
 }
 
-extern "C" int symode_trainer_run(const symode_trainer* T, int epoch0, int n_epochs, int test_eval, void* stream) {
-    using namespace symode;
+// the epoch sequence, stated once: closure, BEGIN, (closure, ACCEPT) x (max_iter - 1), epoch end [, the test closure]
+inline int trainer_run(const TrainerView& v, int epoch0, int n_epochs, int test_eval, void* stream) {
+    const symode_trainer* T = v.T;
     TrainerState st;
     int dp;
     if (int rc = trainer_state(T, st, dp)) return rc;
     if (epoch0 < 0 || n_epochs < 0) return SYMODE_E_BADSIZE;
     for (int e = epoch0; e < epoch0 + n_epochs; ++e) {
         for (int it = 0; it < T->max_iter; ++it) {           // torch.optim.LBFGS.step: max_iter moves, max_iter evaluations
-            if (int rc = symode_trainer_closure(T, nullptr, nullptr, stream)) return rc;
-            if (int rc = symode_trainer_update(T, it == 0 ? LB_BEGIN : LB_ACCEPT, stream)) return rc;
+            if (int rc = trainer_closure(v, nullptr, nullptr, stream)) return rc;
+            if (int rc = trainer_update(v, it == 0 ? LB_BEGIN : LB_ACCEPT, stream)) return rc;
         }
-        if (int rc = symode_trainer_epoch_end(T, e, stream)) return rc;
+        if (int rc = trainer_epoch_end(v, e, stream)) return rc;
         if (test_eval) {
             const long slot = e % T->log_epochs;
-            if (int rc = symode_trainer_closure(T, T->log_test + slot * T->n_problems * 2, st.test_grad, stream)) return rc;
+            if (int rc = trainer_closure(v, T->log_test + slot * T->n_problems * 2, st.test_grad, stream)) return rc;
         }
     }
     return SYMODE_OK;
 }
+
+}  // namespace symode
+
+extern "C" int symode_trainer_closure(const symode_trainer* T, float* loss_out, float* grad_out, void* stream) {
+    return symode::trainer_closure(symode::TrainerView{T, nullptr, 0}, loss_out, grad_out, stream);
+}
+
+extern "C" int symode_trainer_update(const symode_trainer* T, int mode, void* stream) {
+    return symode::trainer_update(symode::TrainerView{T, nullptr, 0}, mode, stream);
+}
+
+extern "C" int symode_trainer_epoch_end(const symode_trainer* T, int epoch, void* stream) {
+    return symode::trainer_epoch_end(symode::TrainerView{T, nullptr, 0}, epoch, stream);
+}
+
+extern "C" int symode_trainer_run(const symode_trainer* T, int epoch0, int n_epochs, int test_eval, void* stream) {
+    return symode::trainer_run(symode::TrainerView{T, nullptr, 0}, epoch0, n_epochs, test_eval, stream);
+}
+
+extern "C" int symode_trainer_grid_closure(const symode_trainer_grid* G, float* loss_out, float* grad_out, void* stream) {
+    symode::TrainerView v;
+    if (int rc = symode::trainer_grid_view(G, v)) return rc;
+    return symode::trainer_closure(v, loss_out, grad_out, stream);
+}
+
+extern "C" int symode_trainer_grid_update(const symode_trainer_grid* G, int mode, void* stream) {
+    symode::TrainerView v;
+    if (int rc = symode::trainer_grid_view(G, v)) return rc;
+    return symode::trainer_update(v, mode, stream);
+}
+
+extern "C" int symode_trainer_grid_epoch_end(const symode_trainer_grid* G, int epoch, void* stream) {
+    symode::TrainerView v;
+    if (int rc = symode::trainer_grid_view(G, v)) return rc;
+    return symode::trainer_epoch_end(v, epoch, stream);
+}
+
+extern "C" int symode_trainer_grid_run(const symode_trainer_grid* G, int epoch0, int n_epochs, int test_eval, void* stream) {
+    symode::TrainerView v;
+    if (int rc = symode::trainer_grid_view(G, v)) return rc;
+    return symode::trainer_run(v, epoch0, n_epochs, test_eval, stream);
+}
+

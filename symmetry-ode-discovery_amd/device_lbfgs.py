@@ -17,12 +17,14 @@ import torch.distributed as dist
 
 from .coef_map import CoefMap
 from .engine import (CLOSURE_GRAM, CLOSURE_LATENT, CLOSURE_STREAM, LBFGS_ACCEPT, LBFGS_BEGIN, TRAINER_FIELDS, SymodeError, TrainerDesc,
-                     get_engine)
+                     TrainerGrid, get_engine)
 from .gram_closure import GramStatistics
 
 NEAR_THRESHOLD_BAND = 1e-4            # sindy.NEAR_THRESHOLD_BAND; repeated here to keep imports light
 
 EVENT_NONE, EVENT_THRESHOLD_CONVERGED, EVENT_THRESHOLD_PERIOD, EVENT_FINAL, EVENT_NAN, EVENT_IDLE = 0, 1, 2, 3, 4, -1
+HYPER_COLUMNS = ('lr', 'w_reg', 'threshold', 'w_sym')     # a row of the per-problem table (SYMODE_TRAINER_HYPER), by hyper's keys
+MAX_PROBLEMS = 65535                                      # of one trainer (symode_trainer: n_problems)
 _FIELD_DTYPES = {"act": torch.uint8, "n_iter": torch.int64, "head": torch.int64, "count": torch.int64, "n_iters": torch.int32,
                  "done": torch.uint8, "nan": torch.uint8, "finished": torch.uint8, "epochs": torch.int32, "near": torch.int32}
 
@@ -33,7 +35,7 @@ class DeviceTrainer:
     def __init__(self, x, dx, poly_order, flags=0, Q=None, use_kron_product=True, allow_constant=True, reversed_sym=None,
                  lr=1.0, threshold=0.1, st_freq=0, w_x=1.0, w_reg=0.0, l1=True, tol=1e-3, max_iter=20, history=100,
                  tol_grad=1e-7, tol_change=1e-9, inv_count=None, engine=None, detail=None, group=None, closure="stream",
-                 statistics=None, coef=None, latent=None):
+                 statistics=None, coef=None, latent=None, hyper=None):
         """x, dx (S, N_local, d) device tensors; ``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from
         Q / use_kron_product / allow_constant); ``reversed_sym = (gx (S, n_g, N, d), jgx (S, n_g, N, d, d), weight)`` as
         batched.BatchedClosure; ``group``: point shards, [loss | grad] summed over the ranks between closure and update;
@@ -46,7 +48,12 @@ class DeviceTrainer:
         dx := dz, ``latent = (B (S, N, d, d), y (S, N, d), w_pair)``, w_x := w_sindy_z; every closure is one
         symode_loss_grad_latent launch (mse = loss_sindy_z, sym = mean |B h - y|^2).  The x-term enters the loss VALUE with
         w_pair and the GRADIENT not at all, as in the reference (SYMODE_CLOSURE_LATENT, include/symode.h).  One rank, streamed
-        points only: ``group`` and ``statistics`` are refused."""
+        points only: ``group`` and ``statistics`` are refused.
+        ``hyper`` (with ``closure="gram"``): a dict with any of the keys ``lr``, ``w_reg``, ``threshold``, ``w_sym`` (the last
+        with the regulariser's matrices only), each one value per PROBLEM -- a hyper-parameter grid on shared matrices
+        (symode_trainer_grid): the trainer has as many problems as the columns have rows, a multiple of the statistics' S
+        sets, problem s fits on set s % S at row s's values, bit for bit the scalar trainer on that set alone; missing
+        columns are filled from the scalar arguments.  Without ``hyper``: the scalar descriptor and entries, as ever."""
         self.engine = engine or get_engine()
         kinds = {"stream": CLOSURE_STREAM, "gram": CLOSURE_GRAM, "latent": CLOSURE_LATENT}
         if closure not in kinds:
@@ -55,7 +62,7 @@ class DeviceTrainer:
         self.gram, self.latent = self.kind == CLOSURE_GRAM, self.kind == CLOSURE_LATENT
         self.order, self.flags = int(poly_order), int(flags)
         # --- the closure kind and its operands: the only per-kind part of the set-up (with _descriptor's branch)
-        self.stats = self.sym = self.latent_ops = self.x = self.dx = None
+        self.stats = self.sym = self.latent_ops = self.x = self.dx = self.hyper = None
         self.pair = self.latent or reversed_sym is not None
         self.w_sym = float(reversed_sym[2]) if reversed_sym is not None else 0.0
         if self.latent:
@@ -66,11 +73,17 @@ class DeviceTrainer:
         if self.gram:
             self.stats = self._gram_statistics(x, dx, reversed_sym, statistics, group)
             self.S, self.d, dev = self.stats.S, self.stats.d, self.stats.device
+            if hyper is not None:                             # the grid: more problems than sets of matrices
+                self.hyper = self._hyper_table(hyper, (lr, w_reg, threshold, self.w_sym), dev)
+                self.S = self.hyper.shape[0]
             self.n_points = self.stats.count
             if inv_count is None:
                 inv_count = self.stats.inv_count()
             group = None                                      # the fit itself needs no collective
         else:
+            if hyper is not None:
+                raise SymodeError(f"hyper (a per-problem table) is for closure='gram', got closure={closure!r}: the streamed and "
+                                  "latent closures read one set of points per problem")
             if statistics is not None:
                 raise SymodeError("statistics are for closure='gram'")
             if not (x.is_cuda and x.dim() == 3 and x.shape == dx.shape and x.dtype == torch.float32):
@@ -128,6 +141,14 @@ class DeviceTrainer:
         self.T = self._descriptor(float(inv_count) if inv_count is not None else 1.0 / (n_global * self.d), w_x, w_reg, l1, lr,
                                   tol_grad, tol_change, max_iter, history, threshold, tol, st_freq)
         self._Tp = ctypes.byref(self.T)
+        # --- the epochs' entry and what it is called with: the grid's takes the descriptor that wraps T and carries the table
+        # (a Gram fit has no collective inside, so the grid never meets _epoch_sharded)
+        self._run_fn, self._Gp = self.engine.lib.symode_trainer_run, self._Tp
+        if self.hyper is not None:
+            self.G = TrainerGrid(self.T, self.hyper.data_ptr(), self.stats.S)
+            self.T = self.G.base                              # (ctypes copied it: this is the one the launches read)
+            self._Tp, self._Gp = ctypes.byref(self.G.base), ctypes.byref(self.G)
+            self._run_fn = self.engine.lib.symode_trainer_grid_run
         self.max_iter = int(max_iter)
         self.threshold = float(threshold)
 
@@ -177,6 +198,34 @@ class DeviceTrainer:
         if group is not None:
             statistics.all_reduce(group)
         return statistics
+
+    def _hyper_table(self, hyper, scalars, dev):
+        """The (n_problems, 4) fp32 device table [lr, w_reg, threshold, w_sym]: every given key one value per problem, every
+        missing column the scalar argument."""
+        if not isinstance(hyper, dict):
+            raise SymodeError(f"hyper must be a dict with keys among {HYPER_COLUMNS}, got {type(hyper).__name__}")
+        unknown = sorted(set(hyper) - set(HYPER_COLUMNS))
+        if unknown:
+            raise SymodeError(f"hyper has unknown keys {unknown}: the per-problem values are {HYPER_COLUMNS}")
+        if not hyper:
+            raise SymodeError(f"hyper is empty: give at least one of {HYPER_COLUMNS}, one value per problem")
+        if 'w_sym' in hyper and not self.stats.regulariser:
+            raise SymodeError("hyper w_sym needs the regulariser's matrices (statistics with R / reversed_sym): the plain closure has "
+                              "no symmetry regulariser")
+        cols = {name: torch.as_tensor(v).detach().to('cpu', torch.float32).reshape(-1) for name, v in hyper.items()}
+        rows = {int(c.numel()) for c in cols.values()}
+        if len(rows) != 1:
+            raise SymodeError(f"hyper columns must hold one value per problem each, got lengths {sorted(rows)}")
+        n = rows.pop()
+        if n < 1 or n % self.stats.S != 0:
+            raise SymodeError(f"hyper has {n} rows, not a multiple of the statistics' {self.stats.S} sets of matrices (problem s "
+                              "fits on set s % S)")
+        if n > MAX_PROBLEMS:
+            raise SymodeError(f"hyper has {n} rows: one trainer takes at most {MAX_PROBLEMS} problems")
+        table = torch.empty(n, len(HYPER_COLUMNS), dtype=torch.float32)
+        for c, (name, scalar) in enumerate(zip(HYPER_COLUMNS, scalars)):
+            table[:, c] = cols[name] if name in cols else float(scalar)
+        return table.to(dev).contiguous()
 
     @staticmethod
     def _latent_operands(z, latent, reversed_sym, group, statistics, w_sindy_z):
@@ -279,7 +328,7 @@ class DeviceTrainer:
             if self.distributed:
                 self._epoch_sharded(e, test_eval)
             else:
-                self._check(lib.symode_trainer_run(self._Tp, e, 1, 1 if test_eval else 0, self._st()), "symode_trainer_run")
+                self._check(self._run_fn(self._Gp, e, 1, 1 if test_eval else 0, self._st()), "symode_trainer_run")
             ev = torch.cuda.Event()
             ev.record(stream)
             return ev

@@ -98,6 +98,12 @@ _SIGNATURES = {
     "symode_trainer_update": (c_int, [c_void_p, c_int, c_void_p]),
     "symode_trainer_epoch_end": (c_int, [c_void_p, c_int, c_void_p]),
     "symode_trainer_run": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "symode_trainer_grid_closure": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "symode_trainer_grid_update": (c_int, [c_void_p, c_int, c_void_p]),
+    "symode_trainer_grid_epoch_end": (c_int, [c_void_p, c_int, c_void_p]),
+    "symode_trainer_grid_run": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "symode_quad_closure_grid": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_void_p, ctypes.c_double,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_adam_epochs": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_int, c_long, c_int, c_int, c_int,
                                    c_void_p, c_int, c_int, c_int] + [c_float] * 6 + [c_int, c_float, c_int, c_int, c_float]
                            + [c_void_p] * 8),
@@ -142,6 +148,14 @@ class TrainerDesc(ctypes.Structure):
                 ("log", c_void_p), ("log_test", c_void_p), ("log_xi", c_void_p), ("log_mask", c_void_p), ("log_params", c_void_p), ("log_epochs", c_int),
                 ("aug_gram", c_void_p), ("rev_gram", c_void_p),
                 ("closure", c_int), ("latent_B", c_void_p), ("latent_y", c_void_p)]
+
+
+TRAINER_HYPER = 4                                           # SYMODE_TRAINER_HYPER: columns of a row, lr, w_reg, threshold, w_sym
+
+
+class TrainerGrid(ctypes.Structure):
+    """``symode_trainer_grid`` of include/symode.h, field for field."""
+    _fields_ = [("base", TrainerDesc), ("hyper", c_void_p), ("n_sets", c_long)]
 
 
 ADAM_PLAIN, ADAM_REVERSED, ADAM_LATENT = 0, 1, 2              # SYMODE_ADAM_* of include/symode.h
@@ -830,16 +844,28 @@ class HipEngine:
                     "symode_symreg_reversed_gram_gather")
         return gram
 
-    def quad_closure(self, G, R, xi, mask, inv_count, w_sym=1.0):
+    def quad_closure(self, G, R, xi, mask, inv_count, w_sym=1.0, hyper=None, n_sets=None):
         """The closure as a quadratic form of fixed fp64 matrices: G (S, p+d, p+d) augmented Gram, R (S, d p, d p) or None,
         xi / mask (S, d, p) (mask may be None).  Returns what loss_grad (R None: loss (S,)) or loss_grad_reversed (loss2
-        (S, 2)) returns, with grad (S, d, p); unbatched G (p+d, p+d) gives unbatched outputs."""
+        (S, 2)) returns, with grad (S, d, p); unbatched G (p+d, p+d) gives unbatched outputs.
+        ``hyper`` (n_problems, 4) fp32 on the device, ``n_sets`` (default: G's sets): symode_quad_closure_grid -- xi / mask
+        (n_problems, d, p), problem s on set s % n_sets with its w_sym from column 3 of row s (``w_sym`` is not read)."""
         batched = G.dim() == 3
         G = self._dev(G, "G", torch.float64).reshape(-1, G.shape[-2], G.shape[-1])
-        S, F = G.shape[0], G.shape[1]
+        n_mat, F = G.shape[0], G.shape[1]
         xi = self._dev(xi, "xi")
         d = xi.shape[-2]
         p = F - d
+        S = n_mat
+        if hyper is not None:
+            n_sets = n_mat if n_sets is None else int(n_sets)
+            hyper = self._dev(hyper, "hyper")
+            if hyper.dim() != 2 or hyper.shape[1] != TRAINER_HYPER or n_sets != n_mat or hyper.shape[0] % n_sets != 0:
+                raise SymodeError(f"hyper {tuple(hyper.shape)} must be (n_problems, {TRAINER_HYPER}) with n_problems a multiple of "
+                                  f"the {n_mat} sets of matrices (n_sets {n_sets})")
+            S = hyper.shape[0]
+        elif n_sets is not None:
+            raise SymodeError("n_sets goes with hyper (symode_quad_closure_grid)")
         if G.shape[2] != F or xi.numel() != S * d * p:
             raise SymodeError(f"G {tuple(G.shape)} and xi {tuple(xi.shape)} do not match")
         mask = None if mask is None else self._dev(mask, "mask")
@@ -847,13 +873,18 @@ class HipEngine:
             raise SymodeError("mask does not match xi")
         if R is not None:
             R = self._dev(R, "R", torch.float64)
-            if R.numel() != S * (d * p) ** 2:
-                raise SymodeError(f"R {tuple(R.shape)} does not match ({S}, {d * p}, {d * p})")
+            if R.numel() != n_mat * (d * p) ** 2:
+                raise SymodeError(f"R {tuple(R.shape)} does not match ({n_mat}, {d * p}, {d * p})")
         loss = torch.empty(S, 2 if R is not None else 1, dtype=torch.float32, device=G.device)
         grad = torch.empty(S, d, p, dtype=torch.float32, device=G.device)
-        self._check(self.lib.symode_quad_closure(self._ptr(G), self._ptr(R), S, d, p, self._ptr(xi), self._ptr(mask),
-                                                 float(inv_count), float(w_sym), self._ptr(loss), self._ptr(grad), self._stream(G)),
-                    "symode_quad_closure")
+        if hyper is not None:
+            self._check(self.lib.symode_quad_closure_grid(self._ptr(G), self._ptr(R), n_sets, S, d, p, self._ptr(xi), self._ptr(mask),
+                                                          float(inv_count), self._ptr(hyper), self._ptr(loss), self._ptr(grad),
+                                                          self._stream(G)), "symode_quad_closure_grid")
+        else:
+            self._check(self.lib.symode_quad_closure(self._ptr(G), self._ptr(R), S, d, p, self._ptr(xi), self._ptr(mask),
+                                                     float(inv_count), float(w_sym), self._ptr(loss), self._ptr(grad),
+                                                     self._stream(G)), "symode_quad_closure")
         loss = loss if R is not None else loss.reshape(S)
         if not batched:
             return loss[0], grad[0]

@@ -11,6 +11,8 @@
     python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --device_shuffle --batch_size 256 --n_seeds 64
     python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --n_seeds 64 --eval_ltp \
         --grid threshold=0.01,0.05,0.075,0.15 --grid lr_sindy=0.1,1.0     # 8 grid points x 64 seeds in every epoch launch
+    python -m symode_amd.main_sweep --config lv/noise99_eq_rsymreg.cfg --n_seeds 64 --gram_closure --eval_ltp \
+        --lbfgs_grid w_sym_reg=0.01,0.1,1 --lbfgs_grid threshold=0.05,0.1   # 6 grid points on the 64 seeds' Gram matrices
 
 plan:   ``_refusal`` decides from the arguments alone whether the sweep runs, before a process group, a data file or a
         device is touched; what it refuses it answers with the per-seed command to run instead.
@@ -36,6 +38,11 @@ value lists, the first axis given slowest, over COMMON seeds in the same launche
 seed k, with seed k's initial coefficients and epoch orders at every point, so the fit of (g, k) is exactly the fit main_sweep
 with that point's scalar flags gives seed k.  The results go to ``eval_results/<save_dir>/grid{g}/seed{n}.npz`` and
 ``eval_results/<save_dir>/grid.json``; ``main`` returns {g: aggregate}.
+
+``--lbfgs_grid name=v1,v2,...`` (repeatable; names lr_sindy, w_sindy_reg, threshold, w_sym_reg; L-BFGS with --gram_closure only)
+is the same grid for the L-BFGS sweep: the seeds' Gram matrices are built once, and the G x n_seeds problems of the device
+trainer read them through ``SeedSweepLBFGS.fit(hyper=...)`` -- no copy of the points, no further data pass or collective.
+Problem order, result files and table are ``--grid``'s; the files also hold the point's w_sym_reg.
 """
 from __future__ import annotations
 
@@ -90,21 +97,27 @@ def _pop_flag(argv, flag):
 GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold'}      # --grid name -> DeviceAdam.fit(hyper=) key
 
 
-def _parse_grid(specs):
-    """``--grid name=v1,v2,...`` strings -> ([(name, [values])] in the order given, None), or (None, why not)."""
+# --lbfgs_grid name -> DeviceTrainer(hyper=) key
+LBFGS_GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold', 'w_sym_reg': 'w_sym'}
+MAX_GRID_PROBLEMS = 65535                                  # problems of one device trainer
+
+
+def _parse_grid(specs, names=GRID_NAMES, flag='--grid'):
+    """``--grid name=v1,v2,...`` strings -> ([(name, [values])] in the order given, None), or (None, why not).  ``names``,
+    ``flag``: the axes and the spelling of the flag that is being read (--lbfgs_grid: LBFGS_GRID_NAMES)."""
     axes = []
     for spec in specs:
         name, eq, values = str(spec).partition('=')
-        if name not in GRID_NAMES:
-            return None, f"--grid {spec}: unknown name '{name}', the grid axes are {', '.join(GRID_NAMES)} (name=v1,v2,...)"
+        if name not in names:
+            return None, f"{flag} {spec}: unknown name '{name}', the grid axes are {', '.join(names)} (name=v1,v2,...)"
         if name in [a[0] for a in axes]:
-            return None, f'--grid {name} is given twice: one value list per name'
+            return None, f'{flag} {name} is given twice: one value list per name'
         try:
             axis = [float(v) for v in values.split(',')] if eq else []
         except ValueError:
             axis = []
         if not axis or not all(np.isfinite(axis)):
-            return None, f"--grid {spec}: the values of {name} must be a non-empty comma-separated list of numbers"
+            return None, f"{flag} {spec}: the values of {name} must be a non-empty comma-separated list of numbers"
         axes.append((name, axis))
     return axes, None
 
@@ -119,11 +132,12 @@ def _grid_problem(problem, n_seeds):
     return divmod(problem, n_seeds)
 
 
-def _refusal(args, method='lbfgs', world=1, engine=None, grid=None):
+def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
-    apply to the default method.  ``grid``: the ``--grid`` strings, if any; their rules come after all others."""
+    apply to the default method.  ``grid``: the ``--grid`` strings, if any; their rules come after all others, and after
+    them those of ``lbfgs_grid``, the ``--lbfgs_grid`` strings (``n_seeds``: for the size of its launch, if known)."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
     cfg = args.get('config')
@@ -162,11 +176,35 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None):
     if args.get('device_shuffle') and (method == 'stlsq' or not adam):
         return ('--device_shuffle draws the epoch order of the minibatch Adam fit inside its launch: it needs '
                 '--sindy_optimizer adam (with the default --method lbfgs), L-BFGS and STLSQ fits have no epoch order')
+    if grid and lbfgs_grid:
+        return '--lbfgs_grid and --grid are the grids of two different sweeps (L-BFGS, Adam): give one of them'
     if grid:
         if method == 'stlsq' or not adam:
             return ('--grid gives every problem of the minibatch Adam launch its own hyper-parameters: it needs '
                     '--sindy_optimizer adam (with the default --method lbfgs); the L-BFGS and STLSQ sweeps take one value each')
         return _parse_grid(grid)[1]
+    if lbfgs_grid:
+        if method == 'stlsq' or adam:
+            return ('--lbfgs_grid gives every problem of the device L-BFGS trainer its own hyper-parameters on shared Gram '
+                    'matrices: it needs --sindy_optimizer lbfgs with the default --method lbfgs (the Adam sweep has --grid, the '
+                    'STLSQ sweep takes one value each)')
+        if not args.get('gram_closure'):
+            return ('--lbfgs_grid needs --gram_closure: the grid points share the seeds\' Gram matrices, and the Gram route\'s '
+                    'results differ from the streamed route\'s in the last bits -- a flag must not switch routes silently')
+        axes, why = _parse_grid(lbfgs_grid, LBFGS_GRID_NAMES, '--lbfgs_grid')
+        if why is not None:
+            return why
+        sym_axis = dict(axes).get('w_sym_reg')
+        if sym_axis is not None and not args['w_sym_reg'] > 0:
+            return ('--lbfgs_grid w_sym_reg needs the symmetry regulariser on the command line (--w_sym_reg > 0 with '
+                    '--sym_reg_type r --load_laligan ... --fix_laligan): without it no regulariser matrices are built')
+        if sym_axis is not None and not all(v > 0 for v in sym_axis):
+            return (f'--lbfgs_grid w_sym_reg={",".join(f"{v:g}" for v in sym_axis)}: every value must be > 0 (a sweep without the '
+                    'regulariser is another run, without --w_sym_reg)')
+        n_points = int(np.prod([len(axis) for _, axis in axes]))
+        if n_seeds is not None and n_points * n_seeds > MAX_GRID_PROBLEMS:
+            return (f'--lbfgs_grid: {n_points} grid points x {n_seeds} seeds = {n_points * n_seeds} problems, one device trainer takes '
+                    f'at most {MAX_GRID_PROBLEMS}')
     return None
 
 
@@ -243,11 +281,27 @@ def _fit_lbfgs(ctx):
     sweep = SeedSweepLBFGS(clos, args['lr_sindy'], args['threshold'], args['st_freq'], w_sindy_x=args['w_sindy_x'],
                            sindy_reg_type=args['sindy_reg_type'], w_sindy_reg=args['w_sindy_reg'],
                            gram_closure=bool(args.get('gram_closure')), statistics=stats)
-    out = sweep.fit(P0, args['num_epochs'])
-    near = [ctx.seeds[i] for i in torch.nonzero(out["near_threshold"]).flatten().tolist()]
-    lines = [f'{len(ctx.seeds)} seeds, epochs used {int(out["epochs"].min())}-{int(out["epochs"].max())}, '
-             f'finished {int(out["finished"].sum())}, NaN {int(out["nan"].sum())}, '
-             f'seeds with near-threshold coefficients {near or "none"}']
+    points = getattr(ctx, 'grid', None)
+    if points is None:
+        out = sweep.fit(P0, args['num_epochs'])
+        near = [ctx.seeds[i] for i in torch.nonzero(out["near_threshold"]).flatten().tolist()]
+        lines = [f'{len(ctx.seeds)} seeds, epochs used {int(out["epochs"].min())}-{int(out["epochs"].max())}, '
+                 f'finished {int(out["finished"].sum())}, NaN {int(out["nan"].sum())}, '
+                 f'seeds with near-threshold coefficients {near or "none"}']
+        return SimpleNamespace(Xi=out['Xi'], mask=out['mask'], lib=lib, lines=lines)
+    # --lbfgs_grid: G points on common seeds, problem g * n_seeds + k = point g on seed k with seed k's matrices and start
+    n_seeds = len(ctx.seeds)
+    column = {'w_sym_reg': lambda v: v / args['w_sindy_x']}                  # the weight relative to the MSE, as w_sym above
+    hyper = {LBFGS_GRID_NAMES[name]: [column.get(name, float)(point[name]) for point in points for _ in ctx.seeds]
+             for name in points[0]}
+    out = sweep.fit(P0.repeat(len(points), 1), args['num_epochs'], hyper=hyper)
+    lines = []
+    for g in range(len(points)):
+        at = slice(g * n_seeds, (g + 1) * n_seeds)
+        near = [ctx.seeds[i] for i in torch.nonzero(out["near_threshold"][at]).flatten().tolist()]
+        lines.append(f'grid {g}: {n_seeds} seeds, epochs used {int(out["epochs"][at].min())}-{int(out["epochs"][at].max())}, '
+                     f'finished {int(out["finished"][at].sum())}, NaN {int(out["nan"][at].sum())}, '
+                     f'seeds with near-threshold coefficients {near or "none"}')
     return SimpleNamespace(Xi=out['Xi'], mask=out['mask'], lib=lib, lines=lines)
 
 
@@ -363,8 +417,8 @@ def _report(ctx, result, val_dataset, eval_ltp, ltp_bound_rel):
 
 
 def _report_grid(ctx, result, val_dataset, eval_ltp, ltp_bound_rel):
-    """--grid: ``_report`` per grid point into eval_results/<save_dir>/grid{g}/ (every seed file also holds the point's
-    lr_sindy, w_sindy_reg and threshold), the table of the points -- values, success rate = mean correct_form_all and, with
+    """--grid / --lbfgs_grid: ``_report`` per grid point into eval_results/<save_dir>/grid{g}/ (every seed file also holds the point's
+    lr_sindy, w_sindy_reg and threshold -- under --lbfgs_grid its w_sym_reg too), the table of the points -- values, success rate = mean correct_form_all and, with
     --eval_ltp, the median over seeds of the per-seed median roll-out error and of val_mse -- on stdout and in
     eval_results/<save_dir>/grid.json, and {g: aggregate}."""
     if ctx.rank != 0:
@@ -382,7 +436,7 @@ def _report_grid(ctx, result, val_dataset, eval_ltp, ltp_bound_rel):
     table, out = [], {}
     for g, point in enumerate(points):
         at = slice(g * n_seeds, (g + 1) * n_seeds)
-        values = {name: float(point.get(name, args[name])) for name in GRID_NAMES}
+        values = {name: float(point.get(name, args[name])) for name in ctx.grid_names}
         extra = {name: np.full(n_seeds, v) for name, v in values.items()}
         if scores is not None:
             extra.update({name: np.asarray(v)[at] for name, v in scores.items()})
@@ -405,7 +459,7 @@ def _report_grid(ctx, result, val_dataset, eval_ltp, ltp_bound_rel):
     if scores is not None:
         best = min(table, key=lambda row: row['ltp_median_error'])          # the first of equals; inf = diverged
         print(f'best by validation roll-out error: grid {best["grid"]} (' +
-              ' '.join(f'{name}={best[name]:g}' for name in GRID_NAMES) + ')')
+              ' '.join(f'{name}={best[name]:g}' for name in ctx.grid_names) + ')')
     return out
 
 
@@ -418,9 +472,10 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     eval_ltp = _pop_flag(argv, '--eval_ltp')
     ltp_bound_rel = _pop(argv, '--ltp_bound_rel', None, float)
     grid = _pop_all(argv, '--grid')
+    lbfgs_grid = _pop_all(argv, '--lbfgs_grid')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
-    why = _refusal(args, method, world, engine, grid=grid or None)
+    why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -440,8 +495,9 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     ctx = SimpleNamespace(args=args, seeds=list(range(args['seed'], args['seed'] + n_seeds)), dev=dev, group=group, rank=rank,
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
                           engine=engine, kw={} if engine is None else {'engine': engine}, grid=None)
-    if grid:
-        ctx.grid_axes = _parse_grid(grid)[0]
+    if grid or lbfgs_grid:
+        ctx.grid_names = GRID_NAMES if grid else LBFGS_GRID_NAMES
+        ctx.grid_axes = _parse_grid(grid)[0] if grid else _parse_grid(lbfgs_grid, LBFGS_GRID_NAMES, '--lbfgs_grid')[0]
         ctx.grid = _grid_points(ctx.grid_axes)
     fit = {('stlsq', 'lbfgs'): _fit_stlsq, ('lbfgs', 'lbfgs'): _fit_lbfgs, ('lbfgs', 'adam'): _fit_adam}
     report = _report if ctx.grid is None else _report_grid

@@ -419,7 +419,7 @@ class SeedSweepLBFGS:
                     and os.environ.get('SYMODE_LBFGS_FUSED', '1') == '1'
                     and P0.shape[1] <= 256 and c.d * c.p <= 256 and getattr(c, 'n_chunks', 1) == 1)
 
-    def _fit_native(self, P0, num_epochs, mask0, on_epoch):
+    def _fit_native(self, P0, num_epochs, mask0, on_epoch, hyper=None):
         from .device_lbfgs import DeviceTrainer
         c = self.c
         stats, rev = None, c.sym if self.statistics is None else None
@@ -438,7 +438,7 @@ class SeedSweepLBFGS:
                            inv_count=None if self.statistics is not None else c.inv_count,
                            engine=c.engine, group=(c.group or dist.group.WORLD) if c.distributed else None,
                            detail=on_epoch is not None and c.S <= 64, closure='stream' if stats is None else 'gram',
-                           statistics=stats)
+                           statistics=stats, hyper=hyper)
         self.trainer = tr
         cb = None
         if on_epoch is not None:
@@ -446,20 +446,29 @@ class SeedSweepLBFGS:
 
             def cb(epoch, rec):                              # the tensor-op form's callback signature
                 done = torch.from_numpy((rec['code'] == 3) | (rec['code'] == 4) | (rec['code'] == -1))
-                return on_epoch(epoch, tr.field('params'), tr.field('mask').view(c.S, c.d, c.p), done.to(dev))
+                return on_epoch(epoch, tr.field('params'), tr.field('mask').view(tr.S, c.d, c.p), done.to(dev))
         out = tr.fit(P0, num_epochs, mask0=mask0, on_epoch=cb)
         self.mask = out['mask'].to(P0.device)
         return {k: v.to(P0.device) for k, v in out.items()}
 
     @torch.no_grad()
-    def fit(self, P0, num_epochs, mask0=None, on_epoch=None):
+    def fit(self, P0, num_epochs, mask0=None, on_epoch=None, hyper=None):
         """P0 (S, n): initial flat parameters per seed ([Xi] or [beta | const]).
+        ``hyper``: the per-problem table of ``DeviceTrainer(hyper=...)`` (keys lr, w_reg, threshold, w_sym, one value per
+        problem) -- a hyper-parameter grid on the seeds' shared Gram matrices: P0 then has one row per PROBLEM (a multiple
+        of the closure's S seeds, problem s on seed s % S).  Gram form on the device trainer only.
         ``on_epoch(epoch, P, mask, done)`` (optional) is called after the epoch's logic with the live device tensors (a
         caller that reads them synchronises; returning True ends the fit) -- per-epoch logs / interval checkpoints.
         Returns dict(Xi, mask, params, epochs (S,), finished (S,), nan (S,))."""
         c = self.c
+        if hyper is not None and not self.gram_closure:
+            raise ValueError('hyper (a per-problem table) needs the Gram form (gram_closure=True or statistics): the streamed '
+                             'closure reads one set of points per problem')
         if self._native_ok(P0):
-            return self._fit_native(P0, num_epochs, mask0, on_epoch)
+            return self._fit_native(P0, num_epochs, mask0, on_epoch, hyper)
+        if hyper is not None:
+            raise ValueError('hyper (a per-problem table) needs the device trainer (a GPU closure of one chunk, d p <= 256, '
+                             'SYMODE_LBFGS_FUSED=1): the tensor-op form takes one value each')
         if self.gram_closure:
             raise ValueError('gram_closure=True needs the device trainer (a GPU closure of one chunk, d p <= 256)')
         P = P0.clone().contiguous()
