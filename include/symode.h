@@ -751,6 +751,28 @@ int symode_host_stlsq_sweep(const double* G, int S, int d, int p, long n_points,
                             int driver, double near_band, float* xi_out, unsigned char* mask_out, int* passes_out,
                             int* near_out, int* fallback_out);
 
+/* Sequential-threshold least squares to convergence ON THE DEVICE, all problems in one launch (all pointers device memory):
+ * what symode_host_stlsq_sweep does with driver = 1 (gels), restated -- ridge system Gtt + gamma^2 I on the current support,
+ * per equation row (the host's joint block-diagonal system never mixes its blocks, so the eliminations and their order are
+ * the same), pivoted Cholesky (largest remaining diagonal first, the first of equals), forward and back substitution, fp32
+ * rounding, strict > (float)threshold on the still-active entries, until the problem's (d, p) mask repeats or max_iter
+ * passes have run.  aug_gram (n_sets, p+d, p+d) fp64 as symode_aug_gram / _gather leave it; problem s reads set s % n_sets
+ * (symode_trainer_grid's convention) and, with hyper (n_problems, 2) fp32 [gamma, threshold], row s in place of the two
+ * scalars -- a hyper-parameter grid on shared matrices: no further data pass, no further collective.  hyper == NULL:
+ * n_problems == n_sets and the scalars hold for all.  p <= 64, d <= 4.
+ * xi_out (n_problems, d, p) fp32, mask_out (n_problems, d, p) bytes, passes_out, near_out (coefficients of an active entry
+ * met within near_band of the threshold, summed over the passes), fell_out (n_problems) ints as the host defines them,
+ * except: a pivot that is not > 0 sets fell_out[s] = 1 and ENDS problem s (its other outputs are then unspecified) -- the
+ * caller solves those problems with symode_host_stlsq_sweep; the rank-revealing fallback and the gelsy rank rule are host
+ * only.  n_points is accepted for symmetry with the host entry (only the gelsy rule reads it).
+ * Refused before any GPU work: d < 1, d > 4, p < 1, p > 64, max_iter < 1, n_sets < 1, n_problems < n_sets or >= 2^31,
+ * hyper == NULL with n_problems != n_sets (SYMODE_E_BADSIZE); any pointer but hyper NULL (SYMODE_E_NULLPTR); aug_gram not
+ * 8-byte, hyper or an fp32 / int output not 4-byte aligned (SYMODE_E_ALIGN).
+ * replaces: train.py:872-887 over sindy.py:250-315, unconstrained case. */
+int symode_stlsq_sweep(const double* aug_gram, long n_sets, long n_problems, int d, int p, long n_points, const float* hyper,
+                       double gamma, double threshold, int max_iter, double near_band, float* xi_out, unsigned char* mask_out,
+                       int* passes_out, int* near_out, int* fell_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

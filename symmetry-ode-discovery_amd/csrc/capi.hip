@@ -7,6 +7,7 @@
 #include "jconst.hpp"
 #include "ops_table.hpp"
 #include "quad_closure.hpp"
+#include "stlsq.hpp"
 
 using namespace symode;
 
@@ -454,6 +455,21 @@ int symode_quad_closure_grid(const double* aug_gram, const double* rev_gram, lon
         return SYMODE_E_ALIGN;
     return (int)launch_quad_closure_grid(aug_gram, rev_gram, (int)n_sets, n_problems, d, p, xi, mask, inv_count, hyper, loss_out,
                                          grad_out, (hipStream_t)stream);
+}
+
+int symode_stlsq_sweep(const double* aug_gram, long n_sets, long n_problems, int d, int p, long n_points, const float* hyper,
+                       double gamma, double threshold, int max_iter, double near_band, float* xi_out, unsigned char* mask_out,
+                       int* passes_out, int* near_out, int* fell_out, void* stream) {
+    (void)n_points;                     // the rows behind a matrix: gelsy's rank rule reads them, the full-rank driver does not
+    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || max_iter < 1) return SYMODE_E_BADSIZE;
+    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
+    if (!hyper && n_problems != n_sets) return SYMODE_E_BADSIZE;
+    if (!aug_gram || !xi_out || !mask_out || !passes_out || !near_out || !fell_out) return SYMODE_E_NULLPTR;
+    if (misaligned(aug_gram, 8) || misaligned(hyper, 4) || misaligned(xi_out, 4) || misaligned(passes_out, 4) ||
+        misaligned(near_out, 4) || misaligned(fell_out, 4))
+        return SYMODE_E_ALIGN;
+    return (int)launch_stlsq_sweep(aug_gram, n_sets, n_problems, d, p, hyper, gamma, threshold, max_iter, near_band, xi_out,
+                                   mask_out, passes_out, near_out, fell_out, (hipStream_t)stream);
 }
 
 int symode_symreg_reversed(const float* x, const float* gx_, const float* jgx, int n_g, long n, int d, int order,

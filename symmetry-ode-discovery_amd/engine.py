@@ -127,6 +127,8 @@ _SIGNATURES = {
     "symode_adam_run": (c_int, [c_void_p, c_void_p]),
     "symode_host_stlsq_sweep": (c_int, [c_void_p, c_int, c_int, c_int, c_long, ctypes.c_double, ctypes.c_double, c_int, c_int,
                                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "symode_stlsq_sweep": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_long, c_void_p, ctypes.c_double, ctypes.c_double, c_int,
+                                   ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
@@ -157,6 +159,8 @@ class TrainerGrid(ctypes.Structure):
     """``symode_trainer_grid`` of include/symode.h, field for field."""
     _fields_ = [("base", TrainerDesc), ("hyper", c_void_p), ("n_sets", c_long)]
 
+
+STLSQ_HYPER = 2                                             # columns of a symode_stlsq_sweep hyper row: gamma, threshold
 
 ADAM_PLAIN, ADAM_REVERSED, ADAM_LATENT = 0, 1, 2              # SYMODE_ADAM_* of include/symode.h
 ADAM_HYPER = 4                                              # columns of a hyper row: lr, w_reg, threshold, w_sym
@@ -843,6 +847,46 @@ class HipEngine:
                                                                 self._ptr(ws), need, self._stream(x)),
                     "symode_symreg_reversed_gram_gather")
         return gram
+
+    def stlsq_sweep(self, G, n_points, gamma, threshold, max_iter, hyper=None, n_problems=None, *, d, near_band=1e-4, to_host=False):
+        """Sequential-threshold least squares to convergence for every problem in ONE launch (symode_stlsq_sweep: the
+        full-rank driver's loop of symode_host_stlsq_sweep on the device).  G (n_sets, p+d, p+d) fp64 on the device, ``d``
+        the number of equation rows (G alone does not say where p ends).  ``hyper`` (n_problems, 2) fp32 on the device,
+        row s = problem s's [gamma, threshold] on set s % n_sets (``gamma`` and ``threshold`` are then not read);
+        ``n_problems`` defaults to the table's rows, or to n_sets without a table.
+        Returns device tensors (Xi (n_problems, d, p) fp32, mask (n_problems, d, p) uint8, passes, near, fell (n_problems,)
+        int32); a problem with ``fell`` set met a pivot that is not positive and is the host's to solve.  ``to_host=True``:
+        the same five as numpy arrays, after one copy of the one buffer they share."""
+        G = self._dev(G, "G", torch.float64)
+        d = int(d)
+        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
+            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
+        n_sets, p = G.shape[0], G.shape[1] - d
+        if hyper is not None:
+            hyper = self._dev(hyper, "hyper")
+            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_HYPER or hyper.device != G.device:
+                raise SymodeError(f"hyper must be (n_problems, {STLSQ_HYPER}) fp32 on {G.device}: one row [gamma, threshold] per problem")
+            if n_problems is not None and int(n_problems) != hyper.shape[0]:
+                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
+            n_problems = hyper.shape[0]
+        S = n_sets if n_problems is None else int(n_problems)
+        # one allocation, [xi | passes | near | fell | mask], so that a caller on the host fetches everything in ONE copy
+        cuts = [0, 4 * S * d * p, 4 * S * (d * p + 1), 4 * S * (d * p + 2), 4 * S * (d * p + 3), 4 * S * (d * p + 3) + S * d * p]
+        buf = torch.empty(max(cuts[-1], 0), dtype=torch.uint8, device=G.device)
+
+        def parts(b, f32, i32):
+            xi, passes, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
+            return xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32)
+
+        xi, mask, passes, near, fell = parts(buf, torch.float32, torch.int32)
+        self._check(self.lib.symode_stlsq_sweep(self._ptr(G), n_sets, S, d, p, int(n_points), self._ptr(hyper), float(gamma),
+                                                float(threshold), int(max_iter), float(near_band), self._ptr(xi), self._ptr(mask),
+                                                self._ptr(passes), self._ptr(near), self._ptr(fell), self._stream(G)),
+                    "symode_stlsq_sweep")
+        if to_host:
+            import numpy as np
+            return parts(buf.cpu().numpy(), np.float32, np.int32)
+        return xi, mask, passes, near, fell
 
     def quad_closure(self, G, R, xi, mask, inv_count, w_sym=1.0, hyper=None, n_sets=None):
         """The closure as a quadratic form of fixed fp64 matrices: G (S, p+d, p+d) augmented Gram, R (S, d p, d p) or None,

@@ -43,6 +43,13 @@ with that point's scalar flags gives seed k.  The results go to ``eval_results/<
 is the same grid for the L-BFGS sweep: the seeds' Gram matrices are built once, and the G x n_seeds problems of the device
 trainer read them through ``SeedSweepLBFGS.fit(hyper=...)`` -- no copy of the points, no further data pass or collective.
 Problem order, result files and table are ``--grid``'s; the files also hold the point's w_sym_reg.
+
+``--device_stlsq`` (with --method stlsq) runs the threshold loop of the STLSQ sweep on the device as well
+(``SeedSweepSTLSQ.solve(device=True)``: one launch for all seeds on the Gram matrices where the gather launch left them, the
+full-rank driver only); outputs and summary lines are those of ``--method stlsq``.  ``--stlsq_grid name=v1,v2,...``
+(repeatable; names threshold, w_sindy_reg; with --device_stlsq only) is the grid of that sweep: the G x n_seeds problems of the
+one launch read the n_seeds matrices -- no further data pass, copy or collective.  Problem order, result files and table are
+``--grid``'s.
 """
 from __future__ import annotations
 
@@ -99,6 +106,7 @@ GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold'
 
 # --lbfgs_grid name -> DeviceTrainer(hyper=) key
 LBFGS_GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold', 'w_sym_reg': 'w_sym'}
+STLSQ_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg'}      # --stlsq_grid name -> SeedSweepSTLSQ.solve(hyper=) key
 MAX_GRID_PROBLEMS = 65535                                  # problems of one device trainer
 
 
@@ -132,12 +140,15 @@ def _grid_problem(problem, n_seeds):
     return divmod(problem, n_seeds)
 
 
-def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None):
+def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None, device_stlsq=False,
+             stlsq_grid=None):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
     apply to the default method.  ``grid``: the ``--grid`` strings, if any; their rules come after all others, and after
-    them those of ``lbfgs_grid``, the ``--lbfgs_grid`` strings (``n_seeds``: for the size of its launch, if known)."""
+    them those of ``lbfgs_grid``, the ``--lbfgs_grid`` strings (``n_seeds``: for the size of its launch, if known).
+    ``device_stlsq``, ``stlsq_grid``: the ``--device_stlsq`` flag and the ``--stlsq_grid`` strings; their rules stand before
+    those of the two other grids, which say what they always said."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
     cfg = args.get('config')
@@ -176,6 +187,10 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     if args.get('device_shuffle') and (method == 'stlsq' or not adam):
         return ('--device_shuffle draws the epoch order of the minibatch Adam fit inside its launch: it needs '
                 '--sindy_optimizer adam (with the default --method lbfgs), L-BFGS and STLSQ fits have no epoch order')
+    if device_stlsq or stlsq_grid:
+        why = _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid)
+        if why is not None:
+            return why
     if grid and lbfgs_grid:
         return '--lbfgs_grid and --grid are the grids of two different sweeps (L-BFGS, Adam): give one of them'
     if grid:
@@ -208,6 +223,37 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     return None
 
 
+def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid):
+    """The rules of --device_stlsq and --stlsq_grid (``_refusal``, which has applied the rules of --method stlsq itself)."""
+    given = ' and '.join(flag for flag, on in (('--device_stlsq', device_stlsq), ('--stlsq_grid', stlsq_grid)) if on)
+    if method != 'stlsq':
+        return (f'{given}: the device fit of the sequential-threshold least-squares sweep and its grid need --method stlsq '
+                f'(the Adam sweep has --grid, the L-BFGS sweep --lbfgs_grid)')
+    if stlsq_grid and (grid or lbfgs_grid):
+        return ('--stlsq_grid, --grid and --lbfgs_grid are the grids of three different sweeps (STLSQ, Adam, L-BFGS): give '
+                'one of them')
+    if stlsq_grid and not device_stlsq:
+        return ('--stlsq_grid needs --device_stlsq: the grid points share the seeds\' Gram matrices on the device, and the '
+                'device fit is the full-rank driver\'s, whose results can differ from the host route\'s in the last bit -- a '
+                'flag must not switch routes silently')
+    if args.get('lstsq_driver') == 'gelsy':
+        return ('--device_stlsq fits with the full-rank driver (gels) only: the rank rule of --lstsq_driver gelsy runs on the '
+                'host route (drop --device_stlsq)')
+    if not stlsq_grid:
+        return None
+    axes, why = _parse_grid(stlsq_grid, STLSQ_GRID_NAMES, '--stlsq_grid')
+    if why is not None:
+        return why
+    for name, axis in axes:
+        if not all(v >= 0 for v in axis):
+            return f'--stlsq_grid {name}={",".join(f"{v:g}" for v in axis)}: every value must be >= 0'
+    n_points = int(np.prod([len(axis) for _, axis in axes]))
+    if n_seeds is not None and n_points * n_seeds > MAX_GRID_PROBLEMS:
+        return (f'--stlsq_grid: {n_points} grid points x {n_seeds} seeds = {n_points * n_seeds} problems, one launch takes at most '
+                f'{MAX_GRID_PROBLEMS}')
+    return None
+
+
 # ---- fit: each takes the sweep's context (main) and returns Xi, mask (S, d, p), the library triple and its summary lines ------
 def _rows(ctx):
     """This rank's columns lo:hi of every seed's subsample of the whole data set (see main)."""
@@ -221,8 +267,22 @@ def _fit_stlsq(ctx):
     lib = (args['poly_order'], args['include_sine'], args['include_exp'])
     sw = SeedSweepSTLSQ(ctx.x_all, ctx.dx_all, *lib, n_seeds=len(ctx.seeds), subsample=args['lbfgs_subsample'], seed0=args['seed'],
                         group=ctx.group, engine=ctx.engine, idx=_rows(ctx), idx_sorted=True)
+    n_seeds, points = len(ctx.seeds), getattr(ctx, 'grid', None)
+    if points is not None:
+        # --stlsq_grid: G points on common seeds, problem g * n_seeds + k = point g on seed k's matrices
+        hyper = {STLSQ_GRID_NAMES[name]: [point[name] for point in points for _ in ctx.seeds] for name in points[0]}
+        Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']),
+                                    lstsq_driver=args.get('lstsq_driver'), device=True, hyper=hyper)
+        lines = [f'{n_seeds} seeds x {sw.n_points} points (over {ctx.world} rank(s)), {len(points)} grid points on their Gram matrices']
+        for g in range(len(points)):
+            at = slice(g * n_seeds, (g + 1) * n_seeds)
+            near = [rec for rec in sw.near_threshold if g * n_seeds <= rec[0] < (g + 1) * n_seeds]
+            lines.append(f'grid {g}: STLSQ passes {int(passes[at].min())}-{int(passes[at].max())}, near-threshold coefficients '
+                         f'(| |coef| - thr | < 1e-4): {near if near else "none"}')
+        return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
+    route = dict(device=True) if getattr(ctx, 'device_stlsq', False) else {}
     Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']),
-                                lstsq_driver=args.get('lstsq_driver'))
+                                lstsq_driver=args.get('lstsq_driver'), **route)
     lines = [f'{len(ctx.seeds)} seeds x {sw.n_points} points (over {ctx.world} rank(s)), STLSQ passes {int(passes.min())}-{int(passes.max())}',
              f'near-threshold coefficients (| |coef| - thr | < 1e-4): {sw.near_threshold if sw.near_threshold else "none"}']
     return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
@@ -473,9 +533,12 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     ltp_bound_rel = _pop(argv, '--ltp_bound_rel', None, float)
     grid = _pop_all(argv, '--grid')
     lbfgs_grid = _pop_all(argv, '--lbfgs_grid')
+    stlsq_grid = _pop_all(argv, '--stlsq_grid')
+    device_stlsq = _pop_flag(argv, '--device_stlsq')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
-    why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds)
+    why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
+                   device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -494,8 +557,13 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     m = int(x_all.shape[0] * args['lbfgs_subsample'])
     ctx = SimpleNamespace(args=args, seeds=list(range(args['seed'], args['seed'] + n_seeds)), dev=dev, group=group, rank=rank,
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
-                          engine=engine, kw={} if engine is None else {'engine': engine}, grid=None)
-    if grid or lbfgs_grid:
+                          engine=engine, kw={} if engine is None else {'engine': engine}, grid=None,
+                          device_stlsq=device_stlsq)
+    if stlsq_grid:
+        ctx.grid_names = STLSQ_GRID_NAMES
+        ctx.grid_axes = _parse_grid(stlsq_grid, STLSQ_GRID_NAMES, '--stlsq_grid')[0]
+        ctx.grid = _grid_points(ctx.grid_axes)
+    elif grid or lbfgs_grid:
         ctx.grid_names = GRID_NAMES if grid else LBFGS_GRID_NAMES
         ctx.grid_axes = _parse_grid(grid)[0] if grid else _parse_grid(lbfgs_grid, LBFGS_GRID_NAMES, '--lbfgs_grid')[0]
         ctx.grid = _grid_points(ctx.grid_axes)

@@ -72,25 +72,120 @@ class SeedSweepSTLSQ:
             self.idx = seeded_subsamples(self.n_local, m, [1_000_003 * (seed0 + s) + rank for s in range(n_seeds)],
                                          x.device, dtype=torch.int32)
             self.m_local = m
-        self._gram = None
+        self._gram, self._gram_dev = None, None
 
-    def grams(self):
-        """(S, p+d, p+d) fp64 on the host, summed over the ranks' shards."""
-        if self._gram is None:
+    def grams(self, device=False):
+        """(S, p+d, p+d) fp64 on the host, summed over the ranks' shards.  ``device=True``: the same all-reduced matrices
+        as the tensor the gather launch (and the all-reduce) left on the device, without the copy."""
+        if not device and self._gram is not None:
+            return self._gram
+        if self._gram_dev is None and self._gram is not None:          # matrices that were handed in on the host
+            self._gram_dev = torch.from_numpy(np.ascontiguousarray(self._gram, dtype=np.float64)).to(self.x.device)
+        if self._gram_dev is None:
             G = self.engine.aug_gram_gather(self.x, self.dx, self.idx, self.order, self.flags)
-            n = torch.tensor([float(self.m_local)], dtype=torch.float64, device=G.device)
             if self.group is not None:
+                n = torch.tensor([float(self.m_local)], dtype=torch.float64, device=G.device)
                 dist.all_reduce(G, op=dist.ReduceOp.SUM, group=self.group)
                 dist.all_reduce(n, op=dist.ReduceOp.SUM, group=self.group)
-            self._gram, self.n_points = G.cpu().numpy(), int(n.item())
+                self.n_points = int(n.item())
+            else:
+                self.n_points = int(self.m_local)
+            self._gram_dev = G
+        if device:
+            return self._gram_dev
+        if self._gram is None:
+            self._gram = self._gram_dev.cpu().numpy()
         return self._gram
 
-    def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None):
+    def _replay(self, s, G_s, w_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes):
+        """Problem s again in numpy, pass by pass from the full mask, for the detailed near-threshold record."""
+        mask[s] = True
+        for it in range(max_iter):
+            xi, _ = stlsq_solve_from_gram(G_s, self.n_points, mask[s], float(w_reg), self.d, lstsq_driver)
+            xi32 = xi.astype(np.float32)
+            self.near_threshold += [(s, it, i, k, v) for i, k, v in near_threshold_cases(xi32, mask[s], threshold)]
+            new_mask = np.logical_and(np.abs(xi32) > np.float32(threshold), mask[s])   # strict >, monotone (sindy.py:194)
+            converged = np.array_equal(new_mask, mask[s])
+            Xi[s], mask[s], passes[s] = xi32, new_mask, it + 1
+            if converged:
+                break
+
+    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper):
+        """``solve(device=True)``: one symode_stlsq_sweep launch on the matrices where the gather launch left them; only
+        Xi, mask, passes, near and fell come back.  The launch takes ridge weight and threshold in fp32, as its per-problem
+        table holds them, with or without a table -- so problem (g, k) of a grid is bit for bit seed k of the scalar device
+        solve with point g's values -- and what is replayed or solved on the host here uses the same rounded values.
+        Every rank holds the same all-reduced matrices and takes the same decisions."""
+        S, d, p = self.S, self.d, self.p
+        f32 = lambda v: float(np.float32(v))                                   # noqa: E731
+        n_problems = S
+        if hyper is not None:
+            unknown = set(hyper) - {'w_reg', 'threshold'}
+            if unknown or not hyper:
+                raise ValueError(f"hyper: the per-problem columns of the STLSQ sweep are w_reg and threshold, got {sorted(hyper)}")
+            lengths = {len(v) for v in hyper.values()}
+            n_problems = lengths.pop()
+            if lengths or n_problems < S or n_problems % S != 0:
+                raise ValueError(f'hyper: every column needs one value per problem, a multiple of the {S} seeds (problem s '
+                                 f'on seed s % {S}); got lengths {sorted({len(v) for v in hyper.values()})}')
+        w = np.array([f32(v) for v in (hyper or {}).get('w_reg', [w_sindy_reg] * n_problems)], dtype=np.float64)
+        thr = np.array([f32(v) for v in (hyper or {}).get('threshold', [threshold] * n_problems)], dtype=np.float64)
+        if not (np.all(np.isfinite(w)) and np.all(np.isfinite(thr)) and np.all(w >= 0) and np.all(thr >= 0)):
+            raise ValueError('the ridge weight and the threshold of every problem must be finite and >= 0')
+        G = self.grams(device=True)
+        table = None
+        if hyper is not None:
+            table = torch.from_numpy(np.stack([w, thr], axis=1).astype(np.float32)).to(G.device)
+        Xi, m8, p32, near, fell = self.engine.stlsq_sweep(G, self.n_points, w[0], thr[0], max_iter, hyper=table, d=d,
+                                                          near_band=NEAR_THRESHOLD_BAND, to_host=True)      # one copy back
+        Xi, mask, passes = np.array(Xi), np.asarray(m8).astype(bool), np.asarray(p32).astype(np.int64)
+        near = np.array(near)
+        self.near_threshold = []
+        held = {}                                                       # set -> its (p+d, p+d) matrix on the host
+
+        def on_host(s):
+            k = s % S
+            if k not in held:
+                held[k] = G[k].cpu().numpy()
+            return held[k]
+
+        if fell.any():
+            # a pivot that was not positive: these problems are the host loop's, rank-revealing fallback and warning included
+            import warnings
+            lib = _lstsq._native()
+            for s in np.nonzero(fell)[0].tolist():
+                Gs = np.ascontiguousarray(on_host(s), dtype=np.float64)[None]
+                xi1, m1 = np.zeros((1, d, p), dtype=np.float32), np.ones((1, d, p), dtype=np.uint8)
+                p1, n1, f1 = (np.zeros(1, dtype=np.int32) for _ in range(3))
+                rc = lib.symode_host_stlsq_sweep(Gs.ctypes.data, 1, d, p, int(self.n_points), float(w[s]), float(thr[s]), int(max_iter),
+                                                 1, float(NEAR_THRESHOLD_BAND), xi1.ctypes.data, m1.ctypes.data, p1.ctypes.data,
+                                                 n1.ctypes.data, f1.ctypes.data)
+                if rc != 0:
+                    raise RuntimeError(f'symode_host_stlsq_sweep failed with code {rc}')
+                Xi[s], mask[s], passes[s], near[s] = xi1[0], m1[0].astype(bool), p1[0], n1[0]
+            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
+                          RuntimeWarning)
+        for s in np.nonzero(near)[0].tolist():
+            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'gels', Xi, mask, passes)
+        return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
+
+    def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None):
         """STLSQ to convergence for every seed (train.py:872-887 per seed).
-        Returns (Xi (S, d, p) float32, mask (S, d, p) float32, passes (S,))."""
-        G = self.grams()
+        Returns (Xi (S, d, p) float32, mask (S, d, p) float32, passes (S,)).
+        ``device=True``: the fit runs on the device (``_solve_device``; the full-rank driver only), the host route stays the
+        default.  ``hyper={"w_reg": [...], "threshold": [...]}`` (with ``device=True``): one value per PROBLEM, n_problems = G x S
+        for a grid of G points on the S seeds' shared matrices, problem s on seed s % S; the arrays returned are then
+        (G S, d, p) and (G S,), and a column left out takes the scalar argument."""
+        if hyper is not None and not device:
+            raise ValueError('hyper (a per-problem table of w_reg / threshold) needs device=True: the host route takes one value each')
         if lstsq_driver is None:                   # torch.linalg.lstsq's default on the device the data lives on (sindy.py)
             lstsq_driver = "gels" if self.x.is_cuda else "gelsy"
+        if device:
+            if lstsq_driver != 'gels':
+                raise ValueError(f"device=True fits with the full-rank driver (gels) only, not lstsq_driver='{lstsq_driver}': the "
+                                 'rank rule of gelsy runs on the host route')
+            return self._solve_device(w_sindy_reg, threshold, max(1, int(max_iter)), hyper)
+        G = self.grams()
         S, d, p = self.S, self.d, self.p
         Xi = np.zeros((S, d, p), dtype=np.float32)
         mask = np.ones((S, d, p), dtype=bool)
@@ -115,18 +210,8 @@ class SeedSweepSTLSQ:
                               RuntimeWarning)
             mask, passes = m8.astype(bool), p32.astype(np.int64)
             todo = [int(s) for s in np.nonzero(near)[0]]
-            for s in todo:
-                mask[s] = True
         for s in todo:
-            for it in range(max_iter):
-                xi, _ = stlsq_solve_from_gram(G[s], self.n_points, mask[s], float(w_sindy_reg), d, lstsq_driver)
-                xi32 = xi.astype(np.float32)
-                self.near_threshold += [(s, it, i, k, v) for i, k, v in near_threshold_cases(xi32, mask[s], threshold)]
-                new_mask = np.logical_and(np.abs(xi32) > np.float32(threshold), mask[s])   # strict >, monotone (sindy.py:194)
-                converged = np.array_equal(new_mask, mask[s])
-                Xi[s], mask[s], passes[s] = xi32, new_mask, it + 1
-                if converged:
-                    break
+            self._replay(s, G[s], w_sindy_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes)
         return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
 
 
