@@ -245,6 +245,35 @@ int symode_loss_grad_reversed_constj_live(const float* x, const float* dx, const
                                           float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes,
                                           void* stream);
 
+/* Is g(x) the linear image J x of x under the compact table?  x (S, n, d), gx (S, n_g, n, d), table (S, n_g, d, d) as
+ * symode_jacobian_constant left it.  flag_out (one int32, device): 1 when, for every component a of every point,
+ *     | gx_a - sum_b J_ab x_b |  <=  4 u sum_b |J_ab| |x_b|,   u = 2^-24,
+ * evaluated in fp64 on the fp32 inputs (any fp32 evaluation of the dot product lies within about 2 u of the sum), and x, gx
+ * and the table are finite; else 0 -- a NaN or an infinity anywhere, an offset (affine actions are not linear), any other map.
+ * m_out (S, n_g, p, p) fp64: the substitution matrix M of each (problem, group element), Theta(J x) = M Theta(x), built in
+ * fp64 from the fp32 table, rows and columns in the library's column order, block diagonal by degree (exact zeros outside
+ * the blocks); meaningful where the flag is 1.  One streaming pass, meant to run once per data set.
+ * d = 2, flags = 0, order 1-5, n_g = 1; anything else: SYMODE_E_UNSUPPORTED.  Added to ABI version 8 (nothing existing
+ * changed).
+ * replaces: nothing in the reference (precompute_symmreg_r, model_utils.py:172-211, stores g(x) per point whatever g is). */
+int symode_linear_action(const float* x, const float* gx, const float* table, int n_g, long n_problems, long n, int d, int order,
+                         int flags, double* m_out, int* flag_out, void* stream);
+
+/* symode_loss_grad_reversed_constj_live under a linear action (symode_linear_action answered 1; m_table is its m_out).
+ * With h = Xi Theta:  u = J h(x) - h(J x) = C Theta(x), C = J Xi - Xi M (fp64 products, once per problem and launch), and
+ * sum_n u Theta(J x)^T = (sum_n u Theta(x)^T) M^T: the point loop reads x and dx alone (16 instead of 24 bytes per point),
+ * evaluates the library once and applies [Xi; C] to it; the gradient is R + w_sym (J^T U - U M^T), formed before the partial
+ * rows.  Results: those of the _constj_live entry on gx = J x exactly, up to rounding -- NOT bit-identical (gx is not read;
+ * u comes from C instead of the difference of two fp32 chains, which is the more accurate where u is round-off).
+ * Where the launcher's table keeps the streamed kernels for the library and column set, and everywhere with
+ * SYMODE_CLOSURE_FOLD=0, the call IS the _constj_live entry on (gx, table), bit for bit.  The body taken is left in word 1 of
+ * the workspace header.  Workspace as for the other closures.  d = 2, flags = 0, order 1-5, n_g = 1; anything else:
+ * SYMODE_E_UNSUPPORTED.  Added to ABI version 8 (nothing existing changed). */
+int symode_loss_grad_reversed_linear(const float* x, const float* dx, const float* gx, const float* table, const double* m_table,
+                                     int n_g, long n_problems, long n, int d, int order, int flags, const float* xi,
+                                     const float* mask, unsigned long long live_columns, float inv_count, float w_sym,
+                                     float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Gram matrix of the reversed regulariser: for S problems (layouts as in symode_symreg_reversed_batched, n_g >= 1)
  *     gram_out[s] (d p, d p) fp64 = sum_g sum_n B^T B,   B[i, (j, a)] = J_g(x_n)[i, j] theta_a(x_n) - delta_ij theta_a(g x_n),
  * rows and columns in Xi's (d, p) row-major order, both triangles filled: the regulariser of symode_symreg_reversed_batched

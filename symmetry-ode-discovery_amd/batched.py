@@ -61,7 +61,7 @@ def allreduce_sums(sums, params, group):
 class BatchedClosure:
     def __init__(self, x, dx, poly_order, include_sine=False, include_exp=False, Q=None, use_kron_product=True,
                  allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True, coef=None,
-                 const_jacobian=None, live_columns=True):
+                 const_jacobian=None, live_columns=True, linear_action=None):
         """``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from Q / use_kron_product / allow_constant).
         ``reversed_sym = (gx (S, n_g, N_local, d), jgx (S, n_g, N_local, d, d), weight)`` adds  weight * the reversed
         symmetry regulariser (model_utils.py:126-170 on precomputed (g(x), J_g(x))) to every problem's loss and gradient:
@@ -78,7 +78,13 @@ class BatchedClosure:
         closures which library columns the map can fill (``CoefMap.live_mask``, read once here): the columns the
         constraint keeps at zero up to the round-off of Q count as exactly zero and cost nothing per point where the
         library has a kernel for the set; False -- the dense launch (A/B, tests).  ``loss_grad_xi`` called directly is
-        dense unless it is given a set."""
+        dense unless it is given a set.
+        ``linear_action``: None (default) -- where the constant-J verdict is yes (d = 2 plain polynomial library, one group
+        element, fused launch), a second pass (engine.linear_action) asks whether g(x) is the linear image J x of x to within
+        4 * 2^-24 per component; if so the fused closure takes the kernel that folds the action into the coefficients: it reads
+        x and dx alone and evaluates the library once per point.  Same closure up to rounding, NOT bit for bit (g(x) is
+        replaced by J x); SYMODE_CLOSURE_FOLD=0 or False keep the streamed kernels.  The verdict is remembered with the
+        version counters and data pointers of x and gx, as jgx's is."""
         assert x.dim() == 3 and x.shape == dx.shape, "x, dx must be (S, N_local, d)"
         self.engine = engine or get_engine()
         self.x, self.dx = x.contiguous(), dx.contiguous()
@@ -119,6 +125,12 @@ class BatchedClosure:
         self._cj_seen, self._cj_table = None, None
         if self._cj_detect:
             self._jacobian_for_launch()
+        self._lin_detect = linear_action is None or bool(linear_action)
+        self._lin_detect = self._lin_detect and self._cj_detect and fuse_sym and self.d == 2 and self.flags == 0 \
+            and 1 <= poly_order <= 5 and self.sym[0].shape[1] == 1 and hasattr(self.engine, 'linear_action')
+        self._lin_seen, self._lin_m, self.linear_detections = None, None, 0
+        if self._lin_detect:
+            self._linear_for_launch()
         self._live = None                                    # the map's column set, where it names a dead column at all
         if live_columns and self._cj_detect:
             live = self.coef.live_mask()
@@ -135,6 +147,22 @@ class BatchedClosure:
             table, const = self.engine.jacobian_constant(jgx)
             self._cj_seen, self._cj_table = seen, (table if const else None)
         return jgx if self._cj_table is None else self._cj_table
+
+    def _linear_for_launch(self):
+        """The fp64 (S, 1, p, p) substitution matrices where g(x) = J x was detected (and J_g is a compact table), else None.
+        The pass runs once per (version, pointer) of x, gx and jgx; ``linear_detections`` counts its runs."""
+        if not self._lin_detect:
+            return None
+        table = self._jacobian_for_launch()
+        if self._cj_table is None:
+            return None
+        gx = self.sym[0]
+        seen = (self.x._version, self.x.data_ptr(), gx._version, gx.data_ptr(), self._cj_seen)
+        if seen != self._lin_seen:
+            m, linear = self.engine.linear_action(self.x, gx, table, self.order, self.flags)
+            self._lin_seen, self._lin_m = seen, (m if linear else None)
+            self.linear_detections += 1
+        return self._lin_m
 
     # -- coefficient plumbing (batched get_Xi, sindy.py:169-176) ----------------------------
     def xi_from(self, beta, const=None):
@@ -153,6 +181,7 @@ class BatchedClosure:
         live_kw = {} if live_columns is None else {'live_columns': live_columns}
         fused = self.sym is not None and self.fuse_sym and hasattr(self.engine, 'loss_grad_reversed')
         jg = self._jacobian_for_launch() if self.sym is not None else None      # (S, n_g, d, d) table or the (S, n_g, N, d, d) tensor
+        lin = self._linear_for_launch() if fused else None                      # M of a detected linear action: the fold kernel
         for ci, ((a, b), buf) in enumerate(zip(self.chunks, self.buffers)):
             n = b - a
             loss = buf[:n]
@@ -165,7 +194,8 @@ class BatchedClosure:
                 l2 = sb[:2 * n].view(n, 2)
                 self.engine.loss_grad_reversed(self.x[a:b], self.dx[a:b], gx[a:b], jg[a:b], Xi[a:b],
                                                None if mask is None else mask[a:b], self.order, self.flags, w_sym=weight,
-                                               inv_count=self.inv_count, out=(l2, grad), **live_kw, **self._ws_kw)
+                                               inv_count=self.inv_count, out=(l2, grad), **live_kw, **self._ws_kw,
+                                               **({} if lin is None else {'linear_m': lin[a:b]}))
                 torch.add(l2[:, 0], l2[:, 1], alpha=weight, out=loss)
                 if self.distributed:
                     works.append(dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True))

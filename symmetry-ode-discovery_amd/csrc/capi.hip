@@ -5,6 +5,7 @@
 
 #include "../../include/symode.h"
 #include "jconst.hpp"
+#include "linear_action.hpp"
 #include "ops_table.hpp"
 #include "quad_closure.hpp"
 #include "stlsq.hpp"
@@ -127,6 +128,20 @@ size_t workspace_doubles(const LibOps* ops, long S, long n) {
     if (!workspace || misaligned(workspace, 8)) return SYMODE_E_WORKSPACE;                   \
     if (workspace_bytes < workspace_doubles(ops, (S_), (n_)) * sizeof(double)) return SYMODE_E_WORKSPACE;
 
+// Workgroups per problem of a reversed-closure launch (the streamed forms and the fold kernel of a linear action alike).
+int reversed_closure_grid(bool fused, const LibOps* ops, long n_problems, long n, int d) {
+    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
+    if (n_problems == 1) {
+        int cap = small_grid_cap(n, true);
+        // the regulariser alone, 32 B/point: the small libraries stream best from ONE workgroup per CU like the other
+        //  reductions -- order 3 at 2^26 points 314 us = 0.855 of HBM on 256 workgroups against 338 on 512; order 4-5 want the
+        //  second one: 340 against 374 us.  The fused closure (40 B/point) keeps the cap of small_grid_cap.
+        if (!fused && cap > 256 && ops->d * ops->p <= 24 && knobs().small_grid < 0) cap = 256;
+        if (cap > 0 && gx > cap) gx = cap;
+    }
+    return gx;
+}
+
 // The reversed-symmetry closure: the one path from its seven C entries to LibOps::symreg_reversed.
 //   fused   MSE + w_sym * regulariser on (x, dx), loss (S, 2); else the regulariser alone, loss (S) (dx, w_sym unused)
 //   constj  jgx is the compact (S, n_g, d, d) table of a point-constant Jacobian (symode_jacobian_constant), not the
@@ -148,15 +163,7 @@ int reversed_closure(bool fused, bool constj, const float* x, const float* dx, c
         misaligned(loss_out, 4) || misaligned(grad_out, 4))
         return SYMODE_E_ALIGN;
     SYMODE_CHECK_WS(n_problems, n);
-    int gx = grid_x_for(n, n_problems, ppt_for(d), 512);
-    if (n_problems == 1) {
-        int cap = small_grid_cap(n, true);
-        // (2) the regulariser alone, 32 B/point: the small libraries stream best from ONE workgroup per CU like the other
-        //  reductions -- order 3 at 2^26 points 314 us = 0.855 of HBM on 256 workgroups against 338 on 512; order 4-5 want the
-        //  second one: 340 against 374 us.  The fused closure (40 B/point) keeps the cap of small_grid_cap.
-        if (!fused && cap > 256 && ops->d * ops->p <= 24 && knobs().small_grid < 0) cap = 256;
-        if (cap > 0 && gx > cap) gx = cap;
-    }
+    const int gx = reversed_closure_grid(fused, ops, n_problems, n, d);   // (2) the regulariser alone has a grid rule of its own
     // (3) without dx there is no second term to weigh the regulariser against: its weight is 1
     return (int)ops->symreg_reversed(x, dx, gx_, jgx, constj, n_g, n_problems, n, xi, mask, live, inv_count,
                                      fused ? w_sym : 1.0f, loss_out, grad_out, (double*)workspace, gx, (hipStream_t)stream);
@@ -393,6 +400,41 @@ int symode_jacobian_constant(const float* jgx, int n_g, long n_problems, long n,
     if (!jgx || !table_out || !flag_out) return SYMODE_E_NULLPTR;
     if (misaligned(jgx, 4) || misaligned(table_out, 4) || misaligned(flag_out, 4)) return SYMODE_E_ALIGN;
     return (int)launch_jacobian_constant(jgx, n_problems * (long)n_g, n, d, table_out, flag_out, (hipStream_t)stream);
+}
+
+int symode_linear_action(const float* x, const float* gx_, const float* table, int n_g, long n_problems, long n, int d, int order,
+                         int flags, double* m_out, int* flag_out, void* stream) {
+    if (d != 2 || flags != 0 || order < 1 || order > MAX_ORDER) return SYMODE_E_UNSUPPORTED;
+    if (n < 1 || n_g < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
+    if (n_g != 1) return SYMODE_E_UNSUPPORTED;
+    if (!x || !gx_ || !table || !m_out || !flag_out) return SYMODE_E_NULLPTR;
+    if (misaligned(x, 4) || misaligned(gx_, 4) || misaligned(table, 4) || misaligned(m_out, 8) || misaligned(flag_out, 4))
+        return SYMODE_E_ALIGN;
+    return (int)launch_linear_action(x, gx_, table, n_problems, n, order, m_out, flag_out, (hipStream_t)stream);
+}
+
+int symode_loss_grad_reversed_linear(const float* x, const float* dx, const float* gx_, const float* table, const double* m_table,
+                                     int n_g, long n_problems, long n, int d, int order, int flags, const float* xi,
+                                     const float* mask, unsigned long long live_columns, float inv_count, float w_sym,
+                                     float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (d != 2 || flags != 0 || order < 1 || order > MAX_ORDER) return SYMODE_E_UNSUPPORTED;
+    if (n_g < 1) return SYMODE_E_BADSIZE;
+    if (n_g != 1) return SYMODE_E_UNSUPPORTED;
+    if (!m_table) return SYMODE_E_NULLPTR;
+    if (misaligned(m_table, 8)) return SYMODE_E_ALIGN;
+    SYMODE_GET_OPS();
+    // where the launcher's table (or SYMODE_CLOSURE_FOLD=0) keeps the streamed kernels, this IS the _constj_live entry
+    if (!ops->symreg_fold || !ops->fold_takes(live_columns))
+        return reversed_closure(true, true, x, dx, gx_, table, n_g, n_problems, n, d, order, flags, xi, mask, inv_count, w_sym,
+                                loss2_out, grad_out, workspace, workspace_bytes, stream, live_columns);
+    if (n < 1 || n_problems < 1 || n_problems > 65535) return SYMODE_E_BADSIZE;
+    if (!x || !dx || !gx_ || !table || !xi || !loss2_out || !grad_out) return SYMODE_E_NULLPTR;
+    if (misaligned(x, 4) || misaligned(dx, 4) || misaligned(gx_, 4) || misaligned(table, 4) || misaligned(xi, 4) || misaligned(mask, 4) ||
+        misaligned(loss2_out, 4) || misaligned(grad_out, 4))
+        return SYMODE_E_ALIGN;
+    SYMODE_CHECK_WS(n_problems, n);
+    return (int)ops->symreg_fold(x, dx, table, m_table, n_problems, n, xi, mask, live_columns, inv_count, w_sym, loss2_out, grad_out,
+                                 (double*)workspace, reversed_closure_grid(true, ops, n_problems, n, d), (hipStream_t)stream);
 }
 
 size_t symode_symreg_reversed_gram_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long n) {

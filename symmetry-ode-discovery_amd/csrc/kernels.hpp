@@ -23,7 +23,7 @@ constexpr int MAP_CHUNKS_PER_THREAD = SYMODE_MAP_CHUNKS;   // chunks a thread of
 // for the tests and tuning tools that compare two settings inside one process; no launch path calls getenv.
 struct Knobs {
     long max_grid, min_grid_x, map_grid, gram_grid, gram_valu_grid, small_grid, reduce_grid;
-    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live;
+    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live, closure_fold;
     long gram_m4_grid;
 };
 
@@ -49,6 +49,7 @@ inline Knobs read_knobs() {
     k.gram_m4_grid = num("SYMODE_GRAM_M4_GRID", -1);
     k.closure_pk = on("SYMODE_CLOSURE_PK");
     k.closure_live = on("SYMODE_CLOSURE_LIVE");
+    k.closure_fold = on("SYMODE_CLOSURE_FOLD");
     return k;
 }
 
@@ -136,6 +137,13 @@ struct LibOps {
     // adam_epochs on the latent branch: a.x, a.dx are z, dz; a.lat_b, a.lat_y, a.lat_e, a.gen_l, a.n_gen (adam.hpp).  Last in
     // the table: an additive entry
     hipError_t (*adam_epochs_latent)(const AdamArgs& a, hipStream_t st);
+    // the fused reversed closure under a linear action g(x) = J x (closure_fold.hpp): jt the (S, 1, d, d) table, mt the fp64
+    // (S, 1, p, p) substitution matrices; nullptr where the library has no such kernel.  fold_takes: does a call with this
+    // column set go there (the launcher's table and SYMODE_CLOSURE_FOLD)?  Additive entries
+    hipError_t (*symreg_fold)(const float* x, const float* dx, const float* jt, const double* mt, long S, long n, const float* xi,
+                              const float* mask, unsigned long long live, float inv_count, float w_sym, float* loss, float* grad,
+                              double* ws, int gx, hipStream_t st);
+    bool (*fold_takes)(unsigned long long live);
 };
 
 // ---------------------------------------------------------------------------------------
@@ -442,6 +450,7 @@ constexpr long WS_MAX_PROBLEMS = 65536;                              // tickets 
 constexpr int WS_BODY_WORD = 1;                                      // header word the reversed closure leaves its body in:
 constexpr unsigned long long WS_BODY_SCALAR = 1, WS_BODY_PACKED = 2; //   which of its two bit-identical bodies the last launch took,
 constexpr unsigned long long WS_BODY_LIVE = 4;                       //   + this where it was the form that leaves out dead columns
+constexpr unsigned long long WS_BODY_FOLD = 8;                       //   the fold kernel of a linear action (closure_fold.hpp), alone or + WS_BODY_LIVE
 constexpr long WS_HEADER_DOUBLES = 8 + WS_MAX_PROBLEMS / 2;          // [magic, 7 reserved | uint32 tickets] in front of the partials
 
 struct Finish {

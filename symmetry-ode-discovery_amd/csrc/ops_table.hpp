@@ -1,6 +1,7 @@
 // One translation unit per state dimension D instantiates every kernel for its libraries.
 #pragma once
 #include "adam.hpp"
+#include "closure_fold.hpp"
 #include "closure_rev.hpp"
 #include "gram.hpp"
 #include "gram_rev.hpp"
@@ -39,7 +40,9 @@ constexpr LibOps make_ops() {
                   &launch_adam_epochs<Lib>,
                   &launch_adam_epochs_reversed<Lib>,
                   &launch_latent_closure<Lib>,
-                  &launch_adam_epochs_latent<Lib>};
+                  &launch_adam_epochs_latent<Lib>,
+                  fold_launcher<Lib>(),
+                  fold_takes_fn<Lib>()};
 }
 
 #define SYMODE_OPS_ALL_FLAGS(D, O) make_ops<D, O, 0>(), make_ops<D, O, 1>(), make_ops<D, O, 2>(), make_ops<D, O, 3>()

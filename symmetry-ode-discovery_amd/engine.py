@@ -64,6 +64,11 @@ _SIGNATURES = {
     "symode_loss_grad_reversed_constj_live": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int,
                                                       c_int, c_void_p, c_void_p, ctypes.c_ulonglong, c_float, c_float, c_void_p,
                                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+    "symode_linear_action": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p]),
+    "symode_loss_grad_reversed_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int,
+                                                 c_int, c_int, c_void_p, c_void_p, ctypes.c_ulonglong, c_float, c_float, c_void_p,
+                                                 c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_loss_grad_latent": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
                                         c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
@@ -631,11 +636,13 @@ class HipEngine:
             raise SymodeError("private workspace too small for this call")
         return loss, grad, ws, 1.0 / (n * d) if inv_count is None else float(inv_count)
 
-    def _closure_call(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, stream, live=None):
+    def _closure_call(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, stream, live=None, linear_m=None):
         """One closure launch, ready to go: (entry name, its argument tuple, the tensors the arguments point into, what
         the caller gets back).  ``dx`` None: the regulariser alone; ``rev`` None: the MSE alone, else what
         _reversed_operands returned; ``live``: the set of library columns that may hold a coefficient (an int, bit k =
-        column k), honoured by the compact-table forms (their _live entries) and without effect elsewhere.  The ONE
+        column k), honoured by the compact-table forms (their _live entries) and without effect elsewhere.
+        ``linear_m``: the substitution matrices of a linear action (``linear_action``), fused compact-table form only: the call
+        goes to symode_loss_grad_reversed_linear.  The ONE
         statement of the closures' C signatures: the eager methods call ``getattr(lib, name)(*args)``, bind_closure
         converts ``args`` once and keeps the call."""
         batched, S, n, d = self._problems(x)
@@ -651,7 +658,14 @@ class HipEngine:
             head += (self._ptr(gx), self._ptr(jgx), n_g)
             keep += (gx, jgx)
             name = ("symode_loss_grad_reversed" if fused else "symode_symreg_reversed_batched") + ("_constj" if constj else "")
-            if constj and live is not None:
+            if linear_m is not None:
+                if not (fused and constj and linear_m.dtype == torch.float64 and linear_m.is_contiguous()
+                        and linear_m.numel() == S * n_g * p * p):
+                    raise SymodeError("linear_m goes with the fused compact-table closure and holds (S, n_g, p, p) float64")
+                head = head[:3] + (self._ptr(jgx), self._ptr(linear_m), n_g)
+                keep += (linear_m,)
+                name, live_arg = "symode_loss_grad_reversed_linear", ((0xFFFFFFFFFFFFFFFF if live is None else int(live)) & 0xFFFFFFFFFFFFFFFF,)
+            elif constj and live is not None:
                 name, live_arg = name + "_live", (int(live) & 0xFFFFFFFFFFFFFFFF,)
         args = head + (S, n, d, order, flags, self._ptr(xi), self._ptr(mask)) + live_arg + (inv,) + ((float(w_sym),) if fused else ()) \
             + (self._ptr(loss), self._ptr(grad), self._ptr(ws), ws.numel() * 8, stream)
@@ -659,9 +673,9 @@ class HipEngine:
         loss, grad = loss.reshape(S, 2) if fused else loss.reshape(S), grad.reshape(S, d, p)
         return name, args, keep, (loss, grad) if batched else (loss[0], grad[0])
 
-    def _closure(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live=None):
+    def _closure(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live=None, linear_m=None):
         name, args, _, result = self._closure_call(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, self._stream(x),
-                                                   live)
+                                                   live, linear_m)
         self._check(getattr(self.lib, name)(*args), name)
         return result
 
@@ -754,29 +768,53 @@ class HipEngine:
                                                       self._stream(jgx)), "symode_jacobian_constant")
         return table, bool(flag.item())
 
+    def linear_action(self, x, gx, table, order, flags=0):
+        """Is g(x) = J x under the compact table of ``jacobian_constant``?  x (S, N, d), gx (S, 1, N, d), table (S, 1, d, d)
+        [one problem: (N, d), (1, N, d), (1, d, d)] -> (M (S, 1, p, p) float64 with Theta(J x) = M Theta(x), is_linear).
+        Per component |gx - J x| <= 4 * 2^-24 * |J| |x| in fp64 (symode.h: symode_linear_action); a NaN, an infinity or an
+        offset answers False.  d = 2 plain polynomial libraries, one group element.  One streaming pass and ONE
+        synchronisation: meant to run once per data set.  With is_linear, ``M`` may be passed as ``linear_m`` to
+        loss_grad_reversed."""
+        x, gx, table = self._dev(x, "x"), self._dev(gx, "gx"), self._dev(table, "table")
+        batched, S, n, d = self._problems(x)
+        n_g = gx.shape[-3]
+        if tuple(gx.shape) != ((S, n_g, n, d) if batched else (n_g, n, d)) or tuple(table.shape) != tuple(gx.shape[:-2]) + (d, d):
+            raise SymodeError(f"gx {tuple(gx.shape)} / table {tuple(table.shape)} do not match x {tuple(x.shape)}")
+        p = self.lib_size(d, order, flags)
+        m = torch.empty((S, n_g, p, p) if batched else (n_g, p, p), dtype=torch.float64, device=x.device)
+        flag = torch.empty(1, dtype=torch.int32, device=x.device)
+        self._check(self.lib.symode_linear_action(self._ptr(x), self._ptr(gx), self._ptr(table), n_g, S, n, d, order, flags,
+                                                  self._ptr(m), self._ptr(flag), self._stream(x)), "symode_linear_action")
+        return m, bool(flag.item())
+
     @staticmethod
     def closure_body(ws):
         """Which body the last reversed-closure launch on workspace ``ws`` took: "scalar", "packed" (the packed-fp32 body of the
         compact-table form, d = 2; SYMODE_CLOSURE_PK=0 turns it off), either with "-live" where it was the kernel that leaves out
-        the columns outside ``live_columns`` (SYMODE_CLOSURE_LIVE=0 turns that off), or None before any.  The kernel leaves it in word 1 of the
+        the columns outside ``live_columns`` (SYMODE_CLOSURE_LIVE=0 turns that off), "fold" / "fold-live" for the kernel of a linear
+        action that reads no g(x) (``linear_m``; SYMODE_CLOSURE_FOLD=0 turns it off), or None before any.  The kernel leaves it in word 1 of the
         workspace header (an initialised workspace only, and only its LAST launch is visible): the two bodies return the same
         bits, so the results cannot tell.  One synchronisation."""
-        return {1: "scalar", 2: "packed", 5: "scalar-live", 6: "packed-live"}.get(int(ws.view(torch.int64)[1].item()))
+        return {1: "scalar", 2: "packed", 5: "scalar-live", 6: "packed-live", 8: "fold", 12: "fold-live"}.get(int(ws.view(torch.int64)[1].item()))
 
     def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None,
-                           live_columns=None):
+                           live_columns=None, linear_m=None):
         """The closure MSE + w_sym * reversed regulariser in ONE pass (x read once, Theta(x) shared by both terms).
         Shapes as loss_grad / symreg_reversed (jgx may be the compact table of a point-constant Jacobian, as there).
         Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mse, regulariser), grad = d(mse + w_sym * regulariser)/dXi
         (S, d, p) [or (d, p)].
         ``live_columns``: an int, bit k set = library column k may hold a coefficient (``CoefMap.live_mask``); with the compact
         table the call goes to the _live entry (symode.h): columns outside the set count as zero, their gradient is zero,
-        and where the library has a kernel for the set it leaves their per-point work out.  None: every column."""
+        and where the library has a kernel for the set it leaves their per-point work out.  None: every column.
+        ``linear_m``: the float64 (S, 1, p, p) matrices of ``linear_action`` where it found g(x) = J x (jgx the compact table):
+        the call goes to symode_loss_grad_reversed_linear, whose kernel reads neither g(x) nor evaluates Theta(g x) -- the
+        same closure up to rounding, not bit for bit; where the library's launcher keeps the streamed kernels it is the
+        call without ``linear_m``."""
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
         rev = self._reversed_operands(x, gx, jgx, compact_ok=True)
-        return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live_columns)
+        return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live_columns, linear_m)
 
     def loss_grad_latent(self, z, dz, B, y, xi, mask, order, flags=0, w_pair=1.0, inv_count=None, out=None, ws=None):
         """The closure of the latent fit in ONE pass (symode_loss_grad_latent): z, dz, y (S, N, d) or (N, d), B (S, N, d, d)

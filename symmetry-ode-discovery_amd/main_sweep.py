@@ -50,6 +50,10 @@ full-rank driver only); outputs and summary lines are those of ``--method stlsq`
 (repeatable; names threshold, w_sindy_reg; with --device_stlsq only) is the grid of that sweep: the G x n_seeds problems of the
 one launch read the n_seeds matrices -- no further data pass, copy or collective.  Problem order, result files and table are
 ``--grid``'s.
+
+``--fold_linear_action`` lets the closure of the reversed regulariser fold a linear group action g(x) = J x into its
+coefficients where the data are found to be one (``BatchedClosure(linear_action=None)``): a faster kernel and the same
+closure up to rounding, not bit for bit -- which is why it has to be asked for here.
 """
 from __future__ import annotations
 
@@ -337,7 +341,9 @@ def _fit_lbfgs(ctx):
         rev = None
         if sym:
             rev = (gx[:, table.long()].transpose(0, 1).contiguous(), jgx[:, table.long()].transpose(0, 1).contiguous(), w_sym)
-        clos = BatchedClosure(X, DX, *lib, reversed_sym=rev, coef=template.coef, group=ctx.group, **ctx.kw)
+        # (the fold kernel of a linear group action is the same closure up to rounding, not bit for bit: asked for by name)
+        clos = BatchedClosure(X, DX, *lib, reversed_sym=rev, coef=template.coef, group=ctx.group,
+                              linear_action=None if getattr(ctx, 'fold_linear_action', False) else False, **ctx.kw)
     sweep = SeedSweepLBFGS(clos, args['lr_sindy'], args['threshold'], args['st_freq'], w_sindy_x=args['w_sindy_x'],
                            sindy_reg_type=args['sindy_reg_type'], w_sindy_reg=args['w_sindy_reg'],
                            gram_closure=bool(args.get('gram_closure')), statistics=stats)
@@ -535,6 +541,7 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     lbfgs_grid = _pop_all(argv, '--lbfgs_grid')
     stlsq_grid = _pop_all(argv, '--stlsq_grid')
     device_stlsq = _pop_flag(argv, '--device_stlsq')
+    fold_linear_action = _pop_flag(argv, '--fold_linear_action')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
@@ -558,7 +565,7 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     ctx = SimpleNamespace(args=args, seeds=list(range(args['seed'], args['seed'] + n_seeds)), dev=dev, group=group, rank=rank,
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
                           engine=engine, kw={} if engine is None else {'engine': engine}, grid=None,
-                          device_stlsq=device_stlsq)
+                          device_stlsq=device_stlsq, fold_linear_action=fold_linear_action)
     if stlsq_grid:
         ctx.grid_names = STLSQ_GRID_NAMES
         ctx.grid_axes = _parse_grid(stlsq_grid, STLSQ_GRID_NAMES, '--stlsq_grid')[0]

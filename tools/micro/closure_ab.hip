@@ -10,6 +10,10 @@
 // launcher's table (closure_rev.hpp, closure_pk_pays) is read off this run.
 // `closure_ab live`: every column against the constant + odd-degree column set (LIVE) of the constant-Jacobian fused closure
 // for the d = 2 plain libraries, both bodies at orders 4-5, same shapes and passes.  closure_live_pays is read off this run.
+// `closure_ab fold`: the fold kernel of a linear action (closure_fold.hpp: x and dx alone, 16 B/point, one library evaluation)
+// against the kernel the launcher ships for the same call, d = 2 plain orders 1-5 on every column and on the constant +
+// odd-degree set at orders 4-5, same shapes and passes; a fold arm with four chunks in flight beside the launcher's two.
+// closure_fold_dense_pays / closure_fold_live_pays are read off this run.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -I symmetry-ode-discovery_amd/csrc
 //              -o tools/micro/closure_ab tools/micro/closure_ab.hip
 #include <hip/hip_runtime.h>
@@ -20,6 +24,7 @@
 #include <cstring>
 #include <vector>
 
+#include "closure_fold.hpp"
 #include "closure_rev.hpp"
 #include "kernels.hpp"
 using namespace symode;
@@ -251,6 +256,40 @@ int main(int argc, char** argv) {
                 }
                 LVRUN(1, false) LVRUN(2, false) LVRUN(3, false) LVRUN(4, false) LVRUN(5, false)
                 LVRUN(4, true) LVRUN(5, true)
+            }
+        CK(hipDeviceSynchronize());
+        return 0;
+    }
+    if (argc > 1 && strcmp(argv[1], "fold") == 0) {
+        double* mt;                                   // (S, p, p) substitution matrices: the identity (the timing does not read their values)
+        CK(hipMalloc(&mt, S * L5::P * L5::P * 8));
+        CK(hipMemset(mt, 0, S * L5::P * L5::P * 8));
+        printf("# fused closure, constant J: shipped streamed kernel (24 B/point) | fold (16 B/point), ring 2 | fold, ring 4: us per launch (min of 3 rounds of 5), three passes\n");
+        const long shapes[2][2] = {{S, NB}, {64, 50000}};
+#define FDRUN(ORDER, SPARSE)                                                                                                       \
+    {                                                                                                                              \
+        using LB = Library<2, ORDER, 0>;                                                                                           \
+        constexpr unsigned long long LV = SPARSE ? odd_degree_columns<LB>() : ~0ull;                                               \
+        constexpr bool PKB = !SPARSE && closure_pk_pays<LB>;                                                                       \
+        const double a_ = time_us([&] { symreg_reversed_kernel<LB, true, 2, 32, true, 3, PKB, LV><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
+                                            x, dx, gx, jgx, 1, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5);               \
+        const double b_ = time_us([&] { symreg_fold_kernel<LB, 2, fold_minw<LB, SPARSE>, LV, fold_sgpr<LB>, fold_sgpr<LB>><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
+                                            x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5);                  \
+        const double c_ = time_us([&] { symreg_fold_kernel<LB, 4, fold_minw<LB, SPARSE>, LV, fold_sgpr<LB>, fold_sgpr<LB>><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
+                                            x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5);                  \
+        printf("pass %d  %5ld x %6ld  order %d (p = %2d) %s  streamed %8.1f us  fold %8.1f us  fold ring 4 %8.1f us  fold/streamed %.3f  ring4/streamed %.3f\n", \
+               pass, Sx, Nx, ORDER, LB::P, SPARSE ? "odd set" : "dense  ", a_, b_, c_, b_ / a_, c_ / a_);                          \
+    }
+        for (int pass = 0; pass < 3; ++pass)
+            for (const auto& sh : shapes) {
+                const long Sx = sh[0], Nx = sh[1];
+                const int gxw = grid_x_for(Nx, Sx, 2, 512);
+                if ((long)gxw * Sx > max_rows) {
+                    fprintf(stderr, "grid %d x %ld needs more partial rows than the workspace holds\n", gxw, Sx);
+                    return 1;
+                }
+                FDRUN(1, false) FDRUN(2, false) FDRUN(3, false) FDRUN(4, false) FDRUN(5, false)
+                FDRUN(4, true) FDRUN(5, true)
             }
         CK(hipDeviceSynchronize());
         return 0;
