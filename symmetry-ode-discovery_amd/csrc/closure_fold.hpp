@@ -30,15 +30,121 @@ constexpr int fold_deg_lo(int k) {
     return g * (g + 1) / 2;
 }
 
+// The packed body's pairing of the live columns from 1 on, two to an aligned register pair in column order: the i-th of them,
+// or -1 past the last (an odd count leaves the last pair half used).
+template <unsigned long long LIVE, int P>
+constexpr int fold_pair_col(int i) {
+    int n = 0;
+    for (int k = 1; k < P; ++k)
+        if (col_live<LIVE>(k)) {
+            if (n == i) return k;
+            ++n;
+        }
+    return -1;
+}
+template <unsigned long long LIVE, int P>
+constexpr int fold_pairs() {
+    int n = 0;
+    for (int k = 1; k < P; ++k) n += col_live<LIVE>(k) ? 1 : 0;
+    return (n + 1) / 2;
+}
+
+// fma(t.SEL broadcast to both halves, b, c) in one v_pk_fma_f32 (pk_fma_bcast, closure_rev.hpp, with the broadcast operand a
+// VGPR pair of two monomials): b a VGPR pair (the residual pair) or an SGPR pair (a coefficient pair).
+// pk_fma_bcast_acc: in place, the result tied to the addend (a sum, a later link of a chain); pk_fma_bcast_first: a chain's
+// first link, which reads the thread's constant first term and must not need a copy of it.
+template <int SEL, bool SGPR>
+__device__ __forceinline__ void pk_fma_bcast_acc(float2v t, float2v b, float2v& acc) {
+    if constexpr (SGPR) {
+        if constexpr (SEL == 0)
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(t), "s"(b));
+        else
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0]" : "+v"(acc) : "v"(t), "s"(b));
+    } else {
+        if constexpr (SEL == 0)
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(t), "v"(b));
+        else
+            asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0]" : "+v"(acc) : "v"(t), "v"(b));
+    }
+}
+template <bool SGPR>
+__device__ __forceinline__ float2v pk_fma_bcast_first(float2v t, float2v b, float2v c) {
+    float2v d;
+    if constexpr (SGPR)
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(t), "s"(b), "v"(c));
+    else
+        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(d) : "v"(t), "v"(b), "v"(c));
+    return d;
+}
+
+// The fold's ring with the chunk addressing off the vector pipe (SADDR): every lane of the launch takes chunk
+// r * nthreads + tid in round r, so a round is ONE uniform offset -- advanced in SGPRs -- plus the lane's own constant 32-bit
+// byte offset: the scalar and the vector offset of a buffer load.  The rounds in which every lane has a chunk are counted
+// once, uniformly; the steady state refills without an index, a compare or a clamp per lane, and the last rounds -- the
+// ragged one among them, where the lanes from `rem` on re-read the round's first chunk, in bounds, and use nothing -- are
+// peeled.  The same chunks reach the same lanes in the same order as chunk_ring(nchunks, tid, nthreads, ..).
+// load(q0, lc, slot): the loads of chunk q0 + lc, q0 uniform; use(slot).  Everything is counted in 32 bits: the launcher
+// keeps chunk_ring where a problem does not fit (fold_saddr_fits).
+template <int R, int NVTOT, typename Load, typename Use>
+__device__ __forceinline__ void chunk_ring_uniform(unsigned nchunks, unsigned tid, unsigned nthreads, Load load, Use use) {
+    if (nchunks == 0) return;
+    const unsigned full = nchunks / nthreads, rem = nchunks - full * nthreads, rounds = full + (rem != 0 ? 1 : 0);
+    const bool mine = tid < rem;
+    float4 ring[R][NVTOT];
+    auto fetch = [&](unsigned r, float4 (&slot)[NVTOT]) { load(r * nthreads, (r < full || mine) ? tid : 0u, slot); };
+    each_point_static<0, R>([&](auto k) {
+        if (k < rounds) fetch(k, ring[k]);
+    });
+    unsigned r = 0;
+    for (; r + 2 * R <= full; r += R) {
+        each_point_static<0, R>([&](auto k) {
+            use(ring[k]);
+            load((r + R + k) * nthreads, tid, ring[k]);
+            __builtin_amdgcn_sched_barrier(0);           // as in chunk_ring: the refill stays behind its slot's use
+        });
+    }
+    for (; r < rounds; r += R) {
+        each_point_static<0, R>([&](auto k) {
+            if (r + k < rounds) {
+                if (r + k < full || mine) use(ring[k]);
+                if (r + R + k < rounds) fetch(r + R + k, ring[k]);
+            }
+        });
+    }
+}
+
 // jt: the compact (S, 1, D, D) table of J; mt: (S, 1, P, P) fp64, M of each problem (row k: Theta_k(J x) in terms of Theta(x)).
 // W_SGPR / C_SGPR: Xi / C in SGPRs.  LIVE, live: as in symreg_reversed_kernel -- the set is a union of whole degrees, so it is
 // closed under M; a column of LIVE outside `live` has a zero coefficient and a zero gradient, its C is formed like any other.
+// PK: the packed-fp32 body over the two equation rows.  The monomials stay scalar, in Lib::eval's order, and sit two to an
+// aligned register pair; the coefficients are the pairs (w[0][k], w[1][k]), (c[0][k], c[1][k]), the residual and the
+// regulariser term the pairs (r_0, r_1), (u_0, u_1), the sums the pairs (R[0][k], R[1][k]), (U[0][k], U[1][k]).  Per live column
+// four v_pk_fma_f32 with Theta_k broadcast to both halves by op_sel -- h2 += Theta_k w2_k, u2 += Theta_k c2_k,
+// R2_k += Theta_k r2, U2_k += Theta_k u2 -- instead of eight v_fmac_f32; the constant column is a v_pk_add_f32 (fma(r, 1, R)
+// = r + R).  Each half is the scalar body's fmaf on the same operands in the same order, sum r^2 and sum u^2 are the scalar
+// body's: bit-identical to it on the same grid.  The pairs are unpacked once per thread before the recombination.
+// SADDR: chunk_ring_uniform instead of chunk_ring, see there; the same chunk-to-lane assignment, bit-identical.
+// The levers ride on the library type, so that a kernel without them keeps the name and the code it had:
+// symreg_fold_kernel<FoldLevers<Lib, PK, SADDR>, ..> is the kernel of Lib with them, symreg_fold_kernel<Lib, ..> the one without.
+template <class L, bool PK_, bool SADDR_>
+struct FoldLevers : L {
+    static constexpr bool FOLD_PK = PK_, FOLD_SADDR = SADDR_;
+};
+template <class L, class = void>
+struct fold_levers {
+    static constexpr bool pk = false, saddr = false;
+};
+template <class L>
+struct fold_levers<L, std::void_t<decltype(L::FOLD_PK)>> {
+    static constexpr bool pk = L::FOLD_PK, saddr = L::FOLD_SADDR;
+};
 template <class Lib, int RING, int MINW, unsigned long long LIVE, bool W_SGPR, bool C_SGPR>
 __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* __restrict__ x, const float* __restrict__ dx,
                                                                   const float* __restrict__ jt, const double* __restrict__ mt,
                                                                   long N, bool vec, const float* __restrict__ xi,
                                                                   const float* __restrict__ mask, float w_sym,
                                                                   double* __restrict__ ws, Finish fin, unsigned long long live) {
+    constexpr bool PK = fold_levers<Lib>::pk, SADDR = fold_levers<Lib>::saddr;
     constexpr int D = Lib::D, P = Lib::P, NACC = 2 + D * P, PPT = Chunk<D>::PPT, NV = Chunk<D>::NV;
     constexpr bool SPARSE = LIVE != ~0ull;
     static_assert(D == 2 && !Lib::SINE && !Lib::EXP, "Theta(J x) = M Theta(x) holds for the plain polynomial libraries; M is built for d = 2");
@@ -50,7 +156,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* _
     const double* ms = mt + s * P * P;
     if (!SPARSE) live = ~0ull;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && fin.header[0] == WS_MAGIC)
-        fin.header[WS_BODY_WORD] = WS_BODY_FOLD | (SPARSE ? WS_BODY_LIVE : 0ull);
+        fin.header[WS_BODY_WORD] = WS_BODY_FOLD | (SPARSE ? WS_BODY_LIVE : 0ull) | (PK ? WS_BODY_FOLD_PK : 0ull) | (SADDR ? WS_BODY_FOLD_SADDR : 0ull);
 
     // C = J Xi - Xi M of this problem, fp64 products of the masked fp32 coefficients the streamed kernels read
     for (int t = threadIdx.x; t < D * P; t += BLOCK) {
@@ -101,46 +207,145 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* _
                 }
         }
     };
+    // PK: the same point on pairs over the two equation rows (see above); h0 / u0 are the chains' first links,
+    // fma(w[j][0], Theta_0 = 1, 0), formed once
+    constexpr int P2 = PK ? P : 1, NPAIR = fold_pairs<LIVE, P>();
+    float2v R2[P2], U2[P2], w2[P2], c2[P2], h0 = float2v{0.0f, 0.0f}, u0 = h0;
+#pragma unroll
+    for (int k = 0; k < P2; ++k) {
+        R2[k] = U2[k] = float2v{0.0f, 0.0f};
+        w2[k] = PK ? float2v{w[k], w[(D - 1) * P + k]} : R2[k];
+        c2[k] = PK ? float2v{c[k], c[(D - 1) * P + k]} : R2[k];
+    }
+    if constexpr (col_live<LIVE>(0)) {
+        h0 = float2v{fmaf(w[0], 1.0f, 0.0f), fmaf(w[(D - 1) * P], 1.0f, 0.0f)};
+        u0 = float2v{fmaf(c[0], 1.0f, 0.0f), fmaf(c[(D - 1) * P], 1.0f, 0.0f)};
+    }
+    auto one_pk = [&](const float (&xp)[D], float2v y2) {
+        if constexpr (PK) {   // (the pair arrays have one slot in the scalar kernels)
+            float th[P];
+            Lib::eval(xp, th);
+            // pair m of the monomials and the columns in its halves (b < 0: the last pair of an odd count, half used)
+            auto pair = [&](auto m) {
+                constexpr int a = fold_pair_col<LIVE, P>(2 * decltype(m)::value), b = fold_pair_col<LIVE, P>(2 * decltype(m)::value + 1);
+                return float2v{th[a], th[b < 0 ? a : b]};
+            };
+            float2v h2 = h0, u2 = u0;
+            each_point_static<0, NPAIR>([&](auto m) {
+                constexpr int a = fold_pair_col<LIVE, P>(2 * decltype(m)::value), b = fold_pair_col<LIVE, P>(2 * decltype(m)::value + 1);
+                const float2v t = pair(m);
+                if constexpr (decltype(m)::value == 0) {
+                    h2 = pk_fma_bcast_first<W_SGPR>(t, w2[a], h0);
+                    u2 = pk_fma_bcast_first<C_SGPR>(t, c2[a], u0);
+                } else {
+                    pk_fma_bcast_acc<0, W_SGPR>(t, w2[a], h2);
+                    pk_fma_bcast_acc<0, C_SGPR>(t, c2[a], u2);
+                }
+                if constexpr (b >= 0) {
+                    pk_fma_bcast_acc<1, W_SGPR>(t, w2[b], h2);
+                    pk_fma_bcast_acc<1, C_SGPR>(t, c2[b], u2);
+                }
+            });
+            const float2v r2 = h2 - y2;
+            sum_r = fmaf(r2.x, r2.x, sum_r);
+            sum_u = fmaf(u2.x, u2.x, sum_u);
+            sum_r = fmaf(r2.y, r2.y, sum_r);
+            sum_u = fmaf(u2.y, u2.y, sum_u);
+            if constexpr (col_live<LIVE>(0)) {
+                R2[0] += r2;
+                U2[0] += u2;
+            }
+            each_point_static<0, NPAIR>([&](auto m) {
+                constexpr int a = fold_pair_col<LIVE, P>(2 * decltype(m)::value), b = fold_pair_col<LIVE, P>(2 * decltype(m)::value + 1);
+                const float2v t = pair(m);
+                pk_fma_bcast_acc<0, false>(t, r2, R2[a]);
+                pk_fma_bcast_acc<0, false>(t, u2, U2[a]);
+                if constexpr (b >= 0) {
+                    pk_fma_bcast_acc<1, false>(t, r2, R2[b]);
+                    pk_fma_bcast_acc<1, false>(t, u2, U2[b]);
+                }
+            });
+        }
+    };
     auto point = [&](long n) {
         float xp[D], yp[D];
         load_point<D>(xs, n, xp);
         load_point<D>(ys, n, yp);
-        one(xp, yp);
+        if constexpr (PK)
+            one_pk(xp, float2v{yp[0], yp[D - 1]});
+        else
+            one(xp, yp);
     };
     // the chunk-to-lane assignment of symreg_reversed_kernel: a grid-wide stride, the ragged tail point by point
     const long tid = (long)blockIdx.x * BLOCK + threadIdx.x, nthreads = (long)gridDim.x * BLOCK;
     if (vec) {
         const long nchunks = N / PPT;
-        chunk_ring<RING, 2 * NV>(
-            nchunks, tid, nthreads,
-            [&](long q, float4 (&slot)[2 * NV]) {
-                float4 vx[NV], vy[NV];
-                load_chunk_raw<D, true>(xs, q, vx);
-                load_chunk_raw<D, true>(ys, q, vy);
+        const auto use = [&](const float4 (&slot)[2 * NV]) {
+            float4 vx[NV], vy[NV];
 #pragma unroll
-                for (int i = 0; i < NV; ++i) {
-                    slot[i] = vx[i];
-                    slot[NV + i] = vy[i];
-                }
-            },
-            [&](long, const float4 (&slot)[2 * NV]) {
-                float4 vx[NV], vy[NV];
-#pragma unroll
-                for (int i = 0; i < NV; ++i) {
-                    vx[i] = slot[i];
-                    vy[i] = slot[NV + i];
-                }
-                float xp[PPT][D], yp[PPT][D];
-                unpack_chunk<D>(vx, xp);
-                unpack_chunk<D>(vy, yp);
-                each_point<PPT>([&](auto i) { one(xp[i], yp[i]); });
+            for (int i = 0; i < NV; ++i) {
+                vx[i] = slot[i];
+                vy[i] = slot[NV + i];
+            }
+            float xp[PPT][D], yp[PPT][D];
+            unpack_chunk<D>(vx, xp);
+            unpack_chunk<D>(vy, yp);
+            each_point<PPT>([&](auto i) {
+                if constexpr (PK)
+                    one_pk(xp[i], float2v{yp[i][0], yp[i][D - 1]});
+                else
+                    one(xp[i], yp[i]);
             });
+        };
+        if constexpr (SADDR) {
+            static_assert(NV == 1, "one 16-byte vector of x and one of dx per chunk");
+            // one buffer descriptor per stream, over the problem's whole chunks (built from the kernel's arguments and
+            // blockIdx.y alone: wave-uniform); the round's base is the scalar offset of the load, the lane's the vector one
+            typedef float f4v __attribute__((ext_vector_type(4)));
+            constexpr int NT_AUX = 2;
+            const int bytes = (int)((unsigned)nchunks * 16u);
+            const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, bytes, 0x00020000);
+            const auto ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ys), 0, bytes, 0x00020000);
+            chunk_ring_uniform<RING, 2 * NV>(
+                (unsigned)nchunks, (unsigned)tid, (unsigned)nthreads,
+                [&](unsigned q0, unsigned lc, float4 (&slot)[2 * NV]) {
+                    // (the whole vector is cast: a bit_cast of one element of the builtin's vector reads element 0 for each)
+                    const f4v vx = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rx, (int)(lc * 16u), (int)(q0 * 16u), NT_AUX));
+                    const f4v vy = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(lc * 16u), (int)(q0 * 16u), NT_AUX));
+                    slot[0] = make_float4(vx.x, vx.y, vx.z, vx.w);
+                    slot[1] = make_float4(vy.x, vy.y, vy.z, vy.w);
+                },
+                use);
+        } else {
+            chunk_ring<RING, 2 * NV>(
+                nchunks, tid, nthreads,
+                [&](long q, float4 (&slot)[2 * NV]) {
+                    float4 vx[NV], vy[NV];
+                    load_chunk_raw<D, true>(xs, q, vx);
+                    load_chunk_raw<D, true>(ys, q, vy);
+#pragma unroll
+                    for (int i = 0; i < NV; ++i) {
+                        slot[i] = vx[i];
+                        slot[NV + i] = vy[i];
+                    }
+                },
+                [&](long, const float4 (&slot)[2 * NV]) { use(slot); });
+        }
         const long n = nchunks * PPT + tid;
         if (n < N) point(n);
     } else {
         for (long n = tid; n < N; n += nthreads) point(n);
     }
 
+    if constexpr (PK) {
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            R[k] = R2[k].x;
+            R[(D - 1) * P + k] = R2[k].y;
+            U[k] = U2[k].x;
+            U[(D - 1) * P + k] = U2[k].y;
+        }
+    }
     // this thread's share of the gradient: R + w_sym ((J - I)^T U - U (M - I)^T)
     float acc[NACC];
     acc[0] = sum_r;
@@ -191,6 +396,38 @@ constexpr bool fold_sgpr = 2 * Lib::D * Lib::P >= 32;
 template <class Lib, bool SPARSE>
 constexpr int fold_minw = (!SPARSE && Lib::D * Lib::P > 32) ? 2 : 3;
 
+// The two levers on the fold body, per instantiation (SPARSE: the odd set), filled in from measurement: taken only where the
+// arm wins in all three passes of tools/micro/closure_ab fold at the bench shape by more than the arms' own spread, and is not
+// slower at 64 x 50 000 by more than the parent arm's spread there (2.8 % at order 5 on the odd set, 21.3-21.9 us; 3.6 % at
+// order 4 dense, 19.6-20.3 us).
+// SYMODE_FOLD_PK=0 keeps the parent's body and addressing everywhere, bit for bit (both levers are bit-identical to it anyway).
+// What a launch took is left in word 1 of the workspace header (WS_BODY_FOLD_PK, WS_BODY_FOLD_SADDR beside WS_BODY_FOLD).
+//   closure_fold_pk_pays     the packed body over the two equation rows (PK)
+//   closure_fold_saddr_pays  the uniform ring, chunk addressing in SGPRs (SADDR)
+// MI355X, ms per launch at the bench shape (8192 x 125 000), parent body | + SADDR | + PK | both, and the ratios to the parent
+// body there and at 64 x 50 000 (profiles/closure_fold_pk.txt):
+//   order 5 odd set   3.307-3.335 | 3.163-3.205 | 3.253-3.291 | 3.199-3.222   0.948-0.969 | 0.975-0.994 | 0.966-0.973   small 1.00-1.02 | 0.97-0.99 | 0.98-1.03
+//   order 5 dense     4.480-4.492 | 4.421-4.447 | 4.331-4.360 | 4.255-4.291   0.987-0.993 | 0.964-0.973 | 0.950-0.958   small 0.98-0.99 | 0.93-0.94 | 0.93-0.95
+//   order 4 dense     3.437-3.462 | 3.319-3.340 | 3.396-3.406 | 3.313-3.328   0.959-0.969 | 0.981-0.989 | 0.961-0.967   small 1.04-1.07 | 0.98-1.01 | 1.01-1.03
+//   orders 1-3 dense, order 4 odd set: 0.995-1.037 in every arm, they sit on the 16-byte stream: nothing taken
+// Order 5 on the odd set (the flagship's) takes the uniform ring alone: the packed body, 313 instead of 517 instructions in the
+// steady-state block, is inside the parent arm's 0.85 % spread in two passes of three and adds nothing on top of the ring.  At
+// 64 x 50 000 the ring is 0-2.3 % slower there (21.7-21.9 against 21.3-21.9 us), inside that arm's 2.8 % spread: taken.
+// Order 5 dense takes both (each wins alone, together 4.2-5.0 %).  Order 4 dense takes neither: the ring's 3-4 % at the bench
+// shape are 4.2-6.7 % lost at 64 x 50 000 (its prologue), beyond the 3.6 % spread; the packed body alone is 1.1-1.9 % against a
+// spread of 0.7 %, too little to carry a kernel of its own.
+template <class Lib, bool SPARSE>
+constexpr bool closure_fold_pk_pays = closure_fold_lib<Lib> && Lib::ORDER == 5 && !SPARSE;
+template <class Lib, bool SPARSE>
+constexpr bool closure_fold_saddr_pays = closure_fold_lib<Lib> && Lib::ORDER == 5;
+// The uniform ring addresses a problem's stream through a buffer descriptor with 32-bit byte offsets: the bytes of one
+// problem's x (n * d * 4) must stay below 2^31, that is n < 2^28 points at d = 2 (and the lane's own offset, grid.x * BLOCK * 16,
+// with them).  Beyond that the launch keeps chunk_ring's 64-bit per-lane indices -- the parent's kernel, the same bits.
+template <int D>
+inline bool fold_saddr_fits(long n, int gx) {
+    return n * D * 4 < (1L << 31) && (long)gx * BLOCK * 16 < (1L << 31);
+}
+
 // does a call with this column set take a fold kernel?
 template <class Lib>
 bool fold_takes(unsigned long long live) {
@@ -217,13 +454,25 @@ hipError_t launch_symreg_fold(const float* x, const float* dx, const float* jt, 
         constexpr unsigned long long columns = Lib::P >= 64 ? ~0ull : (1ull << Lib::P) - 1;
         sparse = knobs().closure_live && (live & columns & ~odd_degree_columns<Lib>()) == 0;
     }
-    if (sparse) {
-        if constexpr (closure_fold_live_pays<Lib>)
-            symreg_fold_kernel<Lib, 2, fold_minw<Lib, true>, odd_degree_columns<Lib>(), fold_sgpr<Lib>, fold_sgpr<Lib>>
-                <<<grid, block, 0, st>>>(x, dx, jt, mt, n, vec, xi, mask, w_sym, part, fin, live);
-    } else {
-        symreg_fold_kernel<Lib, 2, fold_minw<Lib, false>, ~0ull, fold_sgpr<Lib>, fold_sgpr<Lib>>
+    // the column set as a compile-time constant; the levers of the table where SYMODE_FOLD_PK allows them and the uniform ring's
+    // bounds hold (fold_saddr_fits), the parent's kernel -- the same bits -- otherwise
+    const auto launch = [&](auto sp) {
+        constexpr bool SPARSE = decltype(sp)::value, PKB = closure_fold_pk_pays<Lib, SPARSE>, SA = closure_fold_saddr_pays<Lib, SPARSE>;
+        constexpr unsigned long long LIVE = SPARSE ? odd_degree_columns<Lib>() : ~0ull;
+        if constexpr (PKB || SA) {
+            if (knobs().fold_pk && (!SA || fold_saddr_fits<D>(n, gx))) {
+                symreg_fold_kernel<FoldLevers<Lib, PKB, SA>, 2, fold_minw<Lib, SPARSE>, LIVE, fold_sgpr<Lib>, fold_sgpr<Lib>>
+                    <<<grid, block, 0, st>>>(x, dx, jt, mt, n, vec, xi, mask, w_sym, part, fin, live);
+                return;
+            }
+        }
+        symreg_fold_kernel<Lib, 2, fold_minw<Lib, SPARSE>, LIVE, fold_sgpr<Lib>, fold_sgpr<Lib>>
             <<<grid, block, 0, st>>>(x, dx, jt, mt, n, vec, xi, mask, w_sym, part, fin, live);
+    };
+    if (sparse) {
+        if constexpr (closure_fold_live_pays<Lib>) launch(std::true_type{});
+    } else {
+        launch(std::false_type{});
     }
     SYMODE_LAUNCH_CHECK();
     return launch_finalize(fin, part, S, gx, 2 + DP, st);

@@ -23,7 +23,7 @@ constexpr int MAP_CHUNKS_PER_THREAD = SYMODE_MAP_CHUNKS;   // chunks a thread of
 // for the tests and tuning tools that compare two settings inside one process; no launch path calls getenv.
 struct Knobs {
     long max_grid, min_grid_x, map_grid, gram_grid, gram_valu_grid, small_grid, reduce_grid;
-    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live, closure_fold;
+    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live, closure_fold, fold_pk;
     long gram_m4_grid;
 };
 
@@ -50,6 +50,7 @@ inline Knobs read_knobs() {
     k.closure_pk = on("SYMODE_CLOSURE_PK");
     k.closure_live = on("SYMODE_CLOSURE_LIVE");
     k.closure_fold = on("SYMODE_CLOSURE_FOLD");
+    k.fold_pk = on("SYMODE_FOLD_PK");
     return k;
 }
 
@@ -451,6 +452,7 @@ constexpr int WS_BODY_WORD = 1;                                      // header w
 constexpr unsigned long long WS_BODY_SCALAR = 1, WS_BODY_PACKED = 2; //   which of its two bit-identical bodies the last launch took,
 constexpr unsigned long long WS_BODY_LIVE = 4;                       //   + this where it was the form that leaves out dead columns
 constexpr unsigned long long WS_BODY_FOLD = 8;                       //   the fold kernel of a linear action (closure_fold.hpp), alone or + WS_BODY_LIVE
+constexpr unsigned long long WS_BODY_FOLD_PK = 16, WS_BODY_FOLD_SADDR = 32;   //   + the fold kernel's levers: packed body, chunk addressing in SGPRs
 constexpr long WS_HEADER_DOUBLES = 8 + WS_MAX_PROBLEMS / 2;          // [magic, 7 reserved | uint32 tickets] in front of the partials
 
 struct Finish {

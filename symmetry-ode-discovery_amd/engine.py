@@ -795,7 +795,14 @@ class HipEngine:
         action that reads no g(x) (``linear_m``; SYMODE_CLOSURE_FOLD=0 turns it off), or None before any.  The kernel leaves it in word 1 of the
         workspace header (an initialised workspace only, and only its LAST launch is visible): the two bodies return the same
         bits, so the results cannot tell.  One synchronisation."""
-        return {1: "scalar", 2: "packed", 5: "scalar-live", 6: "packed-live", 8: "fold", 12: "fold-live"}.get(int(ws.view(torch.int64)[1].item()))
+        return {1: "scalar", 2: "packed", 5: "scalar-live", 6: "packed-live", 8: "fold", 12: "fold-live"}.get(int(ws.view(torch.int64)[1].item()) & 15)
+
+    @staticmethod
+    def closure_levers(ws):
+        """(packed body, chunk addressing in SGPRs) of the last fold launch on workspace ``ws`` (closure_fold.hpp; SYMODE_FOLD_PK=0
+        turns both off): bits 16 and 32 of the word ``closure_body`` reads.  Both are bit-identical to the plain fold kernel."""
+        word = int(ws.view(torch.int64)[1].item())
+        return bool(word & 16), bool(word & 32)
 
     def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None,
                            live_columns=None, linear_m=None):

@@ -12,8 +12,12 @@
 // for the d = 2 plain libraries, both bodies at orders 4-5, same shapes and passes.  closure_live_pays is read off this run.
 // `closure_ab fold`: the fold kernel of a linear action (closure_fold.hpp: x and dx alone, 16 B/point, one library evaluation)
 // against the kernel the launcher ships for the same call, d = 2 plain orders 1-5 on every column and on the constant +
-// odd-degree set at orders 4-5, same shapes and passes; a fold arm with four chunks in flight beside the launcher's two.
-// closure_fold_dense_pays / closure_fold_live_pays are read off this run.
+// odd-degree set at orders 4-5, same shapes and passes; beside the parent fold body its two levers alone and together (the
+// uniform ring with the chunk addressing in SGPRs, the packed body over the two equation rows) and grid.x = 1 beside the
+// launcher's width.  closure_fold_dense_pays / closure_fold_live_pays / closure_fold_pk_pays / closure_fold_saddr_pays are read
+// off this run.
+// `closure_ab foldcheck`: no timing -- the partial rows of every lever arm of every fold instantiation against the parent body's,
+// bit for bit, on grids with full and ragged rounds (the arms the launcher does not route to are compiled only here).
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -I symmetry-ode-discovery_amd/csrc
 //              -o tools/micro/closure_ab tools/micro/closure_ab.hip
 #include <hip/hip_runtime.h>
@@ -260,25 +264,77 @@ int main(int argc, char** argv) {
         CK(hipDeviceSynchronize());
         return 0;
     }
-    if (argc > 1 && strcmp(argv[1], "fold") == 0) {
-        double* mt;                                   // (S, p, p) substitution matrices: the identity (the timing does not read their values)
+    if (argc > 1 && strcmp(argv[1], "foldcheck") == 0) {
+        // every lever arm of every fold instantiation against the parent body on the same grid: the partial rows, bit for bit
+        // (the arms the launcher does not route to are compiled nowhere else).  64 problems, three workgroups each; 50 000
+        // points: 32 full rounds and a ragged one; 12 288: 8 full rounds, none ragged.  Exit status 1 on any difference.
+        double* mt;
         CK(hipMalloc(&mt, S * L5::P * L5::P * 8));
         CK(hipMemset(mt, 0, S * L5::P * L5::P * 8));
-        printf("# fused closure, constant J: shipped streamed kernel (24 B/point) | fold (16 B/point), ring 2 | fold, ring 4: us per launch (min of 3 rounds of 5), three passes\n");
+        const long Sx = 64, GX = 3, rows = GX * Sx;
+        std::vector<double> want(rows * (2 + D * L5::P)), got(want.size());
+        int bad = 0;
+#define FCLAUNCH(LIBT) symreg_fold_kernel<LIBT, 2, fold_minw<LB, SP>, LV, fold_sgpr<LB>, fold_sgpr<LB>><<<dim3(GX, (unsigned)Sx), dim3(BLOCK)>>>( \
+        x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV)
+#define FCARM(PKB_, SA_)                                                                                                           \
+    {                                                                                                                              \
+        CK(hipMemset(part, 0, nb));                                                                                                \
+        FCLAUNCH(FoldLevers<LB COMMA PKB_ COMMA SA_>);                                                                              \
+        CK(hipDeviceSynchronize());                                                                                                \
+        CK(hipMemcpy(got.data(), part, nb, hipMemcpyDeviceToHost));                                                                \
+        const bool same = memcmp(got.data(), want.data(), nb) == 0;                                                                \
+        bad += same ? 0 : 1;                                                                                                       \
+        printf("%6ld points  order %d (p = %2d) %s  packed %d  saddr %d: %s\n", Nx, LB::ORDER, LB::P, SP ? "odd set" : "dense  ", \
+               (int)PKB_, (int)SA_, same ? "same bits" : "DIFFERENT");                                                             \
+    }
+#define COMMA ,
+#define FCRUN(ORDER, SPARSE)                                                                                                       \
+    {                                                                                                                              \
+        using LB = Library<2, ORDER, 0>;                                                                                           \
+        constexpr unsigned long long LV = SPARSE ? odd_degree_columns<LB>() : ~0ull;                                               \
+        constexpr bool SP = SPARSE;                                                                                                \
+        const size_t nb = rows * (2 + D * LB::P) * sizeof(double);                                                                 \
+        CK(hipMemset(part, 0, nb));                                                                                                \
+        FCLAUNCH(LB);                                                                                                              \
+        CK(hipDeviceSynchronize());                                                                                                \
+        CK(hipMemcpy(want.data(), part, nb, hipMemcpyDeviceToHost));                                                               \
+        double sum = 0.0;                                                                                                          \
+        for (size_t i = 0; i < nb / sizeof(double); ++i) sum += want[i] * want[i];                                                 \
+        if (!(sum > 0.0)) { printf("order %d: the parent body left no partial rows\n", ORDER); bad += 1; }                         \
+        FCARM(false, true) FCARM(true, false) FCARM(true, true)                                                                    \
+    }
+        for (const long Nx : {50000L, 12288L}) {
+            FCRUN(1, false) FCRUN(2, false) FCRUN(3, false) FCRUN(4, false) FCRUN(5, false)
+            FCRUN(4, true) FCRUN(5, true)
+        }
+        printf("# %d arm(s) differ\n", bad);
+        return bad ? 1 : 0;
+    }
+    if (argc > 1 && strcmp(argv[1], "fold") == 0) {
+        double* mt;                                 // (S, p, p) substitution matrices: the identity (the timing does not read their values)
+        CK(hipMalloc(&mt, S * L5::P * L5::P * 8));
+        CK(hipMemset(mt, 0, S * L5::P * L5::P * 8));
+        printf("# fused closure, constant J: shipped streamed kernel (24 B/point) | fold (16 B/point): parent body | + scalar addressing | + packed | both; "
+               "parent body and both at grid.x = 1: us per launch (min of 3 rounds of 5), three passes\n");
         const long shapes[2][2] = {{S, NB}, {64, 50000}};
+#define FDPARENT(GX_)                                                                                                              \
+    time_us([&] { symreg_fold_kernel<LB, 2, fold_minw<LB, SP>, LV, fold_sgpr<LB>, fold_sgpr<LB>><<<dim3(GX_, (unsigned)Sx), dim3(BLOCK)>>>( \
+                      x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5)
+#define FDARM(PKB_, SA_, GX_)                                                                                                      \
+    time_us([&] { symreg_fold_kernel<FoldLevers<LB, PKB_, SA_>, 2, fold_minw<LB, SP>, LV, fold_sgpr<LB>, fold_sgpr<LB>><<<dim3(GX_, (unsigned)Sx), dim3(BLOCK)>>>( \
+                      x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5)
 #define FDRUN(ORDER, SPARSE)                                                                                                       \
     {                                                                                                                              \
         using LB = Library<2, ORDER, 0>;                                                                                           \
         constexpr unsigned long long LV = SPARSE ? odd_degree_columns<LB>() : ~0ull;                                               \
-        constexpr bool PKB = !SPARSE && closure_pk_pays<LB>;                                                                       \
+        constexpr bool SP = SPARSE, PKB = !SPARSE && closure_pk_pays<LB>;                                                          \
         const double a_ = time_us([&] { symreg_reversed_kernel<LB, true, 2, 32, true, 3, PKB, LV><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
                                             x, dx, gx, jgx, 1, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5);               \
-        const double b_ = time_us([&] { symreg_fold_kernel<LB, 2, fold_minw<LB, SPARSE>, LV, fold_sgpr<LB>, fold_sgpr<LB>><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
-                                            x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5);                  \
-        const double c_ = time_us([&] { symreg_fold_kernel<LB, 4, fold_minw<LB, SPARSE>, LV, fold_sgpr<LB>, fold_sgpr<LB>><<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>( \
-                                            x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5);                  \
-        printf("pass %d  %5ld x %6ld  order %d (p = %2d) %s  streamed %8.1f us  fold %8.1f us  fold ring 4 %8.1f us  fold/streamed %.3f  ring4/streamed %.3f\n", \
-               pass, Sx, Nx, ORDER, LB::P, SPARSE ? "odd set" : "dense  ", a_, b_, c_, b_ / a_, c_ / a_);                          \
+        const double b_ = FDPARENT(gxw), c_ = FDARM(false, true, gxw), d_ = FDARM(true, false, gxw), e_ = FDARM(true, true, gxw); \
+        const double f_ = FDPARENT(1), g_ = FDARM(true, true, 1);                                                       \
+        printf("pass %d  %5ld x %6ld  order %d (p = %2d) %s  streamed %8.1f us  fold %8.1f us  +saddr %8.1f  +packed %8.1f  both %8.1f  "   \
+               "grid.x=1: fold %8.1f  both %8.1f  | fold/streamed %.3f  saddr/fold %.3f  packed/fold %.3f  both/fold %.3f\n",       \
+               pass, Sx, Nx, ORDER, LB::P, SPARSE ? "odd set" : "dense  ", a_, b_, c_, d_, e_, f_, g_, b_ / a_, c_ / b_, d_ / b_, e_ / b_); \
     }
         for (int pass = 0; pass < 3; ++pass)
             for (const auto& sh : shapes) {
