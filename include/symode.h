@@ -139,6 +139,32 @@ int symode_aug_gram_gather(const float* x, const float* dx, long n_src, const in
 int symode_weak_gram(const float* x, long n_t, int d, int order, int flags, const float* V, const float* V_drv, int n_test,
                      double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Weak SINDy for the seeds of a sweep at once: every seed reads one window of ONE shared data set, and everything its
+ * fit needs is the (p+d, p+d) normal matrix of the window,
+ *     N = Z^T M Z,   Z = [G | b] (n_test, p+d),   G = V Theta(x_window),   b = -V_drv x_window,
+ * whose blocks N[:p, :p] = G^T M G and N[:p, p:] = G^T M b are the system of sindy.py:365-370.
+ * x (n_ics, n_steps, d) fp32: the data set; windows (n_windows, 2) int32 ON THE DEVICE, row s = [trajectory, start]:
+ * window s is rows start .. start + n_t - 1 of that trajectory.  V, V_drv (n_test, n_t) fp32 as for symode_weak_gram,
+ * M (n_test, n_test) fp64 (= V V^T, sindy.py:348).  n_test <= 128, p <= 64, d <= 4, n_t <= n_steps, n_windows <= 65535.
+ *     aug_out (n_windows, p+d, p+d) fp64 row-major, both triangles, exactly symmetric: the layout symode_aug_gram
+ *             leaves, so symode_stlsq_sweep and symode_host_stlsq_sweep take it as it is (ridge gamma = sqrt(w_sindy_reg));
+ *     z_out   NULL, or (n_windows, R, C) fp64 with R, C of symode_weak_gram: window s holds, bit for bit, what
+ *             symode_weak_gram writes for x[trajectory, start : start + n_t];
+ *     bad_out (n_windows) int32: 1 for a row outside trajectory in [0, n_ics), start in [0, n_steps - n_t] -- such a
+ *             window reads nothing from x and its matrices are all zero -- else 0.  The kernel checks the row before it
+ *             forms an address from it.
+ * Two launches (window contraction on the fp64 matrix cores, then a workgroup per window for the sums and N), fixed
+ * summation order, no atomics: equal inputs give equal bytes.  The workspace holds n_windows * R/16 * C/16 * gx tiles of
+ * 256 doubles behind its header, gx = min(64, ceil(n_t / 256)); symode_weak_gram uses the same gx unless its workspace
+ * is short.
+ * replaces: the window draw and slice of main_wsindy.py:24-29 + sindy.py:362-370, for all seeds of a run-script loop
+ * (`for i in {0..49}; do python main_wsindy.py --seed $i`) at once. */
+int symode_weak_normal_windows(const float* x, long n_ics, long n_steps, int d, int order, int flags,
+                               const int* windows, long n_windows, long n_t,
+                               const float* V, const float* V_drv, int n_test, const double* M,
+                               double* aug_out, double* z_out, int* bad_out,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* S1, linear-latent symmetry regulariser (train.py:502-507 with the intended [1]):
  *   loss = sum_v sum_n || Xi_m J_Theta(z_n)(L_v z_n) - L_v Xi_m Theta(z_n) ||^2,
  *   grad (d, p) = dloss/dxi (masked).  L: (n_gen, d, d). */

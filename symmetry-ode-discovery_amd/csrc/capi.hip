@@ -9,6 +9,7 @@
 #include "ops_table.hpp"
 #include "quad_closure.hpp"
 #include "stlsq.hpp"
+#include "weak_normal.hpp"
 
 using namespace symode;
 
@@ -118,6 +119,12 @@ size_t workspace_doubles(const LibOps* ops, long S, long n) {
     const size_t T4 = (size_t)(F + 3) / 4, m4 = (size_t)S * (size_t)gram_m4_grid(n, S) * (T4 * (T4 + 1) / 2 * 16);
     if (m4 > b) b = m4;
     return (size_t)WS_HEADER_DOUBLES + (a > b ? a : b);      // [magic + tickets | partial rows]
+}
+
+// the time slabs of a weak-form contraction over n_t points: a workgroup = 4 waves x 64 time points per step
+inline long weak_slabs(long n_t) {
+    const long gx = (n_t + 255) / 256;
+    return gx > 64 ? 64 : gx;
 }
 
 #define SYMODE_GET_OPS()                              \
@@ -530,12 +537,36 @@ int symode_weak_gram(const float* x, long n_t, int d, int order, int flags, cons
     if (misaligned(x, 4) || misaligned(V, 4) || misaligned(V_drv, 4) || misaligned(out, 8)) return SYMODE_E_ALIGN;
     SYMODE_CHECK_WS(1, n_t);
     const int RT = (2 * n_test + 15) / 16, CT = (ops->p + ops->d + 15) / 16;
-    long gx = (n_t + 255) / 256;                                   // a workgroup = 4 waves x 64 time points per step
-    if (gx > 64) gx = 64;
+    long gx = weak_slabs(n_t);
     const size_t avail = workspace_bytes / sizeof(double) - (size_t)WS_HEADER_DOUBLES;
     while (gx > 1 && (size_t)gx * RT * CT * 256 > avail) gx /= 2;
     if ((size_t)gx * RT * CT * 256 > avail) return SYMODE_E_WORKSPACE;
     return (int)ops->weak_gram(x, n_t, V, V_drv, n_test, out, (double*)workspace, (int)gx, (hipStream_t)stream);
+}
+
+int symode_weak_normal_windows(const float* x, long n_ics, long n_steps, int d, int order, int flags, const int* windows,
+                               long n_windows, long n_t, const float* V, const float* V_drv, int n_test, const double* M,
+                               double* aug_out, double* z_out, int* bad_out, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    SYMODE_GET_OPS();
+    if (n_t < 1 || n_t > n_steps || n_ics < 1 || n_windows < 1 || n_windows > 65535 || n_test < 1 || n_test > WEAK_NORMAL_MAX_K)
+        return SYMODE_E_BADSIZE;
+    if (ops->p > STLSQ_MAX_P || d > STLSQ_MAX_D) return SYMODE_E_BADSIZE;          // what symode_stlsq_sweep takes
+    if (!x || !windows || !V || !V_drv || !M || !aug_out || !bad_out) return SYMODE_E_NULLPTR;
+    if (misaligned(x, 4) || misaligned(windows, 4) || misaligned(V, 4) || misaligned(V_drv, 4) || misaligned(M, 8) ||
+        misaligned(aug_out, 8) || misaligned(z_out, 8) || misaligned(bad_out, 4))
+        return SYMODE_E_ALIGN;
+    if (!workspace || misaligned(workspace, 8)) return SYMODE_E_WORKSPACE;
+    // symode_weak_gram's slab count for n_t, never halved: window s's partials are then that entry's, addition by addition
+    const long gx = weak_slabs(n_t);
+    const size_t RT = (size_t)(2 * n_test + 15) / 16, CT = (size_t)(ops->p + ops->d + 15) / 16;
+    const size_t need = (size_t)WS_HEADER_DOUBLES + (size_t)n_windows * RT * (size_t)gx * CT * 256;
+    if (workspace_bytes / sizeof(double) < need) return SYMODE_E_WORKSPACE;
+    double* part = (double*)workspace + WS_HEADER_DOUBLES;
+    const hipError_t e = ops->weak_windows(x, n_ics, n_steps, windows, n_windows, n_t, V, V_drv, n_test, part, (int)gx, bad_out,
+                                           (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    return (int)launch_weak_normal(part, (int)gx, n_windows, n_test, ops->p, ops->d, M, aug_out, z_out, (hipStream_t)stream);
 }
 
 int symode_vjp(const float* x, const float* g, long n, int d, int order, int flags, const float* xi, const float* mask,

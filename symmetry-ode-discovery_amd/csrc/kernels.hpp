@@ -145,6 +145,10 @@ struct LibOps {
                               const float* mask, unsigned long long live, float inv_count, float w_sym, float* loss, float* grad,
                               double* ws, int gx, hipStream_t st);
     bool (*fold_takes)(unsigned long long live);
+    // weak_gram's contraction for S windows [trajectory, start] of one data set (n_ics, n_steps, d) (weak.hpp): partials
+    // (S, row tile, gx, CT * 256) and the range flag of every window.  An additive entry
+    hipError_t (*weak_windows)(const float* x, long n_ics, long n_steps, const int* windows, long S, long T, const float* V,
+                               const float* Vd, int K, double* part, int gx, int* bad, hipStream_t st);
 };
 
 // ---------------------------------------------------------------------------------------

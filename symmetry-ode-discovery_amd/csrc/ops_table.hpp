@@ -42,7 +42,8 @@ constexpr LibOps make_ops() {
                   &launch_latent_closure<Lib>,
                   &launch_adam_epochs_latent<Lib>,
                   fold_launcher<Lib>(),
-                  fold_takes_fn<Lib>()};
+                  fold_takes_fn<Lib>(),
+                  &launch_weak_windows<Lib>};
 }
 
 #define SYMODE_OPS_ALL_FLAGS(D, O) make_ops<D, O, 0>(), make_ops<D, O, 1>(), make_ops<D, O, 2>(), make_ops<D, O, 3>()

@@ -50,6 +50,8 @@ _SIGNATURES = {
                                                c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_weak_gram": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
+    "symode_weak_normal_windows": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_long, c_long, c_void_p, c_void_p,
+                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_loss_grad_reversed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_int, c_int, c_void_p,
                                           c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_jacobian_constant": (c_int, [c_void_p, c_int, c_long, c_long, c_int, c_void_p, c_void_p, c_void_p]),
@@ -893,7 +895,8 @@ class HipEngine:
                     "symode_symreg_reversed_gram_gather")
         return gram
 
-    def stlsq_sweep(self, G, n_points, gamma, threshold, max_iter, hyper=None, n_problems=None, *, d, near_band=1e-4, to_host=False):
+    def stlsq_sweep(self, G, n_points, gamma, threshold, max_iter, hyper=None, n_problems=None, *, d, near_band=1e-4, to_host=False,
+                    tail=None):
         """Sequential-threshold least squares to convergence for every problem in ONE launch (symode_stlsq_sweep: the
         full-rank driver's loop of symode_host_stlsq_sweep on the device).  G (n_sets, p+d, p+d) fp64 on the device, ``d``
         the number of equation rows (G alone does not say where p ends).  ``hyper`` (n_problems, 2) fp32 on the device,
@@ -901,7 +904,9 @@ class HipEngine:
         ``n_problems`` defaults to the table's rows, or to n_sets without a table.
         Returns device tensors (Xi (n_problems, d, p) fp32, mask (n_problems, d, p) uint8, passes, near, fell (n_problems,)
         int32); a problem with ``fell`` set met a pivot that is not positive and is the host's to solve.  ``to_host=True``:
-        the same five as numpy arrays, after one copy of the one buffer they share."""
+        the same five as numpy arrays, after one copy of the one buffer they share.  ``tail``: an int32 device tensor that
+        rides in that buffer behind the five (a sixth item of the result), so that a caller with flags of its own to read
+        fetches them in the same copy."""
         G = self._dev(G, "G", torch.float64)
         d = int(d)
         if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
@@ -917,13 +922,18 @@ class HipEngine:
         S = n_sets if n_problems is None else int(n_problems)
         # one allocation, [xi | passes | near | fell | mask], so that a caller on the host fetches everything in ONE copy
         cuts = [0, 4 * S * d * p, 4 * S * (d * p + 1), 4 * S * (d * p + 2), 4 * S * (d * p + 3), 4 * S * (d * p + 3) + S * d * p]
-        buf = torch.empty(max(cuts[-1], 0), dtype=torch.uint8, device=G.device)
+        at = -(-cuts[-1] // 4) * 4                                      # the tail, int32-aligned behind the mask
+        n_tail = 0 if tail is None else 4 * tail.numel()
+        buf = torch.empty(max(at + n_tail, 0), dtype=torch.uint8, device=G.device)
 
         def parts(b, f32, i32):
             xi, passes, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
-            return xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32)
+            five = xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32)
+            return five if tail is None else five + (b[at:at + n_tail].view(i32),)
 
-        xi, mask, passes, near, fell = parts(buf, torch.float32, torch.int32)
+        xi, mask, passes, near, fell = parts(buf, torch.float32, torch.int32)[:5]
+        if tail is not None:
+            buf[at:at + n_tail].view(torch.int32).copy_(self._dev(tail, "tail", torch.int32).reshape(-1))
         self._check(self.lib.symode_stlsq_sweep(self._ptr(G), n_sets, S, d, p, int(n_points), self._ptr(hyper), float(gamma),
                                                 float(threshold), int(max_iter), float(near_band), self._ptr(xi), self._ptr(mask),
                                                 self._ptr(passes), self._ptr(near), self._ptr(fell), self._stream(G)),
@@ -931,7 +941,7 @@ class HipEngine:
         if to_host:
             import numpy as np
             return parts(buf.cpu().numpy(), np.float32, np.int32)
-        return xi, mask, passes, near, fell
+        return parts(buf, torch.float32, torch.int32)
 
     def quad_closure(self, G, R, xi, mask, inv_count, w_sym=1.0, hyper=None, n_sets=None):
         """The closure as a quadratic form of fixed fp64 matrices: G (S, p+d, p+d) augmented Gram, R (S, d p, d p) or None,
@@ -1016,6 +1026,61 @@ class HipEngine:
         self._check(self.lib.symode_weak_gram(self._ptr(x), T, d, order, flags, self._ptr(V), self._ptr(V_drv), K, self._ptr(out),
                                               self._ptr(ws), ws.numel() * 8, self._stream(x)), "symode_weak_gram")
         return out[:K, :p], out[K:2 * K, p:p + d]
+
+    @staticmethod
+    def check_windows(windows, n_ics, n_steps, n_t):
+        """The (S, 2) int32 host table of ``weak_normal_windows``, or SymodeError naming the first row that is not
+        [trajectory in [0, n_ics), start in [0, n_steps - n_t]].  Host arithmetic only."""
+        import numpy as np
+        w = np.asarray(windows)
+        if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] < 1 or not np.issubdtype(w.dtype, np.integer):
+            raise SymodeError(f"windows must be a host integer array (S, 2) of [trajectory, start] rows, got {w.dtype} {w.shape}")
+        if not 1 <= n_t <= n_steps:
+            raise SymodeError(f"n_t = {n_t} must lie in 1 .. n_steps = {n_steps}")
+        w = w.astype(np.int64)
+        bad = (w[:, 0] < 0) | (w[:, 0] >= n_ics) | (w[:, 1] < 0) | (w[:, 1] > n_steps - n_t)
+        if bad.any():
+            s = int(np.argmax(bad))
+            raise SymodeError(f"windows[{s}] = [{w[s, 0]}, {w[s, 1]}] is out of range: trajectory in [0, {n_ics}), start in "
+                              f"[0, {n_steps - n_t}] for n_t = {n_t} of {n_steps} steps")
+        return np.ascontiguousarray(w, dtype=np.int32)
+
+    def weak_normal_windows(self, x, windows, n_t, V, V_drv, M, order, flags=0, want_z=False):
+        """The normal matrices of the weak-SINDy fit for S windows of one data set in ONE call (symode_weak_normal_windows).
+        x (n_ics, n_steps, d) fp32 on the device; ``windows`` (S, 2) host integers, row s = [trajectory, start], checked
+        here (``check_windows``) before anything is uploaded or launched; V, V_drv (K, n_t) fp32 and M = V V^T (K, K) fp64
+        on the device.  Returns (aug (S, p+d, p+d) fp64, bad (S,) int32) on the device, or (aug, z, bad) with
+        ``want_z``: z (S, R, C) fp64, window s what ``symode_weak_gram`` writes for x[trajectory, start:start + n_t].
+        No synchronisation: ``bad`` (the kernel's own range flags, all zero after the check here) is the caller's to
+        fetch with its results."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 3:
+            raise SymodeError("weak_normal_windows expects x (n_ics, n_steps, d)")
+        return self._weak_normal_windows(x, self.check_windows(windows, x.shape[0], x.shape[1], int(n_t)), int(n_t), V, V_drv, M,
+                                         order, flags, want_z)
+
+    def _weak_normal_windows(self, x, w, n_t, V, V_drv, M, order, flags, want_z):
+        """``weak_normal_windows`` behind its host check: ``w`` is the (S, 2) int32 table as the entry gets it."""
+        n_ics, n_steps, d = x.shape
+        x, V, V_drv, M = self._dev(x, "x"), self._dev(V, "V"), self._dev(V_drv, "V_drv"), self._dev(M, "M", torch.float64)
+        K = V.shape[0]
+        if V.dim() != 2 or V.shape != V_drv.shape or V.shape[1] != n_t or tuple(M.shape) != (K, K):
+            raise SymodeError(f"weak_normal_windows expects V, V_drv (K, n_t = {n_t}) and M (K, K); got {tuple(V.shape)}, "
+                              f"{tuple(V_drv.shape)}, {tuple(M.shape)}")
+        S = w.shape[0]
+        p = self.lib_size(d, order, flags)
+        F, R, C = p + d, 16 * ((2 * K + 15) // 16), 16 * ((p + d + 15) // 16)
+        win = torch.from_numpy(w).to(x.device)
+        aug = torch.empty(S, F, F, dtype=torch.float64, device=x.device)
+        z = torch.empty(S, R, C, dtype=torch.float64, device=x.device) if want_z else None
+        bad = torch.empty(S, dtype=torch.int32, device=x.device)
+        gx = min(64, (n_t + 255) // 256)
+        # behind the header, every window's time-slab partials: the entry refuses a shorter scratch instead of halving gx
+        ws = self.workspace(x.device, d, order, flags, 1, n_t, min_bytes=8 * (8 + 32768 + S * gx * (R // 16) * (C // 16) * 256) + 4096)
+        self._check(self.lib.symode_weak_normal_windows(self._ptr(x), n_ics, n_steps, d, order, flags, self._ptr(win), S, n_t,
+                                                        self._ptr(V), self._ptr(V_drv), K, self._ptr(M), self._ptr(aug),
+                                                        self._ptr(z), self._ptr(bad), self._ptr(ws), ws.numel() * 8,
+                                                        self._stream(x)), "symode_weak_normal_windows")
+        return (aug, z, bad) if want_z else (aug, bad)
 
     def vjp(self, x, g, xi, mask, order, flags=0, need_grad_x=True):
         """Reverse mode of forward: returns (grad_x (N, d) or None, grad_xi (d, p))."""

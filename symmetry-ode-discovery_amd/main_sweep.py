@@ -11,13 +11,14 @@
     python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --device_shuffle --batch_size 256 --n_seeds 64
     python -m symode_amd.main_sweep --task dosc --sindy_optimizer adam --n_seeds 64 --eval_ltp \
         --grid threshold=0.01,0.05,0.075,0.15 --grid lr_sindy=0.1,1.0     # 8 grid points x 64 seeds in every epoch launch
+    python -m symode_amd.main_sweep --config dosc/noise20_wsindy.cfg --wsindy --n_seeds 50 [--wsindy_grid threshold=0.1,0.2,0.3]
     python -m symode_amd.main_sweep --config lv/noise99_eq_rsymreg.cfg --n_seeds 64 --gram_closure --eval_ltp \
         --lbfgs_grid w_sym_reg=0.01,0.1,1 --lbfgs_grid threshold=0.05,0.1   # 6 grid points on the 64 seeds' Gram matrices
 
 plan:   ``_refusal`` decides from the arguments alone whether the sweep runs, before a process group, a data file or a
         device is touched; what it refuses it answers with the per-seed command to run instead.
-fit:    ``_fit_stlsq`` (--method stlsq), ``_fit_lbfgs`` (default; the reversed regulariser in stream or --gram_closure form)
-        or ``_fit_adam`` (--sindy_optimizer adam): every seed its own initial coefficients and its own subsample.
+fit:    ``_fit_stlsq`` (--method stlsq), ``_fit_lbfgs`` (default; the reversed regulariser in stream or --gram_closure form),
+        ``_fit_adam`` (--sindy_optimizer adam) or ``_fit_wsindy`` (--wsindy): every seed its own initial coefficients and its own subsample.
 report: ``_report`` on rank 0: the reference's ``eval_results/<save_dir>/seed{n}.npz`` (``--eval_ltp`` adds roll-out error,
         horizon and held-out MSE per seed), the fit's summary, ``evaluation.aggregate_results``.
 
@@ -51,6 +52,14 @@ full-rank driver only); outputs and summary lines are those of ``--method stlsq`
 one launch read the n_seeds matrices -- no further data pass, copy or collective.  Problem order, result files and table are
 ``--grid``'s.
 
+``--wsindy`` sweeps the weak-SINDy fit of ``main_wsindy`` (the `for i in {0..49}; do python main_wsindy.py --seed $i` loops):
+sweep seed n reads the window main_wsindy --seed n reads (``sweep.weak_windows``), all windows are contracted and turned into
+their normal matrices by ONE call (symode_weak_normal_windows) and fitted by ONE symode_stlsq_sweep launch
+(``sweep.SeedSweepWSINDy``); --num_epochs is the pass limit, --num_test_funcs / --test_func_family are main_wsindy's.  The
+parser's default --sindy_optimizer does not matter to it.  ``--wsindy_grid name=v1,v2,...`` (repeatable; names threshold,
+w_sindy_reg; with --wsindy only) is its grid on the windows' shared matrices; problem order, result files and table are
+``--grid``'s.
+
 ``--fold_linear_action`` lets the closure of the reversed regulariser fold a linear group action g(x) = J x into its
 coefficients where the data are found to be one (``BatchedClosure(linear_action=None)``): a faster kernel and the same
 closure up to rounding, not bit for bit -- which is why it has to be asked for here.
@@ -69,13 +78,13 @@ import torch.distributed as dist
 
 from .autoencoder import AutoEncoder
 from .batched import BatchedClosure
-from .dataset import get_dataset
+from .dataset import get_dataset, ode_dt_dict
 from .evaluation import aggregate_results, eval_ltp_sweep, score_coefficients, truth_table, val_mse_sweep
 from .lie import LieGenerator
 from .model_utils import PRECOMPUTE_CHUNK, constraint_basis, load_laligan, symmetry_operands  # noqa: F401  (tests and tests/perf import the operands from here)
 from .parser_utils import get_args, init_ranks
 from .sindy import SINDyRegression
-from .sweep import GramClosure, SeedSweepLBFGS, SeedSweepSTLSQ, seeded_subsamples
+from .sweep import GramClosure, SeedSweepLBFGS, SeedSweepSTLSQ, SeedSweepWSINDy, seeded_subsamples
 
 
 def _pop(argv, flag, default, cast):
@@ -111,6 +120,7 @@ GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold'
 # --lbfgs_grid name -> DeviceTrainer(hyper=) key
 LBFGS_GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold', 'w_sym_reg': 'w_sym'}
 STLSQ_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg'}      # --stlsq_grid name -> SeedSweepSTLSQ.solve(hyper=) key
+WSINDY_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg'}     # --wsindy_grid name -> SeedSweepWSINDy.solve(hyper=) key
 MAX_GRID_PROBLEMS = 65535                                  # problems of one device trainer
 
 
@@ -145,16 +155,20 @@ def _grid_problem(problem, n_seeds):
 
 
 def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None, device_stlsq=False,
-             stlsq_grid=None):
+             stlsq_grid=None, wsindy=False, wsindy_grid=None):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
     apply to the default method.  ``grid``: the ``--grid`` strings, if any; their rules come after all others, and after
     them those of ``lbfgs_grid``, the ``--lbfgs_grid`` strings (``n_seeds``: for the size of its launch, if known).
     ``device_stlsq``, ``stlsq_grid``: the ``--device_stlsq`` flag and the ``--stlsq_grid`` strings; their rules stand before
-    those of the two other grids, which say what they always said."""
+    those of the two other grids, which say what they always said.  ``wsindy``, ``wsindy_grid``: the ``--wsindy`` flag and the
+    ``--wsindy_grid`` strings; theirs is a fit of its own, so its rules (``_refusal_wsindy``) come before the optimiser rules
+    and replace them -- the weak configs set no --sindy_optimizer, and the parser's default must not route them anywhere."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
+    if wsindy or wsindy_grid:
+        return _refusal_wsindy(args, method, world, engine, grid, lbfgs_grid, stlsq_grid, n_seeds, device_stlsq, wsindy, wsindy_grid)
     cfg = args.get('config')
     cmd = (f'python -m symode_amd.main --seed $i --config {cfg}' if cfg else 'python -m symode_amd.main --seed $i ...') + \
         ' for each seed (the per_seed loop of run_scripts/sweep.sh)'
@@ -258,6 +272,52 @@ def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq,
     return None
 
 
+def _refusal_wsindy(args, method, world, engine, grid, lbfgs_grid, stlsq_grid, n_seeds, device_stlsq, wsindy, wsindy_grid):
+    """The rules of --wsindy and --wsindy_grid, all of them: ``_refusal`` asks nothing else of such a run."""
+    cfg = args.get('config')
+    cmd = (f'python -m symode_amd.main_wsindy --seed $i --config {cfg}' if cfg else 'python -m symode_amd.main_wsindy --seed $i ...') + \
+        ' for each seed (the per_seed loop of run_scripts/sweep.sh)'
+    if not wsindy:
+        return '--wsindy_grid needs --wsindy: it is the grid of the weak-SINDy sweep (the other sweeps have --grid, --lbfgs_grid, --stlsq_grid)'
+    if method != 'lbfgs':
+        return f'--wsindy is a fit of its own (weak form, sequential-threshold least squares on the device): drop --method {method}'
+    if args['use_latent']:
+        return f'--wsindy does not cover latent fits (--use_latent); run {cmd}'
+    if args['w_sym_reg'] > 0:
+        return f'--wsindy sweeps the plain weak-form least-squares fit (w_sym_reg 0), main_wsindy has no symmetry regulariser; run {cmd}'
+    if args.get('eq_constraint'):
+        return f'--wsindy sweeps the unconstrained library (no --eq_constraint); run {cmd}'
+    if args.get('lstsq_driver') == 'gelsy':
+        return f'--wsindy fits with the full-rank driver (gels) only: the rank rule of --lstsq_driver gelsy runs on the host; run {cmd}'
+    if args.get('device_shuffle'):
+        return '--device_shuffle draws the epoch order of the minibatch Adam fit: the weak-SINDy sweep has no epoch order (drop it)'
+    if device_stlsq:
+        return '--device_stlsq is the device fit of --method stlsq: the weak-SINDy sweep always fits on the device (drop it)'
+    if grid or lbfgs_grid or stlsq_grid:
+        return ('--grid, --lbfgs_grid and --stlsq_grid are the grids of three other sweeps (Adam, L-BFGS, STLSQ): the weak-SINDy sweep '
+                'takes --wsindy_grid')
+    if world > 1:
+        return ('main_sweep runs the weak-SINDy fits in one process (no collective over seeds): give every GPU its own '
+                'block of seeds, python -m symode_amd.main_sweep --wsindy --seed <first> --n_seeds <count> ... per process')
+    if engine is None and str(args.get('device')) == 'cpu':
+        return 'symode_amd runs the SINDy path on the GPU only (no CPU fallback): a HIP device is required'
+    if n_seeds is not None and n_seeds > MAX_GRID_PROBLEMS:
+        return f'--wsindy: {n_seeds} seeds = {n_seeds} problems, one launch takes at most {MAX_GRID_PROBLEMS}'
+    if not wsindy_grid:
+        return None
+    axes, why = _parse_grid(wsindy_grid, WSINDY_GRID_NAMES, '--wsindy_grid')
+    if why is not None:
+        return why
+    for name, axis in axes:
+        if not all(v >= 0 for v in axis):
+            return f'--wsindy_grid {name}={",".join(f"{v:g}" for v in axis)}: every value must be >= 0'
+    n_points = int(np.prod([len(axis) for _, axis in axes]))
+    if n_seeds is not None and n_points * n_seeds > MAX_GRID_PROBLEMS:
+        return (f'--wsindy_grid: {n_points} grid points x {n_seeds} seeds = {n_points * n_seeds} problems, one launch takes at most '
+                f'{MAX_GRID_PROBLEMS}')
+    return None
+
+
 # ---- fit: each takes the sweep's context (main) and returns Xi, mask (S, d, p), the library triple and its summary lines ------
 def _rows(ctx):
     """This rank's columns lo:hi of every seed's subsample of the whole data set (see main)."""
@@ -288,6 +348,34 @@ def _fit_stlsq(ctx):
     Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']),
                                 lstsq_driver=args.get('lstsq_driver'), **route)
     lines = [f'{len(ctx.seeds)} seeds x {sw.n_points} points (over {ctx.world} rank(s)), STLSQ passes {int(passes.min())}-{int(passes.max())}',
+             f'near-threshold coefficients (| |coef| - thr | < 1e-4): {sw.near_threshold if sw.near_threshold else "none"}']
+    return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
+
+
+def _fit_wsindy(ctx):
+    """--wsindy: the weak-SINDy fit of main_wsindy per seed (main_wsindy.py:24-34, train.py:855-869) from ONE window
+    contraction + normal-matrix call over the seeds' windows and ONE threshold-loop launch (sweep.SeedSweepWSINDy)."""
+    args, train = ctx.args, ctx.train
+    lib = (args['poly_order'], args['include_sine'], args['include_exp'])
+    x3 = train.x.reshape(train.n_ics, train.n_steps, -1).to(ctx.dev)
+    # (main_wsindy hands WSINDyWrapper the whole argument dict: the two keys where a caller sets them, else its defaults)
+    tests = {k: args[k] for k in ('num_test_funcs', 'test_func_family') if k in args}
+    sw = SeedSweepWSINDy(x3, *lib, dt=ode_dt_dict[args['task']], seeds=ctx.seeds, **tests, **ctx.kw)
+    n_seeds, points = len(ctx.seeds), getattr(ctx, 'grid', None)
+    head = f'{n_seeds} seeds x {sw.n_t} time points of one trajectory each, {sw.K} test functions'
+    if points is not None:
+        # --wsindy_grid: G points on common seeds, problem g * n_seeds + k = point g on seed k's matrices
+        hyper = {WSINDY_GRID_NAMES[name]: [point[name] for point in points for _ in ctx.seeds] for name in points[0]}
+        Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']), hyper=hyper)
+        lines = [f'{head}, {len(points)} grid points on their normal matrices']
+        for g in range(len(points)):
+            at = slice(g * n_seeds, (g + 1) * n_seeds)
+            near = [rec for rec in sw.near_threshold if g * n_seeds <= rec[0] < (g + 1) * n_seeds]
+            lines.append(f'grid {g}: STLSQ passes {int(passes[at].min())}-{int(passes[at].max())}, near-threshold coefficients '
+                         f'(| |coef| - thr | < 1e-4): {near if near else "none"}')
+        return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
+    Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']))
+    lines = [f'{head}, STLSQ passes {int(passes.min())}-{int(passes.max())}',
              f'near-threshold coefficients (| |coef| - thr | < 1e-4): {sw.near_threshold if sw.near_threshold else "none"}']
     return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
 
@@ -541,11 +629,13 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     lbfgs_grid = _pop_all(argv, '--lbfgs_grid')
     stlsq_grid = _pop_all(argv, '--stlsq_grid')
     device_stlsq = _pop_flag(argv, '--device_stlsq')
+    wsindy_grid = _pop_all(argv, '--wsindy_grid')
+    wsindy = _pop_flag(argv, '--wsindy')
     fold_linear_action = _pop_flag(argv, '--fold_linear_action')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
-                   device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None)
+                   device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None, wsindy=wsindy, wsindy_grid=wsindy_grid or None)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -565,8 +655,12 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     ctx = SimpleNamespace(args=args, seeds=list(range(args['seed'], args['seed'] + n_seeds)), dev=dev, group=group, rank=rank,
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
                           engine=engine, kw={} if engine is None else {'engine': engine}, grid=None,
-                          device_stlsq=device_stlsq, fold_linear_action=fold_linear_action)
-    if stlsq_grid:
+                          device_stlsq=device_stlsq, fold_linear_action=fold_linear_action, train=train_dataset)
+    if wsindy_grid:
+        ctx.grid_names = WSINDY_GRID_NAMES
+        ctx.grid_axes = _parse_grid(wsindy_grid, WSINDY_GRID_NAMES, '--wsindy_grid')[0]
+        ctx.grid = _grid_points(ctx.grid_axes)
+    elif stlsq_grid:
         ctx.grid_names = STLSQ_GRID_NAMES
         ctx.grid_axes = _parse_grid(stlsq_grid, STLSQ_GRID_NAMES, '--stlsq_grid')[0]
         ctx.grid = _grid_points(ctx.grid_axes)
@@ -576,7 +670,8 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
         ctx.grid = _grid_points(ctx.grid_axes)
     fit = {('stlsq', 'lbfgs'): _fit_stlsq, ('lbfgs', 'lbfgs'): _fit_lbfgs, ('lbfgs', 'adam'): _fit_adam}
     report = _report if ctx.grid is None else _report_grid
-    return report(ctx, fit[method, args['sindy_optimizer']](ctx), val_dataset, eval_ltp, ltp_bound_rel)
+    fitter = _fit_wsindy if wsindy else fit[method, args['sindy_optimizer']]
+    return report(ctx, fitter(ctx), val_dataset, eval_ltp, ltp_bound_rel)
 
 
 if __name__ == '__main__':

@@ -489,6 +489,24 @@ def solve_SINDy(regressor, x, y, w_sindy_reg, st_threshold, max_iter=5, **kwargs
     return residual
 
 
+def weak_test_functions(t, t_max, num_test_funcs=50, test_func_family='trig', device='cuda'):
+    """(t, dt, V, V_drv, V V^T) of the weak form on the time grid ``t`` (reference sindy.py:336-348): V = dt g and
+    V_drv = dt g' (K, T) fp32 on ``device``, V V^T (K, K) fp64 on the host.  The one statement of these expressions:
+    WSINDyWrapper and sweep.SeedSweepWSINDy both take them from here."""
+    t = t.to(device)
+    dt = t[1] - t[0]
+    if test_func_family != 'trig':
+        raise NotImplementedError(f'test_func_family={test_func_family} not implemented')
+    k = torch.arange(1, num_test_funcs + 1, dtype=torch.float32, device=device).view(-1, 1)
+    amp = (2 / t_max) ** 0.5
+    g = amp * torch.sin(k * torch.pi * t / t_max)
+    g_drv = amp * k * np.pi / t_max * torch.cos(k * np.pi * t / t_max)
+    V = (dt * g).contiguous()                                                     # sindy.py:346-347
+    V_drv = (dt * g_drv).contiguous()
+    Vh = V.double().cpu().numpy()
+    return t, dt, V, V_drv, Vh @ Vh.T                                             # (K, K) fp64, data independent
+
+
 class WSINDyWrapper():
     """
     Weak SINDy as a regularised least-squares problem (reference sindy.py:327-395): trigonometric
@@ -502,19 +520,8 @@ class WSINDyWrapper():
     """
 
     def __init__(self, regressor, t, t_max, num_test_funcs=50, test_func_family='trig', device='cuda', **kwargs):
-        self.t = t.to(device)
-        self.dt = self.t[1] - self.t[0]
         self.regressor = regressor
-        if test_func_family != 'trig':
-            raise NotImplementedError(f'test_func_family={test_func_family} not implemented')
-        k = torch.arange(1, num_test_funcs + 1, dtype=torch.float32, device=device).view(-1, 1)
-        amp = (2 / t_max) ** 0.5
-        g = amp * torch.sin(k * torch.pi * self.t / t_max)
-        g_drv = amp * k * np.pi / t_max * torch.cos(k * np.pi * self.t / t_max)
-        self.V = (self.dt * g).contiguous()                                       # sindy.py:346-347
-        self.V_drv = (self.dt * g_drv).contiguous()
-        Vh = self.V.double().cpu().numpy()
-        self._VVt = Vh @ Vh.T                                                     # (K, K) fp64, data independent
+        self.t, self.dt, self.V, self.V_drv, self._VVt = weak_test_functions(t, t_max, num_test_funcs, test_func_family, device)
 
     def solve(self, x, w_sindy_reg, st_threshold, **kwargs):
         reg = self.regressor

@@ -19,7 +19,7 @@ import torch.distributed as dist
 from .coef_map import CoefMap
 from .engine import LBFGS_ACCEPT, LBFGS_BEGIN, get_engine, library_flags
 from . import lstsq as _lstsq
-from .sindy import NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_solve_from_gram
+from .sindy import NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_solve_from_gram, weak_test_functions
 
 
 def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
@@ -44,7 +44,89 @@ def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
     return torch.sort(idx, dim=1).values.to(dtype)
 
 
-class SeedSweepSTLSQ:
+class _DeviceSTLSQ:
+    """The device fit of a sweep whose problems are (p+d, p+d) fp64 matrices on the device: what SeedSweepSTLSQ and
+    SeedSweepWSINDy share.  The class supplies engine, S, d, p, n_points and ``grams(device=True)``."""
+
+    _fetch_with_fit = None                 # an int32 device tensor to bring back in the fit's one copy (SeedSweepWSINDy)
+
+    def _replay(self, s, G_s, w_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes):
+        """Problem s again in numpy, pass by pass from the full mask, for the detailed near-threshold record."""
+        mask[s] = True
+        for it in range(max_iter):
+            xi, _ = stlsq_solve_from_gram(G_s, self.n_points, mask[s], float(w_reg), self.d, lstsq_driver)
+            xi32 = xi.astype(np.float32)
+            self.near_threshold += [(s, it, i, k, v) for i, k, v in near_threshold_cases(xi32, mask[s], threshold)]
+            new_mask = np.logical_and(np.abs(xi32) > np.float32(threshold), mask[s])   # strict >, monotone (sindy.py:194)
+            converged = np.array_equal(new_mask, mask[s])
+            Xi[s], mask[s], passes[s] = xi32, new_mask, it + 1
+            if converged:
+                break
+
+    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper):
+        """``solve(device=True)``: one symode_stlsq_sweep launch on the matrices where the gather launch left them; only
+        Xi, mask, passes, near and fell come back.  The launch takes ridge weight and threshold in fp32, as its per-problem
+        table holds them, with or without a table -- so problem (g, k) of a grid is bit for bit seed k of the scalar device
+        solve with point g's values -- and what is replayed or solved on the host here uses the same rounded values.
+        Every rank holds the same all-reduced matrices and takes the same decisions."""
+        S, d, p = self.S, self.d, self.p
+        f32 = lambda v: float(np.float32(v))                                   # noqa: E731
+        n_problems = S
+        if hyper is not None:
+            unknown = set(hyper) - {'w_reg', 'threshold'}
+            if unknown or not hyper:
+                raise ValueError(f"hyper: the per-problem columns of the STLSQ sweep are w_reg and threshold, got {sorted(hyper)}")
+            lengths = {len(v) for v in hyper.values()}
+            n_problems = lengths.pop()
+            if lengths or n_problems < S or n_problems % S != 0:
+                raise ValueError(f'hyper: every column needs one value per problem, a multiple of the {S} seeds (problem s '
+                                 f'on seed s % {S}); got lengths {sorted({len(v) for v in hyper.values()})}')
+        w = np.array([f32(v) for v in (hyper or {}).get('w_reg', [w_sindy_reg] * n_problems)], dtype=np.float64)
+        thr = np.array([f32(v) for v in (hyper or {}).get('threshold', [threshold] * n_problems)], dtype=np.float64)
+        if not (np.all(np.isfinite(w)) and np.all(np.isfinite(thr)) and np.all(w >= 0) and np.all(thr >= 0)):
+            raise ValueError('the ridge weight and the threshold of every problem must be finite and >= 0')
+        G = self.grams(device=True)
+        table = None
+        if hyper is not None:
+            table = torch.from_numpy(np.stack([w, thr], axis=1).astype(np.float32)).to(G.device)
+        Xi, m8, p32, near, fell, *flags = self.engine.stlsq_sweep(G, self.n_points, w[0], thr[0], max_iter, hyper=table, d=d,
+                                                                  near_band=NEAR_THRESHOLD_BAND, to_host=True,    # one copy back
+                                                                  tail=self._fetch_with_fit)
+        if flags:
+            self._fetched(flags[0])
+        Xi, mask, passes = np.array(Xi), np.asarray(m8).astype(bool), np.asarray(p32).astype(np.int64)
+        near = np.array(near)
+        self.near_threshold = []
+        held = {}                                                       # set -> its (p+d, p+d) matrix on the host
+
+        def on_host(s):
+            k = s % S
+            if k not in held:
+                held[k] = G[k].cpu().numpy()
+            return held[k]
+
+        if fell.any():
+            # a pivot that was not positive: these problems are the host loop's, rank-revealing fallback and warning included
+            import warnings
+            lib = _lstsq._native()
+            for s in np.nonzero(fell)[0].tolist():
+                Gs = np.ascontiguousarray(on_host(s), dtype=np.float64)[None]
+                xi1, m1 = np.zeros((1, d, p), dtype=np.float32), np.ones((1, d, p), dtype=np.uint8)
+                p1, n1, f1 = (np.zeros(1, dtype=np.int32) for _ in range(3))
+                rc = lib.symode_host_stlsq_sweep(Gs.ctypes.data, 1, d, p, int(self.n_points), float(w[s]), float(thr[s]), int(max_iter),
+                                                 1, float(NEAR_THRESHOLD_BAND), xi1.ctypes.data, m1.ctypes.data, p1.ctypes.data,
+                                                 n1.ctypes.data, f1.ctypes.data)
+                if rc != 0:
+                    raise RuntimeError(f'symode_host_stlsq_sweep failed with code {rc}')
+                Xi[s], mask[s], passes[s], near[s] = xi1[0], m1[0].astype(bool), p1[0], n1[0]
+            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
+                          RuntimeWarning)
+        for s in np.nonzero(near)[0].tolist():
+            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'gels', Xi, mask, passes)
+        return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
+
+
+class SeedSweepSTLSQ(_DeviceSTLSQ):
     def __init__(self, x, dx, poly_order, include_sine=False, include_exp=False, n_seeds=64, subsample=0.5, seed0=0,
                  group=None, engine=None, idx=None, idx_sorted=False):
         """x, dx: (N_local, d) rows of the flattened data set (dataset.py:193-194) this rank gathers from.
@@ -97,78 +179,6 @@ class SeedSweepSTLSQ:
             self._gram = self._gram_dev.cpu().numpy()
         return self._gram
 
-    def _replay(self, s, G_s, w_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes):
-        """Problem s again in numpy, pass by pass from the full mask, for the detailed near-threshold record."""
-        mask[s] = True
-        for it in range(max_iter):
-            xi, _ = stlsq_solve_from_gram(G_s, self.n_points, mask[s], float(w_reg), self.d, lstsq_driver)
-            xi32 = xi.astype(np.float32)
-            self.near_threshold += [(s, it, i, k, v) for i, k, v in near_threshold_cases(xi32, mask[s], threshold)]
-            new_mask = np.logical_and(np.abs(xi32) > np.float32(threshold), mask[s])   # strict >, monotone (sindy.py:194)
-            converged = np.array_equal(new_mask, mask[s])
-            Xi[s], mask[s], passes[s] = xi32, new_mask, it + 1
-            if converged:
-                break
-
-    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper):
-        """``solve(device=True)``: one symode_stlsq_sweep launch on the matrices where the gather launch left them; only
-        Xi, mask, passes, near and fell come back.  The launch takes ridge weight and threshold in fp32, as its per-problem
-        table holds them, with or without a table -- so problem (g, k) of a grid is bit for bit seed k of the scalar device
-        solve with point g's values -- and what is replayed or solved on the host here uses the same rounded values.
-        Every rank holds the same all-reduced matrices and takes the same decisions."""
-        S, d, p = self.S, self.d, self.p
-        f32 = lambda v: float(np.float32(v))                                   # noqa: E731
-        n_problems = S
-        if hyper is not None:
-            unknown = set(hyper) - {'w_reg', 'threshold'}
-            if unknown or not hyper:
-                raise ValueError(f"hyper: the per-problem columns of the STLSQ sweep are w_reg and threshold, got {sorted(hyper)}")
-            lengths = {len(v) for v in hyper.values()}
-            n_problems = lengths.pop()
-            if lengths or n_problems < S or n_problems % S != 0:
-                raise ValueError(f'hyper: every column needs one value per problem, a multiple of the {S} seeds (problem s '
-                                 f'on seed s % {S}); got lengths {sorted({len(v) for v in hyper.values()})}')
-        w = np.array([f32(v) for v in (hyper or {}).get('w_reg', [w_sindy_reg] * n_problems)], dtype=np.float64)
-        thr = np.array([f32(v) for v in (hyper or {}).get('threshold', [threshold] * n_problems)], dtype=np.float64)
-        if not (np.all(np.isfinite(w)) and np.all(np.isfinite(thr)) and np.all(w >= 0) and np.all(thr >= 0)):
-            raise ValueError('the ridge weight and the threshold of every problem must be finite and >= 0')
-        G = self.grams(device=True)
-        table = None
-        if hyper is not None:
-            table = torch.from_numpy(np.stack([w, thr], axis=1).astype(np.float32)).to(G.device)
-        Xi, m8, p32, near, fell = self.engine.stlsq_sweep(G, self.n_points, w[0], thr[0], max_iter, hyper=table, d=d,
-                                                          near_band=NEAR_THRESHOLD_BAND, to_host=True)      # one copy back
-        Xi, mask, passes = np.array(Xi), np.asarray(m8).astype(bool), np.asarray(p32).astype(np.int64)
-        near = np.array(near)
-        self.near_threshold = []
-        held = {}                                                       # set -> its (p+d, p+d) matrix on the host
-
-        def on_host(s):
-            k = s % S
-            if k not in held:
-                held[k] = G[k].cpu().numpy()
-            return held[k]
-
-        if fell.any():
-            # a pivot that was not positive: these problems are the host loop's, rank-revealing fallback and warning included
-            import warnings
-            lib = _lstsq._native()
-            for s in np.nonzero(fell)[0].tolist():
-                Gs = np.ascontiguousarray(on_host(s), dtype=np.float64)[None]
-                xi1, m1 = np.zeros((1, d, p), dtype=np.float32), np.ones((1, d, p), dtype=np.uint8)
-                p1, n1, f1 = (np.zeros(1, dtype=np.int32) for _ in range(3))
-                rc = lib.symode_host_stlsq_sweep(Gs.ctypes.data, 1, d, p, int(self.n_points), float(w[s]), float(thr[s]), int(max_iter),
-                                                 1, float(NEAR_THRESHOLD_BAND), xi1.ctypes.data, m1.ctypes.data, p1.ctypes.data,
-                                                 n1.ctypes.data, f1.ctypes.data)
-                if rc != 0:
-                    raise RuntimeError(f'symode_host_stlsq_sweep failed with code {rc}')
-                Xi[s], mask[s], passes[s], near[s] = xi1[0], m1[0].astype(bool), p1[0], n1[0]
-            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
-                          RuntimeWarning)
-        for s in np.nonzero(near)[0].tolist():
-            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'gels', Xi, mask, passes)
-        return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
-
     def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None):
         """STLSQ to convergence for every seed (train.py:872-887 per seed).
         Returns (Xi (S, d, p) float32, mask (S, d, p) float32, passes (S,)).
@@ -213,6 +223,87 @@ class SeedSweepSTLSQ:
         for s in todo:
             self._replay(s, G[s], w_sindy_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes)
         return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
+
+
+# =================================================================================================
+# Seed sweep of the weak-SINDy fit (main_wsindy for S seeds at once)
+# =================================================================================================
+def weak_windows(seeds, n_ics, n_steps, n_t):
+    """(len(seeds), 2) int64 rows [trajectory, start]: for seed n the window ``main_wsindy --seed n`` fits
+    (main_wsindy.py:26-27 after its ``np.random.seed(n)``: first ``start = randint(0, n_steps - n_t)``, then
+    ``traj = randint(0, n_ics)``; ``np.random.RandomState(n)`` is the generator np.random.seed(n) leaves).
+    The two agree whenever ``get_dataset`` draws nothing from numpy's global generator between the seeding and the two
+    draws.  That holds for the four ODE tasks (lv, selkov, dosc, growth) with their data files on disk AND when they are
+    generated: data.py draws initial conditions and noise from torch generators of its own, seeded from the data's seed.
+    It does not hold for rd / mt_rd, whose loader adds noise from numpy's global generator -- tasks with no trajectories
+    to take a window of, which the weak-SINDy drivers do not cover."""
+    if not 1 <= n_t < n_steps:
+        raise ValueError(f'n_t = {n_t} must lie in 1 .. n_steps - 1 = {n_steps - 1}: the window start is drawn from [0, n_steps - n_t)')
+    out = np.zeros((len(seeds), 2), dtype=np.int64)
+    for row, seed in zip(out, seeds):
+        rs = np.random.RandomState(int(seed))
+        row[1] = rs.randint(0, n_steps - n_t)
+        row[0] = rs.randint(0, n_ics)
+    return out
+
+
+class SeedSweepWSINDy(_DeviceSTLSQ):
+    """``main_wsindy`` for S seeds in three launches.  A seed differs from the next only in the window of the shared data
+    it reads; time grid, test functions and M = V V^T are common.  The weak fit on a window is an STLSQ fit on the
+    (p+d, p+d) matrix N = Z^T M Z, Z = [G | b], with ridge gamma = sqrt(w_sindy_reg) (WSINDyWrapper.solve adds
+    w_sindy_reg I to G^T M G, the STLSQ entries gamma^2 I), so: ONE symode_weak_normal_windows call (window contraction,
+    normal matrices) and ONE symode_stlsq_sweep launch, the matrices never leaving the device."""
+
+    def __init__(self, x3, poly_order, include_sine=False, include_exp=False, dt=None, seeds=None, windows=None, n_t=None,
+                 num_test_funcs=50, test_func_family='trig', engine=None):
+        """x3 (n_ics, n_steps, d) on the device, ``dt`` its time step.  ``seeds``: the windows are ``weak_windows``' (sweep
+        seed n reads the window main_wsindy --seed n reads); or ``windows`` (S, 2) [trajectory, start] rows given outright.
+        ``n_t`` points per window, int(0.8 n_steps) by default (main_wsindy.py:26)."""
+        assert x3.dim() == 3 and dt is not None and (seeds is None) != (windows is None)
+        self.engine = engine or get_engine()
+        self.x = x3.contiguous()
+        self.n_ics, self.n_steps, self.d = x3.shape
+        self.order, self.flags = poly_order, library_flags(include_sine, include_exp)
+        self.p = self.engine.lib_size(self.d, poly_order, self.flags)
+        self.n_t = int(0.8 * self.n_steps) if n_t is None else int(n_t)
+        self.n_points = self.n_t
+        self.windows = weak_windows(list(seeds), self.n_ics, self.n_steps, self.n_t) if windows is None else np.asarray(windows)
+        self.S = len(self.windows)
+        t = torch.arange(self.n_t) * dt                                         # main_wsindy.py:31-33
+        _, _, self.V, self.V_drv, self._VVt = weak_test_functions(t, self.n_t * dt, num_test_funcs, test_func_family, x3.device)
+        self.K = self.V.shape[0]
+        self._normal_dev, self._normal, self.bad = None, None, None
+
+    def normals(self, device=False):
+        """(S, p+d, p+d) fp64: every window's N.  ``device=True``: the tensor the one call of the entry left on the device."""
+        if self._normal_dev is None:
+            M = torch.from_numpy(np.ascontiguousarray(self._VVt)).to(self.x.device)
+            self._normal_dev, self._fetch_with_fit = self.engine.weak_normal_windows(self.x, self.windows, self.n_t, self.V,
+                                                                                     self.V_drv, M, self.order, self.flags)
+        if device:
+            return self._normal_dev
+        if self._normal is None:
+            self._normal = self._normal_dev.cpu().numpy()
+        return self._normal
+
+    grams = normals                        # the name _DeviceSTLSQ reads its matrices by
+
+    def _fetched(self, bad):
+        """The kernel's range flags, read in the copy that fetched the fit's results."""
+        self.bad = np.array(bad)
+        if self.bad.any():
+            s = int(np.argmax(self.bad))
+            raise RuntimeError(f'symode_weak_normal_windows flagged windows[{s}] = {self.windows[s].tolist()} as out of range')
+
+    def solve(self, w_sindy_reg, threshold, max_iter=10, hyper=None):
+        """The threshold loop of train_WSINDy (train.py:855-869) for every seed on the device, the full-rank driver (gels).
+        Returns (Xi (S, d, p) float32, mask (S, d, p) float32, passes (S,)); ``near_threshold`` is kept as by
+        SeedSweepSTLSQ.  ``hyper={"w_reg": [...], "threshold": [...]}``: one value per PROBLEM, w_reg in units of
+        w_sindy_reg, problem s on seed s % S (a grid of G points on the S windows' shared matrices)."""
+        gamma = lambda w: float(np.sqrt(w)) if np.isfinite(w) and w >= 0 else float('nan')     # noqa: E731  (refused by name below)
+        if hyper is not None and 'w_reg' in hyper:
+            hyper = dict(hyper, w_reg=[gamma(float(w)) for w in hyper['w_reg']])
+        return self._solve_device(gamma(float(w_sindy_reg)), threshold, max(1, int(max_iter)), hyper)
 
 
 # =================================================================================================
