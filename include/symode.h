@@ -828,6 +828,34 @@ int symode_stlsq_sweep(const double* aug_gram, long n_sets, long n_problems, int
                        double gamma, double threshold, int max_iter, double near_band, float* xi_out, unsigned char* mask_out,
                        int* passes_out, int* near_out, int* fell_out, void* stream);
 
+/* symode_stlsq_sweep under the equivariance constraint Xi = Q beta (+ const), EquivSINDy-c: the same loop, but per pass ONE
+ * joint system over all equation rows in the r' = r + (allow_constant ? d : 0) free parameters.  aug_gram, n_sets, n_problems,
+ * hyper, gamma, threshold, max_iter, near_band, n_points, mask_out, passes_out and near_out are symode_stlsq_sweep's.
+ * q_solve (d p, r') fp64: row j p + k is equation j, library column k of Q (the reference's equation-major indexing of
+ * Q[mask.flatten()], also when use_kron_product is false), then, with allow_constant, d unit columns, column r + j with its 1
+ * in row j p.  q_xi (d p, r) fp32: the map that forms Xi, rows in Xi's (d, p) row-major order (it differs from q_solve's
+ * first r columns exactly when use_kron_product is false).  Both are shared by all problems.
+ * Per pass on the mask M (d, p): the columns of q_solve with a non-zero entry in a row of M, in ascending order (Qe, n of
+ * them); Gq = Qe^T Gm Qe, cq = Qe^T cm in fp64 with Gm = blockdiag(Gtt + gamma^2 I)[M, M], cm = Gty[M] -- sums in ascending
+ * (j, k, l), the upper triangle mirrored; pivoted Cholesky and substitutions as symode_stlsq_sweep; beta32 = (float) of the
+ * solution in its r' slots, 0 in the others; Xi[j, k] = sum_c q_xi[j p + k, c] beta32[c] in fp32, c ascending,
+ * + const32[j] at k = 0 with allow_constant; strict > (float)threshold on the still-active entries.
+ * A pivot that is not > pivot_floor * (first pivot) sets fell_out[s] = 1 and ENDS problem s (its other outputs are then
+ * unspecified): "possibly rank deficient" -- thresholding under the constraint routinely leaves collinear columns, whose last
+ * pivot is round-off of either sign -- and the caller solves those problems on the host with the rank-revealing rule.
+ * xi_out (n_problems, d, p) fp32: Xi of the last solve, unmasked; var_out (n_problems, r') fp32: [beta | const] of it.
+ * p <= 64, d <= 4, r' <= 64.
+ * Refused before any GPU work: d < 1, d > 4, p < 1, p > 64, r < 1, r' > 64, r' > d p, max_iter < 1, n_sets < 1, n_problems <
+ * n_sets or >= 2^31, hyper == NULL with n_problems != n_sets, pivot_floor < 0 or not finite (SYMODE_E_BADSIZE); any pointer but
+ * hyper NULL (SYMODE_E_NULLPTR); aug_gram or q_solve not 8-byte, q_xi, hyper or an fp32 / int output not 4-byte aligned
+ * (SYMODE_E_ALIGN).
+ * replaces: train.py:872-887 over sindy.py:250-315, constrained branch (regressor.constraint). */
+int symode_stlsq_sweep_constrained(const double* aug_gram, long n_sets, long n_problems, int d, int p, long n_points,
+                                   const double* q_solve, const float* q_xi, int r, int allow_constant, const float* hyper,
+                                   double gamma, double threshold, int max_iter, double near_band, double pivot_floor,
+                                   float* xi_out, float* var_out, unsigned char* mask_out, int* passes_out, int* near_out,
+                                   int* fell_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,24 @@ class CoefMap:
         rows = (np.arange(self.p)[None, :] * self.d + np.arange(self.d)[:, None]).reshape(-1)
         return np.ascontiguousarray(Q[rows])
 
+    def solve_matrix(self):
+        """The matrix the constrained least-squares fit solves in (sindy.py:277-282), fp64 numpy (d p, r'), with
+        r' = r + (d if allow_constant else 0): row j p + k is Q's row for equation j, library column k in the reference's
+        equation-major indexing -- ``Q[mask.flatten()]``, taken as it stands also when ``use_kron_product`` is false, where
+        Xi reads Q's rows in the other order (``xi_matrix``); the reference's quirk is kept -- and, with ``allow_constant``,
+        d unit columns behind it: column r + j holds its 1 in row j p, the constant term of equation j."""
+        Q = np.asarray(self._numpy_Q(), dtype=np.float64)
+        if self.allow_constant:
+            Q = np.concatenate([Q, np.zeros((Q.shape[0], self.d))], axis=1)
+            for j in range(self.d):
+                Q[j * self.p, self.r + j] = 1.0
+        return np.ascontiguousarray(Q)
+
+    def xi_matrix(self):
+        """The matrix that forms Xi from beta, fp32 numpy (d p, r) with rows in Xi's (d, p) row-major order:
+        ``effective_Q``, under the name the constrained fit reads it by next to ``solve_matrix``."""
+        return self.effective_Q()
+
     def live_columns(self):
         """(d, p) bool: the entries of Xi the map can make non-zero.  The constraint keeps whole entries of Xi at zero (for
         the planar rotations every even degree), but the rows of Q that say so are not zero: its basis comes out of an SVD

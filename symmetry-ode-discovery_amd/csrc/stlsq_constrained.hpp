@@ -1,0 +1,233 @@
+// Sequential-threshold least squares under the equivariance constraint Xi = Q beta (+ const) on the device
+// (symode_stlsq_sweep_constrained): the constrained branch of sindy.solve_SINDy_one_step (reference sindy.py:250-315),
+// restated from a Gram matrix for one launch over all problems.  Library independent, so only capi.hip includes this header.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+#include "stlsq.hpp"
+
+namespace symode {
+
+constexpr int STLSQC_MAX_R = WAVE;     // free parameters r' = r + (allow_constant ? d : 0): one lane per position of the pivot order
+
+// LDS of a workgroup: Gq (r' x r' fp64, rows of stride r'), the support masks of the STLSQ_MAX_D rows (64-bit words), the
+// list of effective columns (r' ints) and the fp32 variables [beta | const] (r' floats).  33.3 KiB at r' = 64.
+inline size_t stlsqc_lds_bytes(int R) {
+    return (size_t)R * R * sizeof(double) + STLSQ_MAX_D * sizeof(unsigned long long) + (size_t)R * (sizeof(int) + sizeof(float));
+}
+
+// One workgroup of ONE wave per problem.  The constraint couples the equation rows into one joint system of n <= r' <= 64
+// unknowns, so the factorisation -- one lane per position of the pivot order -- is a single wave's work whatever d is, and
+// the build of Gq in front of it is at most d p (p + n) steps per lane.  d waves would build d partial sums that then have
+// to meet in a fixed order through LDS and barriers, to then idle through the solve; with one wave the documented order of
+// the sums (ascending j, k, l) is simply the loop order, and no __syncthreads is needed at all.
+// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): 70 VGPRs (69 without the table), 0 AGPRs, 106 SGPRs
+// of which 9 are kept in VGPR lanes, scratch 0 bytes per lane, no VGPR spill; LDS is dynamic, stlsqc_lds_bytes(r'): 33.3 KiB at
+// r' = 64, 0.4 KiB at r' = 6.
+//
+// Per pass, with the (d, p) mask M held as d 64-bit words in LDS (the same in every lane), lane b the owner of column b:
+//   columns   column c of q_solve (d p, r') is effective when one of its rows with M set is != 0 (the host's test on
+//             Q[mask], sindy.py:284); the effective columns in ascending order are col[0 .. n);
+//   system    Gq = Qe^T Gm Qe and cq = Qe^T cm in fp64, Gm = blockdiag(Gtt + gamma^2 I)[M, M] never formed: for j, then
+//             active k ascending, lane b forms u_b = sum over active l ascending of (Gtt[k, l] + gamma^2 [k == l]) Qe[(j,l), b]
+//             and adds Qe[(j,k), a] u_b into Gq[a, b] for a <= b, Qe[(j,k), b] Gty[k, j] into cq[b].  The lower triangle is
+//             the mirror of the upper one, so Gq is exactly symmetric;
+//   solve     stlsq_sweep_kernel's pivoted Cholesky and substitutions, except that a pivot which is not
+//             > pivot_floor * (first pivot) (or not > 0) flags the problem (fell) and ends it;
+//   Xi        beta32 = (float) of the solution in its r' slots (0 elsewhere); lane k forms Xi[j, k] = sum over c < r ascending
+//             of q_xi[(j p + k), c] beta32[c] in fp32, plus const32[j] at k = 0 when allow_constant;
+//   threshold the host's rule on the still-active entries, near counted on them; stop when the mask repeats.
+// No multiply-add is contracted (-ffp-contract=off).  Every LDS and global index is bounded by d, p, r': no address
+// depends on data.  HYPER, n_sets: as stlsq_sweep_kernel.
+template <bool HYPER>
+__global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* __restrict__ aug, int n_sets, int d, int p,
+                                                                 const double* __restrict__ q_solve,
+                                                                 const float* __restrict__ q_xi, int r, int allow_constant,
+                                                                 const float* __restrict__ hyper, double gamma, double threshold,
+                                                                 int max_iter, double near_band, double pivot_floor,
+                                                                 float* __restrict__ xi_out, float* __restrict__ var_out,
+                                                                 unsigned char* __restrict__ mask_out,
+                                                                 int* __restrict__ passes_out, int* __restrict__ near_out,
+                                                                 int* __restrict__ fell_out) {
+    extern __shared__ double stlsqc_smem[];
+    const int lane = threadIdx.x;
+    const long s = blockIdx.x;
+    const int F = p + d;
+    const int R = r + (allow_constant ? d : 0);
+    double* A = stlsqc_smem;
+    unsigned long long* M = (unsigned long long*)(A + (size_t)R * R);
+    int* col = (int*)(M + STLSQ_MAX_D);
+    float* var = (float*)(col + R);
+    if constexpr (HYPER) {
+        gamma = (double)hyper[s * STLSQ_HYPER];
+        threshold = (double)hyper[s * STLSQ_HYPER + 1];
+    }
+    const double* G = aug + (s % n_sets) * (long)F * F;
+    const double g2 = gamma * gamma;
+    const float thr32 = (float)threshold;
+    if (lane < STLSQ_MAX_D) M[lane] = lane < d ? (p == 64 ? ~0ull : (1ull << p) - 1ull) : 0ull;
+    stlsq_wave_sync();
+    int near = 0, passes = 0, fell = 0;
+    for (int it = 0; it < max_iter; ++it) {
+        // ---- effective columns
+        bool eff = false;
+        if (lane < R) {
+            for (int j = 0; j < d; ++j) {
+                const unsigned long long mj = M[j];
+                for (int k = 0; k < p; ++k)
+                    if ((mj >> k) & 1ull) eff = eff || q_solve[((long)j * p + k) * R + lane] != 0.0;
+            }
+        }
+        const unsigned long long support = __ballot(eff);
+        const int n = __popcll(support);
+        if (eff) col[__popcll(support & ((1ull << lane) - 1ull))] = lane;
+        if (lane < R) var[lane] = 0.0f;
+        stlsq_wave_sync();
+        bool bad = false;
+        if (n > 0) {
+            const bool on = lane < n;
+            const int cb = on ? col[lane] : 0;
+            // ---- system
+            for (int a = 0; a < n; ++a)
+                if (on) A[a * R + lane] = 0.0;
+            double c = 0.0;
+            for (int j = 0; j < d; ++j) {
+                const unsigned long long mj = M[j];
+                for (int k = 0; k < p; ++k) {
+                    if (!((mj >> k) & 1ull)) continue;
+                    double u = 0.0;
+                    for (int l = 0; l < p; ++l) {
+                        if (!((mj >> l) & 1ull)) continue;
+                        const double g = G[(long)k * F + l] + (k == l ? g2 : 0.0);
+                        u += g * q_solve[((long)j * p + l) * R + cb];
+                    }
+                    const double qk = on ? q_solve[((long)j * p + k) * R + cb] : 0.0;
+                    c += qk * G[(long)k * F + p + j];
+                    for (int a = 0; a < n; ++a) {
+                        const double qa = stlsq_lane(qk, a);
+                        if (on && a <= lane) A[a * R + lane] += qa * u;
+                    }
+                }
+            }
+            stlsq_wave_sync();
+            for (int a = 0; a < n; ++a)
+                if (on && a < lane) A[lane * R + a] = A[a * R + lane];
+            stlsq_wave_sync();
+            // ---- factor and solve (stlsq_sweep_kernel's, rows of stride R, and the pivot floor)
+            int orig = lane;
+            double dg = on ? A[lane * R + lane] : 0.0;
+            double first = 0.0;
+            for (int kk = 0; kk < n; ++kk) {
+                double bv = dg;
+                int bi = (lane >= kk && lane < n) ? lane : WAVE;
+#pragma unroll
+                for (int off = WAVE / 2; off > 0; off /= 2) {
+                    const double ov = __shfl_xor(bv, off, WAVE);
+                    const int oi = __shfl_xor(bi, off, WAVE);
+                    if (oi < WAVE && (bi == WAVE || ov > bv || (ov == bv && oi < bi))) {
+                        bv = ov;
+                        bi = oi;
+                    }
+                }
+                const int jp = __builtin_amdgcn_readfirstlane(bi);
+                if (jp != kk) {
+                    const int src = lane == kk ? jp : (lane == jp ? kk : lane);
+                    orig = __shfl(orig, src, WAVE);
+                    dg = __shfl(dg, src, WAVE);
+                    c = __shfl(c, src, WAVE);
+                }
+                const double dkk = stlsq_lane(dg, kk);
+                if (kk == 0) first = dkk;
+                if (!(dkk > pivot_floor * first) || !(dkk > 0.0)) {
+                    bad = true;
+                    break;
+                }
+                const double rr = sqrt(dkk);
+                const int jo = __builtin_amdgcn_readlane(orig, kk);
+                const bool rest = lane > kk && lane < n;
+                double Rt = 0.0;
+                if (rest) {
+                    Rt = A[jo * R + orig] / rr;
+                    A[jo * R + orig] = Rt;
+                }
+                if (lane == kk) A[jo * R + jo] = rr;
+                for (int a = kk + 1; a < n; ++a) {
+                    const double Ra = stlsq_lane(Rt, a);
+                    const int oa = __builtin_amdgcn_readlane(orig, a);
+                    if (rest) A[oa * R + orig] -= Ra * Rt;
+                }
+                const double q = stlsq_lane(c, kk) / rr;
+                if (rest) {
+                    c -= Rt * q;
+                    dg -= Rt * Rt;
+                }
+                if (lane == kk) c = q;
+                stlsq_wave_sync();
+            }
+            if (!bad) {
+                for (int i = n - 1; i >= 0; --i) {
+                    const int jo = __builtin_amdgcn_readlane(orig, i);
+                    const double prod = (lane > i && lane < n) ? A[jo * R + orig] * c : 0.0;
+                    double acc = stlsq_lane(c, i);
+                    for (int t = i + 1; t < n; ++t) acc -= stlsq_lane(prod, t);
+                    const double y = acc / A[jo * R + jo];
+                    if (lane == i) c = y;
+                }
+                if (on) var[col[orig]] = (float)c;
+            }
+        }
+        passes = it + 1;
+        if (bad) {
+            fell = 1;
+            break;
+        }
+        stlsq_wave_sync();
+        // ---- coefficients and threshold
+        if (lane < R) var_out[s * R + lane] = var[lane];
+        int changed = 0;
+        for (int j = 0; j < d; ++j) {
+            const unsigned long long mj = M[j];
+            float v = 0.0f;
+            if (lane < p) {
+                const float* qrow = q_xi + ((long)j * p + lane) * r;
+                for (int cc = 0; cc < r; ++cc) v += qrow[cc] * var[cc];
+                if (allow_constant && lane == 0) v += var[r + j];
+                xi_out[(s * d + j) * p + lane] = v;
+            }
+            const bool m = (mj >> lane) & 1ull;
+            const float av = fabsf(v);
+            near += __popcll(__ballot(m && fabs((double)av - threshold) < near_band));
+            const unsigned long long nm = __ballot(m && av > thr32);
+            changed |= nm != mj;
+            stlsq_wave_sync();                      // every lane has read M[j]
+            if (lane == 0) M[j] = nm;
+        }
+        stlsq_wave_sync();
+        if (!changed) break;
+    }
+    for (int j = 0; j < d; ++j)
+        if (lane < p) mask_out[(s * d + j) * p + lane] = (M[j] >> lane) & 1ull ? 1 : 0;
+    if (lane == 0) {
+        passes_out[s] = passes;
+        near_out[s] = near;
+        fell_out[s] = fell;
+    }
+}
+
+inline hipError_t launch_stlsq_constrained(const double* aug, long n_sets, long n_problems, int d, int p, const double* q_solve,
+                                           const float* q_xi, int r, int allow_constant, const float* hyper, double gamma,
+                                           double threshold, int max_iter, double near_band, double pivot_floor, float* xi_out,
+                                           float* var_out, unsigned char* mask_out, int* passes_out, int* near_out, int* fell_out,
+                                           hipStream_t st) {
+    const int R = r + (allow_constant ? d : 0);
+    auto kernel = hyper ? stlsq_constrained_kernel<true> : stlsq_constrained_kernel<false>;
+    kernel<<<dim3((unsigned)n_problems), dim3(WAVE), stlsqc_lds_bytes(R), st>>>(aug, (int)n_sets, d, p, q_solve, q_xi, r,
+                                                                                allow_constant, hyper, gamma, threshold, max_iter,
+                                                                                near_band, pivot_floor, xi_out, var_out, mask_out,
+                                                                                passes_out, near_out, fell_out);
+    SYMODE_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+}  // namespace symode

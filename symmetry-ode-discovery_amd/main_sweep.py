@@ -52,6 +52,12 @@ full-rank driver only); outputs and summary lines are those of ``--method stlsq`
 one launch read the n_seeds matrices -- no further data pass, copy or collective.  Problem order, result files and table are
 ``--grid``'s.
 
+``--equiv_stlsq`` (with --method stlsq --device_stlsq --eq_constraint) is that device fit under the equivariance constraint
+Xi = Q beta (+ const), EquivSINDy-c: the template regressor of the L-BFGS sweep supplies Q (constraint_basis,
+--constrain_constant), ``SeedSweepSTLSQ.solve(device=True, coef=...)`` solves per pass ONE joint system in the r' <= 64 free
+parameters (symode_stlsq_sweep_constrained) -- one gather launch and one solve launch for the whole sweep, --stlsq_grid and
+--eval_ltp as before.  Without the flag ``--method stlsq --eq_constraint`` is refused as it always was.
+
 ``--wsindy`` sweeps the weak-SINDy fit of ``main_wsindy`` (the `for i in {0..49}; do python main_wsindy.py --seed $i` loops):
 sweep seed n reads the window main_wsindy --seed n reads (``sweep.weak_windows``), all windows are contracted and turned into
 their normal matrices by ONE call (symode_weak_normal_windows) and fitted by ONE symode_stlsq_sweep launch
@@ -155,7 +161,7 @@ def _grid_problem(problem, n_seeds):
 
 
 def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None, device_stlsq=False,
-             stlsq_grid=None, wsindy=False, wsindy_grid=None):
+             stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
@@ -164,9 +170,15 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     ``device_stlsq``, ``stlsq_grid``: the ``--device_stlsq`` flag and the ``--stlsq_grid`` strings; their rules stand before
     those of the two other grids, which say what they always said.  ``wsindy``, ``wsindy_grid``: the ``--wsindy`` flag and the
     ``--wsindy_grid`` strings; theirs is a fit of its own, so its rules (``_refusal_wsindy``) come before the optimiser rules
-    and replace them -- the weak configs set no --sindy_optimizer, and the parser's default must not route them anywhere."""
+    and replace them -- the weak configs set no --sindy_optimizer, and the parser's default must not route them anywhere.
+    ``equiv_stlsq``: the ``--equiv_stlsq`` flag; off, every answer is what it was.  On, its own rules (``_refusal_equiv_stlsq``)
+    come first and the rule that keeps --eq_constraint out of --method stlsq does not apply."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
+    if equiv_stlsq:
+        why = _refusal_equiv_stlsq(args, method, device_stlsq, wsindy or wsindy_grid)
+        if why is not None:
+            return why
     if wsindy or wsindy_grid:
         return _refusal_wsindy(args, method, world, engine, grid, lbfgs_grid, stlsq_grid, n_seeds, device_stlsq, wsindy, wsindy_grid)
     cfg = args.get('config')
@@ -200,7 +212,7 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
         return 'symode_amd runs the SINDy path on the GPU only (no CPU fallback): a HIP device is required'
     if method == 'stlsq' and args['w_sym_reg'] > 0:
         return '--method stlsq sweeps the plain least-squares fit (use --method lbfgs with the symmetry regulariser)'
-    if method == 'stlsq' and args.get('eq_constraint'):
+    if method == 'stlsq' and args.get('eq_constraint') and not equiv_stlsq:
         return '--method stlsq sweeps the unconstrained library (use --method lbfgs for EquivSINDy-c)'
     if args.get('device_shuffle') and (method == 'stlsq' or not adam):
         return ('--device_shuffle draws the epoch order of the minibatch Adam fit inside its launch: it needs '
@@ -238,6 +250,33 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
         if n_seeds is not None and n_points * n_seeds > MAX_GRID_PROBLEMS:
             return (f'--lbfgs_grid: {n_points} grid points x {n_seeds} seeds = {n_points * n_seeds} problems, one device trainer takes '
                     f'at most {MAX_GRID_PROBLEMS}')
+    return None
+
+
+EQUIV_STLSQ_MAX_PARAMS = 64                                # r' of symode_stlsq_sweep_constrained: one lane per free parameter
+
+
+def _refusal_equiv_stlsq(args, method, device_stlsq, wsindy):
+    """The rules of --equiv_stlsq that the arguments alone decide (r' <= 64 is known once Q exists: ``_fit_stlsq``)."""
+    if wsindy:
+        return ('--equiv_stlsq is the constrained fit of --method stlsq: the weak-SINDy sweep (--wsindy) fits the unconstrained '
+                'library (drop one of them)')
+    if method != 'stlsq':
+        return '--equiv_stlsq is the constrained fit of the sequential-threshold least-squares sweep: it needs --method stlsq'
+    if not device_stlsq:
+        return ('--equiv_stlsq needs --device_stlsq: the constrained fit of the sweep runs on the device (the host route of '
+                '--method stlsq sweeps the unconstrained library)')
+    if not args.get('eq_constraint'):
+        return ('--equiv_stlsq needs --eq_constraint: it fits under the equivariance constraint (drop --equiv_stlsq for the '
+                'unconstrained library)')
+    if args.get('lstsq_driver') == 'gelsy':
+        return ('--equiv_stlsq fits with the full-rank driver (gels) only: the rank rule of --lstsq_driver gelsy runs on the '
+                'host (python -m symode_amd.main_sindy per seed)')
+    if args['w_sym_reg'] > 0:
+        return ('--equiv_stlsq sweeps the constrained least-squares fit without a symmetry regulariser (w_sym_reg 0): use '
+                '--method lbfgs with the regulariser')
+    if args['use_latent']:
+        return '--equiv_stlsq does not cover latent fits (--use_latent)'
     return None
 
 
@@ -329,6 +368,18 @@ def _fit_stlsq(ctx):
     (seed, point) index table; the Gram matrices are all-reduced over the ranks."""
     args = ctx.args
     lib = (args['poly_order'], args['include_sine'], args['include_exp'])
+    fit = {}
+    if getattr(ctx, 'equiv_stlsq', False):
+        # --equiv_stlsq: library and constraint are the template's, as the L-BFGS sweep builds it
+        template = _template(ctx)[0]
+        lib = (template.poly_order, template.include_sine, template.include_exp)
+        coef = template.coef
+        n_free = coef.r + (coef.d if coef.allow_constant else 0)
+        if n_free > EQUIV_STLSQ_MAX_PARAMS:
+            raise SystemExit(f"--equiv_stlsq: the constraint leaves r' = {n_free} free parameters ({coef.r} columns of Q"
+                             f"{f' + {coef.d} constants' if coef.allow_constant else ''}), the device fit takes at most "
+                             f'{EQUIV_STLSQ_MAX_PARAMS}; use --method lbfgs')
+        fit = dict(coef=coef)
     sw = SeedSweepSTLSQ(ctx.x_all, ctx.dx_all, *lib, n_seeds=len(ctx.seeds), subsample=args['lbfgs_subsample'], seed0=args['seed'],
                         group=ctx.group, engine=ctx.engine, idx=_rows(ctx), idx_sorted=True)
     n_seeds, points = len(ctx.seeds), getattr(ctx, 'grid', None)
@@ -336,7 +387,7 @@ def _fit_stlsq(ctx):
         # --stlsq_grid: G points on common seeds, problem g * n_seeds + k = point g on seed k's matrices
         hyper = {STLSQ_GRID_NAMES[name]: [point[name] for point in points for _ in ctx.seeds] for name in points[0]}
         Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']),
-                                    lstsq_driver=args.get('lstsq_driver'), device=True, hyper=hyper)
+                                    lstsq_driver=args.get('lstsq_driver'), device=True, hyper=hyper, **fit)
         lines = [f'{n_seeds} seeds x {sw.n_points} points (over {ctx.world} rank(s)), {len(points)} grid points on their Gram matrices']
         for g in range(len(points)):
             at = slice(g * n_seeds, (g + 1) * n_seeds)
@@ -346,7 +397,7 @@ def _fit_stlsq(ctx):
         return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
     route = dict(device=True) if getattr(ctx, 'device_stlsq', False) else {}
     Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']),
-                                lstsq_driver=args.get('lstsq_driver'), **route)
+                                lstsq_driver=args.get('lstsq_driver'), **route, **fit)
     lines = [f'{len(ctx.seeds)} seeds x {sw.n_points} points (over {ctx.world} rank(s)), STLSQ passes {int(passes.min())}-{int(passes.max())}',
              f'near-threshold coefficients (| |coef| - thr | < 1e-4): {sw.near_threshold if sw.near_threshold else "none"}']
     return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
@@ -631,11 +682,13 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     device_stlsq = _pop_flag(argv, '--device_stlsq')
     wsindy_grid = _pop_all(argv, '--wsindy_grid')
     wsindy = _pop_flag(argv, '--wsindy')
+    equiv_stlsq = _pop_flag(argv, '--equiv_stlsq')
     fold_linear_action = _pop_flag(argv, '--fold_linear_action')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
-                   device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None, wsindy=wsindy, wsindy_grid=wsindy_grid or None)
+                   device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None, wsindy=wsindy, wsindy_grid=wsindy_grid or None,
+                   equiv_stlsq=equiv_stlsq)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -655,7 +708,8 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     ctx = SimpleNamespace(args=args, seeds=list(range(args['seed'], args['seed'] + n_seeds)), dev=dev, group=group, rank=rank,
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
                           engine=engine, kw={} if engine is None else {'engine': engine}, grid=None,
-                          device_stlsq=device_stlsq, fold_linear_action=fold_linear_action, train=train_dataset)
+                          device_stlsq=device_stlsq, fold_linear_action=fold_linear_action, train=train_dataset,
+                          equiv_stlsq=equiv_stlsq)
     if wsindy_grid:
         ctx.grid_names = WSINDY_GRID_NAMES
         ctx.grid_axes = _parse_grid(wsindy_grid, WSINDY_GRID_NAMES, '--wsindy_grid')[0]

@@ -346,6 +346,43 @@ def stlsq_solve_from_gram(G, N, mask, gamma, d, driver="gelsy"):
     return Xi, yy - 2 * w @ cm + w @ Gm @ w
 
 
+def stlsq_constrained_from_gram(G, N, mask, gamma, d, coef, driver="gels"):
+    """One pass of the constrained fit Xi = Q beta (+ const) on the support ``mask`` (d, p) from the augmented Gram G: the
+    constrained branch of ``solve_SINDy_one_step`` (sindy.py:270-311) restated without a regressor.  ``coef``: the CoefMap
+    that holds Q.  ``driver``: 'gels' / 'gelsy' as ``lstsq_normal`` takes them, or 'min_norm' -- the rule of
+    ``lstsq._singular_fallback`` on every pass, ``lstsq_normal(Gq, cq, m_rows, 'gelsy', SINGULAR_RCOND)``: what a problem the
+    device fit flagged as possibly rank deficient is solved with.
+    Returns (Xi (d, p) float32 as get_Xi gives it, unmasked; the variables [beta | const] (r',) float64; residual)."""
+    from .lstsq import SINGULAR_RCOND
+    p = G.shape[0] - d
+    Gtt = G[:p, :p] + (gamma * gamma) * np.eye(p)
+    Gty = G[:p, p:]
+    yy = np.trace(G[p:, p:])
+    flat = np.asarray(mask, dtype=bool).reshape(-1)
+    Gb = np.zeros((d * p, d * p))
+    for j in range(d):
+        Gb[j * p:(j + 1) * p, j * p:(j + 1) * p] = Gtt
+    cb = Gty.T.reshape(-1)
+    Gm, cm = Gb[flat][:, flat], cb[flat]
+    m_rows = d * (N + p)
+    Q = coef.solve_matrix()
+    Qm = Q[flat]
+    effective = np.any(Qm != 0.0, axis=0)
+    Qe = Qm[:, effective]
+    Gq, cq = Qe.T @ Gm @ Qe, Qe.T @ cm
+    if not effective.any():                         # an empty support: nothing to solve, Xi = 0
+        b = np.zeros(0)
+    elif driver == 'min_norm':
+        b, _ = lstsq_normal(Gq, cq, m_rows, 'gelsy', SINGULAR_RCOND)
+    else:
+        b, _ = lstsq_normal(Gq, cq, m_rows, driver)
+    full = np.zeros(Q.shape[1])
+    full[effective] = b
+    beta_h = (full[:-d] if coef.allow_constant else full).astype(np.float32)
+    xi = coef.xi(beta_h, full[-d:].astype(np.float32))
+    return xi, full, yy - 2 * b @ cq + b @ Gq @ b
+
+
 def _mask_on_host(regressor):
     """Boolean host copy of the mask without a device round trip when the mask on the device is still the tensor this
     module uploaded last (the mirror keeps that tensor alive, so an equal address means the same storage; in-place

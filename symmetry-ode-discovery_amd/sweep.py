@@ -19,7 +19,8 @@ import torch.distributed as dist
 from .coef_map import CoefMap
 from .engine import LBFGS_ACCEPT, LBFGS_BEGIN, get_engine, library_flags
 from . import lstsq as _lstsq
-from .sindy import NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_solve_from_gram, weak_test_functions
+from .sindy import (NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_constrained_from_gram, stlsq_solve_from_gram,
+                    weak_test_functions)
 
 
 def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
@@ -50,12 +51,16 @@ class _DeviceSTLSQ:
 
     _fetch_with_fit = None                 # an int32 device tensor to bring back in the fit's one copy (SeedSweepWSINDy)
 
-    def _replay(self, s, G_s, w_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes):
-        """Problem s again in numpy, pass by pass from the full mask, for the detailed near-threshold record."""
+    def _replay(self, s, G_s, w_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes, coef=None):
+        """Problem s again in numpy, pass by pass from the full mask, for the detailed near-threshold record.  ``coef`` (a
+        CoefMap with Q): the constrained fit's pass (sindy.stlsq_constrained_from_gram), whose drivers ``lstsq_driver`` names."""
         mask[s] = True
         for it in range(max_iter):
-            xi, _ = stlsq_solve_from_gram(G_s, self.n_points, mask[s], float(w_reg), self.d, lstsq_driver)
-            xi32 = xi.astype(np.float32)
+            if coef is not None:
+                xi32 = stlsq_constrained_from_gram(G_s, self.n_points, mask[s], float(w_reg), self.d, coef, lstsq_driver)[0]
+            else:
+                xi, _ = stlsq_solve_from_gram(G_s, self.n_points, mask[s], float(w_reg), self.d, lstsq_driver)
+                xi32 = xi.astype(np.float32)
             self.near_threshold += [(s, it, i, k, v) for i, k, v in near_threshold_cases(xi32, mask[s], threshold)]
             new_mask = np.logical_and(np.abs(xi32) > np.float32(threshold), mask[s])   # strict >, monotone (sindy.py:194)
             converged = np.array_equal(new_mask, mask[s])
@@ -63,12 +68,15 @@ class _DeviceSTLSQ:
             if converged:
                 break
 
-    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper):
+    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper, coef=None):
         """``solve(device=True)``: one symode_stlsq_sweep launch on the matrices where the gather launch left them; only
         Xi, mask, passes, near and fell come back.  The launch takes ridge weight and threshold in fp32, as its per-problem
         table holds them, with or without a table -- so problem (g, k) of a grid is bit for bit seed k of the scalar device
         solve with point g's values -- and what is replayed or solved on the host here uses the same rounded values.
-        Every rank holds the same all-reduced matrices and takes the same decisions."""
+        Every rank holds the same all-reduced matrices and takes the same decisions.
+        ``coef`` (a CoefMap with Q): the launch is symode_stlsq_sweep_constrained, the fit under Xi = Q beta (+ const); a
+        problem it flags (a pivot under SINGULAR_RCOND^2 of the first: possibly rank deficient) is solved by the host loop
+        with the minimum-norm rule on every pass."""
         S, d, p = self.S, self.d, self.p
         f32 = lambda v: float(np.float32(v))                                   # noqa: E731
         n_problems = S
@@ -89,9 +97,15 @@ class _DeviceSTLSQ:
         table = None
         if hyper is not None:
             table = torch.from_numpy(np.stack([w, thr], axis=1).astype(np.float32)).to(G.device)
-        Xi, m8, p32, near, fell, *flags = self.engine.stlsq_sweep(G, self.n_points, w[0], thr[0], max_iter, hyper=table, d=d,
-                                                                  near_band=NEAR_THRESHOLD_BAND, to_host=True,    # one copy back
-                                                                  tail=self._fetch_with_fit)
+        if coef is not None:
+            q_solve, q_xi = (torch.from_numpy(q).to(G.device) for q in (coef.solve_matrix(), coef.xi_matrix()))
+            Xi, m8, p32, near, fell, _, *flags = self.engine.stlsq_sweep_constrained(
+                G, self.n_points, w[0], thr[0], max_iter, q_solve, q_xi, coef.allow_constant, hyper=table, d=d,
+                pivot_floor=_lstsq.SINGULAR_RCOND ** 2, near_band=NEAR_THRESHOLD_BAND, to_host=True, tail=self._fetch_with_fit)
+        else:
+            Xi, m8, p32, near, fell, *flags = self.engine.stlsq_sweep(G, self.n_points, w[0], thr[0], max_iter, hyper=table, d=d,
+                                                                      near_band=NEAR_THRESHOLD_BAND, to_host=True,    # one copy back
+                                                                      tail=self._fetch_with_fit)
         if flags:
             self._fetched(flags[0])
         Xi, mask, passes = np.array(Xi), np.asarray(m8).astype(bool), np.asarray(p32).astype(np.int64)
@@ -105,7 +119,15 @@ class _DeviceSTLSQ:
                 held[k] = G[k].cpu().numpy()
             return held[k]
 
-        if fell.any():
+        if fell.any() and coef is not None:
+            # possibly rank deficient: the host loop from the full mask, the minimum-norm rule on every pass
+            import warnings
+            for s in np.nonzero(fell)[0].tolist():
+                self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm', Xi, mask, passes, coef)
+                near[s] = 0                                              # (its near-threshold record is the loop's)
+            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
+                          RuntimeWarning)
+        elif fell.any():
             # a pivot that was not positive: these problems are the host loop's, rank-revealing fallback and warning included
             import warnings
             lib = _lstsq._native()
@@ -122,7 +144,7 @@ class _DeviceSTLSQ:
             warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
                           RuntimeWarning)
         for s in np.nonzero(near)[0].tolist():
-            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'gels', Xi, mask, passes)
+            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'gels', Xi, mask, passes, coef)
         return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
 
 
@@ -179,13 +201,18 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
             self._gram = self._gram_dev.cpu().numpy()
         return self._gram
 
-    def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None):
+    def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None, coef=None):
         """STLSQ to convergence for every seed (train.py:872-887 per seed).
         Returns (Xi (S, d, p) float32, mask (S, d, p) float32, passes (S,)).
         ``device=True``: the fit runs on the device (``_solve_device``; the full-rank driver only), the host route stays the
         default.  ``hyper={"w_reg": [...], "threshold": [...]}`` (with ``device=True``): one value per PROBLEM, n_problems = G x S
         for a grid of G points on the S seeds' shared matrices, problem s on seed s % S; the arrays returned are then
-        (G S, d, p) and (G S,), and a column left out takes the scalar argument."""
+        (G S, d, p) and (G S,), and a column left out takes the scalar argument.
+        ``coef`` (a CoefMap with Q): the fit under the equivariance constraint Xi = Q beta (+ const), EquivSINDy-c
+        (solve_SINDy_one_step's constrained branch per seed); Xi is then ``get_Xi`` of the last solve, unmasked.  On the host
+        it is the numpy loop (sindy.stlsq_constrained_from_gram) with the driver given; ``device=True`` as above."""
+        if coef is not None and coef.Q is None:
+            coef = None                                    # a map without Q: the variables are Xi, the unconstrained fit
         if hyper is not None and not device:
             raise ValueError('hyper (a per-problem table of w_reg / threshold) needs device=True: the host route takes one value each')
         if lstsq_driver is None:                   # torch.linalg.lstsq's default on the device the data lives on (sindy.py)
@@ -194,7 +221,7 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
             if lstsq_driver != 'gels':
                 raise ValueError(f"device=True fits with the full-rank driver (gels) only, not lstsq_driver='{lstsq_driver}': the "
                                  'rank rule of gelsy runs on the host route')
-            return self._solve_device(w_sindy_reg, threshold, max(1, int(max_iter)), hyper)
+            return self._solve_device(w_sindy_reg, threshold, max(1, int(max_iter)), hyper, coef)
         G = self.grams()
         S, d, p = self.S, self.d, self.p
         Xi = np.zeros((S, d, p), dtype=np.float32)
@@ -203,7 +230,7 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         self.near_threshold = []              # (seed index, pass, row, col, |coef|): BASELINE.md section 3
         todo = range(S)
         lib = _lstsq._native() if os.environ.get('SYMODE_STLSQ_NATIVE', '1') != '0' else None
-        if lib and lstsq_driver in ('gels', 'gelsy'):
+        if lib and lstsq_driver in ('gels', 'gelsy') and coef is None:
             # the whole loop below for all seeds in ONE native call (host_lstsq.cpp::symode_host_stlsq_sweep: same solver, same
             # inputs, same arithmetic); seeds that met a near-threshold coefficient are replayed here for the detailed record
             Gc = np.ascontiguousarray(G, dtype=np.float64)
@@ -221,7 +248,7 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
             mask, passes = m8.astype(bool), p32.astype(np.int64)
             todo = [int(s) for s in np.nonzero(near)[0]]
         for s in todo:
-            self._replay(s, G[s], w_sindy_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes)
+            self._replay(s, G[s], w_sindy_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes, coef)
         return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
 
 
