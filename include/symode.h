@@ -856,6 +856,33 @@ int symode_stlsq_sweep_constrained(const double* aug_gram, long n_sets, long n_p
                                    float* xi_out, float* var_out, unsigned char* mask_out, int* passes_out, int* near_out,
                                    int* fell_out, void* stream);
 
+/* symode_stlsq_sweep_constrained in its rank-revealing mode: every argument it shares with that entry means what it means
+ * there, and a pass builds the same Gq, cq (same order of sums, exactly symmetric).  The solve of a pass is
+ * symode_host_lstsq_normal's driver 0 with the rcond given here -- what the caller's host replay of a flagged problem performs
+ * on every pass (lstsq_normal(Gq, cq, m, 'gelsy', SINGULAR_RCOND)) -- so problems whose support leaves Q's columns collinear
+ * finish inside the one launch:
+ *   the pivoted Cholesky with the fused forward substitution WITHOUT a pivot floor: a pivot that is not > 0 ends the
+ *   factorisation, the remaining rows of R are zero (csrc/host_lstsq.cpp:55);
+ *   the rank by xGELSY's loop over xLAIC1 estimates (csrc/host_lstsq.cpp:67-84, csrc/laic1.hpp -- one statement of xLAIC1 for
+ *   host and device): position `rank` of the pivot order is accepted while smaxpr * rcond <= sminpr; rcond is the cut on the
+ *   TRIANGULAR factor (the sweep passes lstsq.SINGULAR_RCOND = 1e-7);
+ *   rank == n: the back substitution of symode_stlsq_sweep_constrained, identical arithmetic; rank == 0: the zero solution;
+ *   0 < rank < n: the minimum-norm solution Y = Wm^T (Wm Wm^T)^-1 q, Wm = R[:rank, :], q the first `rank` entries of the forward
+ *   substitution, in the host's order of operations (csrc/host_lstsq.cpp:102-132).
+ * trunc_out (n_problems) ints: the passes of problem s solved with rank < n; rank_out (n_problems) ints: the rank of its last
+ * pass's system (0 on an empty support).  fell_out[s] = 1 only when a diagonal of Wm Wm^T's Cholesky factor is not > 0; the
+ * problem ENDS there (its other outputs are then unspecified) and stays the host's.
+ * Refused before any GPU work: everything symode_stlsq_sweep_constrained refuses, with rcond in place of pivot_floor: rcond not
+ * finite or outside (0, 1) (SYMODE_E_BADSIZE); trunc_out or rank_out NULL (SYMODE_E_NULLPTR) or not 4-byte aligned
+ * (SYMODE_E_ALIGN).
+ * replaces: train.py:872-887 over sindy.py:250-315, constrained branch (regressor.constraint), with torch.linalg.lstsq's
+ * rank-revealing answer where the full-rank driver meets a singular system. */
+int symode_stlsq_sweep_minnorm(const double* aug_gram, long n_sets, long n_problems, int d, int p, long n_points,
+                               const double* q_solve, const float* q_xi, int r, int allow_constant, const float* hyper,
+                               double gamma, double threshold, int max_iter, double near_band, double rcond, float* xi_out,
+                               float* var_out, unsigned char* mask_out, int* passes_out, int* near_out, int* fell_out,
+                               int* trunc_out, int* rank_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -545,6 +545,30 @@ int symode_stlsq_sweep_constrained(const double* aug_gram, long n_sets, long n_p
                                          near_out, fell_out, (hipStream_t)stream);
 }
 
+int symode_stlsq_sweep_minnorm(const double* aug_gram, long n_sets, long n_problems, int d, int p, long n_points,
+                               const double* q_solve, const float* q_xi, int r, int allow_constant, const float* hyper, double gamma,
+                               double threshold, int max_iter, double near_band, double rcond, float* xi_out, float* var_out,
+                               unsigned char* mask_out, int* passes_out, int* near_out, int* fell_out, int* trunc_out, int* rank_out,
+                               void* stream) {
+    (void)n_points;                     // as symode_stlsq_sweep: only gelsy's DEFAULT rank rule would read it
+    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || r < 1 || max_iter < 1) return SYMODE_E_BADSIZE;
+    const long rr = (long)r + (allow_constant ? d : 0);
+    if (rr > STLSQC_MAX_R || rr > (long)d * p) return SYMODE_E_BADSIZE;
+    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
+    if (!hyper && n_problems != n_sets) return SYMODE_E_BADSIZE;
+    if (!std::isfinite(rcond) || !(rcond > 0.0) || !(rcond < 1.0)) return SYMODE_E_BADSIZE;
+    if (!aug_gram || !q_solve || !q_xi || !xi_out || !var_out || !mask_out || !passes_out || !near_out || !fell_out || !trunc_out ||
+        !rank_out)
+        return SYMODE_E_NULLPTR;
+    if (misaligned(aug_gram, 8) || misaligned(q_solve, 8) || misaligned(q_xi, 4) || misaligned(hyper, 4) || misaligned(xi_out, 4) ||
+        misaligned(var_out, 4) || misaligned(passes_out, 4) || misaligned(near_out, 4) || misaligned(fell_out, 4) ||
+        misaligned(trunc_out, 4) || misaligned(rank_out, 4))
+        return SYMODE_E_ALIGN;
+    return (int)launch_stlsq_minnorm(aug_gram, n_sets, n_problems, d, p, q_solve, q_xi, r, allow_constant ? 1 : 0, hyper, gamma,
+                                     threshold, max_iter, near_band, rcond, xi_out, var_out, mask_out, passes_out, near_out, fell_out,
+                                     trunc_out, rank_out, (hipStream_t)stream);
+}
+
 int symode_symreg_reversed(const float* x, const float* gx_, const float* jgx, int n_g, long n, int d, int order,
                            int flags, const float* xi, const float* mask, float* loss_out, float* grad_out,
                            void* workspace, size_t workspace_bytes, void* stream) {

@@ -10,83 +10,17 @@
 #include <vector>
 
 #include "../../include/symode.h"
+#include "laic1.hpp"
 
 namespace {
 
-const double EPS = std::numeric_limits<double>::epsilon();
-inline double sgn(double a) { return a >= 0 ? 1.0 : -1.0; }
-
-// one step of incremental condition estimation (LAPACK xLAIC1, real case)
+// one step of incremental condition estimation (LAPACK xLAIC1, real case): alpha = x^T w here, the rest in laic1.hpp,
+// which the device sweep shares
 void laic1(int job, const std::vector<double>& x, double sest, const double* w, int j, double gamma, double& sestpr,
            double& s, double& c) {
     double alpha = 0;
     for (int i = 0; i < j; ++i) alpha += x[i] * w[i];
-    const double absalp = std::fabs(alpha), absgam = std::fabs(gamma), absest = std::fabs(sest);
-    if (job == 1) {
-        if (sest == 0.0) {
-            const double s1 = std::max(absgam, absalp);
-            if (s1 == 0.0) { s = 0; c = 1; sestpr = 0; return; }
-            s = alpha / s1; c = gamma / s1;
-            const double t = std::sqrt(s * s + c * c);
-            s /= t; c /= t; sestpr = s1 * t; return;
-        }
-        if (absgam <= EPS * absest) {
-            const double t = std::max(absest, absalp), s1 = absest / t, s2 = absalp / t;
-            s = 1; c = 0; sestpr = t * std::sqrt(s1 * s1 + s2 * s2); return;
-        }
-        if (absalp <= EPS * absest) {
-            if (absgam <= absest) { s = 1; c = 0; sestpr = absest; } else { s = 0; c = 1; sestpr = absgam; }
-            return;
-        }
-        if (absest <= EPS * absalp || absest <= EPS * absgam) {
-            const double s1 = absgam, s2 = absalp;
-            if (s1 <= s2) { const double t = s1 / s2; const double q = std::sqrt(1 + t * t); sestpr = s2 * q; c = (gamma / s2) / q; s = sgn(alpha) / q; }
-            else { const double t = s2 / s1; const double q = std::sqrt(1 + t * t); sestpr = s1 * q; s = (alpha / s1) / q; c = sgn(gamma) / q; }
-            return;
-        }
-        const double z1 = alpha / absest, z2 = gamma / absest;
-        const double b = (1.0 - z1 * z1 - z2 * z2) * 0.5, cc = z1 * z1;
-        const double t = b > 0 ? cc / (b + std::sqrt(b * b + cc)) : std::sqrt(b * b + cc) - b;
-        const double sine = -z1 / t, cosine = -z2 / (1.0 + t), nrm = std::sqrt(sine * sine + cosine * cosine);
-        s = sine / nrm; c = cosine / nrm; sestpr = std::sqrt(t + 1.0) * absest; return;
-    }
-    if (sest == 0.0) {
-        sestpr = 0;
-        double sine, cosine;
-        if (std::max(absgam, absalp) == 0.0) { sine = 1; cosine = 0; } else { sine = -gamma; cosine = alpha; }
-        const double s1 = std::max(std::fabs(sine), std::fabs(cosine));
-        s = sine / s1; c = cosine / s1;
-        const double t = std::sqrt(s * s + c * c);
-        s /= t; c /= t; return;
-    }
-    if (absgam <= EPS * absest) { s = 0; c = 1; sestpr = absgam; return; }
-    if (absalp <= EPS * absest) {
-        if (absgam <= absest) { s = 0; c = 1; sestpr = absgam; } else { s = 1; c = 0; sestpr = absest; }
-        return;
-    }
-    if (absest <= EPS * absalp || absest <= EPS * absgam) {
-        const double s1 = absgam, s2 = absalp;
-        if (s1 <= s2) { const double t = s1 / s2; const double q = std::sqrt(1 + t * t); sestpr = absest * (t / q); s = -(gamma / s2) / q; c = sgn(alpha) / q; }
-        else { const double t = s2 / s1; const double q = std::sqrt(1 + t * t); sestpr = absest / q; c = (alpha / s1) / q; s = -sgn(gamma) / q; }
-        return;
-    }
-    const double z1 = alpha / absest, z2 = gamma / absest;
-    const double norma = std::max(1.0 + z1 * z1 + std::fabs(z1 * z2), std::fabs(z1 * z2) + z2 * z2);
-    const double test = 1.0 + 2.0 * (z1 - z2) * (z1 + z2);
-    double sine, cosine;
-    if (test >= 0) {
-        const double b = (z1 * z1 + z2 * z2 + 1.0) * 0.5, cc = z2 * z2;
-        const double t = cc / (b + std::sqrt(std::fabs(b * b - cc)));
-        sine = z1 / (1.0 - t); cosine = -z2 / t;
-        sestpr = std::sqrt(t + 4.0 * EPS * EPS * norma) * absest;
-    } else {
-        const double b = (z2 * z2 + z1 * z1 - 1.0) * 0.5, cc = z1 * z1;
-        const double t = b >= 0 ? -cc / (b + std::sqrt(b * b + cc)) : b - std::sqrt(b * b + cc);
-        sine = -z1 / t; cosine = -z2 / (1.0 + t);
-        sestpr = std::sqrt(1.0 + t + 4.0 * EPS * EPS * norma) * absest;
-    }
-    const double nrm = std::sqrt(sine * sine + cosine * cosine);
-    s = sine / nrm; c = cosine / nrm;
+    symode::laic1(job, alpha, sest, gamma, sestpr, s, c);
 }
 
 }  // namespace

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "laic1.hpp"
 #include "stlsq.hpp"
 
 namespace symode {
@@ -16,6 +17,10 @@ constexpr int STLSQC_MAX_R = WAVE;     // free parameters r' = r + (allow_consta
 inline size_t stlsqc_lds_bytes(int R) {
     return (size_t)R * R * sizeof(double) + STLSQ_MAX_D * sizeof(unsigned long long) + (size_t)R * (sizeof(int) + sizeof(float));
 }
+
+// ... of the rank-revealing mode (MINNORM): a second r' x r' fp64 array behind Gq, for Wm Wm^T and its factor.  64.5 KiB at
+// r' = 64 -- above the 64 KiB a launch gets by default, so the launcher raises the kernel's limit.
+inline size_t stlsqc_minnorm_lds_bytes(int R) { return stlsqc_lds_bytes(R) + (size_t)R * R * sizeof(double); }
 
 // One workgroup of ONE wave per problem.  The constraint couples the equation rows into one joint system of n <= r' <= 64
 // unknowns, so the factorisation -- one lane per position of the pivot order -- is a single wave's work whatever d is, and
@@ -40,7 +45,26 @@ inline size_t stlsqc_lds_bytes(int R) {
 //   threshold the host's rule on the still-active entries, near counted on them; stop when the mask repeats.
 // No multiply-add is contracted (-ffp-contract=off).  Every LDS and global index is bounded by d, p, r': no address
 // depends on data.  HYPER, n_sets: as stlsq_sweep_kernel.
-template <bool HYPER>
+//
+// MINNORM (symode_stlsq_sweep_minnorm; a template bit, so the two instantiations above keep their code): the solve of a
+// pass is symode_host_lstsq_normal's driver 0 with the launch's rcond (`cut`), i.e. what the host replay of a flagged problem
+// performs (lstsq_normal(Gq, cq, m, 'gelsy', SINGULAR_RCOND)), so a problem with collinear columns ends inside the launch:
+//   factor    as above without the pivot floor: a pivot that is not > 0 ends the factorisation at fact = kk, the remaining
+//             rows of R are zero (host_lstsq.cpp:55);
+//   rank      xGELSY's loop over xLAIC1 estimates (host_lstsq.cpp:67-84, laic1.hpp): xmin and xmax hold one element per
+//             lane, indexed by position in the pivot order; alpha is summed in ascending position order through stlsq_lane,
+//             so it is the host's sum; sest, s, c and every branch are wave-uniform (the decision goes through an SGPR);
+//             position `rank` is accepted while smaxpr * cut <= sminpr;
+//   rank == n today's back substitution; rank == 0: Y = 0;
+//   else      Y = Wm^T (Wm Wm^T)^-1 q, Wm = R[:rank, :], q the first `rank` entries of the forward substitution, in the
+//             host's order (host_lstsq.cpp:102-132): M[a, b] = sum over positions t ascending of R(a, t) R(b, t) (from
+//             t = a: the terms before it are exact zeros), lane b the owner of column b; the Cholesky factor of M column
+//             by column, lane a the owner of row a, per entry the subtractions in ascending t; the two substitutions with
+//             the products formed across the lanes and subtracted in the host's order; Y[t] = sum over a ascending of
+//             R(a, t) z[a].  A diagonal of M's factor that is not > 0 sets fell and ends the problem: it stays the host's.
+// trunc_out: the passes solved with rank < n; rank_out: the rank of the last pass's system (0 on an empty support).  Both are
+// read by MINNORM only (NULL otherwise).  Resources of the two MINNORM instantiations: profiles/stlsq_minnorm.txt.
+template <bool HYPER, bool MINNORM = false>
 __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* __restrict__ aug, int n_sets, int d, int p,
                                                                  const double* __restrict__ q_solve,
                                                                  const float* __restrict__ q_xi, int r, int allow_constant,
@@ -49,14 +73,17 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
                                                                  float* __restrict__ xi_out, float* __restrict__ var_out,
                                                                  unsigned char* __restrict__ mask_out,
                                                                  int* __restrict__ passes_out, int* __restrict__ near_out,
-                                                                 int* __restrict__ fell_out) {
+                                                                 int* __restrict__ fell_out, int* __restrict__ trunc_out,
+                                                                 int* __restrict__ rank_out) {
     extern __shared__ double stlsqc_smem[];
     const int lane = threadIdx.x;
     const long s = blockIdx.x;
     const int F = p + d;
     const int R = r + (allow_constant ? d : 0);
     double* A = stlsqc_smem;
-    unsigned long long* M = (unsigned long long*)(A + (size_t)R * R);
+    double* W = A + (size_t)R * R;                     // MINNORM: Wm Wm^T, then its factor
+    unsigned long long* M = (unsigned long long*)(A + (size_t)(MINNORM ? 2 : 1) * R * R);
+    const double cut = pivot_floor;                    // MINNORM: the launch's rcond travels in this argument
     int* col = (int*)(M + STLSQ_MAX_D);
     float* var = (float*)(col + R);
     if constexpr (HYPER) {
@@ -69,6 +96,7 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
     if (lane < STLSQ_MAX_D) M[lane] = lane < d ? (p == 64 ? ~0ull : (1ull << p) - 1ull) : 0ull;
     stlsq_wave_sync();
     int near = 0, passes = 0, fell = 0;
+    int trunc = 0, rank = 0;
     for (int it = 0; it < max_iter; ++it) {
         // ---- effective columns
         bool eff = false;
@@ -85,6 +113,7 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
         if (lane < R) var[lane] = 0.0f;
         stlsq_wave_sync();
         bool bad = false;
+        if constexpr (MINNORM) rank = 0;
         if (n > 0) {
             const bool on = lane < n;
             const int cb = on ? col[lane] : 0;
@@ -118,6 +147,7 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
             int orig = lane;
             double dg = on ? A[lane * R + lane] : 0.0;
             double first = 0.0;
+            int fact = n;
             for (int kk = 0; kk < n; ++kk) {
                 double bv = dg;
                 int bi = (lane >= kk && lane < n) ? lane : WAVE;
@@ -138,10 +168,17 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
                     c = __shfl(c, src, WAVE);
                 }
                 const double dkk = stlsq_lane(dg, kk);
-                if (kk == 0) first = dkk;
-                if (!(dkk > pivot_floor * first) || !(dkk > 0.0)) {
-                    bad = true;
-                    break;
+                if constexpr (MINNORM) {
+                    if (!(dkk > 0.0)) {
+                        fact = kk;
+                        break;
+                    }
+                } else {
+                    if (kk == 0) first = dkk;
+                    if (!(dkk > pivot_floor * first) || !(dkk > 0.0)) {
+                        bad = true;
+                        break;
+                    }
                 }
                 const double rr = sqrt(dkk);
                 const int jo = __builtin_amdgcn_readlane(orig, kk);
@@ -165,8 +202,101 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
                 if (lane == kk) c = q;
                 stlsq_wave_sync();
             }
+            if constexpr (MINNORM) {
+                // ---- rank: lane i holds element i of the two approximate singular vectors
+                stlsq_wave_sync();
+                if (fact > 0) {
+                    const int o0 = __builtin_amdgcn_readlane(orig, 0);
+                    double smax = fabs(A[o0 * R + o0]), smin = smax;
+                    double xmin = lane == 0 ? 1.0 : 0.0, xmax = xmin;
+                    rank = 1;
+                    while (rank < n) {
+                        const int jr = __builtin_amdgcn_readlane(orig, rank);
+                        const double w = lane < rank ? A[orig * R + jr] : 0.0;
+                        const double gam = rank < fact ? A[jr * R + jr] : 0.0;
+                        const double pmin = xmin * w, pmax = xmax * w;
+                        double amin = 0.0, amax = 0.0;
+                        for (int i = 0; i < rank; ++i) {
+                            amin += stlsq_lane(pmin, i);
+                            amax += stlsq_lane(pmax, i);
+                        }
+                        double sminpr, s1, c1, smaxpr, s2, c2;
+                        laic1(2, amin, smin, gam, sminpr, s1, c1);
+                        laic1(1, amax, smax, gam, smaxpr, s2, c2);
+                        if (!__builtin_amdgcn_readfirstlane((int)(smaxpr * cut <= sminpr))) break;
+                        if (lane < rank) {
+                            xmin *= s1;
+                            xmax *= s2;
+                        }
+                        if (lane == rank) {
+                            xmin = c1;
+                            xmax = c2;
+                        }
+                        smin = sminpr;
+                        smax = smaxpr;
+                        ++rank;
+                    }
+                }
+                if (rank < n) ++trunc;
+                if (rank > 0 && rank < n) {
+                    // ---- minimum norm: M = Wm Wm^T, lane b the owner of column b
+                    const bool in = lane < rank;
+                    for (int a = 0; a < rank; ++a) {
+                        const int oa = __builtin_amdgcn_readlane(orig, a);
+                        double acc = 0.0;
+                        for (int t = a; t < n; ++t) {
+                            const int ot = __builtin_amdgcn_readlane(orig, t);
+                            const double rb = (in && lane <= t) ? A[orig * R + ot] : 0.0;
+                            acc += A[oa * R + ot] * rb;
+                        }
+                        if (in) W[a * R + lane] = acc;
+                    }
+                    stlsq_wave_sync();
+                    // ---- its factor in place, column by column, lane a the owner of row a
+                    for (int b = 0; b < rank; ++b) {
+                        double acc = 0.0;
+                        if (in && lane >= b) {
+                            acc = W[lane * R + b];
+                            for (int t = 0; t < b; ++t) acc -= W[lane * R + t] * W[b * R + t];
+                        }
+                        const double dbb = stlsq_lane(acc, b);
+                        if (!(dbb > 0.0)) {
+                            bad = true;
+                            break;
+                        }
+                        const double lbb = sqrt(dbb);
+                        if (in && lane >= b) W[lane * R + b] = lane == b ? lbb : acc / lbb;
+                        stlsq_wave_sync();
+                    }
+                    if (!bad) {
+                        for (int i = 0; i < rank; ++i) {                  // Lc z' = q
+                            const double prod = lane < i ? W[i * R + lane] * c : 0.0;
+                            double acc = stlsq_lane(c, i);
+                            for (int t = 0; t < i; ++t) acc -= stlsq_lane(prod, t);
+                            const double y = acc / W[i * R + i];
+                            if (lane == i) c = y;
+                        }
+                        for (int i = rank - 1; i >= 0; --i) {             // Lc^T z = z'
+                            const double prod = (lane > i && in) ? W[lane * R + i] * c : 0.0;
+                            double acc = stlsq_lane(c, i);
+                            for (int t = i + 1; t < rank; ++t) acc -= stlsq_lane(prod, t);
+                            const double y = acc / W[i * R + i];
+                            if (lane == i) c = y;
+                        }
+                        double y = 0.0;                                   // Y = Wm^T z
+                        for (int a = 0; a < rank; ++a) {
+                            const int oa = __builtin_amdgcn_readlane(orig, a);
+                            const double ra = (on && a <= lane) ? A[oa * R + orig] : 0.0;
+                            y += ra * stlsq_lane(c, a);
+                        }
+                        c = y;
+                    }
+                } else if (rank == 0) {
+                    c = 0.0;
+                }
+            }
             if (!bad) {
-                for (int i = n - 1; i >= 0; --i) {
+                for (int i = (!MINNORM || rank == n) ? n - 1 : -1; i >= 0; --i) {
                     const int jo = __builtin_amdgcn_readlane(orig, i);
                     const double prod = (lane > i && lane < n) ? A[jo * R + orig] * c : 0.0;
                     double acc = stlsq_lane(c, i);
@@ -212,6 +342,10 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
         passes_out[s] = passes;
         near_out[s] = near;
         fell_out[s] = fell;
+        if constexpr (MINNORM) {
+            trunc_out[s] = trunc;
+            rank_out[s] = rank;
+        }
     }
 }
 
@@ -225,7 +359,27 @@ inline hipError_t launch_stlsq_constrained(const double* aug, long n_sets, long 
     kernel<<<dim3((unsigned)n_problems), dim3(WAVE), stlsqc_lds_bytes(R), st>>>(aug, (int)n_sets, d, p, q_solve, q_xi, r,
                                                                                 allow_constant, hyper, gamma, threshold, max_iter,
                                                                                 near_band, pivot_floor, xi_out, var_out, mask_out,
-                                                                                passes_out, near_out, fell_out);
+                                                                                passes_out, near_out, fell_out, nullptr, nullptr);
+    SYMODE_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+// The rank-revealing mode: rcond in place of the pivot floor, two more outputs per problem.
+inline hipError_t launch_stlsq_minnorm(const double* aug, long n_sets, long n_problems, int d, int p, const double* q_solve,
+                                       const float* q_xi, int r, int allow_constant, const float* hyper, double gamma,
+                                       double threshold, int max_iter, double near_band, double rcond, float* xi_out, float* var_out,
+                                       unsigned char* mask_out, int* passes_out, int* near_out, int* fell_out, int* trunc_out,
+                                       int* rank_out, hipStream_t st) {
+    const int R = r + (allow_constant ? d : 0);
+    const size_t lds = stlsqc_minnorm_lds_bytes(R);
+    auto kernel = hyper ? stlsq_constrained_kernel<true, true> : stlsq_constrained_kernel<false, true>;
+    if (lds > 64 * 1024) {                 // beyond the default limit of a launch: gfx950 has 160 KB per workgroup
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    kernel<<<dim3((unsigned)n_problems), dim3(WAVE), lds, st>>>(aug, (int)n_sets, d, p, q_solve, q_xi, r, allow_constant, hyper,
+                                                                gamma, threshold, max_iter, near_band, rcond, xi_out, var_out,
+                                                                mask_out, passes_out, near_out, fell_out, trunc_out, rank_out);
     SYMODE_LAUNCH_CHECK();
     return hipSuccess;
 }

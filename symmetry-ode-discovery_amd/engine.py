@@ -139,6 +139,9 @@ _SIGNATURES = {
     "symode_stlsq_sweep_constrained": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_long, c_void_p, c_void_p, c_int, c_int,
                                                c_void_p, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "symode_stlsq_sweep_minnorm": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_long, c_void_p, c_void_p, c_int, c_int,
+                                           c_void_p, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
@@ -999,6 +1002,65 @@ class HipEngine:
             self._ptr(hyper), float(gamma), float(threshold), int(max_iter), float(near_band), float(pivot_floor), self._ptr(xi),
             self._ptr(var), self._ptr(mask), self._ptr(passes), self._ptr(near), self._ptr(fell), self._stream(G)),
             "symode_stlsq_sweep_constrained")
+        if to_host:
+            import numpy as np
+            return parts(buf.cpu().numpy(), np.float32, np.int32)
+        return parts(buf, torch.float32, torch.int32)
+
+    def stlsq_sweep_minnorm(self, G, n_points, gamma, threshold, max_iter, q_solve, q_xi, allow_constant, hyper=None,
+                            n_problems=None, *, d, rcond, near_band=1e-4, to_host=False, tail=None):
+        """``stlsq_sweep_constrained`` in its rank-revealing mode, ONE launch (symode_stlsq_sweep_minnorm): every pass is solved
+        as ``lstsq_normal(Gq, cq, m, 'gelsy', rcond)`` solves it on the host -- pivoted Cholesky without a pivot floor, the rank
+        by xGELSY's loop over xLAIC1 estimates with ``rcond`` (the cut on the triangular factor), the minimum-norm solution
+        where the rank is short -- so a problem whose support leaves Q's columns collinear ends inside the launch.  The other
+        arguments as ``stlsq_sweep_constrained``.
+        Returns (Xi, mask, passes, near, fell, var, trunc, rank) and, behind them, the tail: ``trunc`` (n_problems,) int32 the
+        passes solved with rank < n, ``rank`` the rank of the last pass's system; ``fell`` is set only where the factor of
+        Wm Wm^T met a diagonal that is not positive (the host's to solve)."""
+        G = self._dev(G, "G", torch.float64)
+        d = int(d)
+        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
+            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
+        n_sets, p = G.shape[0], G.shape[1] - d
+        q_solve, q_xi = self._dev(q_solve, "q_solve", torch.float64), self._dev(q_xi, "q_xi")
+        if q_xi.dim() != 2 or q_xi.shape[0] != d * p or q_xi.device != G.device:
+            raise SymodeError(f"q_xi must be (d p, r) = ({d * p}, r) fp32 on {G.device}, got {tuple(q_xi.shape)}")
+        r = q_xi.shape[1]
+        R = r + (d if allow_constant else 0)
+        if tuple(q_solve.shape) != (d * p, R) or q_solve.device != G.device:
+            raise SymodeError(f"q_solve must be (d p, r') = ({d * p}, {R}) fp64 on {G.device}, got {tuple(q_solve.shape)}")
+        if hyper is not None:
+            hyper = self._dev(hyper, "hyper")
+            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_HYPER or hyper.device != G.device:
+                raise SymodeError(f"hyper must be (n_problems, {STLSQ_HYPER}) fp32 on {G.device}: one row [gamma, threshold] per problem")
+            if n_problems is not None and int(n_problems) != hyper.shape[0]:
+                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
+            n_problems = hyper.shape[0]
+        S = n_sets if n_problems is None else int(n_problems)
+        # one allocation, [xi | var | passes | near | fell | trunc | rank | mask]: a caller on the host fetches everything in ONE copy
+        cuts = [0, 4 * S * d * p]
+        for width in (R, 1, 1, 1, 1, 1):
+            cuts.append(cuts[-1] + 4 * S * width)
+        cuts.append(cuts[-1] + S * d * p)
+        at = -(-cuts[-1] // 4) * 4                                      # the tail, int32-aligned behind the mask
+        n_tail = 0 if tail is None else 4 * tail.numel()
+        buf = torch.empty(max(at + n_tail, 0), dtype=torch.uint8, device=G.device)
+
+        def parts(b, f32, i32):
+            xi, var, passes, near, fell, trunc, rank, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
+            eight = (xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32),
+                     var.view(f32).reshape(S, R), trunc.view(i32), rank.view(i32))
+            return eight if tail is None else eight + (b[at:at + n_tail].view(i32),)
+
+        xi, mask, passes, near, fell, var, trunc, rank = parts(buf, torch.float32, torch.int32)[:8]
+        if tail is not None:
+            buf[at:at + n_tail].view(torch.int32).copy_(self._dev(tail, "tail", torch.int32).reshape(-1))
+        self._check(self.lib.symode_stlsq_sweep_minnorm(
+            self._ptr(G), n_sets, S, d, p, int(n_points), self._ptr(q_solve), self._ptr(q_xi), r, 1 if allow_constant else 0,
+            self._ptr(hyper), float(gamma), float(threshold), int(max_iter), float(near_band), float(rcond), self._ptr(xi),
+            self._ptr(var), self._ptr(mask), self._ptr(passes), self._ptr(near), self._ptr(fell), self._ptr(trunc), self._ptr(rank),
+            self._stream(G)),
+            "symode_stlsq_sweep_minnorm")
         if to_host:
             import numpy as np
             return parts(buf.cpu().numpy(), np.float32, np.int32)

@@ -58,6 +58,11 @@ Xi = Q beta (+ const), EquivSINDy-c: the template regressor of the L-BFGS sweep 
 parameters (symode_stlsq_sweep_constrained) -- one gather launch and one solve launch for the whole sweep, --stlsq_grid and
 --eval_ltp as before.  Without the flag ``--method stlsq --eq_constraint`` is refused as it always was.
 
+``--min_norm_stlsq`` (with --equiv_stlsq only; opt-in) runs that launch in its rank-revealing mode
+(symode_stlsq_sweep_minnorm, ``solve(..., min_norm=True)``): a pass whose support leaves Q's columns collinear is solved by
+the minimum-norm rule inside the launch instead of flagging the seed for the host loop.  The summary gains one line that
+counts the problems with rank-truncated passes; without the flag every word printed is what it was.
+
 ``--wsindy`` sweeps the weak-SINDy fit of ``main_wsindy`` (the `for i in {0..49}; do python main_wsindy.py --seed $i` loops):
 sweep seed n reads the window main_wsindy --seed n reads (``sweep.weak_windows``), all windows are contracted and turned into
 their normal matrices by ONE call (symode_weak_normal_windows) and fitted by ONE symode_stlsq_sweep launch
@@ -161,7 +166,7 @@ def _grid_problem(problem, n_seeds):
 
 
 def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None, device_stlsq=False,
-             stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False):
+             stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False, min_norm_stlsq=False):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
@@ -172,9 +177,12 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     ``--wsindy_grid`` strings; theirs is a fit of its own, so its rules (``_refusal_wsindy``) come before the optimiser rules
     and replace them -- the weak configs set no --sindy_optimizer, and the parser's default must not route them anywhere.
     ``equiv_stlsq``: the ``--equiv_stlsq`` flag; off, every answer is what it was.  On, its own rules (``_refusal_equiv_stlsq``)
-    come first and the rule that keeps --eq_constraint out of --method stlsq does not apply."""
+    come first and the rule that keeps --eq_constraint out of --method stlsq does not apply.
+    ``min_norm_stlsq``: the ``--min_norm_stlsq`` flag, a mode of --equiv_stlsq and refused by name without it."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
+    if min_norm_stlsq and not equiv_stlsq:
+        return _refusal_min_norm_stlsq()
     if equiv_stlsq:
         why = _refusal_equiv_stlsq(args, method, device_stlsq, wsindy or wsindy_grid)
         if why is not None:
@@ -280,6 +288,13 @@ def _refusal_equiv_stlsq(args, method, device_stlsq, wsindy):
     return None
 
 
+def _refusal_min_norm_stlsq():
+    """--min_norm_stlsq without --equiv_stlsq: what it is a mode of, and what that needs in turn."""
+    return ('--min_norm_stlsq needs --equiv_stlsq: it is the rank-revealing mode of the constrained device fit (collinear '
+            'columns of Q on the support are solved by the minimum-norm rule inside the launch), so it needs --method stlsq '
+            '--device_stlsq --equiv_stlsq --eq_constraint; the unconstrained sweep meets no such systems')
+
+
 def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid):
     """The rules of --device_stlsq and --stlsq_grid (``_refusal``, which has applied the rules of --method stlsq itself)."""
     given = ' and '.join(flag for flag, on in (('--device_stlsq', device_stlsq), ('--stlsq_grid', stlsq_grid)) if on)
@@ -380,6 +395,8 @@ def _fit_stlsq(ctx):
                              f"{f' + {coef.d} constants' if coef.allow_constant else ''}), the device fit takes at most "
                              f'{EQUIV_STLSQ_MAX_PARAMS}; use --method lbfgs')
         fit = dict(coef=coef)
+        if getattr(ctx, 'min_norm_stlsq', False):
+            fit['min_norm'] = True
     sw = SeedSweepSTLSQ(ctx.x_all, ctx.dx_all, *lib, n_seeds=len(ctx.seeds), subsample=args['lbfgs_subsample'], seed0=args['seed'],
                         group=ctx.group, engine=ctx.engine, idx=_rows(ctx), idx_sorted=True)
     n_seeds, points = len(ctx.seeds), getattr(ctx, 'grid', None)
@@ -394,13 +411,21 @@ def _fit_stlsq(ctx):
             near = [rec for rec in sw.near_threshold if g * n_seeds <= rec[0] < (g + 1) * n_seeds]
             lines.append(f'grid {g}: STLSQ passes {int(passes[at].min())}-{int(passes[at].max())}, near-threshold coefficients '
                          f'(| |coef| - thr | < 1e-4): {near if near else "none"}')
-        return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
+        return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines + _min_norm_lines(sw, fit))
     route = dict(device=True) if getattr(ctx, 'device_stlsq', False) else {}
     Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']),
                                 lstsq_driver=args.get('lstsq_driver'), **route, **fit)
     lines = [f'{len(ctx.seeds)} seeds x {sw.n_points} points (over {ctx.world} rank(s)), STLSQ passes {int(passes.min())}-{int(passes.max())}',
              f'near-threshold coefficients (| |coef| - thr | < 1e-4): {sw.near_threshold if sw.near_threshold else "none"}']
-    return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
+    return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines + _min_norm_lines(sw, fit))
+
+
+def _min_norm_lines(sw, fit):
+    """--min_norm_stlsq: one more summary line, the problems with passes the launch solved rank-truncated."""
+    if not fit.get('min_norm'):
+        return []
+    hit = sw.rank_truncated
+    return [f'rank-truncated passes (minimum-norm solution inside the launch): {int(hit.sum())} of {hit.size} problems']
 
 
 def _fit_wsindy(ctx):
@@ -683,12 +708,13 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     wsindy_grid = _pop_all(argv, '--wsindy_grid')
     wsindy = _pop_flag(argv, '--wsindy')
     equiv_stlsq = _pop_flag(argv, '--equiv_stlsq')
+    min_norm_stlsq = _pop_flag(argv, '--min_norm_stlsq')
     fold_linear_action = _pop_flag(argv, '--fold_linear_action')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
                    device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None, wsindy=wsindy, wsindy_grid=wsindy_grid or None,
-                   equiv_stlsq=equiv_stlsq)
+                   equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -709,7 +735,7 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
                           engine=engine, kw={} if engine is None else {'engine': engine}, grid=None,
                           device_stlsq=device_stlsq, fold_linear_action=fold_linear_action, train=train_dataset,
-                          equiv_stlsq=equiv_stlsq)
+                          equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq)
     if wsindy_grid:
         ctx.grid_names = WSINDY_GRID_NAMES
         ctx.grid_axes = _parse_grid(wsindy_grid, WSINDY_GRID_NAMES, '--wsindy_grid')[0]

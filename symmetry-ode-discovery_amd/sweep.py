@@ -68,7 +68,7 @@ class _DeviceSTLSQ:
             if converged:
                 break
 
-    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper, coef=None):
+    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper, coef=None, min_norm=False):
         """``solve(device=True)``: one symode_stlsq_sweep launch on the matrices where the gather launch left them; only
         Xi, mask, passes, near and fell come back.  The launch takes ridge weight and threshold in fp32, as its per-problem
         table holds them, with or without a table -- so problem (g, k) of a grid is bit for bit seed k of the scalar device
@@ -76,7 +76,11 @@ class _DeviceSTLSQ:
         Every rank holds the same all-reduced matrices and takes the same decisions.
         ``coef`` (a CoefMap with Q): the launch is symode_stlsq_sweep_constrained, the fit under Xi = Q beta (+ const); a
         problem it flags (a pivot under SINGULAR_RCOND^2 of the first: possibly rank deficient) is solved by the host loop
-        with the minimum-norm rule on every pass."""
+        with the minimum-norm rule on every pass.
+        ``min_norm`` (with ``coef``): the launch is symode_stlsq_sweep_minnorm, which performs that rule on every pass itself
+        (rcond = SINGULAR_RCOND).  A problem whose passes were rank-truncated then costs no host work and no copy of its
+        matrix; what is left to the host is a problem the launch flags (the factor of Wm Wm^T not positive definite) and the
+        replay for the near-threshold record, with the rule the launch applied ('min_norm' where a pass was truncated)."""
         S, d, p = self.S, self.d, self.p
         f32 = lambda v: float(np.float32(v))                                   # noqa: E731
         n_problems = S
@@ -97,7 +101,13 @@ class _DeviceSTLSQ:
         table = None
         if hyper is not None:
             table = torch.from_numpy(np.stack([w, thr], axis=1).astype(np.float32)).to(G.device)
-        if coef is not None:
+        trunc = np.zeros(n_problems, dtype=np.int32)
+        if coef is not None and min_norm:
+            q_solve, q_xi = (torch.from_numpy(q).to(G.device) for q in (coef.solve_matrix(), coef.xi_matrix()))
+            Xi, m8, p32, near, fell, _, trunc, _, *flags = self.engine.stlsq_sweep_minnorm(
+                G, self.n_points, w[0], thr[0], max_iter, q_solve, q_xi, coef.allow_constant, hyper=table, d=d,
+                rcond=_lstsq.SINGULAR_RCOND, near_band=NEAR_THRESHOLD_BAND, to_host=True, tail=self._fetch_with_fit)
+        elif coef is not None:
             q_solve, q_xi = (torch.from_numpy(q).to(G.device) for q in (coef.solve_matrix(), coef.xi_matrix()))
             Xi, m8, p32, near, fell, _, *flags = self.engine.stlsq_sweep_constrained(
                 G, self.n_points, w[0], thr[0], max_iter, q_solve, q_xi, coef.allow_constant, hyper=table, d=d,
@@ -119,7 +129,8 @@ class _DeviceSTLSQ:
                 held[k] = G[k].cpu().numpy()
             return held[k]
 
-        if fell.any() and coef is not None:
+        self.rank_truncated = np.array(trunc) > 0                       # (n_problems,): a pass solved with rank < n on the device
+        if coef is not None and (fell.any() or self.rank_truncated.any()):
             # possibly rank deficient: the host loop from the full mask, the minimum-norm rule on every pass
             import warnings
             for s in np.nonzero(fell)[0].tolist():
@@ -144,7 +155,7 @@ class _DeviceSTLSQ:
             warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
                           RuntimeWarning)
         for s in np.nonzero(near)[0].tolist():
-            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'gels', Xi, mask, passes, coef)
+            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm' if trunc[s] > 0 else 'gels', Xi, mask, passes, coef)
         return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
 
 
@@ -201,7 +212,7 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
             self._gram = self._gram_dev.cpu().numpy()
         return self._gram
 
-    def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None, coef=None):
+    def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None, coef=None, min_norm=False):
         """STLSQ to convergence for every seed (train.py:872-887 per seed).
         Returns (Xi (S, d, p) float32, mask (S, d, p) float32, passes (S,)).
         ``device=True``: the fit runs on the device (``_solve_device``; the full-rank driver only), the host route stays the
@@ -210,7 +221,23 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         (G S, d, p) and (G S,), and a column left out takes the scalar argument.
         ``coef`` (a CoefMap with Q): the fit under the equivariance constraint Xi = Q beta (+ const), EquivSINDy-c
         (solve_SINDy_one_step's constrained branch per seed); Xi is then ``get_Xi`` of the last solve, unmasked.  On the host
-        it is the numpy loop (sindy.stlsq_constrained_from_gram) with the driver given; ``device=True`` as above."""
+        it is the numpy loop (sindy.stlsq_constrained_from_gram) with the driver given; ``device=True`` as above.
+        ``min_norm=True`` (with ``device=True`` and a ``coef`` that holds Q; opt-in): the rank-revealing mode of the constrained
+        launch (symode_stlsq_sweep_minnorm).  A pass whose support leaves Q's columns collinear is solved inside the launch
+        by the minimum-norm rule the host loop would apply (``lstsq_normal(Gq, cq, m, 'gelsy', SINGULAR_RCOND)``), so such
+        problems are not handed to the host; the RuntimeWarning that names the minimum-norm answer is raised all the same,
+        and ``self.rank_truncated`` (n_problems,) bool says which problems it concerns."""
+        if min_norm:
+            if not device:
+                raise ValueError('min_norm=True needs device=True: it is a mode of the device launch (on the host route '
+                                 "lstsq_driver='gelsy' is the rank-revealing fit)")
+            if coef is None or coef.Q is None:
+                raise ValueError('min_norm=True needs coef=<a CoefMap that holds Q>: it is the rank-revealing mode of the '
+                                 'constrained fit Xi = Q beta (+ const); the unconstrained launch meets no collinear columns')
+            if lstsq_driver == 'gelsy':
+                raise ValueError("min_norm=True does not go with lstsq_driver='gelsy': the launch cuts the rank at SINGULAR_RCOND "
+                                 "on the triangular factor (the full-rank driver's fallback), gelsy's default rule "
+                                 'eps32 * max(m, n) runs on the host route')
         if coef is not None and coef.Q is None:
             coef = None                                    # a map without Q: the variables are Xi, the unconstrained fit
         if hyper is not None and not device:
@@ -221,7 +248,7 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
             if lstsq_driver != 'gels':
                 raise ValueError(f"device=True fits with the full-rank driver (gels) only, not lstsq_driver='{lstsq_driver}': the "
                                  'rank rule of gelsy runs on the host route')
-            return self._solve_device(w_sindy_reg, threshold, max(1, int(max_iter)), hyper, coef)
+            return self._solve_device(w_sindy_reg, threshold, max(1, int(max_iter)), hyper, coef, min_norm)
         G = self.grams()
         S, d, p = self.S, self.d, self.p
         Xi = np.zeros((S, d, p), dtype=np.float32)
