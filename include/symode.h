@@ -300,6 +300,25 @@ int symode_loss_grad_reversed_linear(const float* x, const float* dx, const floa
                                      const float* mask, unsigned long long live_columns, float inv_count, float w_sym,
                                      float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* symode_loss_grad_reversed_linear with the regulariser taken from the library's Gram matrix instead of the points.
+ * g_table (S, 1, p, p) fp64: G = sum_n Theta(x_n) Theta(x_n)^T of each problem over the n points of THIS call, RAW sums (no
+ * inv_count) -- the top-left p x p block of symode_aug_gram on the same x.  A function of x alone: build it once per data
+ * set.  Then  sum_n |u_n|^2 = sum_j c_j G c_j^T  and  U = sum_n u_n Theta^T = C G,  so the point loop carries the residual
+ * alone (Theta, h = Xi Theta, r, sum r^2, R: fp32, the bits of the _linear entry's kernel on the same grid) and ONE workgroup
+ * per problem forms C, U, the value and (J - I)^T U - U (M - I)^T in fp64 and adds them to its fp64 partial row.
+ * loss2_out[:, 0] is bit-identical to the _linear entry's; loss2_out[:, 1] and the regulariser's share of the gradient agree
+ * with it up to rounding (they are the more accurate: fp64 against fp32 sums over the points).  The term is linear in G:
+ * shards of points add.  Where the launcher's table keeps the plain fold kernel for the library and column set, and
+ * everywhere with SYMODE_FOLD_GRAM=0, the call IS symode_loss_grad_reversed_linear, bit for bit (SYMODE_FOLD_GRAM=2: the
+ * Gram form for every fold library, for tests).  The form taken is left in word 1 of the workspace header (bit 64).
+ * Refuses what the _linear entry refuses, and a null (SYMODE_E_NULLPTR) or misaligned (SYMODE_E_ALIGN) g_table.
+ * Added to ABI version 8 (nothing existing changed). */
+int symode_loss_grad_reversed_linear_gram(const float* x, const float* dx, const float* gx, const float* table,
+                                          const double* m_table, const double* g_table, int n_g, long n_problems, long n, int d,
+                                          int order, int flags, const float* xi, const float* mask,
+                                          unsigned long long live_columns, float inv_count, float w_sym, float* loss2_out,
+                                          float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Gram matrix of the reversed regulariser: for S problems (layouts as in symode_symreg_reversed_batched, n_g >= 1)
  *     gram_out[s] (d p, d p) fp64 = sum_g sum_n B^T B,   B[i, (j, a)] = J_g(x_n)[i, j] theta_a(x_n) - delta_ij theta_a(g x_n),
  * rows and columns in Xi's (d, p) row-major order, both triangles filled: the regulariser of symode_symreg_reversed_batched

@@ -61,7 +61,7 @@ def allreduce_sums(sums, params, group):
 class BatchedClosure:
     def __init__(self, x, dx, poly_order, include_sine=False, include_exp=False, Q=None, use_kron_product=True,
                  allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True, coef=None,
-                 const_jacobian=None, live_columns=True, linear_action=None):
+                 const_jacobian=None, live_columns=True, linear_action=None, regulariser_gram=None):
         """``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from Q / use_kron_product / allow_constant).
         ``reversed_sym = (gx (S, n_g, N_local, d), jgx (S, n_g, N_local, d, d), weight)`` adds  weight * the reversed
         symmetry regulariser (model_utils.py:126-170 on precomputed (g(x), J_g(x))) to every problem's loss and gradient:
@@ -84,7 +84,13 @@ class BatchedClosure:
         4 * 2^-24 per component; if so the fused closure takes the kernel that folds the action into the coefficients: it reads
         x and dx alone and evaluates the library once per point.  Same closure up to rounding, NOT bit for bit (g(x) is
         replaced by J x); SYMODE_CLOSURE_FOLD=0 or False keep the streamed kernels.  The verdict is remembered with the
-        version counters and data pointers of x and gx, as jgx's is."""
+        version counters and data pointers of x and gx, as jgx's is.
+        ``regulariser_gram``: None (default) -- where the linear verdict is yes, the library Gram G = sum_n Theta Theta^T of this
+        rank's shard of every problem is built once (engine.aug_gram, its top-left p x p block) and handed to the fold closure:
+        the regulariser and its gradient become a d p p fp64 product per problem and the point loop carries the residual alone
+        (engine.loss_grad_reversed, ``gram=``).  The term is linear in G, so the [loss | grad] all-reduce stays what it is.
+        G is remembered with x's version counter and data pointer and rebuilt when either moves (``gram_builds`` counts);
+        SYMODE_FOLD_GRAM=0 or False keep the plain fold kernel."""
         assert x.dim() == 3 and x.shape == dx.shape, "x, dx must be (S, N_local, d)"
         self.engine = engine or get_engine()
         self.x, self.dx = x.contiguous(), dx.contiguous()
@@ -95,6 +101,8 @@ class BatchedClosure:
         self.coef = coef if coef is not None else CoefMap(self.d, self.p, Q, use_kron_product, allow_constant)
         self.group = group
         self.distributed = group is not None or (world_size or 1) > 1
+        # world_size without a group and without a process group at all: the caller adds the shards' packed outputs itself
+        self._collective = self.distributed and (group is not None or dist.is_initialized())
         self.world = world_size if world_size is not None else (dist.get_world_size(group) if self.distributed else 1)
         self.n_global = self.n_local * self.world
         if group is not None:                                # shards need not be equal: the count is summed once, at set-up
@@ -131,6 +139,10 @@ class BatchedClosure:
         self._lin_seen, self._lin_m, self.linear_detections = None, None, 0
         if self._lin_detect:
             self._linear_for_launch()
+        self._gram_on = (regulariser_gram is None or bool(regulariser_gram)) and self._lin_detect and hasattr(self.engine, 'aug_gram')
+        self._gram_seen, self._gram, self.gram_builds = None, None, 0
+        if self._gram_on:
+            self._gram_for_launch()
         self._live = None                                    # the map's column set, where it names a dead column at all
         if live_columns and self._cj_detect:
             live = self.coef.live_mask()
@@ -164,6 +176,18 @@ class BatchedClosure:
             self.linear_detections += 1
         return self._lin_m
 
+    def _gram_for_launch(self):
+        """The fp64 (S, 1, p, p) raw library Gram sums of x where the fold closure is taken, else None.  Built once per
+        (version, pointer) of x; ``gram_builds`` counts."""
+        if not self._gram_on or self._linear_for_launch() is None:
+            return None
+        seen = (self.x._version, self.x.data_ptr())
+        if seen != self._gram_seen:
+            G = self.engine.aug_gram(self.x, self.dx, self.order, self.flags)
+            self._gram_seen, self._gram = seen, G[:, None, :self.p, :self.p].contiguous()
+            self.gram_builds += 1
+        return self._gram
+
     # -- coefficient plumbing (batched get_Xi, sindy.py:169-176) ----------------------------
     def xi_from(self, beta, const=None):
         return self.coef.xi(beta, const)
@@ -182,6 +206,7 @@ class BatchedClosure:
         fused = self.sym is not None and self.fuse_sym and hasattr(self.engine, 'loss_grad_reversed')
         jg = self._jacobian_for_launch() if self.sym is not None else None      # (S, n_g, d, d) table or the (S, n_g, N, d, d) tensor
         lin = self._linear_for_launch() if fused else None                      # M of a detected linear action: the fold kernel
+        gram = self._gram_for_launch() if lin is not None else None             # G of x: the fold kernel's Gram form
         for ci, ((a, b), buf) in enumerate(zip(self.chunks, self.buffers)):
             n = b - a
             loss = buf[:n]
@@ -195,9 +220,10 @@ class BatchedClosure:
                 self.engine.loss_grad_reversed(self.x[a:b], self.dx[a:b], gx[a:b], jg[a:b], Xi[a:b],
                                                None if mask is None else mask[a:b], self.order, self.flags, w_sym=weight,
                                                inv_count=self.inv_count, out=(l2, grad), **live_kw, **self._ws_kw,
-                                               **({} if lin is None else {'linear_m': lin[a:b]}))
+                                               **({} if lin is None else {'linear_m': lin[a:b]}),
+                                               **({} if gram is None else {'gram': gram[a:b]}))
                 torch.add(l2[:, 0], l2[:, 1], alpha=weight, out=loss)
-                if self.distributed:
+                if self._collective:
                     works.append(dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
                 continue
             l, g = self.engine.loss_grad(self.x[a:b], self.dx[a:b], Xi[a:b], None if mask is None else mask[a:b],
@@ -216,7 +242,7 @@ class BatchedClosure:
                     sl.copy_(l2)
                     sg.copy_(g2)
                 buf.add_(sb, alpha=weight)
-            if self.distributed:
+            if self._collective:
                 works.append(dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
         for w in works:
             w.wait()

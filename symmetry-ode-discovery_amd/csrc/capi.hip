@@ -422,15 +422,11 @@ int symode_linear_action(const float* x, const float* gx_, const float* table, i
     return (int)launch_linear_action(x, gx_, table, n_problems, n, order, m_out, flag_out, (hipStream_t)stream);
 }
 
-int symode_loss_grad_reversed_linear(const float* x, const float* dx, const float* gx_, const float* table, const double* m_table,
-                                     int n_g, long n_problems, long n, int d, int order, int flags, const float* xi,
-                                     const float* mask, unsigned long long live_columns, float inv_count, float w_sym,
-                                     float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (d != 2 || flags != 0 || order < 1 || order > MAX_ORDER) return SYMODE_E_UNSUPPORTED;
-    if (n_g < 1) return SYMODE_E_BADSIZE;
-    if (n_g != 1) return SYMODE_E_UNSUPPORTED;
-    if (!m_table) return SYMODE_E_NULLPTR;
-    if (misaligned(m_table, 8)) return SYMODE_E_ALIGN;
+// The two entries of the folded linear action: g_table null is the plain one.
+static int fold_closure(const float* x, const float* dx, const float* gx_, const float* table, const double* m_table,
+                        const double* g_table, int n_g, long n_problems, long n, int d, int order, int flags, const float* xi,
+                        const float* mask, unsigned long long live_columns, float inv_count, float w_sym, float* loss2_out,
+                        float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
     SYMODE_GET_OPS();
     // where the launcher's table (or SYMODE_CLOSURE_FOLD=0) keeps the streamed kernels, this IS the _constj_live entry
     if (!ops->symreg_fold || !ops->fold_takes(live_columns))
@@ -442,8 +438,36 @@ int symode_loss_grad_reversed_linear(const float* x, const float* dx, const floa
         misaligned(loss2_out, 4) || misaligned(grad_out, 4))
         return SYMODE_E_ALIGN;
     SYMODE_CHECK_WS(n_problems, n);
-    return (int)ops->symreg_fold(x, dx, table, m_table, n_problems, n, xi, mask, live_columns, inv_count, w_sym, loss2_out, grad_out,
-                                 (double*)workspace, reversed_closure_grid(true, ops, n_problems, n, d), (hipStream_t)stream);
+    return (int)ops->symreg_fold(x, dx, table, m_table, g_table, n_problems, n, xi, mask, live_columns, inv_count, w_sym, loss2_out,
+                                 grad_out, (double*)workspace, reversed_closure_grid(true, ops, n_problems, n, d), (hipStream_t)stream);
+}
+
+int symode_loss_grad_reversed_linear(const float* x, const float* dx, const float* gx_, const float* table, const double* m_table,
+                                     int n_g, long n_problems, long n, int d, int order, int flags, const float* xi,
+                                     const float* mask, unsigned long long live_columns, float inv_count, float w_sym,
+                                     float* loss2_out, float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (d != 2 || flags != 0 || order < 1 || order > MAX_ORDER) return SYMODE_E_UNSUPPORTED;
+    if (n_g < 1) return SYMODE_E_BADSIZE;
+    if (n_g != 1) return SYMODE_E_UNSUPPORTED;
+    if (!m_table) return SYMODE_E_NULLPTR;
+    if (misaligned(m_table, 8)) return SYMODE_E_ALIGN;
+    return fold_closure(x, dx, gx_, table, m_table, nullptr, n_g, n_problems, n, d, order, flags, xi, mask, live_columns, inv_count,
+                        w_sym, loss2_out, grad_out, workspace, workspace_bytes, stream);
+}
+
+int symode_loss_grad_reversed_linear_gram(const float* x, const float* dx, const float* gx_, const float* table,
+                                          const double* m_table, const double* g_table, int n_g, long n_problems, long n, int d,
+                                          int order, int flags, const float* xi, const float* mask,
+                                          unsigned long long live_columns, float inv_count, float w_sym, float* loss2_out,
+                                          float* grad_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (d != 2 || flags != 0 || order < 1 || order > MAX_ORDER) return SYMODE_E_UNSUPPORTED;
+    if (n_g < 1) return SYMODE_E_BADSIZE;
+    if (n_g != 1) return SYMODE_E_UNSUPPORTED;
+    if (!m_table || !g_table) return SYMODE_E_NULLPTR;
+    if (misaligned(m_table, 8) || misaligned(g_table, 8)) return SYMODE_E_ALIGN;
+    // SYMODE_FOLD_GRAM=0: the entry without the table (the launcher's own table is asked per column set, in the launch)
+    return fold_closure(x, dx, gx_, table, m_table, knobs().fold_gram ? g_table : nullptr, n_g, n_problems, n, d, order, flags, xi,
+                        mask, live_columns, inv_count, w_sym, loss2_out, grad_out, workspace, workspace_bytes, stream);
 }
 
 size_t symode_symreg_reversed_gram_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long n) {

@@ -138,17 +138,44 @@ template <class L>
 struct fold_levers<L, std::void_t<decltype(L::FOLD_PK)>> {
     static constexpr bool pk = L::FOLD_PK, saddr = L::FOLD_SADDR;
 };
-template <class Lib, int RING, int MINW, unsigned long long LIVE, bool W_SGPR, bool C_SGPR>
+//
+// The Gram form (FoldGram<L>, GRAM below): the regulariser does not go through the points at all.  With G = sum_n Theta Theta^T
+// of the problem (gt: the (S, 1, P, P) fp64 raw sums, a function of x alone, built once per data set),
+//   sum_n |u_n|^2 = sum_j c_j G c_j^T,      U = sum_n u_n Theta^T = C G,
+// so the point loop is the monomials, h = Xi Theta, r, sum r^2 and R += r Theta^T -- the statements above without every c, u
+// and U: sum_r and R are the plain fold kernel's bits on the same grid.  Workgroup 0 of each problem forms C, U = C G, the
+// value and T = (J - I)^T U - U (M - I)^T in fp64 (J - I, M - I not rounded to fp32) and adds value and w_sym T to ITS OWN
+// partial row as the row is written, in double: once per problem whatever grid.x is, through whichever finalisation.  The
+// other workgroups read neither M nor G; slot 1 of their rows is 0.  Same NACC, workspace layout and finalisation.
+template <class L>
+struct FoldGram : L {
+    static constexpr bool FOLD_GRAM = true;
+};
+template <class L, class = void>
+struct fold_gram {
+    static constexpr bool value = false;
+};
+template <class L>
+struct fold_gram<L, std::void_t<decltype(L::FOLD_GRAM)>> {
+    static constexpr bool value = L::FOLD_GRAM;
+};
+
+// One template for both forms: the plain kernel has the arguments (and so the name) it had, the Gram form takes gt, one more
+// pointer, behind them -- the trailing pack is empty or that pointer.
+template <class Lib, int RING, int MINW, unsigned long long LIVE, bool W_SGPR, bool C_SGPR, class... GT>
 __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* __restrict__ x, const float* __restrict__ dx,
                                                                   const float* __restrict__ jt, const double* __restrict__ mt,
                                                                   long N, bool vec, const float* __restrict__ xi,
                                                                   const float* __restrict__ mask, float w_sym,
-                                                                  double* __restrict__ ws, Finish fin, unsigned long long live) {
-    constexpr bool PK = fold_levers<Lib>::pk, SADDR = fold_levers<Lib>::saddr;
+                                                                  double* __restrict__ ws, Finish fin, unsigned long long live,
+                                                                  GT... gtp) {
+    constexpr bool PK = fold_levers<Lib>::pk, SADDR = fold_levers<Lib>::saddr, GRAM = fold_gram<Lib>::value;
     constexpr int D = Lib::D, P = Lib::P, NACC = 2 + D * P, PPT = Chunk<D>::PPT, NV = Chunk<D>::NV;
     constexpr bool SPARSE = LIVE != ~0ull;
+    static_assert(sizeof...(GT) == (GRAM ? 1 : 0), "the Gram form, and it alone, takes the Gram table");
     static_assert(D == 2 && !Lib::SINE && !Lib::EXP, "Theta(J x) = M Theta(x) holds for the plain polynomial libraries; M is built for d = 2");
-    __shared__ float cs[D * P], mm[P * P], jm[D * D];
+    __shared__ float cs[GRAM ? 1 : D * P], mm[GRAM ? 1 : P * P], jm[GRAM ? 1 : D * D];
+    __shared__ double cd[GRAM ? D * P : 1], ud[GRAM ? D * P : 1], row_add[GRAM ? NACC : 1];
     const long s = blockIdx.y;
     const float* xs = x + s * N * D;
     const float* ys = dx + s * N * D;
@@ -156,32 +183,76 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* _
     const double* ms = mt + s * P * P;
     if (!SPARSE) live = ~0ull;
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && fin.header[0] == WS_MAGIC)
-        fin.header[WS_BODY_WORD] = WS_BODY_FOLD | (SPARSE ? WS_BODY_LIVE : 0ull) | (PK ? WS_BODY_FOLD_PK : 0ull) | (SADDR ? WS_BODY_FOLD_SADDR : 0ull);
+        fin.header[WS_BODY_WORD] = WS_BODY_FOLD | (SPARSE ? WS_BODY_LIVE : 0ull) | (PK ? WS_BODY_FOLD_PK : 0ull) |
+                                   (SADDR ? WS_BODY_FOLD_SADDR : 0ull) | (GRAM ? WS_BODY_FOLD_GRAM : 0ull);
 
-    // C = J Xi - Xi M of this problem, fp64 products of the masked fp32 coefficients the streamed kernels read
-    for (int t = threadIdx.x; t < D * P; t += BLOCK) {
-        const int j = t / P, k = t % P;
-        const auto wv = [&](int b, int l) -> double {
-            if (!col_live<LIVE>(l) || ((live >> l) & 1ull) == 0) return 0.0;
-            float v = xi[s * D * P + b * P + l];
-            if (mask != nullptr) v *= mask[s * D * P + b * P + l];
-            return (double)v;
-        };
-        double c = 0.0;
-        for (int b = 0; b < D; ++b) c += (double)js[j * D + b] * wv(b, k);
-        for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l) c -= wv(j, l) * ms[l * P + k];
-        cs[t] = (float)c;
+    // C = J Xi - Xi M of this problem, fp64 products of the masked fp32 coefficients the streamed kernels read; the Gram form
+    // keeps it in fp64, and forms it in workgroup 0 of the problem alone (the condition is uniform over the workgroup)
+    if (!GRAM || blockIdx.x == 0) {
+        for (int t = threadIdx.x; t < D * P; t += BLOCK) {
+            const int j = t / P, k = t % P;
+            const auto wv = [&](int b, int l) -> double {
+                if (!col_live<LIVE>(l) || ((live >> l) & 1ull) == 0) return 0.0;
+                float v = xi[s * D * P + b * P + l];
+                if (mask != nullptr) v *= mask[s * D * P + b * P + l];
+                return (double)v;
+            };
+            double c = 0.0;
+            for (int b = 0; b < D; ++b) c += (double)js[j * D + b] * wv(b, k);
+            for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l) c -= wv(j, l) * ms[l * P + k];
+            if constexpr (GRAM)
+                cd[t] = col_live<LIVE>(k) ? c : 0.0;
+            else
+                cs[t] = (float)c;
+        }
     }
-    for (int t = threadIdx.x; t < P * P; t += BLOCK) mm[t] = (float)(ms[t] - (t / P == t % P ? 1.0 : 0.0));
-    if (threadIdx.x < D * D) jm[threadIdx.x] = (float)((double)js[threadIdx.x] - (threadIdx.x / D == threadIdx.x % D ? 1.0 : 0.0));
-    __syncthreads();
+    if constexpr (GRAM) {
+        // the regulariser of this problem: U = C G, sum_j c_j G c_j^T and T, left for this workgroup's partial row
+        if (blockIdx.x == 0) {
+            const double* gs = [](const double* g) { return g; }(gtp...) + s * P * P;
+            __syncthreads();
+            // U = C G over the columns of LIVE, in column order
+            for (int t = threadIdx.x; t < D * P; t += BLOCK) {
+                const int j = t / P, k = t % P;
+                double u = 0.0;
+                if (col_live<LIVE>(k))
+                    for (int l = 0; l < P; ++l)
+                        if (col_live<LIVE>(l)) u = __builtin_fma(cd[j * P + l], gs[l * P + k], u);
+                ud[t] = u;
+            }
+            __syncthreads();
+            // T = (J - I)^T U - U (M - I)^T over the degree block of the column, J - I and M - I in fp64; sum_j c_j G c_j^T
+            for (int t = threadIdx.x; t < D * P; t += BLOCK) {
+                const int j = t / P, k = t % P;
+                double v = 0.0;
+                if (col_live<LIVE>(k) && ((live >> k) & 1ull) != 0) {
+                    for (int a = 0; a < D; ++a) v = __builtin_fma((double)js[a * D + j] - (a == j ? 1.0 : 0.0), ud[a * P + k], v);
+                    for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l)
+                        v = __builtin_fma(-(ms[k * P + l] - (k == l ? 1.0 : 0.0)), ud[j * P + l], v);
+                    v *= (double)w_sym;
+                }
+                row_add[2 + t] = v;
+            }
+            if (threadIdx.x == BLOCK - 1) {
+                double v = 0.0;
+                for (int t = 0; t < D * P; ++t) v = __builtin_fma(cd[t], ud[t], v);
+                row_add[0] = 0.0;
+                row_add[1] = v;
+            }
+            __syncthreads();
+        }
+    } else {
+        for (int t = threadIdx.x; t < P * P; t += BLOCK) mm[t] = (float)(ms[t] - (t / P == t % P ? 1.0 : 0.0));
+        if (threadIdx.x < D * D) jm[threadIdx.x] = (float)((double)js[threadIdx.x] - (threadIdx.x / D == threadIdx.x % D ? 1.0 : 0.0));
+        __syncthreads();
+    }
 
     float w[D * P], c[D * P];
     load_xi<Lib, W_SGPR ? 1 : 1 << 20, 1 << 20, LIVE>(xi, mask, s, w, live);
 #pragma unroll
     for (int i = 0; i < D * P; ++i) {
-        c[i] = col_live<LIVE>(i % P) ? cs[i] : 0.0f;
-        if constexpr (C_SGPR) {
+        c[i] = (!GRAM && col_live<LIVE>(i % P)) ? cs[GRAM ? 0 : i] : 0.0f;
+        if constexpr (C_SGPR && !GRAM) {
             if (col_live<LIVE>(i % P)) c[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, c[i])));
         }
     }
@@ -193,17 +264,17 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* _
         float th[P], h[D], u[D];
         Lib::eval(xp, th);
         apply_xi<Lib, LIVE>(w, th, h);
-        apply_xi<Lib, LIVE>(c, th, u);
+        if constexpr (!GRAM) apply_xi<Lib, LIVE>(c, th, u);
 #pragma unroll
         for (int j = 0; j < D; ++j) {
             const float r = h[j] - yp[j];
             sum_r = fmaf(r, r, sum_r);
-            sum_u = fmaf(u[j], u[j], sum_u);
+            if constexpr (!GRAM) sum_u = fmaf(u[j], u[j], sum_u);
 #pragma unroll
             for (int k = 0; k < P; ++k)
                 if (col_live<LIVE>(k)) {
                     R[j * P + k] = fmaf(r, th[k], R[j * P + k]);
-                    U[j * P + k] = fmaf(u[j], th[k], U[j * P + k]);
+                    if constexpr (!GRAM) U[j * P + k] = fmaf(u[j], th[k], U[j * P + k]);
                 }
         }
     };
@@ -236,33 +307,33 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* _
                 const float2v t = pair(m);
                 if constexpr (decltype(m)::value == 0) {
                     h2 = pk_fma_bcast_first<W_SGPR>(t, w2[a], h0);
-                    u2 = pk_fma_bcast_first<C_SGPR>(t, c2[a], u0);
+                    if constexpr (!GRAM) u2 = pk_fma_bcast_first<C_SGPR>(t, c2[a], u0);
                 } else {
                     pk_fma_bcast_acc<0, W_SGPR>(t, w2[a], h2);
-                    pk_fma_bcast_acc<0, C_SGPR>(t, c2[a], u2);
+                    if constexpr (!GRAM) pk_fma_bcast_acc<0, C_SGPR>(t, c2[a], u2);
                 }
                 if constexpr (b >= 0) {
                     pk_fma_bcast_acc<1, W_SGPR>(t, w2[b], h2);
-                    pk_fma_bcast_acc<1, C_SGPR>(t, c2[b], u2);
+                    if constexpr (!GRAM) pk_fma_bcast_acc<1, C_SGPR>(t, c2[b], u2);
                 }
             });
             const float2v r2 = h2 - y2;
             sum_r = fmaf(r2.x, r2.x, sum_r);
-            sum_u = fmaf(u2.x, u2.x, sum_u);
+            if constexpr (!GRAM) sum_u = fmaf(u2.x, u2.x, sum_u);
             sum_r = fmaf(r2.y, r2.y, sum_r);
-            sum_u = fmaf(u2.y, u2.y, sum_u);
+            if constexpr (!GRAM) sum_u = fmaf(u2.y, u2.y, sum_u);
             if constexpr (col_live<LIVE>(0)) {
                 R2[0] += r2;
-                U2[0] += u2;
+                if constexpr (!GRAM) U2[0] += u2;
             }
             each_point_static<0, NPAIR>([&](auto m) {
                 constexpr int a = fold_pair_col<LIVE, P>(2 * decltype(m)::value), b = fold_pair_col<LIVE, P>(2 * decltype(m)::value + 1);
                 const float2v t = pair(m);
                 pk_fma_bcast_acc<0, false>(t, r2, R2[a]);
-                pk_fma_bcast_acc<0, false>(t, u2, U2[a]);
+                if constexpr (!GRAM) pk_fma_bcast_acc<0, false>(t, u2, U2[a]);
                 if constexpr (b >= 0) {
                     pk_fma_bcast_acc<1, false>(t, r2, R2[b]);
-                    pk_fma_bcast_acc<1, false>(t, u2, U2[b]);
+                    if constexpr (!GRAM) pk_fma_bcast_acc<1, false>(t, u2, U2[b]);
                 }
             });
         }
@@ -356,16 +427,25 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* _
         for (int k = 0; k < P; ++k) {
             float t = 0.0f;
             if (col_live<LIVE>(k)) {
+                if constexpr (GRAM) {
+                    t = R[j * P + k];                    // (the regulariser's share is workgroup 0's, in double: row_add)
+                } else {
 #pragma unroll
-                for (int a = 0; a < D; ++a) t = fmaf(jm[a * D + j], U[a * P + k], t);
+                    for (int a = 0; a < D; ++a) t = fmaf(jm[GRAM ? 0 : a * D + j], U[a * P + k], t);
 #pragma unroll
-                for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l) t = fmaf(-mm[k * P + l], U[j * P + l], t);
-                t = fmaf(w_sym, t, R[j * P + k]);
+                    for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l) t = fmaf(-mm[GRAM ? 0 : k * P + l], U[j * P + l], t);
+                    t = fmaf(w_sym, t, R[j * P + k]);
+                }
                 if (SPARSE && ((live >> k) & 1ull) == 0) t = 0.0f;
             }
             acc[2 + j * P + k] = t;
         }
-    emit_partials<NACC>(acc, ws, fin);
+    if constexpr (GRAM) {
+        const bool first = blockIdx.x == 0;
+        emit_partials<NACC>(acc, ws, fin, [&](int k, double v) { return (first && k >= 1) ? v + row_add[k] : v; });
+    } else {
+        emit_partials<NACC>(acc, ws, fin);
+    }
 }
 
 // Libraries with the fold kernels: the d = 2 plain polynomial ones, dense at every order and on odd_degree_columns where the
@@ -428,6 +508,35 @@ inline bool fold_saddr_fits(long n, int gx) {
     return n * D * 4 < (1L << 31) && (long)gx * BLOCK * 16 < (1L << 31);
 }
 
+// The Gram form (FoldGram), per instantiation, by the same rule.  SYMODE_FOLD_GRAM=0: nowhere -- the call that brings a Gram
+// table is the call without one, bit for bit; 2: every fold library (the tests reach the instantiations the table leaves out).
+// tools/micro/closure_ab foldgram on the MI355X, three interleaved passes, ms per launch at the bench shape (8192 x 125 000):
+// the fold kernel shipped for the instantiation | Gram form, plain | + SADDR | + PK | both, the ratio of the plain Gram form to
+// the shipped kernel there and at 64 x 50 000 (profiles/closure_fold_gram.txt); the order-3 dense fold kernel of the same
+// passes, the 16-byte floor so far, took 2.684-2.700:
+//   order 5 odd set   3.173-3.195 | 2.591-2.597 | 2.588-2.593 | 2.620-2.631 | 2.612-2.622   0.812-0.817   small 0.83-0.86
+//   order 5 dense     4.310-4.332 | 2.903-2.917 | 2.783-2.821 | 2.934-2.961 | 2.857-2.881   0.670-0.674   small 0.76-0.78
+//   order 4 dense     3.477-3.500 | 2.571-2.573 | 2.571-2.577 | 2.584-2.590 | 2.584-2.593   0.735-0.740   small 0.79-0.80
+//   order 3 dense     2.681-2.696 | 2.579-2.583 | 2.588-2.592 | 2.579-2.588 | 2.587-2.597   0.958-0.962   small 0.87-0.91
+//   order 4 odd set   2.565-2.574 | 2.583-2.585 |     every arm 1.004-1.010 of the shipped kernel: not taken
+// Taken where the issue expected it and, by the same rule, at order 3 dense: 3.8-4.2 % in every pass against spreads of 0.6 %
+// (shipped) and 0.2 % (Gram), 9-13 % at 64 x 50 000.  Every taken form is at 2.57-2.60 ms, 6.3-6.4 TB/s of its 16 B/point,
+// but the dense one of order 5 (5.6 TB/s).  Orders 1-2: not measured, the plain kernels stay.
+// No lever: on the Gram form the uniform ring is inside 0.2 % at the bench shape except at order 5 dense (3-4 %), and there it
+// is 5-6 % slower at 64 x 50 000 (21.1-21.2 against 19.8-20.0 us, a spread of 1 %); the packed body loses everywhere; four
+// chunks in flight are within 0.5 % of two.  So the Gram form has ONE instantiation per library and column set.
+template <class Lib, bool SPARSE>
+constexpr bool closure_fold_gram_pays = closure_fold_lib<Lib> && (Lib::ORDER == 5 || (Lib::ORDER >= 3 && !SPARSE));
+// half the sums and no C: three waves per SIMD asked for every instantiation
+constexpr int fold_gram_minw = 3;
+template <class Lib>
+bool fold_gram_takes(bool sparse) {
+    const int knob = knobs().fold_gram;
+    if (knob == 0) return false;
+    if (knob == 2) return true;
+    return sparse ? closure_fold_gram_pays<Lib, true> : closure_fold_gram_pays<Lib, false>;
+}
+
 // does a call with this column set take a fold kernel?
 template <class Lib>
 bool fold_takes(unsigned long long live) {
@@ -439,10 +548,12 @@ bool fold_takes(unsigned long long live) {
     return closure_fold_dense_pays<Lib>;
 }
 
+// gt: the (S, 1, P, P) fp64 Gram table of the library on x, or null; with it the launch takes the Gram form where
+// fold_gram_takes says so (one kernel per library and column set, without the levers), the plain kernel otherwise.
 template <class Lib>
-hipError_t launch_symreg_fold(const float* x, const float* dx, const float* jt, const double* mt, long S, long n, const float* xi,
-                              const float* mask, unsigned long long live, float inv_count, float w_sym, float* loss, float* grad,
-                              double* ws, int gx, hipStream_t st) {
+hipError_t launch_symreg_fold(const float* x, const float* dx, const float* jt, const double* mt, const double* gt, long S, long n,
+                              const float* xi, const float* mask, unsigned long long live, float inv_count, float w_sym, float* loss,
+                              float* grad, double* ws, int gx, hipStream_t st) {
     constexpr int D = Lib::D, DP = D * Lib::P;
     double* part = ws + WS_HEADER_DOUBLES;
     Finish fin = make_finish(ws, mask, inv_count, 2.0f * inv_count, loss, grad);
@@ -459,6 +570,11 @@ hipError_t launch_symreg_fold(const float* x, const float* dx, const float* jt, 
     const auto launch = [&](auto sp) {
         constexpr bool SPARSE = decltype(sp)::value, PKB = closure_fold_pk_pays<Lib, SPARSE>, SA = closure_fold_saddr_pays<Lib, SPARSE>;
         constexpr unsigned long long LIVE = SPARSE ? odd_degree_columns<Lib>() : ~0ull;
+        if (gt != nullptr && fold_gram_takes<Lib>(SPARSE)) {
+            symreg_fold_kernel<FoldGram<Lib>, 2, fold_gram_minw, LIVE, fold_sgpr<Lib>, fold_sgpr<Lib>>
+                <<<grid, block, 0, st>>>(x, dx, jt, mt, n, vec, xi, mask, w_sym, part, fin, live, gt);
+            return;
+        }
         if constexpr (PKB || SA) {
             if (knobs().fold_pk && (!SA || fold_saddr_fits<D>(n, gx))) {
                 symreg_fold_kernel<FoldLevers<Lib, PKB, SA>, 2, fold_minw<Lib, SPARSE>, LIVE, fold_sgpr<Lib>, fold_sgpr<Lib>>
@@ -478,7 +594,7 @@ hipError_t launch_symreg_fold(const float* x, const float* dx, const float* jt, 
     return launch_finalize(fin, part, S, gx, 2 + DP, st);
 }
 
-typedef hipError_t (*FoldFn)(const float*, const float*, const float*, const double*, long, long, const float*, const float*,
+typedef hipError_t (*FoldFn)(const float*, const float*, const float*, const double*, const double*, long, long, const float*, const float*,
                              unsigned long long, float, float, float*, float*, double*, int, hipStream_t);
 typedef bool (*FoldTakesFn)(unsigned long long);
 

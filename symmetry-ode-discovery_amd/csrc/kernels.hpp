@@ -23,7 +23,7 @@ constexpr int MAP_CHUNKS_PER_THREAD = SYMODE_MAP_CHUNKS;   // chunks a thread of
 // for the tests and tuning tools that compare two settings inside one process; no launch path calls getenv.
 struct Knobs {
     long max_grid, min_grid_x, map_grid, gram_grid, gram_valu_grid, small_grid, reduce_grid;
-    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live, closure_fold, fold_pk;
+    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live, closure_fold, fold_pk, fold_gram;
     long gram_m4_grid;
 };
 
@@ -51,6 +51,7 @@ inline Knobs read_knobs() {
     k.closure_live = on("SYMODE_CLOSURE_LIVE");
     k.closure_fold = on("SYMODE_CLOSURE_FOLD");
     k.fold_pk = on("SYMODE_FOLD_PK");
+    k.fold_gram = (int)num("SYMODE_FOLD_GRAM", 1);
     return k;
 }
 
@@ -141,9 +142,10 @@ struct LibOps {
     // the fused reversed closure under a linear action g(x) = J x (closure_fold.hpp): jt the (S, 1, d, d) table, mt the fp64
     // (S, 1, p, p) substitution matrices; nullptr where the library has no such kernel.  fold_takes: does a call with this
     // column set go there (the launcher's table and SYMODE_CLOSURE_FOLD)?  Additive entries
-    hipError_t (*symreg_fold)(const float* x, const float* dx, const float* jt, const double* mt, long S, long n, const float* xi,
-                              const float* mask, unsigned long long live, float inv_count, float w_sym, float* loss, float* grad,
-                              double* ws, int gx, hipStream_t st);
+    // gt: the fp64 (S, 1, p, p) Gram table of the library on x for the kernel's Gram form, or null
+    hipError_t (*symreg_fold)(const float* x, const float* dx, const float* jt, const double* mt, const double* gt, long S, long n,
+                              const float* xi, const float* mask, unsigned long long live, float inv_count, float w_sym, float* loss,
+                              float* grad, double* ws, int gx, hipStream_t st);
     bool (*fold_takes)(unsigned long long live);
     // weak_gram's contraction for S windows [trajectory, start] of one data set (n_ics, n_steps, d) (weak.hpp): partials
     // (S, row tile, gx, CT * 256) and the range flag of every window.  An additive entry
@@ -457,6 +459,7 @@ constexpr unsigned long long WS_BODY_SCALAR = 1, WS_BODY_PACKED = 2; //   which 
 constexpr unsigned long long WS_BODY_LIVE = 4;                       //   + this where it was the form that leaves out dead columns
 constexpr unsigned long long WS_BODY_FOLD = 8;                       //   the fold kernel of a linear action (closure_fold.hpp), alone or + WS_BODY_LIVE
 constexpr unsigned long long WS_BODY_FOLD_PK = 16, WS_BODY_FOLD_SADDR = 32;   //   + the fold kernel's levers: packed body, chunk addressing in SGPRs
+constexpr unsigned long long WS_BODY_FOLD_GRAM = 64;                 //   + its Gram form: the regulariser from the library Gram, once per problem
 constexpr long WS_HEADER_DOUBLES = 8 + WS_MAX_PROBLEMS / 2;          // [magic, 7 reserved | uint32 tickets] in front of the partials
 
 struct Finish {
@@ -521,23 +524,29 @@ __device__ __forceinline__ void combine_rows(const double* __restrict__ src, int
 // `lds`: the block reduction's staging area, reduce_lds_floats(BLOCK) floats.  The second form lets a kernel that holds
 // a large LDS region of its own during the point loop (the Euler reverse sweep's state column) hand that region over
 // instead of adding 17 KB per workgroup to it; the caller's threads are past their last access to it (barrier inside).
-template <int NACC>
-__device__ __forceinline__ void emit_partials_in(float (&acc)[NACC], double* __restrict__ part, const Finish& fin, float* lds);
+// `row`: what goes into slot k of this workgroup's fp64 partial row, given the workgroup's sum v of the threads' fp32
+// partials: v itself (RowAsIs, every kernel but one), or v plus a term the workgroup holds in double (the Gram form of the
+// fold closure adds its regulariser to ONE row per problem this way, closure_fold.hpp).
+struct RowAsIs {
+    __device__ __forceinline__ double operator()(int, double v) const { return v; }
+};
+template <int NACC, class Row = RowAsIs>
+__device__ __forceinline__ void emit_partials_in(float (&acc)[NACC], double* __restrict__ part, const Finish& fin, float* lds, Row row = Row());
 
-template <int NACC>
-__device__ __forceinline__ void emit_partials(float (&acc)[NACC], double* __restrict__ part, const Finish& fin) {
+template <int NACC, class Row = RowAsIs>
+__device__ __forceinline__ void emit_partials(float (&acc)[NACC], double* __restrict__ part, const Finish& fin, Row row = Row()) {
     __shared__ float lds[reduce_lds_floats(BLOCK)];
-    emit_partials_in<NACC>(acc, part, fin, lds);
+    emit_partials_in<NACC>(acc, part, fin, lds, row);
 }
 
-template <int NACC>
-__device__ __forceinline__ void emit_partials_in(float (&acc)[NACC], double* __restrict__ part, const Finish& fin, float* lds) {
+template <int NACC, class Row>
+__device__ __forceinline__ void emit_partials_in(float (&acc)[NACC], double* __restrict__ part, const Finish& fin, float* lds, Row row) {
     __shared__ unsigned last_flag;
     const long s = blockIdx.y;
     const int G = gridDim.x;
     double* dst = part + (s * G + blockIdx.x) * NACC;
     if (!fin.fused) {
-        block_reduce_emit_lds<NACC, BLOCK>(acc, lds, [&](int k, double v) { dst[k] = v; });
+        block_reduce_emit_lds<NACC, BLOCK>(acc, lds, [&](int k, double v) { dst[k] = row(k, v); });
         return;
     }
     if (fin.header[0] != WS_MAGIC) {                     // workspace never initialised: fail loudly, touch no ticket
@@ -556,7 +565,7 @@ __device__ __forceinline__ void emit_partials_in(float (&acc)[NACC], double* __r
         // ticket add; the last block makes ONE agent-scope acquire before anybody reads the rows with plain loads.
         // ~3 us per launch dearer than the sc1 form below (a write-back and an invalidate on the critical path of the last
         // block), which is why it is not the default; same sums in the same order, so the same bits (tested).
-        block_reduce_emit_lds<NACC, BLOCK>(acc, lds, [&](int k, double v) { dst[k] = v; });
+        block_reduce_emit_lds<NACC, BLOCK>(acc, lds, [&](int k, double v) { dst[k] = row(k, v); });
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -577,7 +586,7 @@ __device__ __forceinline__ void emit_partials_in(float (&acc)[NACC], double* __r
         return;
     }
     block_reduce_emit_lds<NACC, BLOCK>(acc, lds, [&](int k, double v) {
-        __hip_atomic_store(dst + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(dst + k, row(k, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave has its row out before the ticket
     __syncthreads();

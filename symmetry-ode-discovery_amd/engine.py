@@ -71,6 +71,9 @@ _SIGNATURES = {
     "symode_loss_grad_reversed_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int,
                                                  c_int, c_int, c_void_p, c_void_p, ctypes.c_ulonglong, c_float, c_float, c_void_p,
                                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "symode_loss_grad_reversed_linear_gram": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long,
+                                                      c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_ulonglong, c_float, c_float,
+                                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_loss_grad_latent": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
                                         c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
@@ -644,13 +647,15 @@ class HipEngine:
             raise SymodeError("private workspace too small for this call")
         return loss, grad, ws, 1.0 / (n * d) if inv_count is None else float(inv_count)
 
-    def _closure_call(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, stream, live=None, linear_m=None):
+    def _closure_call(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, stream, live=None, linear_m=None,
+                      gram=None):
         """One closure launch, ready to go: (entry name, its argument tuple, the tensors the arguments point into, what
         the caller gets back).  ``dx`` None: the regulariser alone; ``rev`` None: the MSE alone, else what
         _reversed_operands returned; ``live``: the set of library columns that may hold a coefficient (an int, bit k =
         column k), honoured by the compact-table forms (their _live entries) and without effect elsewhere.
         ``linear_m``: the substitution matrices of a linear action (``linear_action``), fused compact-table form only: the call
-        goes to symode_loss_grad_reversed_linear.  The ONE
+        goes to symode_loss_grad_reversed_linear; ``gram``: with ``linear_m``, the float64 (S, 1, p, p) raw library Gram sums
+        of x: the call goes to symode_loss_grad_reversed_linear_gram.  The ONE
         statement of the closures' C signatures: the eager methods call ``getattr(lib, name)(*args)``, bind_closure
         converts ``args`` once and keeps the call."""
         batched, S, n, d = self._problems(x)
@@ -673,6 +678,14 @@ class HipEngine:
                 head = head[:3] + (self._ptr(jgx), self._ptr(linear_m), n_g)
                 keep += (linear_m,)
                 name, live_arg = "symode_loss_grad_reversed_linear", ((0xFFFFFFFFFFFFFFFF if live is None else int(live)) & 0xFFFFFFFFFFFFFFFF,)
+                if gram is not None:
+                    if not (gram.is_cuda and gram.dtype == torch.float64 and gram.is_contiguous() and gram.numel() == S * n_g * p * p):
+                        raise SymodeError("gram holds (S, 1, p, p) float64 on the device, contiguous")
+                    head = head[:5] + (self._ptr(gram),) + head[5:]
+                    keep += (gram,)
+                    name += "_gram"
+            elif gram is not None:
+                raise SymodeError("gram goes with linear_m")
             elif constj and live is not None:
                 name, live_arg = name + "_live", (int(live) & 0xFFFFFFFFFFFFFFFF,)
         args = head + (S, n, d, order, flags, self._ptr(xi), self._ptr(mask)) + live_arg + (inv,) + ((float(w_sym),) if fused else ()) \
@@ -681,9 +694,9 @@ class HipEngine:
         loss, grad = loss.reshape(S, 2) if fused else loss.reshape(S), grad.reshape(S, d, p)
         return name, args, keep, (loss, grad) if batched else (loss[0], grad[0])
 
-    def _closure(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live=None, linear_m=None):
+    def _closure(self, x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live=None, linear_m=None, gram=None):
         name, args, _, result = self._closure_call(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, self._stream(x),
-                                                   live, linear_m)
+                                                   live, linear_m, gram)
         self._check(getattr(self.lib, name)(*args), name)
         return result
 
@@ -812,8 +825,14 @@ class HipEngine:
         word = int(ws.view(torch.int64)[1].item())
         return bool(word & 16), bool(word & 32)
 
+    @staticmethod
+    def closure_gram(ws):
+        """Did the last fold launch on workspace ``ws`` take the Gram form (closure_fold.hpp: the regulariser from the library
+        Gram, once per problem; SYMODE_FOLD_GRAM=0 turns it off)?  Bit 64 of the word ``closure_body`` reads."""
+        return bool(int(ws.view(torch.int64)[1].item()) & 64)
+
     def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None,
-                           live_columns=None, linear_m=None):
+                           live_columns=None, linear_m=None, gram=None):
         """The closure MSE + w_sym * reversed regulariser in ONE pass (x read once, Theta(x) shared by both terms).
         Shapes as loss_grad / symreg_reversed (jgx may be the compact table of a point-constant Jacobian, as there).
         Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mse, regulariser), grad = d(mse + w_sym * regulariser)/dXi
@@ -824,12 +843,18 @@ class HipEngine:
         ``linear_m``: the float64 (S, 1, p, p) matrices of ``linear_action`` where it found g(x) = J x (jgx the compact table):
         the call goes to symode_loss_grad_reversed_linear, whose kernel reads neither g(x) nor evaluates Theta(g x) -- the
         same closure up to rounding, not bit for bit; where the library's launcher keeps the streamed kernels it is the
-        call without ``linear_m``."""
+        call without ``linear_m``.
+        ``gram``: with ``linear_m``, the float64 (S, 1, p, p) RAW sums G = sum_n Theta(x_n) Theta(x_n)^T of each problem over the
+        points of this call (``aug_gram(x, dx, order)[..., :p, :p]``, contiguous): the call goes to
+        symode_loss_grad_reversed_linear_gram, whose point loop carries the residual alone -- the regulariser and its gradient
+        are a d p p fp64 product per problem.  loss2[:, 0] keeps its bits, the rest agrees up to rounding; where the
+        launcher's table keeps the plain fold kernel, and with SYMODE_FOLD_GRAM=0, it is the call without ``gram``
+        (``closure_gram(ws)`` tells)."""
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
         rev = self._reversed_operands(x, gx, jgx, compact_ok=True)
-        return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live_columns, linear_m)
+        return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live_columns, linear_m, gram)
 
     def loss_grad_latent(self, z, dz, B, y, xi, mask, order, flags=0, w_pair=1.0, inv_count=None, out=None, ws=None):
         """The closure of the latent fit in ONE pass (symode_loss_grad_latent): z, dz, y (S, N, d) or (N, d), B (S, N, d, d)

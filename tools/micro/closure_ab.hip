@@ -18,6 +18,10 @@
 // off this run.
 // `closure_ab foldcheck`: no timing -- the partial rows of every lever arm of every fold instantiation against the parent body's,
 // bit for bit, on grids with full and ragged rounds (the arms the launcher does not route to are compiled only here).
+// `closure_ab foldgram`: the Gram form of the fold kernel (the regulariser from the library Gram, nothing of it in the point
+// loop) beside the shipped fold kernel, its lever arms and ring depth 4, against the order-3 dense fold kernel as the 16-byte
+// floor; before the timing, sum_r and R of every arm's partial rows against the parent body's, bit for bit.
+// closure_fold_gram_pays is read off this run.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -I symmetry-ode-discovery_amd/csrc
 //              -o tools/micro/closure_ab tools/micro/closure_ab.hip
 #include <hip/hip_runtime.h>
@@ -309,6 +313,93 @@ int main(int argc, char** argv) {
         }
         printf("# %d arm(s) differ\n", bad);
         return bad ? 1 : 0;
+    }
+    if (argc > 1 && strcmp(argv[1], "foldgram") == 0) {
+        // The Gram form of the fold kernel (FoldGram: no c, u, U in the point loop) beside the fold kernel the launcher ships for
+        // the same instantiation: plain | + uniform ring | + packed | both, same shapes and passes as `fold`; the order-3 dense fold
+        // kernel of the same pass is the 16-byte floor.  First, no timing: sum_r and the R slots of every partial row of every
+        // Gram arm against the parent body's at w_sym = 0 (where its rows hold R alone), bit for bit, 64 problems x 3 workgroups.
+        double *mt, *gt;
+        CK(hipMalloc(&mt, S * L5::P * L5::P * 8));
+        CK(hipMemset(mt, 0, S * L5::P * L5::P * 8));
+        CK(hipMalloc(&gt, S * L5::P * L5::P * 8));
+        CK(hipMemset(gt, 0, S * L5::P * L5::P * 8));
+        int bad = 0;
+#define COMMA ,
+#define FGK(LIBT, MW) symreg_fold_kernel<LIBT, 2, MW, LV, fold_sgpr<LB>, fold_sgpr<LB>>
+#define FGCHECK(PKB_, SA_)                                                                                                         \
+    {                                                                                                                              \
+        CK(hipMemset(part, 0, nb));                                                                                                \
+        FGK(FoldGram<FoldLevers<LB COMMA PKB_ COMMA SA_>>, fold_gram_minw)<<<dim3(GX, (unsigned)Sc), dim3(BLOCK)>>>(                \
+            x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.0f, part, fin2, LV, gt);                                                     \
+        CK(hipDeviceSynchronize());                                                                                                \
+        CK(hipMemcpy(got.data(), part, nb, hipMemcpyDeviceToHost));                                                                \
+        long diff = 0;                                                                                                             \
+        for (long r_ = 0; r_ < rows; ++r_)                                                                                         \
+            for (int k_ = 0; k_ < NA; ++k_)                                                                                        \
+                if (k_ != 1 && memcmp(&got[r_ * NA + k_], &want[r_ * NA + k_], 8) != 0) ++diff;                                    \
+        bad += diff ? 1 : 0;                                                                                                       \
+        printf("%6ld points  order %d (p = %2d) %s  gram, packed %d  saddr %d: %s\n", Nx, LB::ORDER, LB::P, SP ? "odd set" : "dense  ", \
+               (int)PKB_, (int)SA_, diff ? "DIFFERENT" : "same sum_r and R");                                                      \
+    }
+#define FGCRUN(ORDER, SPARSE)                                                                                                      \
+    {                                                                                                                              \
+        using LB = Library<2, ORDER, 0>;                                                                                           \
+        constexpr unsigned long long LV = SPARSE ? odd_degree_columns<LB>() : ~0ull;                                               \
+        constexpr bool SP = SPARSE;                                                                                                \
+        constexpr int NA = 2 + D * LB::P;                                                                                          \
+        const size_t nb = rows * NA * sizeof(double);                                                                              \
+        CK(hipMemset(part, 0, nb));                                                                                                \
+        FGK(LB, fold_minw<LB COMMA SP>)<<<dim3(GX, (unsigned)Sc), dim3(BLOCK)>>>(x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.0f, part, fin2, LV); \
+        CK(hipDeviceSynchronize());                                                                                                \
+        CK(hipMemcpy(want.data(), part, nb, hipMemcpyDeviceToHost));                                                               \
+        FGCHECK(false, false) FGCHECK(false, true) FGCHECK(true, false) FGCHECK(true, true)                                        \
+    }
+        {
+            const long Sc = 64, GX = 3, rows = GX * Sc;
+            std::vector<double> want(rows * (2 + D * L5::P)), got(want.size());
+            for (const long Nx : {50000L, 12288L}) {
+                FGCRUN(1, false) FGCRUN(2, false) FGCRUN(3, false) FGCRUN(4, false) FGCRUN(5, false)
+                FGCRUN(4, true) FGCRUN(5, true)
+            }
+            printf("# %d arm(s) differ\n", bad);
+            if (bad) return 1;
+        }
+        printf("# fold kernel shipped for the instantiation | Gram form: plain | + scalar addressing | + packed | both | both, ring 4: "
+               "us per launch (min of 3 rounds of 5), three passes; floor = the order-3 dense fold kernel of the pass\n");
+        const long shapes[2][2] = {{S, NB}, {64, 50000}};
+#define FGARM(PKB_, SA_, RG_)                                                                                                      \
+    time_us([&] { symreg_fold_kernel<FoldGram<FoldLevers<LB, PKB_, SA_>>, RG_, fold_gram_minw, LV, fold_sgpr<LB>, fold_sgpr<LB>>   \
+                      <<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>(x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV, gt); }, 5)
+#define FGRUN(ORDER, SPARSE)                                                                                                       \
+    {                                                                                                                              \
+        using LB = Library<2, ORDER, 0>;                                                                                           \
+        constexpr unsigned long long LV = SPARSE ? odd_degree_columns<LB>() : ~0ull;                                               \
+        constexpr bool SP = SPARSE, PKS = closure_fold_pk_pays<LB, SP>, SAS = closure_fold_saddr_pays<LB, SP>;                      \
+        const double a_ = time_us([&] { symreg_fold_kernel<FoldLevers<LB, PKS, SAS>, 2, fold_minw<LB, SP>, LV, fold_sgpr<LB>, fold_sgpr<LB>> \
+                                            <<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>(x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, LV); }, 5); \
+        const double b_ = FGARM(false, false, 2), c_ = FGARM(false, true, 2), d_ = FGARM(true, false, 2), e_ = FGARM(true, true, 2), \
+                     f_ = FGARM(true, true, 4);                                                                                    \
+        printf("pass %d  %5ld x %6ld  order %d (p = %2d) %s  shipped %8.1f us  gram %8.1f  +saddr %8.1f  +packed %8.1f  both %8.1f  both ring4 %8.1f"   \
+               "  | /shipped %.3f %.3f %.3f %.3f %.3f  | /floor %.3f %.3f %.3f %.3f %.3f\n",                                       \
+               pass, Sx, Nx, ORDER, LB::P, SPARSE ? "odd set" : "dense  ", a_, b_, c_, d_, e_, f_, b_ / a_, c_ / a_, d_ / a_, e_ / a_, f_ / a_, \
+               b_ / floor_, c_ / floor_, d_ / floor_, e_ / floor_, f_ / floor_);                                                   \
+    }
+        for (int pass = 0; pass < 3; ++pass)
+            for (const auto& sh : shapes) {
+                const long Sx = sh[0], Nx = sh[1];
+                const int gxw = grid_x_for(Nx, Sx, 2, 512);
+                if ((long)gxw * Sx > max_rows) {
+                    fprintf(stderr, "grid %d x %ld needs more partial rows than the workspace holds\n", gxw, Sx);
+                    return 1;
+                }
+                const double floor_ = time_us([&] { symreg_fold_kernel<L3, 2, 3, ~0ull, fold_sgpr<L3>, fold_sgpr<L3>>
+                                                        <<<dim3(gxw, (unsigned)Sx), dim3(BLOCK)>>>(x, dx, jgx, mt, Nx, true, xi5, nullptr, 0.1f, part, fin2, ~0ull); }, 5);
+                printf("pass %d  %5ld x %6ld  floor: order 3 dense fold kernel %8.1f us\n", pass, Sx, Nx, floor_);
+                FGRUN(4, false) FGRUN(5, false) FGRUN(4, true) FGRUN(5, true) FGRUN(3, false) FGRUN(2, false) FGRUN(1, false)
+            }
+        CK(hipDeviceSynchronize());
+        return 0;
     }
     if (argc > 1 && strcmp(argv[1], "fold") == 0) {
         double* mt;                                 // (S, p, p) substitution matrices: the identity (the timing does not read their values)
