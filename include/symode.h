@@ -902,6 +902,32 @@ int symode_stlsq_sweep_minnorm(const double* aug_gram, long n_sets, long n_probl
                                float* var_out, unsigned char* mask_out, int* passes_out, int* near_out, int* fell_out,
                                int* trunc_out, int* rank_out, void* stream);
 
+/* symode_stlsq_sweep with the reversed symmetry regulariser, EquivSINDy-r: the same threshold loop, but per pass the
+ * minimiser of mse + w_sym * reg on the support M, which is ONE joint linear system over all equation rows because the
+ * regulariser's matrix couples them.  aug_gram, n_sets, n_problems, gamma, threshold, max_iter, near_band, n_points,
+ * mask_out, passes_out and near_out are symode_stlsq_sweep's.  rev_gram (n_sets, d p, d p) fp64 as
+ * symode_symreg_reversed_gram / _gather leave it: raw sums, rows and columns in Xi's (d, p) row-major order; problem s
+ * reads set s % n_sets of both.  hyper NULL, or (n_problems, 3) fp32 [gamma, threshold, w_sym], row s in place of the three
+ * scalars.  The launch takes the three values in fp32 with or without a table, so problem (g, k) of a grid is bit for bit
+ * seed k of the scalar launch with point g's values.
+ * Per pass: the support in ascending (j, k), n entries (n = 0: the zero solution, which ends the problem);
+ * A[a, b] = [j_a == j_b] (Gtt[k_a, k_b] + gamma^2 [k_a == k_b]) + w_sym R[j_a p + k_a, j_b p + k_b] in fp64, the upper triangle
+ * mirrored, b[a] = Gty[k_a, j_a] (the 1 / (N d) of mse and reg cancels); pivoted Cholesky and substitutions as
+ * symode_stlsq_sweep_constrained (one statement, csrc/stlsq_joint.hpp): a pivot that is not > pivot_floor * (first pivot)
+ * sets fell_out[s] = 1 and ENDS problem s (its other outputs are then unspecified), the caller solves it on the host;
+ * Xi = (float) of the solution scattered into (d, p), zeros off the support; strict > (float)threshold on the still-active
+ * entries.  xi_out (n_problems, d, p) fp32: the last solve.  d <= 4, p <= 64, d p <= 64.
+ * Refused before any GPU work: d < 1, d > 4, p < 1, p > 64, d p > 64, max_iter < 1, n_sets < 1, n_problems < n_sets or >= 2^31,
+ * hyper == NULL with n_problems != n_sets, gamma, threshold, w_sym or pivot_floor < 0 or not finite (SYMODE_E_BADSIZE); any
+ * pointer but hyper NULL (SYMODE_E_NULLPTR); aug_gram or rev_gram not 8-byte, hyper or an fp32 / int output not 4-byte aligned
+ * (SYMODE_E_ALIGN).
+ * replaces: nothing in the reference; the stationarity condition of train.py:663-679 (sym_reg_type 'r') on the data of
+ * train.py:626-629, thresholded as train.py:872-887. */
+int symode_stlsq_sweep_symreg(const double* aug_gram, const double* rev_gram, long n_sets, long n_problems, int d, int p,
+                              long n_points, const float* hyper, double gamma, double threshold, double w_sym, int max_iter,
+                              double near_band, double pivot_floor, float* xi_out, unsigned char* mask_out, int* passes_out,
+                              int* near_out, int* fell_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 #include "quad_closure.hpp"
 #include "stlsq.hpp"
 #include "stlsq_constrained.hpp"
+#include "stlsq_symreg.hpp"
 #include "weak_normal.hpp"
 
 using namespace symode;
@@ -591,6 +592,27 @@ int symode_stlsq_sweep_minnorm(const double* aug_gram, long n_sets, long n_probl
     return (int)launch_stlsq_minnorm(aug_gram, n_sets, n_problems, d, p, q_solve, q_xi, r, allow_constant ? 1 : 0, hyper, gamma,
                                      threshold, max_iter, near_band, rcond, xi_out, var_out, mask_out, passes_out, near_out, fell_out,
                                      trunc_out, rank_out, (hipStream_t)stream);
+}
+
+int symode_stlsq_sweep_symreg(const double* aug_gram, const double* rev_gram, long n_sets, long n_problems, int d, int p,
+                              long n_points, const float* hyper, double gamma, double threshold, double w_sym, int max_iter,
+                              double near_band, double pivot_floor, float* xi_out, unsigned char* mask_out, int* passes_out,
+                              int* near_out, int* fell_out, void* stream) {
+    (void)n_points;                     // as symode_stlsq_sweep: only gelsy's rank rule would read it
+    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || (long)d * p > STLSQS_MAX_DP || max_iter < 1) return SYMODE_E_BADSIZE;
+    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
+    if (!hyper && n_problems != n_sets) return SYMODE_E_BADSIZE;
+    const double values[4] = {(double)(float)gamma, (double)(float)threshold, (double)(float)w_sym, pivot_floor};   // as the launch holds them
+    for (const double v : values)
+        if (!(v >= 0.0) || !std::isfinite(v)) return SYMODE_E_BADSIZE;
+    if (!aug_gram || !rev_gram || !xi_out || !mask_out || !passes_out || !near_out || !fell_out) return SYMODE_E_NULLPTR;
+    if (misaligned(aug_gram, 8) || misaligned(rev_gram, 8) || misaligned(hyper, 4) || misaligned(xi_out, 4) ||
+        misaligned(passes_out, 4) || misaligned(near_out, 4) || misaligned(fell_out, 4))
+        return SYMODE_E_ALIGN;
+    // the three values in fp32, as a row of the table holds them
+    return (int)launch_stlsq_symreg(aug_gram, rev_gram, n_sets, n_problems, d, p, hyper, (float)gamma, (float)threshold, (float)w_sym,
+                                    max_iter, near_band, pivot_floor, xi_out, mask_out, passes_out, near_out, fell_out,
+                                    (hipStream_t)stream);
 }
 
 int symode_symreg_reversed(const float* x, const float* gx_, const float* jgx, int n_g, long n, int d, int order,

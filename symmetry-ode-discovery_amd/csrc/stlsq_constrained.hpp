@@ -7,6 +7,7 @@
 #include "kernels.hpp"
 #include "laic1.hpp"
 #include "stlsq.hpp"
+#include "stlsq_joint.hpp"
 
 namespace symode {
 
@@ -38,7 +39,8 @@ inline size_t stlsqc_minnorm_lds_bytes(int R) { return stlsqc_lds_bytes(R) + (si
 //             active k ascending, lane b forms u_b = sum over active l ascending of (Gtt[k, l] + gamma^2 [k == l]) Qe[(j,l), b]
 //             and adds Qe[(j,k), a] u_b into Gq[a, b] for a <= b, Qe[(j,k), b] Gty[k, j] into cq[b].  The lower triangle is
 //             the mirror of the upper one, so Gq is exactly symmetric;
-//   solve     stlsq_sweep_kernel's pivoted Cholesky and substitutions, except that a pivot which is not
+//   solve     stlsq_sweep_kernel's pivoted Cholesky and substitutions (stated for joint systems in stlsq_joint.hpp, which
+//             stlsq_symreg_kernel shares), except that a pivot which is not
 //             > pivot_floor * (first pivot) (or not > 0) flags the problem (fell) and ends it;
 //   Xi        beta32 = (float) of the solution in its r' slots (0 elsewhere); lane k forms Xi[j, k] = sum over c < r ascending
 //             of q_xi[(j p + k), c] beta32[c] in fp32, plus const32[j] at k = 0 when allow_constant;
@@ -143,65 +145,9 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
             for (int a = 0; a < n; ++a)
                 if (on && a < lane) A[lane * R + a] = A[a * R + lane];
             stlsq_wave_sync();
-            // ---- factor and solve (stlsq_sweep_kernel's, rows of stride R, and the pivot floor)
-            int orig = lane;
-            double dg = on ? A[lane * R + lane] : 0.0;
-            double first = 0.0;
-            int fact = n;
-            for (int kk = 0; kk < n; ++kk) {
-                double bv = dg;
-                int bi = (lane >= kk && lane < n) ? lane : WAVE;
-#pragma unroll
-                for (int off = WAVE / 2; off > 0; off /= 2) {
-                    const double ov = __shfl_xor(bv, off, WAVE);
-                    const int oi = __shfl_xor(bi, off, WAVE);
-                    if (oi < WAVE && (bi == WAVE || ov > bv || (ov == bv && oi < bi))) {
-                        bv = ov;
-                        bi = oi;
-                    }
-                }
-                const int jp = __builtin_amdgcn_readfirstlane(bi);
-                if (jp != kk) {
-                    const int src = lane == kk ? jp : (lane == jp ? kk : lane);
-                    orig = __shfl(orig, src, WAVE);
-                    dg = __shfl(dg, src, WAVE);
-                    c = __shfl(c, src, WAVE);
-                }
-                const double dkk = stlsq_lane(dg, kk);
-                if constexpr (MINNORM) {
-                    if (!(dkk > 0.0)) {
-                        fact = kk;
-                        break;
-                    }
-                } else {
-                    if (kk == 0) first = dkk;
-                    if (!(dkk > pivot_floor * first) || !(dkk > 0.0)) {
-                        bad = true;
-                        break;
-                    }
-                }
-                const double rr = sqrt(dkk);
-                const int jo = __builtin_amdgcn_readlane(orig, kk);
-                const bool rest = lane > kk && lane < n;
-                double Rt = 0.0;
-                if (rest) {
-                    Rt = A[jo * R + orig] / rr;
-                    A[jo * R + orig] = Rt;
-                }
-                if (lane == kk) A[jo * R + jo] = rr;
-                for (int a = kk + 1; a < n; ++a) {
-                    const double Ra = stlsq_lane(Rt, a);
-                    const int oa = __builtin_amdgcn_readlane(orig, a);
-                    if (rest) A[oa * R + orig] -= Ra * Rt;
-                }
-                const double q = stlsq_lane(c, kk) / rr;
-                if (rest) {
-                    c -= Rt * q;
-                    dg -= Rt * Rt;
-                }
-                if (lane == kk) c = q;
-                stlsq_wave_sync();
-            }
+            // ---- factor and solve (stlsq_joint.hpp: stlsq_sweep_kernel's, rows of stride R, and the pivot floor)
+            int orig, fact;
+            bad = stlsq_joint_factor<MINNORM>(A, R, n, lane, orig, c, pivot_floor, fact);
             if constexpr (MINNORM) {
                 // ---- rank: lane i holds element i of the two approximate singular vectors
                 stlsq_wave_sync();
@@ -296,14 +242,7 @@ __global__ __launch_bounds__(WAVE) void stlsq_constrained_kernel(const double* _
                 }
             }
             if (!bad) {
-                for (int i = (!MINNORM || rank == n) ? n - 1 : -1; i >= 0; --i) {
-                    const int jo = __builtin_amdgcn_readlane(orig, i);
-                    const double prod = (lane > i && lane < n) ? A[jo * R + orig] * c : 0.0;
-                    double acc = stlsq_lane(c, i);
-                    for (int t = i + 1; t < n; ++t) acc -= stlsq_lane(prod, t);
-                    const double y = acc / A[jo * R + jo];
-                    if (lane == i) c = y;
-                }
+                if (!MINNORM || rank == n) stlsq_joint_back(A, R, n, lane, orig, c);
                 if (on) var[col[orig]] = (float)c;
             }
         }

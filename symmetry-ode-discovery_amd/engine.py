@@ -145,6 +145,9 @@ _SIGNATURES = {
     "symode_stlsq_sweep_minnorm": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_long, c_void_p, c_void_p, c_int, c_int,
                                            c_void_p, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "symode_stlsq_sweep_symreg": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_long, c_void_p, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
@@ -177,6 +180,7 @@ class TrainerGrid(ctypes.Structure):
 
 
 STLSQ_HYPER = 2                                             # columns of a symode_stlsq_sweep hyper row: gamma, threshold
+STLSQ_SYMREG_HYPER = 3                                      # ... of a symode_stlsq_sweep_symreg row: gamma, threshold, w_sym
 
 ADAM_PLAIN, ADAM_REVERSED, ADAM_LATENT = 0, 1, 2              # SYMODE_ADAM_* of include/symode.h
 ADAM_HYPER = 4                                              # columns of a hyper row: lr, w_reg, threshold, w_sym
@@ -1086,6 +1090,57 @@ class HipEngine:
             self._ptr(var), self._ptr(mask), self._ptr(passes), self._ptr(near), self._ptr(fell), self._ptr(trunc), self._ptr(rank),
             self._stream(G)),
             "symode_stlsq_sweep_minnorm")
+        if to_host:
+            import numpy as np
+            return parts(buf.cpu().numpy(), np.float32, np.int32)
+        return parts(buf, torch.float32, torch.int32)
+
+    def stlsq_sweep_symreg(self, G, R, n_points, gamma, threshold, w_sym, max_iter, hyper=None, n_problems=None, *, d, pivot_floor,
+                           near_band=1e-4, to_host=False, tail=None):
+        """``stlsq_sweep`` with the reversed symmetry regulariser in ONE launch (symode_stlsq_sweep_symreg): per pass the
+        minimiser of mse + w_sym * reg on the support, one joint system in the n <= d p <= 64 active coefficients.  G,
+        ``n_problems``, ``d``, ``near_band``, ``to_host`` and ``tail`` as ``stlsq_sweep``; R (n_sets, d p, d p) fp64 on the device
+        (``symreg_reversed_gram(_gather)``: raw sums); ``hyper`` (n_problems, 3) fp32 on the device, row s = problem s's
+        [gamma, threshold, w_sym]; ``pivot_floor`` as ``stlsq_sweep_constrained``.  The launch takes gamma, threshold and w_sym in
+        fp32 with or without a table.
+        Returns (Xi (n_problems, d, p) fp32 -- of the last solve, zeros off its support --, mask uint8, passes, near, fell int32)
+        and, behind them, the tail; a problem with ``fell`` set is possibly rank deficient and the host's to solve."""
+        G = self._dev(G, "G", torch.float64)
+        d = int(d)
+        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
+            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
+        n_sets, p = G.shape[0], G.shape[1] - d
+        R = self._dev(R, "R", torch.float64)
+        if tuple(R.shape) != (n_sets, d * p, d * p) or R.device != G.device:
+            raise SymodeError(f"R must be (n_sets, d p, d p) = ({n_sets}, {d * p}, {d * p}) fp64 on {G.device}, got {tuple(R.shape)}")
+        if hyper is not None:
+            hyper = self._dev(hyper, "hyper")
+            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_SYMREG_HYPER or hyper.device != G.device:
+                raise SymodeError(f"hyper must be (n_problems, {STLSQ_SYMREG_HYPER}) fp32 on {G.device}: one row [gamma, threshold, "
+                                  f"w_sym] per problem")
+            if n_problems is not None and int(n_problems) != hyper.shape[0]:
+                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
+            n_problems = hyper.shape[0]
+        S = n_sets if n_problems is None else int(n_problems)
+        # one allocation, [xi | passes | near | fell | mask], so that a caller on the host fetches everything in ONE copy
+        cuts = [0, 4 * S * d * p, 4 * S * (d * p + 1), 4 * S * (d * p + 2), 4 * S * (d * p + 3), 4 * S * (d * p + 3) + S * d * p]
+        at = -(-cuts[-1] // 4) * 4                                      # the tail, int32-aligned behind the mask
+        n_tail = 0 if tail is None else 4 * tail.numel()
+        buf = torch.empty(max(at + n_tail, 0), dtype=torch.uint8, device=G.device)
+
+        def parts(b, f32, i32):
+            xi, passes, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
+            five = xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32)
+            return five if tail is None else five + (b[at:at + n_tail].view(i32),)
+
+        xi, mask, passes, near, fell = parts(buf, torch.float32, torch.int32)[:5]
+        if tail is not None:
+            buf[at:at + n_tail].view(torch.int32).copy_(self._dev(tail, "tail", torch.int32).reshape(-1))
+        self._check(self.lib.symode_stlsq_sweep_symreg(
+            self._ptr(G), self._ptr(R), n_sets, S, d, p, int(n_points), self._ptr(hyper), float(gamma), float(threshold), float(w_sym),
+            int(max_iter), float(near_band), float(pivot_floor), self._ptr(xi), self._ptr(mask), self._ptr(passes), self._ptr(near),
+            self._ptr(fell), self._stream(G)),
+            "symode_stlsq_sweep_symreg")
         if to_host:
             import numpy as np
             return parts(buf.cpu().numpy(), np.float32, np.int32)

@@ -63,6 +63,14 @@ parameters (symode_stlsq_sweep_constrained) -- one gather launch and one solve l
 the minimum-norm rule inside the launch instead of flagging the seed for the host loop.  The summary gains one line that
 counts the problems with rank-truncated passes; without the flag every word printed is what it was.
 
+``--symreg_stlsq`` (with --method stlsq --device_stlsq --w_sym_reg > 0 --sym_reg_type r --load_laligan ... --fix_laligan) is that
+device fit with the reversed symmetry regulariser, EquivSINDy-r: on a fixed batch the regulariser is the quadratic form
+v^T R v, so the minimiser of mse + w_sym * reg on a support is the solution of one linear system and the fit is sequential
+thresholding without an optimiser.  [G | R | count] are built as under --gram_closure (one gather launch each, ONE all-reduce),
+``SeedSweepSTLSQ.solve(device=True, rev=(R, w_sym))`` solves per pass ONE joint system in the d p <= 64 coefficients
+(symode_stlsq_sweep_symreg); w_sym = w_sym_reg / w_sindy_x.  Under the flag --stlsq_grid also takes w_sym_reg=v1,v2,...
+(values > 0).  Without the flag ``--method stlsq --w_sym_reg > 0`` is refused as it always was.
+
 ``--wsindy`` sweeps the weak-SINDy fit of ``main_wsindy`` (the `for i in {0..49}; do python main_wsindy.py --seed $i` loops):
 sweep seed n reads the window main_wsindy --seed n reads (``sweep.weak_windows``), all windows are contracted and turned into
 their normal matrices by ONE call (symode_weak_normal_windows) and fitted by ONE symode_stlsq_sweep launch
@@ -131,6 +139,8 @@ GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold'
 # --lbfgs_grid name -> DeviceTrainer(hyper=) key
 LBFGS_GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'threshold', 'w_sym_reg': 'w_sym'}
 STLSQ_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg'}      # --stlsq_grid name -> SeedSweepSTLSQ.solve(hyper=) key
+# ... under --symreg_stlsq: the weight of the reversed regulariser as a third axis
+SYMREG_STLSQ_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg', 'w_sym_reg': 'w_sym'}
 WSINDY_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg'}     # --wsindy_grid name -> SeedSweepWSINDy.solve(hyper=) key
 MAX_GRID_PROBLEMS = 65535                                  # problems of one device trainer
 
@@ -166,7 +176,7 @@ def _grid_problem(problem, n_seeds):
 
 
 def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None, device_stlsq=False,
-             stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False, min_norm_stlsq=False):
+             stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False, min_norm_stlsq=False, symreg_stlsq=False):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
@@ -178,9 +188,16 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     and replace them -- the weak configs set no --sindy_optimizer, and the parser's default must not route them anywhere.
     ``equiv_stlsq``: the ``--equiv_stlsq`` flag; off, every answer is what it was.  On, its own rules (``_refusal_equiv_stlsq``)
     come first and the rule that keeps --eq_constraint out of --method stlsq does not apply.
-    ``min_norm_stlsq``: the ``--min_norm_stlsq`` flag, a mode of --equiv_stlsq and refused by name without it."""
+    ``min_norm_stlsq``: the ``--min_norm_stlsq`` flag, a mode of --equiv_stlsq and refused by name without it.
+    ``symreg_stlsq``: the ``--symreg_stlsq`` flag; off, every answer is what it was.  On, its own rules
+    (``_refusal_symreg_stlsq``) come first, the rule that keeps the symmetry regulariser out of --method stlsq does not apply,
+    and --stlsq_grid reads SYMREG_STLSQ_GRID_NAMES."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
+    if symreg_stlsq:
+        why = _refusal_symreg_stlsq(args, method, device_stlsq, wsindy or wsindy_grid, equiv_stlsq, min_norm_stlsq)
+        if why is not None:
+            return why
     if min_norm_stlsq and not equiv_stlsq:
         return _refusal_min_norm_stlsq()
     if equiv_stlsq:
@@ -218,7 +235,7 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
                 'block of seeds, python -m symode_amd.main_sweep --seed <first> --n_seeds <count> ... per process')
     if engine is None and str(args.get('device')) == 'cpu':
         return 'symode_amd runs the SINDy path on the GPU only (no CPU fallback): a HIP device is required'
-    if method == 'stlsq' and args['w_sym_reg'] > 0:
+    if method == 'stlsq' and args['w_sym_reg'] > 0 and not symreg_stlsq:
         return '--method stlsq sweeps the plain least-squares fit (use --method lbfgs with the symmetry regulariser)'
     if method == 'stlsq' and args.get('eq_constraint') and not equiv_stlsq:
         return '--method stlsq sweeps the unconstrained library (use --method lbfgs for EquivSINDy-c)'
@@ -226,7 +243,8 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
         return ('--device_shuffle draws the epoch order of the minibatch Adam fit inside its launch: it needs '
                 '--sindy_optimizer adam (with the default --method lbfgs), L-BFGS and STLSQ fits have no epoch order')
     if device_stlsq or stlsq_grid:
-        why = _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid)
+        why = _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid,
+                                    SYMREG_STLSQ_GRID_NAMES if symreg_stlsq else STLSQ_GRID_NAMES)
         if why is not None:
             return why
     if grid and lbfgs_grid:
@@ -261,6 +279,7 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     return None
 
 
+SYMREG_STLSQ_MAX_COEFS = 64                                # d p of symode_stlsq_sweep_symreg: one lane per coefficient
 EQUIV_STLSQ_MAX_PARAMS = 64                                # r' of symode_stlsq_sweep_constrained: one lane per free parameter
 
 
@@ -295,8 +314,45 @@ def _refusal_min_norm_stlsq():
             '--device_stlsq --equiv_stlsq --eq_constraint; the unconstrained sweep meets no such systems')
 
 
-def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid):
-    """The rules of --device_stlsq and --stlsq_grid (``_refusal``, which has applied the rules of --method stlsq itself)."""
+def _refusal_symreg_stlsq(args, method, device_stlsq, wsindy, equiv_stlsq, min_norm_stlsq):
+    """The rules of --symreg_stlsq that the arguments alone decide (d p <= 64 is known once the library is: ``_fit_stlsq``)."""
+    if wsindy:
+        return ('--symreg_stlsq is the regularised fit of --method stlsq: the weak-SINDy sweep (--wsindy) has no symmetry '
+                'regulariser (drop one of them)')
+    if method != 'stlsq':
+        return ('--symreg_stlsq is the sequential-threshold least-squares sweep with the reversed symmetry regulariser: it '
+                'needs --method stlsq')
+    if not device_stlsq:
+        return ('--symreg_stlsq needs --device_stlsq: the regularised fit of the sweep runs on the device (the host route of '
+                '--method stlsq sweeps the plain least-squares fit)')
+    if args.get('eq_constraint') or equiv_stlsq:
+        return ('--symreg_stlsq does not go with --eq_constraint / --equiv_stlsq: the regularised fit under the equivariance '
+                'constraint is not covered (use --method lbfgs)')
+    if min_norm_stlsq:
+        return ('--symreg_stlsq does not go with --min_norm_stlsq: the rank-revealing mode belongs to the constrained launch '
+                '(--equiv_stlsq)')
+    if not args['w_sym_reg'] > 0:
+        return ('--symreg_stlsq needs --w_sym_reg > 0: it is the fit with the symmetry regulariser (drop --symreg_stlsq for the '
+                'plain least-squares fit)')
+    if args['sym_reg_type'] != 'r':
+        return (f"--symreg_stlsq covers the reversed symmetry regulariser only (--sym_reg_type r), not '{args['sym_reg_type']}': "
+                'the other regularisers are not quadratic in the coefficients')
+    if args['load_laligan'] is None:
+        return ('--symreg_stlsq needs --load_laligan: the regulariser\'s matrices are built from the group action of a saved '
+                'LaLiGAN')
+    if not args['fix_laligan']:
+        return '--symreg_stlsq needs --fix_laligan: g(x), J_g(x) are computed once, from a frozen LaLiGAN'
+    if args.get('lstsq_driver') == 'gelsy':
+        return ('--symreg_stlsq fits with the full-rank driver (gels) only: the rank rule of --lstsq_driver gelsy has no '
+                'regularised form')
+    if args['use_latent']:
+        return '--symreg_stlsq does not cover latent fits (--use_latent)'
+    return None
+
+
+def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid, names=STLSQ_GRID_NAMES):
+    """The rules of --device_stlsq and --stlsq_grid (``_refusal``, which has applied the rules of --method stlsq itself).
+    ``names``: the axes of the grid (SYMREG_STLSQ_GRID_NAMES under --symreg_stlsq, whose w_sym_reg values must be > 0)."""
     given = ' and '.join(flag for flag, on in (('--device_stlsq', device_stlsq), ('--stlsq_grid', stlsq_grid)) if on)
     if method != 'stlsq':
         return (f'{given}: the device fit of the sequential-threshold least-squares sweep and its grid need --method stlsq '
@@ -313,10 +369,13 @@ def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq,
                 'host route (drop --device_stlsq)')
     if not stlsq_grid:
         return None
-    axes, why = _parse_grid(stlsq_grid, STLSQ_GRID_NAMES, '--stlsq_grid')
+    axes, why = _parse_grid(stlsq_grid, names, '--stlsq_grid')
     if why is not None:
         return why
     for name, axis in axes:
+        if name == 'w_sym_reg' and not all(v > 0 for v in axis):
+            return (f'--stlsq_grid w_sym_reg={",".join(f"{v:g}" for v in axis)}: every value must be > 0 (a sweep without the '
+                    'regulariser is another run, without --symreg_stlsq)')
         if not all(v >= 0 for v in axis):
             return f'--stlsq_grid {name}={",".join(f"{v:g}" for v in axis)}: every value must be >= 0'
     n_points = int(np.prod([len(axis) for _, axis in axes]))
@@ -397,12 +456,34 @@ def _fit_stlsq(ctx):
         fit = dict(coef=coef)
         if getattr(ctx, 'min_norm_stlsq', False):
             fit['min_norm'] = True
+    names, column, laligan = STLSQ_GRID_NAMES, {}, None
+    if getattr(ctx, 'symreg_stlsq', False):
+        # --symreg_stlsq: library and LaLiGAN are the template's, as the L-BFGS sweep builds it
+        template, _, laligan = _template(ctx)
+        lib = (template.poly_order, template.include_sine, template.include_exp)
+        n_coef = template.latent_dim * template.coef.p
+        if n_coef > SYMREG_STLSQ_MAX_COEFS:
+            raise SystemExit(f'--symreg_stlsq: the library has d p = {template.latent_dim} x {template.coef.p} = {n_coef} '
+                             f'coefficients, the device fit takes at most {SYMREG_STLSQ_MAX_COEFS}; use --method lbfgs')
+    rows = _rows(ctx)
     sw = SeedSweepSTLSQ(ctx.x_all, ctx.dx_all, *lib, n_seeds=len(ctx.seeds), subsample=args['lbfgs_subsample'], seed0=args['seed'],
-                        group=ctx.group, engine=ctx.engine, idx=_rows(ctx), idx_sorted=True)
+                        group=ctx.group, engine=ctx.engine, idx=rows, idx_sorted=True)
+    if laligan is not None:
+        # [G | R | count] as _fit_lbfgs builds them under --gram_closure: no per-seed copy of the points, ONE all-reduce
+        from .gram_closure import GramStatistics
+        x_used, gx, jgx, table, used = symmetry_operands(ctx.x_all, rows, *laligan)
+        stats = GramStatistics(len(ctx.seeds), template.latent_dim, template.poly_order, template.flags, regulariser=True,
+                               device=ctx.dev, **ctx.kw)
+        stats.add_gathered(x_used, ctx.dx_all[used].contiguous(), table, gx, jgx)
+        if ctx.group is not None:
+            stats.all_reduce(ctx.group)
+        sw.set_grams(stats.G, stats.count)
+        fit = dict(rev=(stats.R, args['w_sym_reg'] / args['w_sindy_x']))     # the weight relative to the MSE, as _fit_lbfgs
+        names, column = SYMREG_STLSQ_GRID_NAMES, {'w_sym_reg': lambda v: v / args['w_sindy_x']}
     n_seeds, points = len(ctx.seeds), getattr(ctx, 'grid', None)
     if points is not None:
         # --stlsq_grid: G points on common seeds, problem g * n_seeds + k = point g on seed k's matrices
-        hyper = {STLSQ_GRID_NAMES[name]: [point[name] for point in points for _ in ctx.seeds] for name in points[0]}
+        hyper = {names[name]: [column.get(name, float)(point[name]) for point in points for _ in ctx.seeds] for name in points[0]}
         Xi, mask, passes = sw.solve(args['w_sindy_reg'], args['threshold'], max_iter=max(1, args['num_epochs']),
                                     lstsq_driver=args.get('lstsq_driver'), device=True, hyper=hyper, **fit)
         lines = [f'{n_seeds} seeds x {sw.n_points} points (over {ctx.world} rank(s)), {len(points)} grid points on their Gram matrices']
@@ -709,12 +790,13 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     wsindy = _pop_flag(argv, '--wsindy')
     equiv_stlsq = _pop_flag(argv, '--equiv_stlsq')
     min_norm_stlsq = _pop_flag(argv, '--min_norm_stlsq')
+    symreg_stlsq = _pop_flag(argv, '--symreg_stlsq')
     fold_linear_action = _pop_flag(argv, '--fold_linear_action')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
                    device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None, wsindy=wsindy, wsindy_grid=wsindy_grid or None,
-                   equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq)
+                   equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -735,14 +817,14 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
                           engine=engine, kw={} if engine is None else {'engine': engine}, grid=None,
                           device_stlsq=device_stlsq, fold_linear_action=fold_linear_action, train=train_dataset,
-                          equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq)
+                          equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq)
     if wsindy_grid:
         ctx.grid_names = WSINDY_GRID_NAMES
         ctx.grid_axes = _parse_grid(wsindy_grid, WSINDY_GRID_NAMES, '--wsindy_grid')[0]
         ctx.grid = _grid_points(ctx.grid_axes)
     elif stlsq_grid:
-        ctx.grid_names = STLSQ_GRID_NAMES
-        ctx.grid_axes = _parse_grid(stlsq_grid, STLSQ_GRID_NAMES, '--stlsq_grid')[0]
+        ctx.grid_names = SYMREG_STLSQ_GRID_NAMES if symreg_stlsq else STLSQ_GRID_NAMES
+        ctx.grid_axes = _parse_grid(stlsq_grid, ctx.grid_names, '--stlsq_grid')[0]
         ctx.grid = _grid_points(ctx.grid_axes)
     elif grid or lbfgs_grid:
         ctx.grid_names = GRID_NAMES if grid else LBFGS_GRID_NAMES

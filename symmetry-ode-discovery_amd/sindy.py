@@ -383,6 +383,42 @@ def stlsq_constrained_from_gram(G, N, mask, gamma, d, coef, driver="gels"):
     return xi, full, yy - 2 * b @ cq + b @ Gq @ b
 
 
+def stlsq_symreg_system(G, R, mask, gamma, w_sym, d):
+    """(A (n, n), b (n,)) of the pass with the reversed symmetry regulariser on the support ``mask`` (d, p), the support in
+    ascending (j, k): A = (blockdiag(Gtt + gamma^2 I) + w_sym R)[M, M], b = Gty[M].  G (p+d, p+d) and R (d p, d p) are raw
+    sums over the same points, so the 1 / (N d) of mse and reg cancels (gram_closure's quadratic form)."""
+    p = G.shape[0] - d
+    Gtt = G[:p, :p] + (gamma * gamma) * np.eye(p)
+    flat = np.asarray(mask, dtype=bool).reshape(-1)
+    Gb = np.zeros((d * p, d * p))
+    for j in range(d):
+        Gb[j * p:(j + 1) * p, j * p:(j + 1) * p] = Gtt
+    A = Gb + float(w_sym) * np.asarray(R, dtype=np.float64).reshape(d * p, d * p)
+    return A[flat][:, flat], G[:p, p:].T.reshape(-1)[flat]
+
+
+def stlsq_symreg_from_gram(G, R, n_points, mask, gamma, w_sym, d, driver="gels"):
+    """One pass of the fit with the reversed symmetry regulariser (EquivSINDy-r) on the support ``mask`` (d, p): the
+    minimiser of mse + w_sym * reg (train.py:663-679 on the fixed batch of train.py:626-629) is the solution of ONE linear
+    system, ``stlsq_symreg_system``.  ``driver``: 'gels' / 'gelsy' as ``lstsq_normal`` takes them, or 'min_norm' with the
+    meaning it has in ``stlsq_constrained_from_gram``.
+    Returns (Xi (d, p) float32, zeros off the support; the solution (n,) float64)."""
+    from .lstsq import SINGULAR_RCOND
+    p = G.shape[0] - d
+    mask = np.asarray(mask, dtype=bool)
+    A, b = stlsq_symreg_system(G, R, mask, gamma, w_sym, d)
+    m_rows = d * (n_points + p)
+    if not mask.any():                              # an empty support: nothing to solve, Xi = 0
+        w = np.zeros(0)
+    elif driver == 'min_norm':
+        w, _ = lstsq_normal(A, b, m_rows, 'gelsy', SINGULAR_RCOND)
+    else:
+        w, _ = lstsq_normal(A, b, m_rows, driver)
+    xi = np.zeros((d, p), dtype=np.float32)
+    xi[mask] = np.asarray(w, dtype=np.float64).astype(np.float32)
+    return xi, w
+
+
 def _mask_on_host(regressor):
     """Boolean host copy of the mask without a device round trip when the mask on the device is still the tensor this
     module uploaded last (the mirror keeps that tensor alive, so an equal address means the same storage; in-place

@@ -20,7 +20,7 @@ from .coef_map import CoefMap
 from .engine import LBFGS_ACCEPT, LBFGS_BEGIN, get_engine, library_flags
 from . import lstsq as _lstsq
 from .sindy import (NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_constrained_from_gram, stlsq_solve_from_gram,
-                    weak_test_functions)
+                    stlsq_symreg_from_gram, weak_test_functions)
 
 
 def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
@@ -51,12 +51,15 @@ class _DeviceSTLSQ:
 
     _fetch_with_fit = None                 # an int32 device tensor to bring back in the fit's one copy (SeedSweepWSINDy)
 
-    def _replay(self, s, G_s, w_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes, coef=None):
+    def _replay(self, s, G_s, w_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes, coef=None, rev=None):
         """Problem s again in numpy, pass by pass from the full mask, for the detailed near-threshold record.  ``coef`` (a
-        CoefMap with Q): the constrained fit's pass (sindy.stlsq_constrained_from_gram), whose drivers ``lstsq_driver`` names."""
+        CoefMap with Q): the constrained fit's pass (sindy.stlsq_constrained_from_gram), whose drivers ``lstsq_driver`` names.
+        ``rev`` (problem s's R (d p, d p), its w_sym): the pass with the reversed regulariser (sindy.stlsq_symreg_from_gram)."""
         mask[s] = True
         for it in range(max_iter):
-            if coef is not None:
+            if rev is not None:
+                xi32 = stlsq_symreg_from_gram(G_s, rev[0], self.n_points, mask[s], float(w_reg), float(rev[1]), self.d, lstsq_driver)[0]
+            elif coef is not None:
                 xi32 = stlsq_constrained_from_gram(G_s, self.n_points, mask[s], float(w_reg), self.d, coef, lstsq_driver)[0]
             else:
                 xi, _ = stlsq_solve_from_gram(G_s, self.n_points, mask[s], float(w_reg), self.d, lstsq_driver)
@@ -68,7 +71,7 @@ class _DeviceSTLSQ:
             if converged:
                 break
 
-    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper, coef=None, min_norm=False):
+    def _solve_device(self, w_sindy_reg, threshold, max_iter, hyper, coef=None, min_norm=False, rev=None):
         """``solve(device=True)``: one symode_stlsq_sweep launch on the matrices where the gather launch left them; only
         Xi, mask, passes, near and fell come back.  The launch takes ridge weight and threshold in fp32, as its per-problem
         table holds them, with or without a table -- so problem (g, k) of a grid is bit for bit seed k of the scalar device
@@ -80,12 +83,18 @@ class _DeviceSTLSQ:
         ``min_norm`` (with ``coef``): the launch is symode_stlsq_sweep_minnorm, which performs that rule on every pass itself
         (rcond = SINGULAR_RCOND).  A problem whose passes were rank-truncated then costs no host work and no copy of its
         matrix; what is left to the host is a problem the launch flags (the factor of Wm Wm^T not positive definite) and the
-        replay for the near-threshold record, with the rule the launch applied ('min_norm' where a pass was truncated)."""
+        replay for the near-threshold record, with the rule the launch applied ('min_norm' where a pass was truncated).
+        ``rev`` ((S, d p, d p) fp64 matrices R of the reversed regulariser, w_sym): the launch is symode_stlsq_sweep_symreg,
+        per pass the minimiser of mse + w_sym * reg; ``hyper`` then also takes a ``w_sym`` column, and the launch holds that
+        value in fp32 as well.  A problem it flags is solved by the host loop with the minimum-norm rule on every pass."""
         S, d, p = self.S, self.d, self.p
         f32 = lambda v: float(np.float32(v))                                   # noqa: E731
         n_problems = S
         if hyper is not None:
-            unknown = set(hyper) - {'w_reg', 'threshold'}
+            unknown = set(hyper) - ({'w_reg', 'threshold'} if rev is None else {'w_reg', 'threshold', 'w_sym'})
+            if unknown and rev is not None:
+                raise ValueError('hyper: the per-problem columns of the STLSQ sweep with the reversed regulariser are w_reg, '
+                                 f'threshold and w_sym, got {sorted(hyper)}')
             if unknown or not hyper:
                 raise ValueError(f"hyper: the per-problem columns of the STLSQ sweep are w_reg and threshold, got {sorted(hyper)}")
             lengths = {len(v) for v in hyper.values()}
@@ -97,12 +106,24 @@ class _DeviceSTLSQ:
         thr = np.array([f32(v) for v in (hyper or {}).get('threshold', [threshold] * n_problems)], dtype=np.float64)
         if not (np.all(np.isfinite(w)) and np.all(np.isfinite(thr)) and np.all(w >= 0) and np.all(thr >= 0)):
             raise ValueError('the ridge weight and the threshold of every problem must be finite and >= 0')
+        if rev is not None:
+            wsym = np.array([f32(v) for v in (hyper or {}).get('w_sym', [rev[1]] * n_problems)], dtype=np.float64)
+            if not (np.all(np.isfinite(wsym)) and np.all(wsym >= 0)):
+                raise ValueError('the weight w_sym of the reversed regulariser must be finite and >= 0 for every problem')
         G = self.grams(device=True)
         table = None
-        if hyper is not None:
+        if rev is not None:
+            R = torch.as_tensor(rev[0]).to(device=G.device, dtype=torch.float64).reshape(S, d * p, d * p).contiguous()
+            if hyper is not None:
+                table = torch.from_numpy(np.stack([w, thr, wsym], axis=1).astype(np.float32)).to(G.device)
+        elif hyper is not None:
             table = torch.from_numpy(np.stack([w, thr], axis=1).astype(np.float32)).to(G.device)
         trunc = np.zeros(n_problems, dtype=np.int32)
-        if coef is not None and min_norm:
+        if rev is not None:
+            Xi, m8, p32, near, fell, *flags = self.engine.stlsq_sweep_symreg(
+                G, R, self.n_points, w[0], thr[0], wsym[0], max_iter, hyper=table, d=d, pivot_floor=_lstsq.SINGULAR_RCOND ** 2,
+                near_band=NEAR_THRESHOLD_BAND, to_host=True, tail=self._fetch_with_fit)
+        elif coef is not None and min_norm:
             q_solve, q_xi = (torch.from_numpy(q).to(G.device) for q in (coef.solve_matrix(), coef.xi_matrix()))
             Xi, m8, p32, near, fell, _, trunc, _, *flags = self.engine.stlsq_sweep_minnorm(
                 G, self.n_points, w[0], thr[0], max_iter, q_solve, q_xi, coef.allow_constant, hyper=table, d=d,
@@ -121,7 +142,7 @@ class _DeviceSTLSQ:
         Xi, mask, passes = np.array(Xi), np.asarray(m8).astype(bool), np.asarray(p32).astype(np.int64)
         near = np.array(near)
         self.near_threshold = []
-        held = {}                                                       # set -> its (p+d, p+d) matrix on the host
+        held, held_rev = {}, {}                                         # set -> its (p+d, p+d) matrix on the host; ... its R
 
         def on_host(s):
             k = s % S
@@ -129,8 +150,25 @@ class _DeviceSTLSQ:
                 held[k] = G[k].cpu().numpy()
             return held[k]
 
+        def rev_on_host(s):
+            if rev is None:
+                return None
+            k = s % S
+            if k not in held_rev:
+                held_rev[k] = R[k].cpu().numpy()
+            return held_rev[k], wsym[s]
+
         self.rank_truncated = np.array(trunc) > 0                       # (n_problems,): a pass solved with rank < n on the device
-        if coef is not None and (fell.any() or self.rank_truncated.any()):
+        if rev is not None:
+            if fell.any():
+                # possibly rank deficient: the host loop from the full mask, the minimum-norm rule on every pass
+                import warnings
+                for s in np.nonzero(fell)[0].tolist():
+                    self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm', Xi, mask, passes, rev=rev_on_host(s))
+                    near[s] = 0                                          # (its near-threshold record is the loop's)
+                warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
+                              RuntimeWarning)
+        elif coef is not None and (fell.any() or self.rank_truncated.any()):
             # possibly rank deficient: the host loop from the full mask, the minimum-norm rule on every pass
             import warnings
             for s in np.nonzero(fell)[0].tolist():
@@ -155,7 +193,8 @@ class _DeviceSTLSQ:
             warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
                           RuntimeWarning)
         for s in np.nonzero(near)[0].tolist():
-            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm' if trunc[s] > 0 else 'gels', Xi, mask, passes, coef)
+            self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm' if trunc[s] > 0 else 'gels', Xi, mask, passes, coef,
+                         rev_on_host(s))
         return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
 
 
@@ -212,7 +251,13 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
             self._gram = self._gram_dev.cpu().numpy()
         return self._gram
 
-    def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None, coef=None, min_norm=False):
+    def set_grams(self, G, n_points):
+        """Hand in the seeds' (S, p+d, p+d) fp64 matrices on the device, already summed over the ranks, and the points behind
+        each (a caller that built them beside other statistics, in one collective): ``grams`` then gathers nothing."""
+        self._gram_dev, self._gram, self.n_points = G, None, int(n_points)
+
+    def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None, coef=None, min_norm=False,
+              rev=None):
         """STLSQ to convergence for every seed (train.py:872-887 per seed).
         Returns (Xi (S, d, p) float32, mask (S, d, p) float32, passes (S,)).
         ``device=True``: the fit runs on the device (``_solve_device``; the full-rank driver only), the host route stays the
@@ -226,7 +271,35 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         launch (symode_stlsq_sweep_minnorm).  A pass whose support leaves Q's columns collinear is solved inside the launch
         by the minimum-norm rule the host loop would apply (``lstsq_normal(Gq, cq, m, 'gelsy', SINGULAR_RCOND)``), so such
         problems are not handed to the host; the RuntimeWarning that names the minimum-norm answer is raised all the same,
-        and ``self.rank_truncated`` (n_problems,) bool says which problems it concerns."""
+        and ``self.rank_truncated`` (n_problems,) bool says which problems it concerns.
+        ``rev=(R, w_sym)``: the fit with the reversed symmetry regulariser, EquivSINDy-r -- per pass the minimiser of
+        mse + w_sym * reg on the support, one linear system (sindy.stlsq_symreg_system).  R (S, d p, d p) fp64, host or device,
+        raw sums over each seed's points (``symreg_reversed_gram_gather`` on the rows behind ``grams``).  On the host it is the
+        numpy loop (sindy.stlsq_symreg_from_gram), the full-rank driver by default; ``device=True`` is ONE
+        symode_stlsq_sweep_symreg launch, ``hyper`` then also takes a ``w_sym`` column.  d p <= 64."""
+        if rev is not None:
+            if coef is not None and coef.Q is not None:
+                raise ValueError('rev (the reversed symmetry regulariser) does not go with coef (the equivariance constraint): '
+                                 'the combined system Qe^T (Gm + w_sym R) Qe is not covered')
+            if min_norm:
+                raise ValueError('rev (the reversed symmetry regulariser) does not go with min_norm=True: the rank-revealing mode '
+                                 'is the constrained launch\'s')
+            if lstsq_driver == 'gelsy':
+                raise ValueError("rev (the reversed symmetry regulariser) does not go with lstsq_driver='gelsy': the regularised "
+                                 'system is solved with the full-rank driver (gels)')
+            if self.d * self.p > 64:
+                raise ValueError(f'rev (the reversed symmetry regulariser): d p = {self.d} x {self.p} = {self.d * self.p} unknowns, '
+                                 'the joint system of a pass takes at most 64')
+            if len(rev) != 2 or tuple(rev[0].shape) != (self.S, self.d * self.p, self.d * self.p):
+                raise ValueError(f'rev must be (R, w_sym) with R (S, d p, d p) = ({self.S}, {self.d * self.p}, {self.d * self.p})')
+            if not (np.isfinite(float(rev[1])) and float(rev[1]) >= 0 and np.isfinite(float(w_sindy_reg)) and float(w_sindy_reg) >= 0
+                    and np.isfinite(float(threshold)) and float(threshold) >= 0):
+                raise ValueError('rev (the reversed symmetry regulariser): w_sym, the ridge weight and the threshold must be finite '
+                                 'and >= 0')
+            if lstsq_driver is None:
+                lstsq_driver = 'gels'
+        elif hyper is not None and 'w_sym' in hyper:
+            raise ValueError('hyper: a w_sym column needs rev=(R, w_sym): without the regulariser\'s matrices there is nothing to weigh')
         if min_norm:
             if not device:
                 raise ValueError('min_norm=True needs device=True: it is a mode of the device launch (on the host route '
@@ -248,7 +321,7 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
             if lstsq_driver != 'gels':
                 raise ValueError(f"device=True fits with the full-rank driver (gels) only, not lstsq_driver='{lstsq_driver}': the "
                                  'rank rule of gelsy runs on the host route')
-            return self._solve_device(w_sindy_reg, threshold, max(1, int(max_iter)), hyper, coef, min_norm)
+            return self._solve_device(w_sindy_reg, threshold, max(1, int(max_iter)), hyper, coef, min_norm, rev)
         G = self.grams()
         S, d, p = self.S, self.d, self.p
         Xi = np.zeros((S, d, p), dtype=np.float32)
@@ -257,6 +330,11 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         self.near_threshold = []              # (seed index, pass, row, col, |coef|): BASELINE.md section 3
         todo = range(S)
         lib = _lstsq._native() if os.environ.get('SYMODE_STLSQ_NATIVE', '1') != '0' else None
+        if rev is not None:
+            R = rev[0].detach().cpu().numpy() if torch.is_tensor(rev[0]) else np.asarray(rev[0])
+            for s in todo:
+                self._replay(s, G[s], w_sindy_reg, threshold, max_iter, lstsq_driver, Xi, mask, passes, rev=(R[s], float(rev[1])))
+            return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), passes
         if lib and lstsq_driver in ('gels', 'gelsy') and coef is None:
             # the whole loop below for all seeds in ONE native call (host_lstsq.cpp::symode_host_stlsq_sweep: same solver, same
             # inputs, same arithmetic); seeds that met a near-threshold coefficient are replayed here for the detailed record
