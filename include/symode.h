@@ -319,6 +319,34 @@ int symode_loss_grad_reversed_linear_gram(const float* x, const float* dx, const
                                           unsigned long long live_columns, float inv_count, float w_sym, float* loss2_out,
                                           float* grad_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* symode_loss_grad_reversed_linear_gram with the residual, too, taken from a matrix built once: no pass over the points.
+ * aug_table (S, p+d, p+d) fp64: symode_aug_gram of each problem's x, dx, RAW sums, [Gtt Gty; Gty^T Gyy]; a function of x and dx
+ * alone.  With W = xi * mask (columns outside live_columns count as 0):
+ *     sum_n |W Theta_n - dx_n|^2 = tr(W Gtt W^T) - 2 tr(W Gty) + tr(Gyy),     sum_n r_n Theta_n^T = W Gtt - Gty^T,
+ * and the regulariser from Gtt, m_table and table (S, 1, d, d) by the statements of the _linear_gram entry's kernel.  fp64
+ * throughout, one rounding to fp32 per output; one wave per problem, one launch.  x, dx and gx are not read.
+ * Outputs: loss2_out (S, 2) = (mse, regulariser), grad_out (S, d, p) = d(mse + w_sym regulariser)/dxi, masked, zero outside
+ * live_columns; loss_out (S) = mse + w_sym regulariser (may be NULL).  inv_count is a double here.
+ * The coefficient map in the same launch: with q (d p, r) fp32 given, xi must be NULL and Xi = reshape(q beta) + const:
+ * beta (S, r) with rows beta_stride floats apart (>= r); flat = q beta in fp64, viewed as (d, p) (use_kron != 0) or as the transposed (p, d) view; const_ (S, d), rows
+ * const_stride floats apart (>= d), or NULL is added to column 0; ONE rounding to fp32, from where on the call is the call on that xi (written to xi_out (S, d, p)
+ * when not NULL).  Then also g_beta_out (S, r) = vec(grad) q in the same view and g_const_out (S, d) = grad[:, :, 0] (or
+ * NULL), both from the fp64 gradient, rounded once.  Without q: beta, const_, xi_out, g_beta_out, g_const_out must be NULL.
+ * The shards of a point-sharded problem add: every output but xi_out is linear in aug_table.
+ * workspace: an initialised one (symode_workspace_init); only its header is used -- word 1 gets what the fold kernel of the
+ * same column set leaves there, in its Gram form, plus bit 128.
+ * d = 2, flags = 0, order 1-5, n_g = 1; anything else, and every call under SYMODE_CLOSURE_FOLD=0, SYMODE_FOLD_GRAM=0 or
+ * SYMODE_FOLD_RESID_GRAM=0 (the caller keeps the entries with a point loop): SYMODE_E_UNSUPPORTED.  r outside [1, d p]:
+ * SYMODE_E_BADSIZE.  Added to ABI version 8 (nothing existing changed).
+ * replaces: the closure body train.py:663-664 + 675-679 + 689 with get_Xi (sindy.py:169-176) and its transpose. */
+int symode_loss_grad_reversed_linear_quad(const double* aug_table, const double* m_table, const float* table, int n_g, long n_problems,
+                                          int d, int order, int flags, const float* xi, const float* q, const float* beta,
+                                          long beta_stride, const float* const_, long const_stride, int r, int use_kron,
+                                          const float* mask,
+                                          unsigned long long live_columns, double inv_count, float w_sym, float* loss2_out,
+                                          float* loss_out, float* grad_out, float* xi_out, float* g_beta_out, float* g_const_out,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Gram matrix of the reversed regulariser: for S problems (layouts as in symode_symreg_reversed_batched, n_g >= 1)
  *     gram_out[s] (d p, d p) fp64 = sum_g sum_n B^T B,   B[i, (j, a)] = J_g(x_n)[i, j] theta_a(x_n) - delta_ij theta_a(g x_n),
  * rows and columns in Xi's (d, p) row-major order, both triangles filled: the regulariser of symode_symreg_reversed_batched

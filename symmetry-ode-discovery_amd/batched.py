@@ -61,7 +61,7 @@ def allreduce_sums(sums, params, group):
 class BatchedClosure:
     def __init__(self, x, dx, poly_order, include_sine=False, include_exp=False, Q=None, use_kron_product=True,
                  allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True, coef=None,
-                 const_jacobian=None, live_columns=True, linear_action=None, regulariser_gram=None):
+                 const_jacobian=None, live_columns=True, linear_action=None, regulariser_gram=None, residual_gram=None):
         """``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from Q / use_kron_product / allow_constant).
         ``reversed_sym = (gx (S, n_g, N_local, d), jgx (S, n_g, N_local, d, d), weight)`` adds  weight * the reversed
         symmetry regulariser (model_utils.py:126-170 on precomputed (g(x), J_g(x))) to every problem's loss and gradient:
@@ -89,8 +89,15 @@ class BatchedClosure:
         rank's shard of every problem is built once (engine.aug_gram, its top-left p x p block) and handed to the fold closure:
         the regulariser and its gradient become a d p p fp64 product per problem and the point loop carries the residual alone
         (engine.loss_grad_reversed, ``gram=``).  The term is linear in G, so the [loss | grad] all-reduce stays what it is.
-        G is remembered with x's version counter and data pointer and rebuilt when either moves (``gram_builds`` counts);
-        SYMODE_FOLD_GRAM=0 or False keep the plain fold kernel."""
+        The matrix is remembered with the version counters and data pointers of x and dx and rebuilt when any of them moves
+        (``gram_builds`` counts); SYMODE_FOLD_GRAM=0 or False keep the plain fold kernel.
+        ``residual_gram``: None (default) -- with ``regulariser_gram``, the WHOLE augmented matrix [Theta | dx]^T [Theta | dx] is
+        kept and the closure has no point loop at all (engine.loss_grad_reversed, ``aug=``): the residual is the quadratic form
+        of the rows and columns the regulariser leaves out, a call reads 8 KB per problem instead of x and dx, and the one
+        pass over the points is the set-up's.  ``evaluate`` on one chunk without point shards hands the launch the coefficient
+        map as well (``coef=``): Xi from (beta, const) and the gradient by them come out of the same kernel.  Linear in the
+        matrix like the regulariser, so the all-reduce stays what it is.  SYMODE_FOLD_RESID_GRAM=0 or False give the step
+        with the point loop, bit for bit."""
         assert x.dim() == 3 and x.shape == dx.shape, "x, dx must be (S, N_local, d)"
         self.engine = engine or get_engine()
         self.x, self.dx = x.contiguous(), dx.contiguous()
@@ -140,9 +147,11 @@ class BatchedClosure:
         if self._lin_detect:
             self._linear_for_launch()
         self._gram_on = (regulariser_gram is None or bool(regulariser_gram)) and self._lin_detect and hasattr(self.engine, 'aug_gram')
-        self._gram_seen, self._gram, self.gram_builds = None, None, 0
+        self._gram_seen, self._gram, self._aug, self.gram_builds = None, None, None, 0
+        self._resid_on = (residual_gram is None or bool(residual_gram)) and self._gram_on and hasattr(self.engine, 'closure_quad_enabled')
         if self._gram_on:
             self._gram_for_launch()
+        self._alias_out = None                               # g_beta / g_const of an ``alias=True`` evaluation with the map in the launch
         self._live = None                                    # the map's column set, where it names a dead column at all
         if live_columns and self._cj_detect:
             live = self.coef.live_mask()
@@ -177,16 +186,23 @@ class BatchedClosure:
         return self._lin_m
 
     def _gram_for_launch(self):
-        """The fp64 (S, 1, p, p) raw library Gram sums of x where the fold closure is taken, else None.  Built once per
-        (version, pointer) of x; ``gram_builds`` counts."""
+        """The fp64 (S, 1, p, p) raw library Gram sums of x where the fold closure is taken, else None; ``self._aug`` is the
+        whole (S, p+d, p+d) augmented matrix they are the top-left block of.  Built once per (version, pointer) of x and dx;
+        ``gram_builds`` counts."""
         if not self._gram_on or self._linear_for_launch() is None:
             return None
-        seen = (self.x._version, self.x.data_ptr())
+        seen = (self.x._version, self.x.data_ptr(), self.dx._version, self.dx.data_ptr())
         if seen != self._gram_seen:
             G = self.engine.aug_gram(self.x, self.dx, self.order, self.flags)
-            self._gram_seen, self._gram = seen, G[:, None, :self.p, :self.p].contiguous()
+            self._gram_seen, self._aug, self._gram = seen, G, G[:, None, :self.p, :self.p].contiguous()
             self.gram_builds += 1
         return self._gram
+
+    def _quad_for_launch(self):
+        """The augmented matrices where the closure without a point loop is taken (``residual_gram``), else None."""
+        if not self._resid_on or self._gram_for_launch() is None or not self.engine.closure_quad_enabled():
+            return None
+        return self._aug
 
     # -- coefficient plumbing (batched get_Xi, sindy.py:169-176) ----------------------------
     def xi_from(self, beta, const=None):
@@ -196,17 +212,41 @@ class BatchedClosure:
         return self.coef.grad(grad_xi)
 
     # -- the hot path -------------------------------------------------------------------------
-    def loss_grad_xi(self, Xi, mask=None, alias=False, live_columns=None):
+    def loss_grad_xi(self, Xi, mask=None, alias=False, live_columns=None, coef=None):
         """loss (S,), dloss/dXi (S, d, p) summed over all ranks' shards.  ``alias=True``: with a single chunk the results
         are returned as views of the packed buffer the kernel wrote (no copies; overwritten by the next evaluation).
         ``live_columns``: the library columns Xi can be non-zero in (an int, bit k = column k), for the symmetry launches
-        (engine.loss_grad_reversed); None: every column."""
+        (engine.loss_grad_reversed); None: every column.
+        ``coef`` = (beta, const) in the place of Xi (``evaluate``: one chunk, no point shards, the closure without a point
+        loop): the launch forms Xi itself and the call returns (loss, g_beta, g_const) instead."""
         works = []
         live_kw = {} if live_columns is None else {'live_columns': live_columns}
         fused = self.sym is not None and self.fuse_sym and hasattr(self.engine, 'loss_grad_reversed')
         jg = self._jacobian_for_launch() if self.sym is not None else None      # (S, n_g, d, d) table or the (S, n_g, N, d, d) tensor
         lin = self._linear_for_launch() if fused else None                      # M of a detected linear action: the fold kernel
         gram = self._gram_for_launch() if lin is not None else None             # G of x: the fold kernel's Gram form
+        aug = self._quad_for_launch() if gram is not None else None             # [Theta | dx]^T [Theta | dx]: no point loop
+        if coef is not None:
+            # ONE launch for the step: Xi from the variables, the closure, the gradient by the variables; what is returned is
+            # written where it is returned from -- fresh tensors, or with ``alias`` buffers of this object
+            (a, b), buf = self.chunks[0], self.buffers[0]
+            n, dev = self.S, self.x.device
+            beta, const = coef
+            gx, jgx, weight = self.sym
+            if alias:
+                if self._alias_out is None:
+                    self._alias_out = (torch.empty(n, self.coef.r, dtype=torch.float32, device=dev),
+                                       torch.empty(n, self.d, 1, dtype=torch.float32, device=dev) if self.coef.allow_constant else None)
+                loss, (g_beta, g_const) = buf[:n], self._alias_out
+            else:
+                loss = torch.empty(n, dtype=torch.float32, device=dev)
+                g_beta = torch.empty(n, self.coef.r, dtype=torch.float32, device=dev)
+                g_const = torch.empty(n, self.d, 1, dtype=torch.float32, device=dev) if self.coef.allow_constant else None
+            self.engine.loss_grad_reversed(self.x, self.dx, gx, jg, None, mask, self.order, self.flags, w_sym=weight,
+                                           inv_count=self.inv_count, out=(self.sym_buffers[0][:2 * n], buf[n:], loss), **live_kw,
+                                           **self._ws_kw, linear_m=lin, aug=aug, coef=(self.coef, beta, const),
+                                           coef_out=(None, g_beta, g_const))
+            return loss, g_beta, g_const
         for ci, ((a, b), buf) in enumerate(zip(self.chunks, self.buffers)):
             n = b - a
             loss = buf[:n]
@@ -217,12 +257,19 @@ class BatchedClosure:
                 gx, jgx, weight = self.sym
                 sb = self.sym_buffers[ci]
                 l2 = sb[:2 * n].view(n, 2)
-                self.engine.loss_grad_reversed(self.x[a:b], self.dx[a:b], gx[a:b], jg[a:b], Xi[a:b],
-                                               None if mask is None else mask[a:b], self.order, self.flags, w_sym=weight,
-                                               inv_count=self.inv_count, out=(l2, grad), **live_kw, **self._ws_kw,
-                                               **({} if lin is None else {'linear_m': lin[a:b]}),
-                                               **({} if gram is None else {'gram': gram[a:b]}))
-                torch.add(l2[:, 0], l2[:, 1], alpha=weight, out=loss)
+                if aug is not None:
+                    # ... or reads no point at all, and leaves mse + weight * regulariser in the loss slot itself
+                    self.engine.loss_grad_reversed(self.x[a:b], self.dx[a:b], gx[a:b], jg[a:b], Xi[a:b],
+                                                   None if mask is None else mask[a:b], self.order, self.flags, w_sym=weight,
+                                                   inv_count=self.inv_count, out=(l2, grad, loss), **live_kw, **self._ws_kw,
+                                                   linear_m=lin[a:b], aug=aug[a:b])
+                else:
+                    self.engine.loss_grad_reversed(self.x[a:b], self.dx[a:b], gx[a:b], jg[a:b], Xi[a:b],
+                                                   None if mask is None else mask[a:b], self.order, self.flags, w_sym=weight,
+                                                   inv_count=self.inv_count, out=(l2, grad), **live_kw, **self._ws_kw,
+                                                   **({} if lin is None else {'linear_m': lin[a:b]}),
+                                                   **({} if gram is None else {'gram': gram[a:b]}))
+                    torch.add(l2[:, 0], l2[:, 1], alpha=weight, out=loss)
                 if self._collective:
                     works.append(dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
                 continue
@@ -255,6 +302,9 @@ class BatchedClosure:
 
     def evaluate(self, beta, const=None, mask=None, alias=False):
         """Closure of all S problems: (loss (S,), d/dbeta [or d/dXi when unconstrained], d/dconst)."""
+        if self.coef.Q is not None and self.coef.r > 0 and not self.distributed and len(self.chunks) == 1 and self.sym is not None \
+                and self.fuse_sym and self._resid_on and self._linear_for_launch() is not None and self._quad_for_launch() is not None:
+            return self.loss_grad_xi(None, mask, alias=alias, live_columns=self._live, coef=(beta, const))
         Xi = self.xi_from(beta, const)
         loss, grad = self.loss_grad_xi(Xi, mask, alias=alias, live_columns=self._live)
         g_beta, g_const = self.grads_to(grad)

@@ -36,6 +36,17 @@ class CoefMap:
             self._Qnp = self.Q.detach().cpu().numpy() if torch.is_tensor(self.Q) else np.asarray(self.Q)
         return self._Qnp
 
+    def device_Q(self, device):
+        """Q as a launch reads it (engine.loss_grad_reversed, ``coef=``): fp32, contiguous (d p, r), on ``device``, rows in Q's
+        own order (the launch is told ``use_kron``).  Kept while Q's version counter and data pointer stay what they were."""
+        Q = self.Q
+        key = (torch.device(device), Q._version, Q.data_ptr())
+        seen = getattr(self, "_Qdev", None)
+        if seen is None or seen[0] != key:
+            seen = (key, Q.detach().to(device=device, dtype=torch.float32).contiguous())
+            self._Qdev = seen
+        return seen[1]
+
     def split(self, P):
         """(beta, const) views of a flat (n,) or (S, n) tensor; (Xi, None) when unconstrained."""
         lead = P.shape[:-1]

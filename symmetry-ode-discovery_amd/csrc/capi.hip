@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "../../include/symode.h"
+#include "closure_quad.hpp"
 #include "jconst.hpp"
 #include "linear_action.hpp"
 #include "ops_table.hpp"
@@ -469,6 +470,33 @@ int symode_loss_grad_reversed_linear_gram(const float* x, const float* dx, const
     // SYMODE_FOLD_GRAM=0: the entry without the table (the launcher's own table is asked per column set, in the launch)
     return fold_closure(x, dx, gx_, table, m_table, knobs().fold_gram ? g_table : nullptr, n_g, n_problems, n, d, order, flags, xi,
                         mask, live_columns, inv_count, w_sym, loss2_out, grad_out, workspace, workspace_bytes, stream);
+}
+
+// The fold closure without a point loop (closure_quad.hpp): one kernel per library, the column set is a run-time argument.
+int symode_loss_grad_reversed_linear_quad(const double* aug_table, const double* m_table, const float* table, int n_g, long n_problems,
+                                          int d, int order, int flags, const float* xi, const float* q, const float* beta,
+                                          long beta_stride, const float* const_, long const_stride, int r, int use_kron,
+                                          const float* mask,
+                                          unsigned long long live_columns, double inv_count, float w_sym, float* loss2_out,
+                                          float* loss_out, float* grad_out, float* xi_out, float* g_beta_out, float* g_const_out,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    if (d != 2 || flags != 0 || order < 1 || order > 5) return SYMODE_E_UNSUPPORTED;
+    if (n_g < 1 || n_problems < 1 || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
+    if (n_g != 1) return SYMODE_E_UNSUPPORTED;
+    // the switches that keep the point-loop kernels: the caller goes to the _linear / _linear_gram entries then
+    if (!knobs().closure_fold || !knobs().fold_gram || !knobs().fold_resid_gram) return SYMODE_E_UNSUPPORTED;
+    const bool mapped = q != nullptr;
+    if (!aug_table || !m_table || !table || !loss2_out || !grad_out) return SYMODE_E_NULLPTR;
+    if (mapped ? (!beta || !g_beta_out || xi) : (!xi || beta || const_ || xi_out || g_beta_out || g_const_out)) return SYMODE_E_NULLPTR;
+    if (mapped && (r < 1 || r > 2 * symode_lib_size(2, order, 0) || beta_stride < r || (const_ && const_stride < 2))) return SYMODE_E_BADSIZE;
+    if (misaligned(aug_table, 8) || misaligned(m_table, 8) || misaligned(table, 4) || misaligned(xi, 4) || misaligned(q, 4) ||
+        misaligned(beta, 4) || misaligned(const_, 4) || misaligned(mask, 4) || misaligned(loss2_out, 4) || misaligned(loss_out, 4) ||
+        misaligned(grad_out, 4) || misaligned(xi_out, 4) || misaligned(g_beta_out, 4) || misaligned(g_const_out, 4))
+        return SYMODE_E_ALIGN;
+    if (!workspace || misaligned(workspace, 8) || workspace_bytes < (size_t)WS_HEADER_DOUBLES * sizeof(double)) return SYMODE_E_WORKSPACE;
+    const QuadMap map{q, beta, const_, beta_stride, const_stride, r, use_kron != 0 ? 1 : 0, xi_out, g_beta_out, g_const_out};
+    return (int)launch_closure_quad_order(order, aug_table, m_table, table, n_problems, xi, map, mask, live_columns, w_sym, inv_count,
+                                          loss2_out, loss_out, grad_out, (double*)workspace, (hipStream_t)stream);
 }
 
 size_t symode_symreg_reversed_gram_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long n) {

@@ -160,6 +160,56 @@ struct fold_gram<L, std::void_t<decltype(L::FOLD_GRAM)>> {
     static constexpr bool value = L::FOLD_GRAM;
 };
 
+// The regulariser's statements, stated once for symreg_fold_kernel and for the kernel without a point loop (closure_quad.hpp).
+// fold_c: entry (j, k) of C = J Xi - Xi M in fp64; wv(b, l) is the masked coefficient as a double (0 in a dead column).
+template <int D, int P, class WV>
+__device__ __forceinline__ double fold_c(int j, int k, const float* js, const double* ms, const WV& wv) {
+    double c = 0.0;
+    for (int b = 0; b < D; ++b) c += (double)js[j * D + b] * wv(b, k);
+    for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l) c -= wv(j, l) * ms[l * P + k];
+    return c;
+}
+// fold_gram_term: from cd = C (D x P, in LDS, written by the caller's threads before the call) the rows U = C G into ud, and
+// into row_add slot 1 the value sum_j c_j G c_j^T and slots 2.. the share w_sym T of the gradient, T = (J - I)^T U - U (M - I)^T
+// with J - I and M - I in fp64.  The caller's threads t0, t0 + STEP, .. share the D P entries, `last` names the one that adds
+// the value up; gs: G of the problem, rows LDG doubles apart; sync(): the barrier between the stages (the first one makes cd
+// visible, the last one row_add).
+template <int D, int P, unsigned long long LIVE, int STEP, int LDG, class Sync>
+__device__ __forceinline__ void fold_gram_term(int t0, bool last, const float* js, const double* ms,
+                                               const double* gs, unsigned long long live, float w_sym,
+                                               const double* cd, double* ud, double* row_add, Sync sync) {
+    sync();
+    // U = C G over the columns of LIVE, in column order
+    for (int t = t0; t < D * P; t += STEP) {
+        const int j = t / P, k = t % P;
+        double u = 0.0;
+        if (col_live<LIVE>(k))
+            for (int l = 0; l < P; ++l)
+                if (col_live<LIVE>(l)) u = __builtin_fma(cd[j * P + l], gs[l * LDG + k], u);
+        ud[t] = u;
+    }
+    sync();
+    // T = (J - I)^T U - U (M - I)^T over the degree block of the column, J - I and M - I in fp64; sum_j c_j G c_j^T
+    for (int t = t0; t < D * P; t += STEP) {
+        const int j = t / P, k = t % P;
+        double v = 0.0;
+        if (col_live<LIVE>(k) && ((live >> k) & 1ull) != 0) {
+            for (int a = 0; a < D; ++a) v = __builtin_fma((double)js[a * D + j] - (a == j ? 1.0 : 0.0), ud[a * P + k], v);
+            for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l)
+                v = __builtin_fma(-(ms[k * P + l] - (k == l ? 1.0 : 0.0)), ud[j * P + l], v);
+            v *= (double)w_sym;
+        }
+        row_add[2 + t] = v;
+    }
+    if (last) {
+        double v = 0.0;
+        for (int t = 0; t < D * P; ++t) v = __builtin_fma(cd[t], ud[t], v);
+        row_add[0] = 0.0;
+        row_add[1] = v;
+    }
+    sync();
+}
+
 // One template for both forms: the plain kernel has the arguments (and so the name) it had, the Gram form takes gt, one more
 // pointer, behind them -- the trailing pack is empty or that pointer.
 template <class Lib, int RING, int MINW, unsigned long long LIVE, bool W_SGPR, bool C_SGPR, class... GT>
@@ -197,9 +247,7 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* _
                 if (mask != nullptr) v *= mask[s * D * P + b * P + l];
                 return (double)v;
             };
-            double c = 0.0;
-            for (int b = 0; b < D; ++b) c += (double)js[j * D + b] * wv(b, k);
-            for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l) c -= wv(j, l) * ms[l * P + k];
+            const double c = fold_c<D, P>(j, k, js, ms, wv);
             if constexpr (GRAM)
                 cd[t] = col_live<LIVE>(k) ? c : 0.0;
             else
@@ -210,36 +258,8 @@ __global__ __launch_bounds__(BLOCK, MINW) void symreg_fold_kernel(const float* _
         // the regulariser of this problem: U = C G, sum_j c_j G c_j^T and T, left for this workgroup's partial row
         if (blockIdx.x == 0) {
             const double* gs = [](const double* g) { return g; }(gtp...) + s * P * P;
-            __syncthreads();
-            // U = C G over the columns of LIVE, in column order
-            for (int t = threadIdx.x; t < D * P; t += BLOCK) {
-                const int j = t / P, k = t % P;
-                double u = 0.0;
-                if (col_live<LIVE>(k))
-                    for (int l = 0; l < P; ++l)
-                        if (col_live<LIVE>(l)) u = __builtin_fma(cd[j * P + l], gs[l * P + k], u);
-                ud[t] = u;
-            }
-            __syncthreads();
-            // T = (J - I)^T U - U (M - I)^T over the degree block of the column, J - I and M - I in fp64; sum_j c_j G c_j^T
-            for (int t = threadIdx.x; t < D * P; t += BLOCK) {
-                const int j = t / P, k = t % P;
-                double v = 0.0;
-                if (col_live<LIVE>(k) && ((live >> k) & 1ull) != 0) {
-                    for (int a = 0; a < D; ++a) v = __builtin_fma((double)js[a * D + j] - (a == j ? 1.0 : 0.0), ud[a * P + k], v);
-                    for (int l = fold_deg_lo(k); l < fold_deg_hi(k); ++l)
-                        v = __builtin_fma(-(ms[k * P + l] - (k == l ? 1.0 : 0.0)), ud[j * P + l], v);
-                    v *= (double)w_sym;
-                }
-                row_add[2 + t] = v;
-            }
-            if (threadIdx.x == BLOCK - 1) {
-                double v = 0.0;
-                for (int t = 0; t < D * P; ++t) v = __builtin_fma(cd[t], ud[t], v);
-                row_add[0] = 0.0;
-                row_add[1] = v;
-            }
-            __syncthreads();
+            fold_gram_term<D, P, LIVE, BLOCK, P>((int)threadIdx.x, threadIdx.x == BLOCK - 1, js, ms, gs, live, w_sym, cd, ud, row_add,
+                                                 [] { __syncthreads(); });
         }
     } else {
         for (int t = threadIdx.x; t < P * P; t += BLOCK) mm[t] = (float)(ms[t] - (t / P == t % P ? 1.0 : 0.0));

@@ -74,6 +74,10 @@ _SIGNATURES = {
     "symode_loss_grad_reversed_linear_gram": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long,
                                                       c_int, c_int, c_int, c_void_p, c_void_p, ctypes.c_ulonglong, c_float, c_float,
                                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "symode_loss_grad_reversed_linear_quad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                      c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p, ctypes.c_ulonglong, ctypes.c_double,
+                                                      c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_size_t, c_void_p]),
     "symode_loss_grad_latent": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
                                         c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
@@ -835,8 +839,94 @@ class HipEngine:
         Gram, once per problem; SYMODE_FOLD_GRAM=0 turns it off)?  Bit 64 of the word ``closure_body`` reads."""
         return bool(int(ws.view(torch.int64)[1].item()) & 64)
 
+    @staticmethod
+    def closure_quad(ws):
+        """Did the last fold launch on workspace ``ws`` run without a point loop (closure_quad.hpp: residual and regulariser from
+        the augmented Gram, ``aug=``; SYMODE_FOLD_RESID_GRAM=0 turns it off)?  Bit 128 of the word ``closure_body`` reads."""
+        return bool(int(ws.view(torch.int64)[1].item()) & 128)
+
+    @staticmethod
+    def closure_quad_enabled():
+        """Do the library's switches allow the ``aug=`` route (symode_loss_grad_reversed_linear_quad)?  The three variables as
+        the library reads them (off when the value starts with '0' / is the number 0); the library reads them at load and at
+        ``reload_env``, and refuses the call where they say no -- a caller that wants the point-loop kernels then asks here."""
+        env = os.environ
+        return not (env.get("SYMODE_CLOSURE_FOLD", "1")[:1] == "0" or env.get("SYMODE_FOLD_RESID_GRAM", "1")[:1] == "0"
+                    or env.get("SYMODE_FOLD_GRAM", "1").strip() in ("0", "+0", "-0", "00", ""))
+
+    def _closure_quad_call(self, x, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live, linear_m, aug, coef, coef_out):
+        """The launch of ``loss_grad_reversed(aug=...)``: the arguments of symode_loss_grad_reversed_linear_quad, checked."""
+        batched, S, n, d = self._problems(x)
+        gx, jgx, n_g, constj = rev
+        p = self.lib_size(d, order, flags)
+        if not (constj and linear_m is not None and linear_m.is_cuda and linear_m.dtype == torch.float64 and linear_m.is_contiguous()
+                and linear_m.numel() == S * n_g * p * p):
+            raise SymodeError("aug goes with the compact table and linear_m, (S, n_g, p, p) float64 on the device, contiguous")
+        if not (aug.is_cuda and aug.dtype == torch.float64 and aug.is_contiguous() and aug.numel() == S * (p + d) * (p + d)):
+            raise SymodeError("aug holds (S, p+d, p+d) float64 on the device, contiguous")
+        mask = None if mask is None else self._dev(mask, "mask")
+        if mask is not None and mask.numel() != S * d * p:
+            raise SymodeError(f"mask has {mask.numel()} elements, expected {S}x{d}x{p}")
+        dev = x.device
+        keep = [aug, linear_m, jgx, mask]
+        if coef is None:
+            xi = self._dev(xi, "xi")
+            if xi.numel() != S * d * p:
+                raise SymodeError(f"xi has {xi.numel()} elements, expected {S}x{d}x{p}")
+            map_args, extra = (self._ptr(xi), None, None, 0, None, 0, 0, 0), (None, None, None)
+            keep.append(xi)
+            mapped = ()
+        else:
+            cmap, beta, const = coef
+            Q = cmap.device_Q(dev)
+            r = cmap.r
+            # rows of a flat [beta | const] state are taken where they lie: only the last axis has to be dense
+            rows = lambda t, w: t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.shape[0] == S and t.numel() == S * w \
+                and all(st == 1 for st in t.stride()[1:]) and t.stride(0) >= w
+            beta = beta if rows(beta, r) else self._dev(beta, "beta")
+            if (cmap.d, cmap.p) != (d, p) or beta.numel() != S * r:
+                raise SymodeError(f"coef maps ({cmap.d}, {cmap.p}) from {r} variables; beta has {beta.numel()} elements for {S} problems of ({d}, {p})")
+            const = None if (const is None or not cmap.allow_constant) else (const if rows(const, d) else self._dev(const, "const"))
+            if const is not None and const.numel() != S * d:
+                raise SymodeError(f"const has {const.numel()} elements, expected {S}x{d}")
+            if coef_out is None:
+                xi_out = None
+                g_beta = torch.empty(S, r, dtype=torch.float32, device=dev)
+                g_const = torch.empty(S, d, 1, dtype=torch.float32, device=dev) if cmap.allow_constant else None
+            else:
+                xi_out, g_beta, g_const = (None if o is None else self._dev(o, "coef_out") for o in coef_out)
+                if g_beta is None or g_beta.numel() != S * r or (g_const is not None and g_const.numel() != S * d) or \
+                        (xi_out is not None and xi_out.numel() != S * d * p):
+                    raise SymodeError("coef_out = (xi_out (S, d, p) or None, g_beta (S, r), g_const (S, d, 1) or None)")
+            ld = lambda t, w: t.stride(0) if (t.dim() >= 2 and t.shape[0] == S and S > 1) else w
+            map_args = (None, self._ptr(Q), self._ptr(beta), ld(beta, r), self._ptr(const), 0 if const is None else ld(const, d), r,
+                        1 if cmap.use_kron else 0)
+            extra = (self._ptr(xi_out), self._ptr(g_beta), self._ptr(g_const))
+            keep += [Q, beta, const, xi_out, g_beta, g_const]
+            mapped = (g_beta.reshape(S, r), None if g_const is None else g_const.reshape(S, d, 1)) if batched else \
+                (g_beta.reshape(r), None if g_const is None else g_const.reshape(d, 1))
+        loss = None
+        if out is None:
+            loss2 = torch.empty(S, 2, dtype=torch.float32, device=dev)
+            grad = torch.empty(S, d, p, dtype=torch.float32, device=dev)
+        else:
+            loss2, grad = self._dev(out[0], "out"), self._dev(out[1], "out")
+            loss = self._dev(out[2], "out") if len(out) > 2 and out[2] is not None else None
+            if loss2.numel() != 2 * S or grad.numel() != S * d * p or (loss is not None and loss.numel() != S):
+                raise SymodeError(f"out buffers hold {loss2.numel()} / {grad.numel()} elements, expected {2 * S} / {S * d * p} [/ {S}]")
+        if ws is None:
+            ws = self.workspace(dev, d, order, flags, S, n)
+        inv = 1.0 / (n * d) if inv_count is None else float(inv_count)
+        live = (0xFFFFFFFFFFFFFFFF if live is None else int(live)) & 0xFFFFFFFFFFFFFFFF
+        args = (self._ptr(aug), self._ptr(linear_m), self._ptr(jgx), n_g, S, d, order, flags) + map_args + \
+            (self._ptr(mask), live, inv, float(w_sym), self._ptr(loss2), self._ptr(loss), self._ptr(grad)) + extra + \
+            (self._ptr(ws), ws.numel() * 8, self._stream(x))
+        keep += [loss2, loss, grad, ws]
+        loss2, grad = loss2.reshape(S, 2), grad.reshape(S, d, p)
+        return "symode_loss_grad_reversed_linear_quad", args, keep, ((loss2, grad) if batched else (loss2[0], grad[0])) + mapped
+
     def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None,
-                           live_columns=None, linear_m=None, gram=None):
+                           live_columns=None, linear_m=None, gram=None, aug=None, coef=None, coef_out=None):
         """The closure MSE + w_sym * reversed regulariser in ONE pass (x read once, Theta(x) shared by both terms).
         Shapes as loss_grad / symreg_reversed (jgx may be the compact table of a point-constant Jacobian, as there).
         Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mse, regulariser), grad = d(mse + w_sym * regulariser)/dXi
@@ -853,11 +943,29 @@ class HipEngine:
         symode_loss_grad_reversed_linear_gram, whose point loop carries the residual alone -- the regulariser and its gradient
         are a d p p fp64 product per problem.  loss2[:, 0] keeps its bits, the rest agrees up to rounding; where the
         launcher's table keeps the plain fold kernel, and with SYMODE_FOLD_GRAM=0, it is the call without ``gram``
-        (``closure_gram(ws)`` tells)."""
+        (``closure_gram(ws)`` tells).
+        ``aug``: with ``linear_m``, in the place of ``gram``: the whole float64 (S, p+d, p+d) augmented Gram ``aug_gram(x, dx, order)``
+        of the points of this call.  The call goes to symode_loss_grad_reversed_linear_quad, which has no point loop at all: the
+        residual, too, is a quadratic form of the matrix (``closure_quad(ws)`` tells).  x, dx and gx give the shapes and are not
+        read.  ``out`` may carry a third buffer, loss (S,), that receives mse + w_sym * regulariser.  The library refuses the call
+        under SYMODE_CLOSURE_FOLD=0, SYMODE_FOLD_GRAM=0 or SYMODE_FOLD_RESID_GRAM=0 (``closure_quad_enabled()``): pass ``gram``.
+        ``coef`` = (CoefMap, beta (S, r), const (S, d, 1) or None), with ``aug``: the launch forms Xi from the variables itself
+        (``xi`` is not read; Q beta in fp64, one rounding to fp32) and also returns the gradient by the variables:
+        (loss2, grad, g_beta (S, r), g_const (S, d, 1) or None).  ``coef_out`` = (xi_out or None, g_beta, g_const or None): buffers
+        for these, xi_out (S, d, p) receiving the Xi the launch formed."""
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
         rev = self._reversed_operands(x, gx, jgx, compact_ok=True)
+        if aug is not None:
+            if gram is not None:
+                raise SymodeError("aug takes the place of gram")
+            name, args, _, result = self._closure_quad_call(x, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live_columns,
+                                                            linear_m, aug, coef, coef_out)
+            self._check(getattr(self.lib, name)(*args), name)
+            return result
+        if coef is not None or coef_out is not None:
+            raise SymodeError("coef goes with aug")
         return self._closure(x, dx, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live_columns, linear_m, gram)
 
     def loss_grad_latent(self, z, dz, B, y, xi, mask, order, flags=0, w_pair=1.0, inv_count=None, out=None, ws=None):
