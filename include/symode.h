@@ -956,6 +956,36 @@ int symode_stlsq_sweep_symreg(const double* aug_gram, const double* rev_gram, lo
                               double near_band, double pivot_floor, float* xi_out, unsigned char* mask_out, int* passes_out,
                               int* near_out, int* fell_out, void* stream);
 
+/* The sparsity path of the least-squares fit ON THE DEVICE, all problems in one launch (all pointers device memory): stepwise
+ * sparse regression by backward elimination, scored on held-out data -- no threshold is asked for.  aug_gram (n_sets, p+d,
+ * p+d) and val_gram (n_val_sets, p+d, p+d) fp64 as symode_aug_gram / _gather leave them (raw sums; the second from the
+ * held-out rows); problem s reads training set s % n_sets and validation set s % n_val_sets.  gamma = sqrt(w_sindy_reg) is the
+ * ridge weight.  p <= 64, d <= 4.  Per equation row j, step t = 0 .. p has t columns removed:
+ *   solve      t < p: (Gtt[M, M] + gamma^2 I) x = Gty[M, j] on the active columns M with the statements of one pass of
+ *              symode_stlsq_sweep (pivoted Cholesky, fused forward substitution, back substitution, nothing contracted);
+ *              v = (float)x on M and 0 elsewhere; t = p: v = 0.  path_xi[s, j, t, :] = v;
+ *   errors     for H = the training and the validation matrix, in fp64 with w = (double)v: q_k = sum over l in M ascending of
+ *              H[k][l] w_l from 0.0, r_k = w_k (q_k - 2 H[k][p+j]), e = H[p+j][p+j] then e += r_k for k ascending over M;
+ *              rss_train[s, j, t], rss_val[s, j, t] = e.  The ridge term is in neither; nothing is clamped;
+ *   eliminate  t < p: the active column with the smallest |v| (fp32 compare, the lowest index of equals) leaves,
+ *              order[s, j, t] = that column; with two or more active columns the step counts in near_out[s] when the
+ *              runner-up's |v| minus the smallest, both widened to fp64, is < near_band.
+ * Then e_min = min_t rss_val[s, j, t], cut = (1 + tol) max(e_min, 0) + floor_rel val_gram[p+j][p+j], best[s, j] = the LARGEST
+ * t with rss_val[s, j, t] <= cut (the argmin qualifies), xi_out[s, j, :] = path_xi[s, j, best, :] and mask_out its support.
+ * A pivot that is not > 0 sets fell_out[s] = 1 and ENDS problem s (its other outputs are then unspecified), as for
+ * symode_stlsq_sweep.  n_points is accepted for symmetry with the siblings.
+ * path_xi (n_problems, d, p+1, p) fp32; order (n_problems, d, p) ints; rss_train, rss_val (n_problems, d, p+1) fp64; best
+ * (n_problems, d) ints; xi_out (n_problems, d, p) fp32; mask_out (n_problems, d, p) bytes; near_out, fell_out (n_problems) ints.
+ * Refused before any GPU work: d < 1, d > 4, p < 1, p > 64, n_sets < 1, n_problems < n_sets or >= 2^31, n_val_sets < 1 or
+ * > n_problems, gamma, tol, floor_rel or near_band < 0 or not finite (SYMODE_E_BADSIZE); any pointer NULL (SYMODE_E_NULLPTR);
+ * aug_gram, val_gram, rss_train or rss_val not 8-byte, an fp32 / int output not 4-byte aligned (SYMODE_E_ALIGN).
+ * Added to ABI version 8 (nothing existing changed).
+ * replaces: nothing in the reference; the threshold loop of train.py:872-887 with the threshold chosen by held-out error. */
+int symode_stlsq_path(const double* aug_gram, const double* val_gram, long n_sets, long n_val_sets, long n_problems, int d, int p,
+                      long n_points, double gamma, double tol, double floor_rel, double near_band, float* path_xi, int* order,
+                      double* rss_train, double* rss_val, int* best, float* xi_out, unsigned char* mask_out, int* near_out,
+                      int* fell_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

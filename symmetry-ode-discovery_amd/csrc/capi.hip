@@ -12,6 +12,7 @@
 #include "quad_closure.hpp"
 #include "stlsq.hpp"
 #include "stlsq_constrained.hpp"
+#include "stlsq_path.hpp"
 #include "stlsq_symreg.hpp"
 #include "weak_normal.hpp"
 
@@ -574,6 +575,27 @@ int symode_stlsq_sweep(const double* aug_gram, long n_sets, long n_problems, int
         return SYMODE_E_ALIGN;
     return (int)launch_stlsq_sweep(aug_gram, n_sets, n_problems, d, p, hyper, gamma, threshold, max_iter, near_band, xi_out,
                                    mask_out, passes_out, near_out, fell_out, (hipStream_t)stream);
+}
+
+int symode_stlsq_path(const double* aug_gram, const double* val_gram, long n_sets, long n_val_sets, long n_problems, int d, int p,
+                      long n_points, double gamma, double tol, double floor_rel, double near_band, float* path_xi, int* order,
+                      double* rss_train, double* rss_val, int* best, float* xi_out, unsigned char* mask_out, int* near_out,
+                      int* fell_out, void* stream) {
+    (void)n_points;                     // as symode_stlsq_sweep: only gelsy's rank rule would read it
+    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P) return SYMODE_E_BADSIZE;
+    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
+    if (n_val_sets < 1 || n_val_sets > n_problems) return SYMODE_E_BADSIZE;
+    for (double v : {gamma, tol, floor_rel, near_band})
+        if (!(v >= 0.0) || !std::isfinite(v)) return SYMODE_E_BADSIZE;
+    if (!aug_gram || !val_gram || !path_xi || !order || !rss_train || !rss_val || !best || !xi_out || !mask_out || !near_out ||
+        !fell_out)
+        return SYMODE_E_NULLPTR;
+    if (misaligned(aug_gram, 8) || misaligned(val_gram, 8) || misaligned(rss_train, 8) || misaligned(rss_val, 8) ||
+        misaligned(path_xi, 4) || misaligned(order, 4) || misaligned(best, 4) || misaligned(xi_out, 4) || misaligned(near_out, 4) ||
+        misaligned(fell_out, 4))
+        return SYMODE_E_ALIGN;
+    return (int)launch_stlsq_path(aug_gram, val_gram, n_sets, n_val_sets, n_problems, d, p, gamma, tol, floor_rel, near_band, path_xi,
+                                  order, rss_train, rss_val, best, xi_out, mask_out, near_out, fell_out, (hipStream_t)stream);
 }
 
 int symode_stlsq_sweep_constrained(const double* aug_gram, long n_sets, long n_problems, int d, int p, long n_points,

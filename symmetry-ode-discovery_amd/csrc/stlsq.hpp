@@ -31,6 +31,77 @@ __device__ __forceinline__ double stlsq_lane(double v, int lane) {
     return __hiloint2double(hi, lo);
 }
 
+// The solve of one pass on one equation row, stated once for stlsq_sweep_kernel and stlsq_path_kernel (stlsq_path.hpp):
+// the support's n > 0 columns are listed in sel (ascending), xrow holds zeros; on return xrow[column] is the solution on
+// the support (system, factor and solve as the comment of stlsq_sweep_kernel states them).  True at a pivot that is not
+// > 0, with xrow untouched.  The caller syncs the wave before (sel, xrow) and after (xrow).
+__device__ __forceinline__ bool stlsq_row_solve(const double* __restrict__ G, int F, int p, int j, double g2, int n, int lane,
+                                                double* A, double* xrow, const int* sel) {
+    const bool on = lane < n;
+    const int col = on ? sel[lane] : 0;
+    for (int a = 0; a < n; ++a) {
+        const int ra = sel[a];
+        if (on) A[a * p + lane] = G[(long)ra * F + col] + (ra == col ? g2 : 0.0);
+    }
+    double c = on ? G[(long)col * F + p + j] : 0.0;
+    stlsq_wave_sync();
+    int orig = lane;
+    double dg = on ? A[lane * p + lane] : 0.0;
+    for (int kk = 0; kk < n; ++kk) {
+        double bv = dg;
+        int bi = (lane >= kk && lane < n) ? lane : WAVE;
+#pragma unroll
+        for (int off = WAVE / 2; off > 0; off /= 2) {
+            const double ov = __shfl_xor(bv, off, WAVE);
+            const int oi = __shfl_xor(bi, off, WAVE);
+            if (oi < WAVE && (bi == WAVE || ov > bv || (ov == bv && oi < bi))) {
+                bv = ov;
+                bi = oi;
+            }
+        }
+        const int jp = __builtin_amdgcn_readfirstlane(bi);
+        if (jp != kk) {
+            const int src = lane == kk ? jp : (lane == jp ? kk : lane);
+            orig = __shfl(orig, src, WAVE);
+            dg = __shfl(dg, src, WAVE);
+            c = __shfl(c, src, WAVE);
+        }
+        const double dkk = stlsq_lane(dg, kk);
+        if (!(dkk > 0.0)) return true;
+        const double r = sqrt(dkk);
+        const int jo = __builtin_amdgcn_readlane(orig, kk);
+        const bool rest = lane > kk && lane < n;
+        double Rt = 0.0;
+        if (rest) {
+            Rt = A[jo * p + orig] / r;
+            A[jo * p + orig] = Rt;
+        }
+        if (lane == kk) A[jo * p + jo] = r;
+        for (int a = kk + 1; a < n; ++a) {
+            const double Ra = stlsq_lane(Rt, a);
+            const int oa = __builtin_amdgcn_readlane(orig, a);
+            if (rest) A[oa * p + orig] -= Ra * Rt;
+        }
+        const double q = stlsq_lane(c, kk) / r;
+        if (rest) {
+            c -= Rt * q;
+            dg -= Rt * Rt;
+        }
+        if (lane == kk) c = q;
+        stlsq_wave_sync();
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        const int jo = __builtin_amdgcn_readlane(orig, i);
+        const double prod = (lane > i && lane < n) ? A[jo * p + orig] * c : 0.0;
+        double acc = stlsq_lane(c, i);
+        for (int t = i + 1; t < n; ++t) acc -= stlsq_lane(prod, t);
+        const double y = acc / A[jo * p + jo];
+        if (lane == i) c = y;
+    }
+    if (on) xrow[sel[orig]] = c;
+    return false;
+}
+
 // One workgroup per problem, one wave per equation row j; lane k of the wave owns library column k (mask bit, fp32
 // coefficient).  Per pass the wave solves the ridge system on row j's support -- the host solves the masked case as ONE
 // block-diagonal system over the rows, whose blocks never mix (a zero off-block entry of the factor leaves every sum it
@@ -85,76 +156,7 @@ __global__ __launch_bounds__(WAVE * STLSQ_MAX_D) void stlsq_sweep_kernel(const d
         if (m) sel[__popcll(support & ((1ull << lane) - 1ull))] = lane;
         if (lane < p) xrow[lane] = 0.0;
         stlsq_wave_sync();
-        bool bad = false;
-        if (n > 0) {
-            const bool on = lane < n;
-            const int col = on ? sel[lane] : 0;
-            for (int a = 0; a < n; ++a) {
-                const int ra = sel[a];
-                if (on) A[a * p + lane] = G[(long)ra * F + col] + (ra == col ? g2 : 0.0);
-            }
-            double c = on ? G[(long)col * F + p + j] : 0.0;
-            stlsq_wave_sync();
-            int orig = lane;
-            double dg = on ? A[lane * p + lane] : 0.0;
-            for (int kk = 0; kk < n; ++kk) {
-                double bv = dg;
-                int bi = (lane >= kk && lane < n) ? lane : WAVE;
-#pragma unroll
-                for (int off = WAVE / 2; off > 0; off /= 2) {
-                    const double ov = __shfl_xor(bv, off, WAVE);
-                    const int oi = __shfl_xor(bi, off, WAVE);
-                    if (oi < WAVE && (bi == WAVE || ov > bv || (ov == bv && oi < bi))) {
-                        bv = ov;
-                        bi = oi;
-                    }
-                }
-                const int jp = __builtin_amdgcn_readfirstlane(bi);
-                if (jp != kk) {
-                    const int src = lane == kk ? jp : (lane == jp ? kk : lane);
-                    orig = __shfl(orig, src, WAVE);
-                    dg = __shfl(dg, src, WAVE);
-                    c = __shfl(c, src, WAVE);
-                }
-                const double dkk = stlsq_lane(dg, kk);
-                if (!(dkk > 0.0)) {
-                    bad = true;
-                    break;
-                }
-                const double r = sqrt(dkk);
-                const int jo = __builtin_amdgcn_readlane(orig, kk);
-                const bool rest = lane > kk && lane < n;
-                double Rt = 0.0;
-                if (rest) {
-                    Rt = A[jo * p + orig] / r;
-                    A[jo * p + orig] = Rt;
-                }
-                if (lane == kk) A[jo * p + jo] = r;
-                for (int a = kk + 1; a < n; ++a) {
-                    const double Ra = stlsq_lane(Rt, a);
-                    const int oa = __builtin_amdgcn_readlane(orig, a);
-                    if (rest) A[oa * p + orig] -= Ra * Rt;
-                }
-                const double q = stlsq_lane(c, kk) / r;
-                if (rest) {
-                    c -= Rt * q;
-                    dg -= Rt * Rt;
-                }
-                if (lane == kk) c = q;
-                stlsq_wave_sync();
-            }
-            if (!bad) {
-                for (int i = n - 1; i >= 0; --i) {
-                    const int jo = __builtin_amdgcn_readlane(orig, i);
-                    const double prod = (lane > i && lane < n) ? A[jo * p + orig] * c : 0.0;
-                    double acc = stlsq_lane(c, i);
-                    for (int t = i + 1; t < n; ++t) acc -= stlsq_lane(prod, t);
-                    const double y = acc / A[jo * p + jo];
-                    if (lane == i) c = y;
-                }
-                if (on) xrow[sel[orig]] = c;
-            }
-        }
+        const bool bad = n > 0 && stlsq_row_solve(G, F, p, j, g2, n, lane, A, xrow, sel);
         stlsq_wave_sync();
         int changed = 0;
         if (!bad) {

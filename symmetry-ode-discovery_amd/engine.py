@@ -152,6 +152,9 @@ _SIGNATURES = {
     "symode_stlsq_sweep_symreg": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_long, c_void_p, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    "symode_stlsq_path": (c_int, [c_void_p, c_void_p, c_long, c_long, c_long, c_int, c_int, c_long, ctypes.c_double, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
@@ -1085,6 +1088,57 @@ class HipEngine:
             import numpy as np
             return parts(buf.cpu().numpy(), np.float32, np.int32)
         return parts(buf, torch.float32, torch.int32)
+
+    def stlsq_path(self, G, V, n_points, gamma, tol, floor_rel, n_problems=None, *, d, near_band=1e-4, to_host=False,
+                   keep_path=False):
+        """The sparsity path of every problem in ONE launch (symode_stlsq_path): backward elimination from the full library to
+        the empty model, every model scored on the held-out matrix, the sparsest one within ``tol`` of the best kept.  G
+        (n_sets, p+d, p+d) and V (n_val_sets, p+d, p+d) fp64 on the device, raw sums of the training and the held-out rows;
+        problem s reads sets s % n_sets and s % n_val_sets; ``n_problems`` defaults to n_sets.  ``gamma`` the ridge weight.
+        Returns a dict of device tensors: Xi (n_problems, d, p) fp32, mask (n_problems, d, p) uint8, order (n_problems, d, p)
+        int32, rss_train, rss_val (n_problems, d, p+1) fp64, best (n_problems, d), near, fell (n_problems,) int32 -- a problem
+        with ``fell`` set met a pivot that is not positive and is the host's to solve -- and path_xi (n_problems, d, p+1, p)
+        fp32.  ``to_host=True``: numpy arrays after ONE copy of the buffer the small outputs share; path_xi (the one large
+        output) is then fetched only with ``keep_path=True`` and left out of the dict otherwise -- that saves its copy, not its
+        allocation or the kernel's writes: the entry always writes the path."""
+        G = self._dev(G, "G", torch.float64)
+        V = self._dev(V, "V", torch.float64)
+        d = int(d)
+        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
+            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
+        if V.dim() != 3 or V.shape[1:] != G.shape[1:] or V.device != G.device:
+            raise SymodeError(f"V must be (n_val_sets, p + d, p + d) = (n_val_sets, {G.shape[1]}, {G.shape[2]}) on {G.device}, "
+                              f"got {tuple(V.shape)} on {V.device}")
+        n_sets, p = G.shape[0], G.shape[1] - d
+        S = n_sets if n_problems is None else int(n_problems)
+        sizes = [8 * S * d * (p + 1), 8 * S * d * (p + 1), 4 * S * d * p, 4 * S * d * p, 4 * S * d, 4 * S, 4 * S, S * d * p]
+        cuts = [0]
+        for n in sizes:
+            cuts.append(cuts[-1] + n)
+        buf = torch.empty(max(cuts[-1], 0), dtype=torch.uint8, device=G.device)    # fp64 first, bytes last: every part aligned
+        path = torch.empty(max(S, 0), d, p + 1, p, dtype=torch.float32, device=G.device)
+
+        def parts(b, f64, f32, i32):
+            tr, va, xi, order, best, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
+            return dict(Xi=xi.view(f32).reshape(S, d, p), mask=mask.reshape(S, d, p), order=order.view(i32).reshape(S, d, p),
+                        rss_train=tr.view(f64).reshape(S, d, p + 1), rss_val=va.view(f64).reshape(S, d, p + 1),
+                        best=best.view(i32).reshape(S, d), near=near.view(i32), fell=fell.view(i32))
+
+        o = parts(buf, torch.float64, torch.float32, torch.int32)
+        self._check(self.lib.symode_stlsq_path(self._ptr(G), self._ptr(V), n_sets, V.shape[0], S, d, p, int(n_points), float(gamma),
+                                               float(tol), float(floor_rel), float(near_band), self._ptr(path), self._ptr(o["order"]),
+                                               self._ptr(o["rss_train"]), self._ptr(o["rss_val"]), self._ptr(o["best"]),
+                                               self._ptr(o["Xi"]), self._ptr(o["mask"]), self._ptr(o["near"]), self._ptr(o["fell"]),
+                                               self._stream(G)),
+                    "symode_stlsq_path")
+        if to_host:
+            import numpy as np
+            o = parts(buf.cpu().numpy(), np.float64, np.float32, np.int32)
+            if keep_path:
+                o["path_xi"] = path.cpu().numpy()
+            return o
+        o["path_xi"] = path
+        return o
 
     def stlsq_sweep_constrained(self, G, n_points, gamma, threshold, max_iter, q_solve, q_xi, allow_constant, hyper=None,
                                 n_problems=None, *, d, pivot_floor, near_band=1e-4, to_host=False, tail=None):

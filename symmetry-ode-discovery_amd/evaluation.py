@@ -62,6 +62,8 @@ def aggregate_results(run_name, min_seed=0, max_seed=100, mse_multiplier=1.0):
     for filename in sorted(os.listdir(directory)):
         if not filename.endswith('.npz'):
             continue
+        if not (filename.startswith('seed') and filename[4:-4].isdigit()):     # path.npz of main_sweep --stlsq_path: no seed's file
+            continue
         seed = int(filename.split('.')[0][4:])
         if seed >= max_seed or seed < min_seed:
             continue

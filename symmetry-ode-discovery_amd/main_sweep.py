@@ -79,6 +79,14 @@ parser's default --sindy_optimizer does not matter to it.  ``--wsindy_grid name=
 w_sindy_reg; with --wsindy only) is its grid on the windows' shared matrices; problem order, result files and table are
 ``--grid``'s.
 
+``--stlsq_path [--path_tol v]`` (with --method stlsq --device_stlsq) asks for no threshold: per seed and equation row the sparsity
+path -- solve on the full library, drop the smallest coefficient, solve again, down to the empty model -- is walked in ONE launch
+(symode_stlsq_path, ``SeedSweepSTLSQ.solve_path``), every model of the path is scored on the validation set's matrix, and the
+sparsest model whose held-out error is within path_tol (default 0.02) of the best is kept.  Result files, --eval_ltp and the
+aggregate are those of ``--method stlsq``; ``eval_results/<save_dir>/path.npz`` holds order, rss_train, rss_val and best of all
+seeds.  --threshold is not used.  Not covered, and refused by name: the constrained and the regularised fits, --wsindy, the grids,
+--lstsq_driver gelsy, --use_latent.
+
 ``--fold_linear_action`` lets the closure of the reversed regulariser fold a linear group action g(x) = J x into its
 coefficients where the data are found to be one (``BatchedClosure(linear_action=None)``): a faster kernel and the same
 closure up to rounding, not bit for bit -- which is why it has to be asked for here.
@@ -176,7 +184,8 @@ def _grid_problem(problem, n_seeds):
 
 
 def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None, device_stlsq=False,
-             stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False, min_norm_stlsq=False, symreg_stlsq=False):
+             stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False, min_norm_stlsq=False, symreg_stlsq=False,
+             stlsq_path=False, path_tol=None):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
@@ -191,9 +200,20 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     ``min_norm_stlsq``: the ``--min_norm_stlsq`` flag, a mode of --equiv_stlsq and refused by name without it.
     ``symreg_stlsq``: the ``--symreg_stlsq`` flag; off, every answer is what it was.  On, its own rules
     (``_refusal_symreg_stlsq``) come first, the rule that keeps the symmetry regulariser out of --method stlsq does not apply,
-    and --stlsq_grid reads SYMREG_STLSQ_GRID_NAMES."""
+    and --stlsq_grid reads SYMREG_STLSQ_GRID_NAMES.
+    ``stlsq_path``, ``path_tol``: the ``--stlsq_path`` flag and the ``--path_tol`` value (None: not given); off, every answer
+    is what it was.  On, its own rules (``_refusal_stlsq_path``) come first; what they let through is a plain
+    ``--method stlsq --device_stlsq`` run, which the rules below judge as they always did."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
+    if path_tol is not None and not stlsq_path:
+        return ('--path_tol needs --stlsq_path: it is the tolerance of the sparsity path (the sparsest model within path_tol of '
+                'the best held-out error); the threshold loop takes --threshold')
+    if stlsq_path:
+        why = _refusal_stlsq_path(args, method, engine, device_stlsq, equiv_stlsq, min_norm_stlsq, symreg_stlsq,
+                                  wsindy or wsindy_grid, grid or lbfgs_grid or stlsq_grid, path_tol)
+        if why is not None:
+            return why
     if symreg_stlsq:
         why = _refusal_symreg_stlsq(args, method, device_stlsq, wsindy or wsindy_grid, equiv_stlsq, min_norm_stlsq)
         if why is not None:
@@ -350,6 +370,40 @@ def _refusal_symreg_stlsq(args, method, device_stlsq, wsindy, equiv_stlsq, min_n
     return None
 
 
+PATH_TOL = 0.02                                            # --path_tol's default (profiles/stlsq_path.txt: how it was chosen)
+
+
+def _refusal_stlsq_path(args, method, engine, device_stlsq, equiv_stlsq, min_norm_stlsq, symreg_stlsq, wsindy, any_grid, path_tol):
+    """The rules of --stlsq_path, all decided by the arguments alone."""
+    if method != 'stlsq':
+        return ('--stlsq_path is the sparsity path of the sequential least-squares sweep (backward elimination scored on the '
+                'validation set): it needs --method stlsq')
+    if not device_stlsq:
+        return ('--stlsq_path needs --device_stlsq: the path of every seed is one launch on the device (the host route of '
+                '--method stlsq runs the threshold loop)')
+    if args.get('eq_constraint') or equiv_stlsq or min_norm_stlsq:
+        return ('--stlsq_path does not go with --eq_constraint / --equiv_stlsq / --min_norm_stlsq: the path under the equivariance '
+                'constraint is a joint system over the rows and is not covered (drop them, or fit with --equiv_stlsq and a threshold)')
+    if args['w_sym_reg'] > 0 or symreg_stlsq:
+        return ('--stlsq_path does not go with --w_sym_reg > 0 / --symreg_stlsq: the path with the symmetry regulariser is a joint '
+                'system over the rows and is not covered (drop them, or fit with --symreg_stlsq and a threshold)')
+    if wsindy:
+        return ('--stlsq_path is the path of --method stlsq: the weak-SINDy sweep (--wsindy) is not covered (drop one of them)')
+    if any_grid:
+        return ('--stlsq_path does not go with --grid / --lbfgs_grid / --stlsq_grid / --wsindy_grid: the path visits every '
+                'support a threshold grid could reach and asks for no threshold (drop the grid)')
+    if args.get('lstsq_driver') == 'gelsy':
+        return ('--stlsq_path fits with the full-rank driver (gels) only: the rank rule of --lstsq_driver gelsy runs on the '
+                'host route (drop one of them)')
+    if args['use_latent']:
+        return '--stlsq_path does not cover latent fits (--use_latent)'
+    if engine is None and str(args.get('device')) == 'cpu':
+        return '--stlsq_path runs on the GPU only (no CPU fallback): a HIP device is required'
+    if path_tol is not None and not (np.isfinite(path_tol) and path_tol >= 0):
+        return f'--path_tol {path_tol:g}: the tolerance of the sparsity path must be a finite number >= 0'
+    return None
+
+
 def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid, names=STLSQ_GRID_NAMES):
     """The rules of --device_stlsq and --stlsq_grid (``_refusal``, which has applied the rules of --method stlsq itself).
     ``names``: the axes of the grid (SYMREG_STLSQ_GRID_NAMES under --symreg_stlsq, whose w_sym_reg values must be > 0)."""
@@ -468,6 +522,8 @@ def _fit_stlsq(ctx):
     rows = _rows(ctx)
     sw = SeedSweepSTLSQ(ctx.x_all, ctx.dx_all, *lib, n_seeds=len(ctx.seeds), subsample=args['lbfgs_subsample'], seed0=args['seed'],
                         group=ctx.group, engine=ctx.engine, idx=rows, idx_sorted=True)
+    if getattr(ctx, 'stlsq_path', False):
+        return _fit_stlsq_path(ctx, sw, lib)
     if laligan is not None:
         # [G | R | count] as _fit_lbfgs builds them under --gram_closure: no per-seed copy of the points, ONE all-reduce
         from .gram_closure import GramStatistics
@@ -499,6 +555,29 @@ def _fit_stlsq(ctx):
     lines = [f'{len(ctx.seeds)} seeds x {sw.n_points} points (over {ctx.world} rank(s)), STLSQ passes {int(passes.min())}-{int(passes.max())}',
              f'near-threshold coefficients (| |coef| - thr | < 1e-4): {sw.near_threshold if sw.near_threshold else "none"}']
     return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines + _min_norm_lines(sw, fit))
+
+
+def _fit_stlsq_path(ctx, sw, lib):
+    """--stlsq_path: the seeds' matrices as ``_fit_stlsq`` builds them, the validation set's matrix (every rank forms it from
+    the whole set: no collective), ONE symode_stlsq_path launch (``SeedSweepSTLSQ.solve_path``).  Rank 0 also writes
+    eval_results/<save_dir>/path.npz: order, rss_train, rss_val and best of all seeds."""
+    args, val = ctx.args, ctx.val
+    tol = PATH_TOL if ctx.path_tol is None else ctx.path_tol
+    V = sw.val_grams(val.x.to(ctx.dev), val.dx.to(ctx.dev))
+    Xi, mask, record = sw.solve_path(args['w_sindy_reg'], V, tol)
+    if ctx.rank == 0:
+        eval_dir = f'eval_results/{args["save_dir"]}'
+        os.makedirs(eval_dir, exist_ok=True)
+        np.savez(f'{eval_dir}/path.npz', seeds=np.asarray(ctx.seeds), path_tol=tol,
+                 **{k: record[k] for k in ('order', 'rss_train', 'rss_val', 'best')})
+    size = sw.p - record['best']                                          # (S, d): columns the chosen model keeps
+    lines = [f'{len(ctx.seeds)} seeds x {sw.n_points} points (over {ctx.world} rank(s)), sparsity path of {sw.p + 1} models per row, '
+             f'scored on {val.x.shape[0]} validation points, path_tol {tol:g}',
+             'chosen support size per row: ' + ', '.join(f'row {j}: {int(size[:, j].min())}-{int(size[:, j].max())}'
+                                                         for j in range(size.shape[1])),
+             f'near-tie eliminations: {int((record["near"] > 0).sum())} of {len(ctx.seeds)} problems',
+             f'--threshold ({args["threshold"]:g}) is not used by the path']
+    return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
 
 
 def _min_norm_lines(sw, fit):
@@ -791,12 +870,15 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     equiv_stlsq = _pop_flag(argv, '--equiv_stlsq')
     min_norm_stlsq = _pop_flag(argv, '--min_norm_stlsq')
     symreg_stlsq = _pop_flag(argv, '--symreg_stlsq')
+    stlsq_path = _pop_flag(argv, '--stlsq_path')
+    path_tol = _pop(argv, '--path_tol', None, float)
     fold_linear_action = _pop_flag(argv, '--fold_linear_action')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
                    device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None, wsindy=wsindy, wsindy_grid=wsindy_grid or None,
-                   equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq)
+                   equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq, stlsq_path=stlsq_path,
+                   path_tol=path_tol)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -817,7 +899,8 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
                           world=world, x_all=x_all, dx_all=dx_all, m=m, lo=rank * m // world, hi=(rank + 1) * m // world,
                           engine=engine, kw={} if engine is None else {'engine': engine}, grid=None,
                           device_stlsq=device_stlsq, fold_linear_action=fold_linear_action, train=train_dataset,
-                          equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq)
+                          equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq,
+                          stlsq_path=stlsq_path, path_tol=path_tol, val=val_dataset)
     if wsindy_grid:
         ctx.grid_names = WSINDY_GRID_NAMES
         ctx.grid_axes = _parse_grid(wsindy_grid, WSINDY_GRID_NAMES, '--wsindy_grid')[0]

@@ -419,6 +419,71 @@ def stlsq_symreg_from_gram(G, R, n_points, mask, gamma, w_sym, d, driver="gels")
     return xi, w
 
 
+def stlsq_path_rss(H, p, j, sel, w):
+    """e = Hyy - 2 w^T c + w^T H w of equation row j's coefficients w (p,) fp64 with support ``sel`` (ascending columns) on the
+    raw sums H (p+d, p+d), in symode_stlsq_path's order of operations: q_k = sum_l H[k][l] w_l over the support ascending from
+    0.0, r_k = w_k (q_k - 2 H[k][p+j]), e = H[p+j][p+j] plus the r_k for k ascending.  Nothing is clamped."""
+    e = H[p + j, p + j]
+    for k in sel:
+        q = 0.0
+        for l in sel:
+            q += H[k, l] * w[l]
+        e += w[k] * (q - 2.0 * H[k, p + j])
+    return e
+
+
+def stlsq_path_select(rss_val, vyy, tol, floor_rel):
+    """The step symode_stlsq_path keeps: the LARGEST t with rss_val[t] <= (1 + tol) max(min rss_val, 0) + floor_rel vyy."""
+    e_min = min(float(v) for v in rss_val)
+    cut = (1.0 + tol) * (e_min if e_min > 0.0 else 0.0) + floor_rel * vyy
+    ok = [t for t, v in enumerate(rss_val) if v <= cut]
+    return ok[-1] if ok else len(rss_val) - 1
+
+
+def stlsq_path_from_gram(G, V, gamma, tol, floor_rel, near_band, d, n_points=0):
+    """The sparsity path of ONE problem in numpy, the host twin of symode_stlsq_path: per equation row backward elimination
+    from the full library to the empty model -- solve the ridge system on the active columns
+    (``lstsq_normal(..., 'gels')``, with its minimum-norm fallback and RuntimeWarning on a singular support), round to fp32,
+    score the model on the training matrix G and the held-out matrix V (both (p+d, p+d) raw sums, ``stlsq_path_rss``), drop
+    the active column with the smallest |coefficient| (fp32 compare, the lowest index of equals) -- then keep the sparsest
+    model whose held-out error is within ``tol`` of the best (``stlsq_path_select``).  ``near`` counts the eliminations whose
+    runner-up was within ``near_band``.  ``n_points``: the rows behind G (only a rank-revealing fallback reads it).
+    Returns (Xi (d, p) float32, mask (d, p) bool, record) with record = dict(order (d, p) int32, rss_train, rss_val
+    (d, p+1) float64, best (d,) int32, near int, path_xi (d, p+1, p) float32)."""
+    G, V = np.asarray(G, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    p = G.shape[0] - d
+    Gtt = G[:p, :p] + (gamma * gamma) * np.eye(p)
+    path = np.zeros((d, p + 1, p), dtype=np.float32)
+    order = np.zeros((d, p), dtype=np.int32)
+    rss_train, rss_val = np.zeros((d, p + 1)), np.zeros((d, p + 1))
+    best = np.zeros(d, dtype=np.int32)
+    near = 0
+    for j in range(d):
+        active = np.ones(p, dtype=bool)
+        for t in range(p + 1):
+            sel = np.nonzero(active)[0]
+            if len(sel):
+                w, _ = lstsq_normal(Gtt[np.ix_(sel, sel)], G[sel, p + j], int(n_points) + len(sel), 'gels')
+                path[j, t, sel] = np.asarray(w, dtype=np.float64).astype(np.float32)
+            w64 = path[j, t].astype(np.float64)
+            rss_train[j, t] = stlsq_path_rss(G, p, j, sel, w64)
+            rss_val[j, t] = stlsq_path_rss(V, p, j, sel, w64)
+            if len(sel):
+                av = np.abs(path[j, t, sel])
+                out = int(np.argmin(av))                         # the first of equals: the lowest column index
+                if len(sel) > 1:
+                    up = np.delete(av, out).min()
+                    near += int(float(up) - float(av[out]) < near_band)
+                order[j, t] = sel[out]
+                active[sel[out]] = False
+        best[j] = stlsq_path_select(rss_val[j], V[p + j, p + j], tol, floor_rel)
+    Xi = np.stack([path[j, best[j]] for j in range(d)])
+    mask = np.zeros((d, p), dtype=bool)
+    for j in range(d):
+        mask[j, order[j, best[j]:]] = True                     # the columns that leave at step best or later are active there
+    return Xi, mask, dict(order=order, rss_train=rss_train, rss_val=rss_val, best=best, near=near, path_xi=path)
+
+
 def _mask_on_host(regressor):
     """Boolean host copy of the mask without a device round trip when the mask on the device is still the tensor this
     module uploaded last (the mirror keeps that tensor alive, so an equal address means the same storage; in-place

@@ -19,8 +19,8 @@ import torch.distributed as dist
 from .coef_map import CoefMap
 from .engine import LBFGS_ACCEPT, LBFGS_BEGIN, get_engine, library_flags
 from . import lstsq as _lstsq
-from .sindy import (NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_constrained_from_gram, stlsq_solve_from_gram,
-                    stlsq_symreg_from_gram, weak_test_functions)
+from .sindy import (NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_constrained_from_gram, stlsq_path_from_gram,
+                    stlsq_solve_from_gram, stlsq_symreg_from_gram, weak_test_functions)
 
 
 def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
@@ -255,6 +255,66 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         """Hand in the seeds' (S, p+d, p+d) fp64 matrices on the device, already summed over the ranks, and the points behind
         each (a caller that built them beside other statistics, in one collective): ``grams`` then gathers nothing."""
         self._gram_dev, self._gram, self.n_points = G, None, int(n_points)
+
+    def val_grams(self, x_val, dx_val):
+        """(1, p+d, p+d) fp64 on the device: the augmented Gram matrix of the held-out rows x_val, dx_val (N_val, d), one dense
+        symode_aug_gram launch -- ``solve_path``'s ``val_gram``, shared by all seeds (n_val_sets = 1).  Under several ranks
+        every rank hands in the WHOLE validation set and forms the same matrix, so there is no collective."""
+        assert x_val.dim() == 2 and x_val.shape == dx_val.shape and x_val.shape[1] == self.d
+        dev = self.x.device
+        return self.engine.aug_gram(x_val.to(dev).contiguous()[None], dx_val.to(dev).contiguous()[None], self.order, self.flags)
+
+    def solve_path(self, w_sindy_reg, val_gram, tol, floor_rel=1e-10, device=True, keep_path=False):
+        """The sparsity path for every seed: backward elimination from the full library to the empty model (solve, drop the
+        smallest coefficient, solve again), every model scored on the held-out matrix ``val_gram`` ((n_val, p+d, p+d) fp64 raw
+        sums, host or device, n_val = 1 or S: ``val_grams``), and per equation row the sparsest model kept whose held-out
+        error is <= (1 + tol) max(best, 0) + floor_rel Vyy.  No threshold is asked for.
+        ``floor_rel`` = 1e-10 keeps the rule meaningful where the best error is rounding noise around 0 (an exact fit): it is
+        two decades above the (p + 1)^2 2^-53 ~ 5e-13 rounding level of the quadratic forms, relative to Vyy, at p = 64.
+        ``device=True``: ONE symode_stlsq_path launch on the matrices where ``grams(device=True)`` left them and one copy
+        back of the small outputs; a problem the launch flags (a pivot that is not positive) goes to the host twin
+        (sindy.stlsq_path_from_gram) with the RuntimeWarning of the full-rank driver, and only those problems' matrices are
+        copied.  ``device=False``: the host twin for every seed.
+        Returns (Xi (S, d, p) float32, mask (S, d, p) float32, record) with record = dict(order (S, d, p), rss_train, rss_val
+        (S, d, p+1), best (S, d), near (S,)) and, with ``keep_path=True``, path_xi (S, d, p+1, p)."""
+        S, d, p = self.S, self.d, self.p
+        for name, v in (('w_sindy_reg', w_sindy_reg), ('tol', tol), ('floor_rel', floor_rel)):
+            if not (np.isfinite(float(v)) and float(v) >= 0):
+                raise ValueError(f'solve_path: {name} must be finite and >= 0, got {v}')
+        shape = tuple(val_gram.shape)
+        if len(shape) != 3 or shape[1:] != (p + d, p + d) or shape[0] not in (1, S):
+            raise ValueError(f'solve_path: val_gram must be (n_val, p + d, p + d) = (1 or {S}, {p + d}, {p + d}), got {shape}')
+        gamma = float(np.sqrt(float(w_sindy_reg)))
+        keys = ('order', 'rss_train', 'rss_val', 'best', 'near') + (('path_xi',) if keep_path else ())
+
+        def twin(Gs, Vs):
+            xi, m, rec = stlsq_path_from_gram(Gs, Vs, gamma, float(tol), float(floor_rel), NEAR_THRESHOLD_BAND, d, self.n_points)
+            return xi, m, rec
+
+        if not device:
+            G = self.grams()
+            Vh = val_gram.detach().cpu().numpy() if torch.is_tensor(val_gram) else np.asarray(val_gram, dtype=np.float64)
+            out = [twin(G[s], Vh[s % shape[0]]) for s in range(S)]
+            record = {k: np.stack([np.asarray(o[2][k]) for o in out]) for k in keys}
+            record['near'] = record['near'].astype(np.int32)              # (the launch's type)
+            return (torch.from_numpy(np.stack([o[0] for o in out])),
+                    torch.from_numpy(np.stack([o[1] for o in out]).astype(np.float32)), record)
+        G = self.grams(device=True)
+        V = torch.as_tensor(val_gram).to(device=G.device, dtype=torch.float64).contiguous()
+        o = self.engine.stlsq_path(G, V, self.n_points, gamma, float(tol), float(floor_rel), d=d, near_band=NEAR_THRESHOLD_BAND,
+                                   to_host=True, keep_path=keep_path)
+        Xi, mask = np.array(o['Xi']), np.asarray(o['mask']).astype(bool)
+        record = {k: np.array(o[k]) for k in keys}
+        if o['fell'].any():
+            # a pivot that was not positive: these problems are the host twin's, minimum-norm fallback and warning included
+            import warnings
+            for s in np.nonzero(o['fell'])[0].tolist():
+                Xi[s], mask[s], rec = twin(G[s].cpu().numpy(), V[s % shape[0]].cpu().numpy())
+                for k in keys:
+                    record[k][s] = rec[k]
+            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
+                          RuntimeWarning)
+        return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), record
 
     def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None, coef=None, min_norm=False,
               rev=None):
