@@ -347,6 +347,36 @@ int symode_loss_grad_reversed_linear_quad(const double* aug_table, const double*
                                           float* loss_out, float* grad_out, float* xi_out, float* g_beta_out, float* g_const_out,
                                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* symode_loss_grad_reversed_linear_quad with the map, reduced ONCE to a quadratic form in the fit's own variables.  For fixed
+ * aug_table, m_table, table, q, mask, live_columns and w_sym that entry's loss is an exact quadratic in z = (beta, const),
+ * K = r + d_c numbers per problem (d_c = 2 with has_const, else 0).  With P z = view(q beta) + const on column 0 (masked, dead
+ * columns 0) and g(W) the gradient by xi that entry forms at coefficients W (no rounding of W to fp32 here):
+ *     column i of H = 1/2 P^T (g(P e_i) - g(0)),   h = -1/2 P^T g(0),   c0 = inv_count tr(Gyy),
+ *     b_out[s] = 1/2 (B + B^T),  B = [[H, -h], [-h^T, c0]]   (K+1, K+1) fp64, row-major, (S, K+1, K+1) in all,
+ * so that with v = [z; 1]:  loss = v^T B v  and  d loss / d z = 2 (B v)[:K].  fp64 throughout; one wave per problem walks the
+ * K + 1 states; a set-up step, to be repeated when any operand changes.  mask (S, 2, p) fp32 or NULL.
+ * order 1-5 (d = 2, plain polynomial library, one group element); other orders, and every call under SYMODE_QUAD_REDUCED=0 or a
+ * switch that refuses symode_loss_grad_reversed_linear_quad: SYMODE_E_UNSUPPORTED.  r outside [1, 2 p] or K + 1 > 16:
+ * SYMODE_E_BADSIZE.  No workspace.  Added to ABI version 8 (nothing existing changed).
+ * replaces: nothing in the reference; the fixed-data part of the closure body train.py:663-689, formed once per fit. */
+int symode_quad_reduce(const double* aug_table, const double* m_table, const float* table, long n_problems, int order,
+                       const float* q, int r, int use_kron, int has_const, unsigned long long live_columns, double inv_count,
+                       float w_sym, const float* mask, double* b_out, void* stream);
+
+/* The step on the reduced form: b (S, K+1, K+1) fp64 of symode_quad_reduce, k = K, d_c = 0 or the number of constants;
+ * beta (S, K - d_c) fp32 with rows beta_stride floats apart (>= K - d_c), const_ (S, d_c) with rows const_stride floats apart
+ * (>= d_c; NULL, with g_const_out, when d_c = 0).  loss_out (S) = v^T B v, g_beta_out (S, K - d_c) and g_const_out (S, d_c) =
+ * 2 (B v)[:K], each formed in fp64 and rounded to fp32 once.  A group of 16 lanes per problem, no shared memory; reads
+ * 8 (K+1)^2 bytes per problem.  Xi, the loss pair and the gradient by Xi are not formed.
+ * workspace: an initialised one (symode_workspace_init); only its header is used -- word 1 gets what
+ * symode_loss_grad_reversed_linear_quad leaves there for the same order and live_columns, plus bit 256.
+ * K + 1 > 16, k < 1, d_c outside [0, k), a stride below its row: SYMODE_E_BADSIZE; switches and orders as symode_quad_reduce.
+ * Added to ABI version 8 (nothing existing changed).
+ * replaces: the closure body train.py:663-664 + 675-679 + 689 with get_Xi (sindy.py:169-176) and its transpose. */
+int symode_quad_step(const double* b, long n_problems, int k, int d_c, int order, unsigned long long live_columns,
+                     const float* beta, long beta_stride, const float* const_, long const_stride, float* loss_out,
+                     float* g_beta_out, float* g_const_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Gram matrix of the reversed regulariser: for S problems (layouts as in symode_symreg_reversed_batched, n_g >= 1)
  *     gram_out[s] (d p, d p) fp64 = sum_g sum_n B^T B,   B[i, (j, a)] = J_g(x_n)[i, j] theta_a(x_n) - delta_ij theta_a(g x_n),
  * rows and columns in Xi's (d, p) row-major order, both triangles filled: the regulariser of symode_symreg_reversed_batched

@@ -61,7 +61,7 @@ def allreduce_sums(sums, params, group):
 class BatchedClosure:
     def __init__(self, x, dx, poly_order, include_sine=False, include_exp=False, Q=None, use_kron_product=True,
                  allow_constant=True, group=None, world_size=None, n_chunks=1, engine=None, reversed_sym=None, fuse_sym=True, coef=None,
-                 const_jacobian=None, live_columns=True, linear_action=None, regulariser_gram=None, residual_gram=None):
+                 const_jacobian=None, live_columns=True, linear_action=None, regulariser_gram=None, residual_gram=None, reduced=None):
         """``coef``: the variables <-> Xi map (coef_map.CoefMap; default: built from Q / use_kron_product / allow_constant).
         ``reversed_sym = (gx (S, n_g, N_local, d), jgx (S, n_g, N_local, d, d), weight)`` adds  weight * the reversed
         symmetry regulariser (model_utils.py:126-170 on precomputed (g(x), J_g(x))) to every problem's loss and gradient:
@@ -97,7 +97,19 @@ class BatchedClosure:
         pass over the points is the set-up's.  ``evaluate`` on one chunk without point shards hands the launch the coefficient
         map as well (``coef=``): Xi from (beta, const) and the gradient by them come out of the same kernel.  Linear in the
         matrix like the regulariser, so the all-reduce stays what it is.  SYMODE_FOLD_RESID_GRAM=0 or False give the step
-        with the point loop, bit for bit."""
+        with the point loop, bit for bit.
+        ``reduced``: None (default) -- where ``evaluate`` takes that one-launch step and is called without a mask, the closure
+        is reduced once to its quadratic form in the variables, loss = v^T B v with v = [beta; const; 1] and B (K+1, K+1) fp64
+        per problem, K = r + d (engine.quad_reduce), and a step reads B alone (engine.quad_step_plan: one allocation, one
+        call).  Taken when K + 1 <= 16 and (K+1)^2 < (p+d)^2 + p^2, i.e. when B is the smaller table.  The form is exact for
+        the fp64 closure; it differs from the one-launch step, which rounds Xi to fp32 once, by less than one fp32 rounding of
+        the outputs.  B is remembered with the version counters and data pointers of x, dx, gx, jgx and Q, the weight and
+        the column set, and built again when any of them moves (``reduced_builds`` counts).  On this route the loss pair and
+        the gradient by Xi are not formed: ``sym_buffers`` and ``buffers[0][n:]`` keep what the last other launch left there.
+        A call WITH a mask keeps the one-launch kernel: SeedSweepLBFGS mutates its mask in place, also inside a captured
+        iteration, and a replayed graph runs no Python, so no version key could follow it.  A call made while the current
+        stream is capturing builds nothing: without a valid B it takes the one-launch kernel.  SYMODE_QUAD_REDUCED=0 or False
+        give the one-launch step, bit for bit."""
         assert x.dim() == 3 and x.shape == dx.shape, "x, dx must be (S, N_local, d)"
         self.engine = engine or get_engine()
         self.x, self.dx = x.contiguous(), dx.contiguous()
@@ -156,6 +168,37 @@ class BatchedClosure:
         if live_columns and self._cj_detect:
             live = self.coef.live_mask()
             self._live = None if live == 0xFFFFFFFFFFFFFFFF else live
+        K = self.coef.r + (self.d if self.coef.allow_constant else 0)
+        self._reduced_on = (reduced is None or bool(reduced)) and self._resid_on and self.coef.Q is not None and self.coef.r > 0 \
+            and not self.distributed and len(self.chunks) == 1 and self.fuse_sym and hasattr(self.engine, 'quad_step_plan') \
+            and K + 1 <= 16 and (K + 1) ** 2 < (self.p + self.d) ** 2 + self.p ** 2
+        self._reduced_seen, self._reduced_step, self.reduced_builds = None, None, 0
+
+    def _reduced_key(self):
+        """What the reduced form was built from: the keys of ``_gram_for_launch`` and ``_linear_for_launch``, the weight, the
+        column set and Q"""
+        x, dx, (gx, jgx, weight), Q = self.x, self.dx, self.sym, self.coef.Q
+        return (x._version, x.data_ptr(), dx._version, dx.data_ptr(), gx._version, gx.data_ptr(), jgx._version, jgx.data_ptr(),
+                weight, self._live, Q._version, Q.data_ptr())
+
+    def _reduced_for_launch(self):
+        """The prepared step on the reduced form B of the closure ``evaluate`` would launch, built once per ``_reduced_key``
+        (``reduced_builds`` counts); None where that closure is not the one without a point loop, where the library's
+        switches refuse the form, and -- nothing is built inside a capture -- while the current stream is capturing."""
+        self._reduced_seen, self._reduced_step = None, None
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        lin = self._linear_for_launch()
+        aug = self._quad_for_launch() if lin is not None else None
+        if aug is None or not self.engine.closure_reduced_enabled():
+            return None
+        key = self._reduced_key()
+        B = self.engine.quad_reduce(aug, lin, self._cj_table, self.order, self.coef, self.sym[2], self.inv_count, self._live)
+        self._reduced_step = self.engine.quad_step_plan(B, self.order, self._live, self.coef.r,
+                                                        self.d if self.coef.allow_constant else 0, self._ws_kw['ws'])
+        self._reduced_seen = key
+        self.reduced_builds += 1
+        return self._reduced_step
 
     def _jacobian_for_launch(self):
         """What the closures get as J_g: the compact table when the detection pass found every slab constant, else the
@@ -301,7 +344,20 @@ class BatchedClosure:
         return loss, grad
 
     def evaluate(self, beta, const=None, mask=None, alias=False):
-        """Closure of all S problems: (loss (S,), d/dbeta [or d/dXi when unconstrained], d/dconst)."""
+        """Closure of all S problems: (loss (S,), d/dbeta [or d/dXi when unconstrained], d/dconst).
+        Without a mask, where the constructor's ``reduced`` route holds, the call is the step on the reduced form: the three
+        results are views of one packed buffer (fresh per call unless ``alias``), and the loss pair and d/dXi are not formed --
+        ``sym_buffers`` and ``buffers[0][n:]`` keep their last contents.  A call with a mask, and a call under stream capture
+        that finds no valid form, take the one-launch kernel."""
+        if self._reduced_on and mask is None and (const is not None or not self.coef.allow_constant):
+            # the step on the reduced form: a comparison of the keys, one packed allocation, one call (engine.ReducedStep)
+            step = self._reduced_step
+            if step is None or self._reduced_seen != self._reduced_key():
+                step = self._reduced_for_launch()
+            if step is not None:
+                out = self.engine.loss_grad_reversed(None, None, None, None, None, None, self.order, reduced=(step, beta, const, alias))
+                if out is not None:
+                    return out
         if self.coef.Q is not None and self.coef.r > 0 and not self.distributed and len(self.chunks) == 1 and self.sym is not None \
                 and self.fuse_sym and self._resid_on and self._linear_for_launch() is not None and self._quad_for_launch() is not None:
             return self.loss_grad_xi(None, mask, alias=alias, live_columns=self._live, coef=(beta, const))

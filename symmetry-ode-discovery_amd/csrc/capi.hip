@@ -6,6 +6,7 @@
 
 #include "../../include/symode.h"
 #include "closure_quad.hpp"
+#include "closure_reduced.hpp"
 #include "jconst.hpp"
 #include "linear_action.hpp"
 #include "ops_table.hpp"
@@ -498,6 +499,42 @@ int symode_loss_grad_reversed_linear_quad(const double* aug_table, const double*
     const QuadMap map{q, beta, const_, beta_stride, const_stride, r, use_kron != 0 ? 1 : 0, xi_out, g_beta_out, g_const_out};
     return (int)launch_closure_quad_order(order, aug_table, m_table, table, n_problems, xi, map, mask, live_columns, w_sym, inv_count,
                                           loss2_out, loss_out, grad_out, (double*)workspace, (hipStream_t)stream);
+}
+
+// The closure without a point loop as a quadratic form in (beta, const) (closure_reduced.hpp): the set-up and the step.
+static bool quad_reduced_on() {
+    return knobs().closure_fold && knobs().fold_gram && knobs().fold_resid_gram && knobs().quad_reduced;
+}
+
+int symode_quad_reduce(const double* aug_table, const double* m_table, const float* table, long n_problems, int order,
+                       const float* q, int r, int use_kron, int has_const, unsigned long long live_columns, double inv_count,
+                       float w_sym, const float* mask, double* b_out, void* stream) {
+    if (order < 1 || order > 5 || !quad_reduced_on()) return SYMODE_E_UNSUPPORTED;
+    if (n_problems < 1 || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
+    if (r < 1 || r > 2 * symode_lib_size(2, order, 0) || r + (has_const ? 2 : 0) + 1 > REDUCED_GROUP) return SYMODE_E_BADSIZE;
+    if (!aug_table || !m_table || !table || !q || !b_out) return SYMODE_E_NULLPTR;
+    if (misaligned(aug_table, 8) || misaligned(m_table, 8) || misaligned(table, 4) || misaligned(q, 4) || misaligned(mask, 4) ||
+        misaligned(b_out, 8))
+        return SYMODE_E_ALIGN;
+    return (int)launch_quad_reduce_order(order, aug_table, m_table, table, n_problems, q, r, use_kron != 0 ? 1 : 0,
+                                         has_const != 0 ? 1 : 0, mask, live_columns, w_sym, inv_count, b_out, (hipStream_t)stream);
+}
+
+int symode_quad_step(const double* b, long n_problems, int k, int d_c, int order, unsigned long long live_columns,
+                     const float* beta, long beta_stride, const float* const_, long const_stride, float* loss_out,
+                     float* g_beta_out, float* g_const_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (order < 1 || order > 5 || !quad_reduced_on()) return SYMODE_E_UNSUPPORTED;
+    if (n_problems < 1 || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
+    if (k < 1 || k + 1 > REDUCED_GROUP || d_c < 0 || d_c >= k) return SYMODE_E_BADSIZE;
+    if (!b || !beta || !loss_out || !g_beta_out) return SYMODE_E_NULLPTR;
+    if (d_c > 0 ? (!const_ || !g_const_out) : (const_ || g_const_out)) return SYMODE_E_NULLPTR;
+    if (beta_stride < k - d_c || (d_c > 0 && const_stride < d_c)) return SYMODE_E_BADSIZE;
+    if (misaligned(b, 8) || misaligned(beta, 4) || misaligned(const_, 4) || misaligned(loss_out, 4) || misaligned(g_beta_out, 4) ||
+        misaligned(g_const_out, 4))
+        return SYMODE_E_ALIGN;
+    if (!workspace || misaligned(workspace, 8) || workspace_bytes < (size_t)WS_HEADER_DOUBLES * sizeof(double)) return SYMODE_E_WORKSPACE;
+    return (int)launch_quad_step(order, live_columns, b, n_problems, k, d_c, beta, beta_stride, const_, const_stride, loss_out,
+                                 g_beta_out, g_const_out, (double*)workspace, (hipStream_t)stream);
 }
 
 size_t symode_symreg_reversed_gram_workspace_bytes(int d, int order, int flags, int n_g, long n_problems, long n) {

@@ -126,18 +126,23 @@ __global__ __launch_bounds__(BLOCK) void closure_quad_kernel(const double* __res
     }
 }
 
+// the header word of the fold kernel of the same column set (closure_fold.hpp: launch_symreg_fold), Gram form, + the new bit
 template <class Lib>
-hipError_t launch_closure_quad(const double* aug, const double* mt, const float* jt, long S, const float* xi, const QuadMap& map,
-                               const float* mask, unsigned long long live, float w_sym, double inv, float* loss2, float* loss,
-                               float* grad, double* ws, hipStream_t st) {
-    constexpr int NW = BLOCK / WAVE;
-    // the header word of the fold kernel of the same column set (closure_fold.hpp: launch_symreg_fold), Gram form, + the new bit
+unsigned long long closure_quad_body(unsigned long long live) {
     bool sparse = false;
     if constexpr (closure_fold_live_pays<Lib>) {
         constexpr unsigned long long columns = Lib::P >= 64 ? ~0ull : (1ull << Lib::P) - 1;
         sparse = knobs().closure_live && (live & columns & ~odd_degree_columns<Lib>()) == 0;
     }
-    const unsigned long long body = WS_BODY_FOLD | (sparse ? WS_BODY_LIVE : 0ull) | WS_BODY_FOLD_GRAM | WS_BODY_FOLD_QUAD;
+    return WS_BODY_FOLD | (sparse ? WS_BODY_LIVE : 0ull) | WS_BODY_FOLD_GRAM | WS_BODY_FOLD_QUAD;
+}
+
+template <class Lib>
+hipError_t launch_closure_quad(const double* aug, const double* mt, const float* jt, long S, const float* xi, const QuadMap& map,
+                               const float* mask, unsigned long long live, float w_sym, double inv, float* loss2, float* loss,
+                               float* grad, double* ws, hipStream_t st) {
+    constexpr int NW = BLOCK / WAVE;
+    const unsigned long long body = closure_quad_body<Lib>(live);
     closure_quad_kernel<Lib><<<dim3((unsigned)((S + NW - 1) / NW)), dim3(BLOCK), 0, st>>>(
         aug, mt, jt, S, xi, map, mask, live, w_sym, inv, loss2, loss, grad, (unsigned long long*)ws, body);
     SYMODE_LAUNCH_CHECK();

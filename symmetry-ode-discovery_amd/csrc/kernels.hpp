@@ -23,7 +23,7 @@ constexpr int MAP_CHUNKS_PER_THREAD = SYMODE_MAP_CHUNKS;   // chunks a thread of
 // for the tests and tuning tools that compare two settings inside one process; no launch path calls getenv.
 struct Knobs {
     long max_grid, min_grid_x, map_grid, gram_grid, gram_valu_grid, small_grid, reduce_grid;
-    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live, closure_fold, fold_pk, fold_gram, fold_resid_gram;
+    int fused_finalize, euler_stack, gram_valu, gram_split, gram_valu_gather, segmented, row_split, gram_m4, closure_pk, closure_live, closure_fold, fold_pk, fold_gram, fold_resid_gram, quad_reduced;
     long gram_m4_grid;
 };
 
@@ -53,6 +53,7 @@ inline Knobs read_knobs() {
     k.fold_pk = on("SYMODE_FOLD_PK");
     k.fold_gram = (int)num("SYMODE_FOLD_GRAM", 1);
     k.fold_resid_gram = on("SYMODE_FOLD_RESID_GRAM");
+    k.quad_reduced = on("SYMODE_QUAD_REDUCED");
     return k;
 }
 

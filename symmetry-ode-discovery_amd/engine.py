@@ -78,6 +78,10 @@ _SIGNATURES = {
                                                       c_void_p, c_long, c_void_p, c_long, c_int, c_int, c_void_p, ctypes.c_ulonglong, ctypes.c_double,
                                                       c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                       c_size_t, c_void_p]),
+    "symode_quad_reduce": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_int, c_int, c_int, ctypes.c_ulonglong,
+                                   ctypes.c_double, c_float, c_void_p, c_void_p, c_void_p]),
+    "symode_quad_step": (c_int, [c_void_p, c_long, c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_long, c_void_p, c_long,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_loss_grad_latent": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p,
                                         c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "symode_symreg_reversed_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_long, c_long]),
@@ -241,6 +245,65 @@ def reload_env() -> None:
 
 def library_flags(include_sine: bool, include_exp: bool) -> int:
     return (FLAG_SINE if include_sine else 0) | (FLAG_EXP if include_exp else 0)
+
+
+class ReducedStep:
+    """A prepared ``symode_quad_step`` launch on one reduced form B (``HipEngine.quad_step_plan``): the pointers, sizes and
+    header arguments that stand while B stands are kept, so that a call is one allocation -- a packed fp32 buffer
+    [loss (S) | g_beta (S, r) | g_const (S, d_c)] of which the results are views -- and one ctypes call.  ``alias=True``
+    writes into one buffer of this object instead and returns the same views every time."""
+
+    def __init__(self, eng, B, order, live, r, dc, ws):
+        self.eng, self.B, self.ws = eng, B, ws                       # kept alive with the pointers below
+        self.S, self.r, self.dc, self.device = B.shape[0], r, dc, B.device
+        self._fn = eng.lib.symode_quad_step
+        self._head = (B.data_ptr(), self.S, r + dc, dc, order, live)
+        self._tail = (ws.data_ptr(), ws.numel() * 8)
+        self._sizes = [self.S, self.S * r, self.S * dc] if dc else [self.S, self.S * r]
+        self._n_out = sum(self._sizes)
+        self._alias = None
+
+    def _views(self, buf):
+        parts = buf.split_with_sizes(self._sizes)
+        return parts[0], parts[1].view(self.S, self.r), (parts[2].view(self.S, self.dc, 1) if self.dc else None)
+
+    def _rows(self, t, w, name):
+        """(tensor, row stride) of an (S, w[, 1]) fp32 operand read where it lies; anything else is made dense first"""
+        S = self.S
+        st = t.stride()
+        if t.dtype is torch.float32 and t.device == self.device and len(st) >= 2 and t.shape[0] == S and t.shape[1] == w \
+                and t.numel() == S * w and st[1] == 1 and (st[0] >= w or S == 1):
+            return t, (st[0] if S > 1 else w)
+        t = HipEngine._dev(t, name)
+        if t.numel() != S * w:
+            raise SymodeError(f"{name} has {t.numel()} elements, expected {S}x{w}")
+        return t, w
+
+    def __call__(self, beta, const, alias=False):
+        """(loss, g_beta, g_const or None), or None where the library's switches refuse the step (SYMODE_QUAD_REDUCED=0 and
+        the switches of the closure it stands for): the caller then takes that closure's own launch."""
+        beta, ldb = self._rows(beta, self.r, "beta")
+        if self.dc:
+            const, ldc = self._rows(const, self.dc, "const")
+            cptr = const.data_ptr()
+        else:
+            cptr, ldc = None, 0
+        if alias:
+            if self._alias is None:
+                buf = torch.empty(self._n_out, dtype=torch.float32, device=self.device)
+                self._alias = (buf, self._views(buf))
+            buf, views = self._alias
+        else:
+            buf, views = torch.empty(self._n_out, dtype=torch.float32, device=self.device), None
+        base = buf.data_ptr()
+        S4 = 4 * self.S
+        rc = self._fn(*self._head, beta.data_ptr(), ldb, cptr, ldc, base, base + S4, (base + S4 * (1 + self.r)) if self.dc else None,
+                      *self._tail, torch.cuda.current_stream(self.device).cuda_stream)
+        if rc == -1:                                                 # SYMODE_E_UNSUPPORTED: a switch, read by the library alone
+            return None
+        if rc != 0:
+            self.eng._check(rc, "symode_quad_step")
+        return self._views(buf) if views is None else views
 
 
 class HipEngine:
@@ -857,6 +920,98 @@ class HipEngine:
         return not (env.get("SYMODE_CLOSURE_FOLD", "1")[:1] == "0" or env.get("SYMODE_FOLD_RESID_GRAM", "1")[:1] == "0"
                     or env.get("SYMODE_FOLD_GRAM", "1").strip() in ("0", "+0", "-0", "00", ""))
 
+    @staticmethod
+    def closure_reduced(ws):
+        """Was the last closure launch on workspace ``ws`` the step on the reduced form (closure_reduced.hpp: ``quad_step``, a
+        quadratic form in (beta, const); SYMODE_QUAD_REDUCED=0 turns it off)?  Bit 256 of the word ``closure_body`` reads."""
+        return bool(int(ws.view(torch.int64)[1].item()) & 256)
+
+    @staticmethod
+    def closure_reduced_enabled():
+        """Do the library's switches allow ``quad_reduce`` / ``quad_step``?  Those of ``closure_quad_enabled`` and
+        SYMODE_QUAD_REDUCED, as the library reads them; it refuses the calls where they say no."""
+        return HipEngine.closure_quad_enabled() and os.environ.get("SYMODE_QUAD_REDUCED", "1")[:1] != "0"
+
+    def quad_reduce(self, aug, linear_m, table, order, coef, w_sym, inv_count, live_columns=None, mask=None):
+        """The closure of ``loss_grad_reversed(aug=, coef=)`` reduced to a quadratic form in the variables (symode_quad_reduce):
+        aug (S, p+d, p+d) float64, linear_m (S, 1, p, p) float64, table (S, 1, d, d) fp32, ``coef`` a CoefMap with Q, mask
+        (S, d, p) fp32 or None -> B (S, K+1, K+1) float64, K = r + (d if the model reads const else 0), with
+        loss = v^T B v and d loss / d (beta, const) = 2 (B v)[:K] for v = [beta; const; 1].  A set-up call: B holds for these
+        operands, ``w_sym``, ``inv_count`` and ``live_columns`` and is built again when any of them changes."""
+        aug, linear_m, table = self._dev(aug, "aug", torch.float64), self._dev(linear_m, "linear_m", torch.float64), self._dev(table, "table")
+        d, p, r = coef.d, coef.p, coef.r
+        if d != 2 or coef.Q is None or r < 1:
+            raise SymodeError("quad_reduce takes a d = 2 coefficient map with Q")
+        if aug.dim() != 3 or aug.shape[1:] != (p + d, p + d):
+            raise SymodeError(f"aug holds (S, p+d, p+d) float64, got {tuple(aug.shape)}")
+        S = aug.shape[0]
+        if linear_m.numel() != S * p * p or table.numel() != S * d * d:
+            raise SymodeError(f"linear_m {tuple(linear_m.shape)} / table {tuple(table.shape)} do not hold (S, 1, p, p) / (S, 1, d, d)")
+        mask = None if mask is None else self._dev(mask, "mask")
+        if mask is not None and mask.numel() != S * d * p:
+            raise SymodeError(f"mask has {mask.numel()} elements, expected {S}x{d}x{p}")
+        K = r + (d if coef.allow_constant else 0)
+        if K + 1 > 16:
+            raise SymodeError(f"the reduced form holds at most 15 variables per problem, the map has {K}")
+        Q = coef.device_Q(aug.device)
+        live = (0xFFFFFFFFFFFFFFFF if live_columns is None else int(live_columns)) & 0xFFFFFFFFFFFFFFFF
+        B = torch.empty(S, K + 1, K + 1, dtype=torch.float64, device=aug.device)
+        self._check(self.lib.symode_quad_reduce(self._ptr(aug), self._ptr(linear_m), self._ptr(table), S, order, self._ptr(Q), r,
+                                                1 if coef.use_kron else 0, 1 if coef.allow_constant else 0, live, float(inv_count),
+                                                float(w_sym), self._ptr(mask), self._ptr(B), self._stream(aug)), "symode_quad_reduce")
+        return B
+
+    def quad_step(self, B, beta, const, order, live_columns=None, out=None, ws=None):
+        """One closure evaluation on the reduced form (symode_quad_step): B (S, K+1, K+1) float64 of ``quad_reduce``, beta
+        (S, r) fp32, const (S, d_c, 1) fp32 or None (K = r + d_c); rows of beta and const may be strided (views of a flat
+        [beta | const] state), only the last axis has to be dense.  Returns (loss (S,), g_beta (S, r), g_const (S, d_c, 1) or
+        None), fp32; ``out`` = (loss, g_beta, g_const or None): buffers for them.  ``order`` and ``live_columns`` name the
+        closure B was reduced from: the launch leaves that closure's header word, plus bit 256, in ``ws``."""
+        B = self._dev(B, "B", torch.float64)
+        if B.dim() != 3 or B.shape[1] != B.shape[2] or not 2 <= B.shape[1] <= 16:
+            raise SymodeError(f"B holds (S, K+1, K+1) float64 with K + 1 <= 16, got {tuple(B.shape)}")
+        S, K = B.shape[0], B.shape[1] - 1
+        rows = lambda t, w: t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.shape[0] == S and t.numel() == S * w \
+            and all(st == 1 for st in t.stride()[1:]) and t.stride(0) >= w
+        dc = 0 if const is None else const.numel() // S
+        r = K - dc
+        if r < 1 or (const is not None and const.numel() != S * dc):
+            raise SymodeError(f"const has {0 if const is None else const.numel()} elements for {S} problems of {K} variables")
+        beta = beta if rows(beta, r) else self._dev(beta, "beta")
+        if beta.numel() != S * r:
+            raise SymodeError(f"beta has {beta.numel()} elements, expected {S}x{r}")
+        if const is not None and not rows(const, dc):
+            const = self._dev(const, "const")
+        ld = lambda t, w: t.stride(0) if (t.dim() >= 2 and t.shape[0] == S and S > 1) else w
+        dev = B.device
+        if out is None:
+            loss = torch.empty(S, dtype=torch.float32, device=dev)
+            g_beta = torch.empty(S, r, dtype=torch.float32, device=dev)
+            g_const = torch.empty(S, dc, 1, dtype=torch.float32, device=dev) if dc else None
+        else:
+            loss, g_beta, g_const = (None if o is None else self._dev(o, "out") for o in out)
+            if loss is None or g_beta is None or loss.numel() != S or g_beta.numel() != S * r or (g_const is None) != (dc == 0) \
+                    or (g_const is not None and g_const.numel() != S * dc):
+                raise SymodeError("out = (loss (S,), g_beta (S, r), g_const (S, d_c, 1) or None)")
+        if ws is None:
+            ws = self.workspace(dev, 2, order, 0, S, 1)
+        live = (0xFFFFFFFFFFFFFFFF if live_columns is None else int(live_columns)) & 0xFFFFFFFFFFFFFFFF
+        self._check(self.lib.symode_quad_step(self._ptr(B), S, K, dc, order, live, self._ptr(beta), ld(beta, r), self._ptr(const),
+                                              0 if const is None else ld(const, dc), self._ptr(loss), self._ptr(g_beta),
+                                              self._ptr(g_const), self._ptr(ws), ws.numel() * 8, self._stream(B)), "symode_quad_step")
+        return loss, g_beta.reshape(S, r), None if g_const is None else g_const.reshape(S, dc, 1)
+
+    def quad_step_plan(self, B, order, live_columns, r, dc, ws):
+        """The step on B, prepared: everything of ``quad_step`` that cannot change while B stands (``ReducedStep``)."""
+        B = self._dev(B, "B", torch.float64)
+        K = r + dc
+        if B.dim() != 3 or tuple(B.shape[1:]) != (K + 1, K + 1) or r < 1 or dc < 0 or K + 1 > 16:
+            raise SymodeError(f"B {tuple(B.shape)} does not hold (S, K+1, K+1) for K = {r} + {dc} <= 15")
+        if ws is None or not ws.is_cuda or ws.dtype != torch.float64 or ws.device != B.device:
+            raise SymodeError("the prepared step takes an initialised workspace on B's device (new_workspace)")
+        live = (0xFFFFFFFFFFFFFFFF if live_columns is None else int(live_columns)) & 0xFFFFFFFFFFFFFFFF
+        return ReducedStep(self, B, order, live, r, dc, ws)
+
     def _closure_quad_call(self, x, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live, linear_m, aug, coef, coef_out):
         """The launch of ``loss_grad_reversed(aug=...)``: the arguments of symode_loss_grad_reversed_linear_quad, checked."""
         batched, S, n, d = self._problems(x)
@@ -929,7 +1084,7 @@ class HipEngine:
         return "symode_loss_grad_reversed_linear_quad", args, keep, ((loss2, grad) if batched else (loss2[0], grad[0])) + mapped
 
     def loss_grad_reversed(self, x, dx, gx, jgx, xi, mask, order, flags=0, w_sym=1.0, inv_count=None, out=None, ws=None,
-                           live_columns=None, linear_m=None, gram=None, aug=None, coef=None, coef_out=None):
+                           live_columns=None, linear_m=None, gram=None, aug=None, coef=None, coef_out=None, reduced=None):
         """The closure MSE + w_sym * reversed regulariser in ONE pass (x read once, Theta(x) shared by both terms).
         Shapes as loss_grad / symreg_reversed (jgx may be the compact table of a point-constant Jacobian, as there).
         Returns (loss2, grad): loss2 (S, 2) [or (2,)] = (mse, regulariser), grad = d(mse + w_sym * regulariser)/dXi
@@ -955,7 +1110,13 @@ class HipEngine:
         ``coef`` = (CoefMap, beta (S, r), const (S, d, 1) or None), with ``aug``: the launch forms Xi from the variables itself
         (``xi`` is not read; Q beta in fp64, one rounding to fp32) and also returns the gradient by the variables:
         (loss2, grad, g_beta (S, r), g_const (S, d, 1) or None).  ``coef_out`` = (xi_out or None, g_beta, g_const or None): buffers
-        for these, xi_out (S, d, p) receiving the Xi the launch formed."""
+        for these, xi_out (S, d, p) receiving the Xi the launch formed.
+        ``reduced`` = (ReducedStep, beta, const, alias): the same closure as a prepared step on its reduced form
+        (``quad_step_plan``).  The call is handed on in the first statement and nothing else is read or checked -- every other
+        argument may be None; it enters here so that whatever wraps this method to watch the reversed closures (a timer, a
+        trace) sees these steps too.  Returns (loss, g_beta, g_const), or None where the library's switches refuse the step."""
+        if reduced is not None:
+            return reduced[0](reduced[1], reduced[2], reduced[3])
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
