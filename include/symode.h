@@ -1016,6 +1016,47 @@ int symode_stlsq_path(const double* aug_gram, const double* val_gram, long n_set
                       double* rss_train, double* rss_val, int* best, float* xi_out, unsigned char* mask_out, int* near_out,
                       int* fell_out, void* stream);
 
+/* symode_stlsq_path with the reversed symmetry regulariser, EquivSINDy-r: the sparsity path of the minimiser of
+ * mse + w_sym * reg, so that the regularised fit no longer asks for a threshold either.  The regulariser's matrix couples the
+ * equation rows, so the path is ONE chain over the joint (d, p) support of n0 = d p <= 64 entries, not one per row.
+ * aug_gram, val_gram, n_sets, n_val_sets, n_problems, n_points, tol, floor_rel and near_band are symode_stlsq_path's; rev_gram
+ * (n_sets, d p, d p) fp64, pivot_floor and the fp32 rounding of gamma and w_sym are symode_stlsq_sweep_symreg's.  hyper NULL,
+ * or (n_problems, 2) fp32 [gamma, w_sym], row s in place of the two scalars; the launch takes the two values in fp32 with or
+ * without a table, so problem (g, k) of a table is bit for bit the scalar launch on set k with row g's values.
+ * Step t = 0 .. n0 has t entries of the support M removed:
+ *   solve      t < n0: the statements of one pass of symode_stlsq_sweep_symreg on M (support in ascending (j, k), its A and b,
+ *              csrc/stlsq_joint.hpp) -- step 0 is bit for bit that entry with max_iter = 1, threshold = 0; a pivot that is
+ *              not > pivot_floor * (first pivot), or not > 0, sets fell_out[s] = 1 and ENDS problem s (its other outputs are
+ *              then unspecified), the caller solves it on the host; v = (float) of the solution scattered to (d, p), zeros
+ *              off M; t = n0: v = 0.  path_xi[s, t, :, :] = v;
+ *   scores     in fp64 with w = (double)v, nothing contracted, nothing clamped.  For H = the training and the validation
+ *              matrix: per row j, with M_j the row's columns, q_k = sum over l in M_j ascending of H[k][l] w_jl from 0.0,
+ *              r_k = w_jk (q_k - 2 H[k][p+j]), e_j = H[p+j][p+j] then e_j += r_k for k ascending over M_j (symode_stlsq_path's
+ *              form); the score starts at 0.0 and takes e_j for j ascending: mse_train[s, t], mse_val[s, t] (raw sums, the
+ *              ridge term in neither).  reg_train[s, t] = v^T R v over the flat index b = j p + k: q_b = sum over a in M
+ *              ascending of R[b][a] w_a from 0.0, r_b = w_b q_b, the form from 0.0 takes r_b for b ascending over M.  The
+ *              regulariser is not scored on held-out data;
+ *   eliminate  t < n0: the active entry with the smallest |v| (fp32 compare, the lowest flat index j p + k of equals) leaves,
+ *              order[s, t] = that flat index; with two or more active entries the step counts in near_out[s] when the
+ *              runner-up's |v| minus the smallest, both widened to fp64, is < near_band.
+ * Then Vyy = sum_j val_gram[p+j][p+j] (from 0.0, j ascending: the empty model's mse_val), e_min = min_t mse_val[s, t],
+ * cut = (1 + tol) max(e_min, 0) + floor_rel Vyy, best[s] = the LARGEST t with mse_val[s, t] <= cut, xi_out[s] =
+ * path_xi[s, best] (solved once more: the same bits) and mask_out[s] its support, the entries order[s, best:].
+ * path_xi (n_problems, n0+1, d, p) fp32; order (n_problems, n0) ints; mse_train, reg_train, mse_val (n_problems, n0+1) fp64;
+ * best, near_out, fell_out (n_problems) ints; xi_out (n_problems, d, p) fp32; mask_out (n_problems, d, p) bytes.
+ * Refused before any GPU work: d < 1, d > 4, p < 1, p > 64, d p > 64, n_sets < 1, n_problems < n_sets or >= 2^31, n_val_sets < 1
+ * or > n_problems, gamma, w_sym, tol, floor_rel, near_band or pivot_floor < 0 or not finite (SYMODE_E_BADSIZE); any pointer
+ * but hyper NULL (SYMODE_E_NULLPTR); aug_gram, rev_gram, val_gram or a score array not 8-byte, hyper or an fp32 / int output
+ * not 4-byte aligned (SYMODE_E_ALIGN).
+ * Added to ABI version 8 (nothing existing changed).
+ * replaces: nothing in the reference; the threshold loop of train.py:872-887 on the stationarity condition of
+ * train.py:663-679 (sym_reg_type 'r'), with the threshold chosen by held-out error. */
+int symode_stlsq_path_symreg(const double* aug_gram, const double* rev_gram, const double* val_gram, long n_sets, long n_val_sets,
+                             long n_problems, int d, int p, long n_points, const float* hyper, double gamma, double w_sym,
+                             double tol, double floor_rel, double near_band, double pivot_floor, float* path_xi, int* order,
+                             double* mse_train, double* reg_train, double* mse_val, int* best, float* xi_out,
+                             unsigned char* mask_out, int* near_out, int* fell_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include "stlsq_constrained.hpp"
 #include "stlsq_path.hpp"
 #include "stlsq_symreg.hpp"
+#include "stlsq_path_symreg.hpp"
 #include "weak_normal.hpp"
 
 using namespace symode;
@@ -700,6 +701,31 @@ int symode_stlsq_sweep_symreg(const double* aug_gram, const double* rev_gram, lo
     return (int)launch_stlsq_symreg(aug_gram, rev_gram, n_sets, n_problems, d, p, hyper, (float)gamma, (float)threshold, (float)w_sym,
                                     max_iter, near_band, pivot_floor, xi_out, mask_out, passes_out, near_out, fell_out,
                                     (hipStream_t)stream);
+}
+
+int symode_stlsq_path_symreg(const double* aug_gram, const double* rev_gram, const double* val_gram, long n_sets, long n_val_sets,
+                             long n_problems, int d, int p, long n_points, const float* hyper, double gamma, double w_sym, double tol,
+                             double floor_rel, double near_band, double pivot_floor, float* path_xi, int* order, double* mse_train,
+                             double* reg_train, double* mse_val, int* best, float* xi_out, unsigned char* mask_out, int* near_out,
+                             int* fell_out, void* stream) {
+    (void)n_points;                     // as symode_stlsq_sweep: only gelsy's rank rule would read it
+    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || (long)d * p > STLSQS_MAX_DP) return SYMODE_E_BADSIZE;
+    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
+    if (n_val_sets < 1 || n_val_sets > n_problems) return SYMODE_E_BADSIZE;
+    const double values[6] = {(double)(float)gamma, (double)(float)w_sym, tol, floor_rel, near_band, pivot_floor};   // as the launch holds them
+    for (const double v : values)
+        if (!(v >= 0.0) || !std::isfinite(v)) return SYMODE_E_BADSIZE;
+    if (!aug_gram || !rev_gram || !val_gram || !path_xi || !order || !mse_train || !reg_train || !mse_val || !best || !xi_out ||
+        !mask_out || !near_out || !fell_out)
+        return SYMODE_E_NULLPTR;
+    if (misaligned(aug_gram, 8) || misaligned(rev_gram, 8) || misaligned(val_gram, 8) || misaligned(mse_train, 8) ||
+        misaligned(reg_train, 8) || misaligned(mse_val, 8) || misaligned(hyper, 4) || misaligned(path_xi, 4) || misaligned(order, 4) ||
+        misaligned(best, 4) || misaligned(xi_out, 4) || misaligned(near_out, 4) || misaligned(fell_out, 4))
+        return SYMODE_E_ALIGN;
+    // the two values in fp32, as a row of the table holds them
+    return (int)launch_stlsq_path_symreg(aug_gram, rev_gram, val_gram, n_sets, n_val_sets, n_problems, d, p, hyper, (float)gamma,
+                                         (float)w_sym, tol, floor_rel, near_band, pivot_floor, path_xi, order, mse_train, reg_train,
+                                         mse_val, best, xi_out, mask_out, near_out, fell_out, (hipStream_t)stream);
 }
 
 int symode_symreg_reversed(const float* x, const float* gx_, const float* jgx, int n_g, long n, int d, int order,

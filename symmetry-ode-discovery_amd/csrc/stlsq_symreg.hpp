@@ -20,6 +20,59 @@ inline size_t stlsqs_lds_bytes(int dp) {
     return (size_t)dp * dp * sizeof(double) + STLSQ_MAX_D * sizeof(unsigned long long) + (size_t)dp * (sizeof(int) + sizeof(float));
 }
 
+// One pass's solve, stated once for stlsq_symreg_kernel and stlsq_path_symreg_kernel (stlsq_path_symreg.hpp): support,
+// system, factorisation and substitutions as the comment of stlsq_symreg_kernel states them.  M holds the d mask words (the
+// same in every lane), G the (p+d, p+d) and Rv the (d p, d p) raw sums -- global memory or LDS, the statements are the same.
+// On return n_out is the size of the support, xs (d p floats) the solution rounded to fp32 and scattered to (d, p), zeros off the
+// support; true for a flagged pivot (xs is then unspecified).  The caller synchronises the wave before it reads xs.
+__device__ __forceinline__ bool stlsqs_pass_solve(const double* G, const double* Rv, int d, int p, double g2, double w_sym,
+                                                  double pivot_floor, const unsigned long long* M, int lane, double* A, int* sel,
+                                                  float* xs, int& n_out) {
+    const int F = p + d, DP = d * p;
+    // ---- support
+    int n = 0;                          // (a local: the size reaches the caller once, at the end)
+    for (int j = 0; j < d; ++j) {
+        const unsigned long long mj = M[j];
+        if ((mj >> lane) & 1ull) sel[n + __popcll(mj & ((1ull << lane) - 1ull))] = (j << 8) | lane;
+        n += __popcll(mj);
+    }
+    if (lane < DP) xs[lane] = 0.0f;
+    stlsq_wave_sync();
+    bool bad = false;
+    if (n > 0) {
+        const bool on = lane < n;
+        const int eb = on ? sel[lane] : 0;
+        const int jb = eb >> 8, kb = eb & 255;
+        const int ob = jb * p + kb;
+        // ---- system
+        for (int a = 0; a < n; ++a) {
+            const int ea = __builtin_amdgcn_readfirstlane(sel[a]);
+            const int ja = ea >> 8, ka = ea & 255;
+            if (on && a <= lane) {
+                const double block = ja == jb ? G[(long)ka * F + kb] + (ka == kb ? g2 : 0.0) : 0.0;
+                A[a * DP + lane] = block + w_sym * Rv[((long)ja * p + ka) * DP + ob];
+            }
+        }
+        double c = on ? G[(long)kb * F + p + jb] : 0.0;
+        stlsq_wave_sync();
+        for (int a = 0; a < n; ++a)
+            if (on && a < lane) A[lane * DP + a] = A[a * DP + lane];
+        stlsq_wave_sync();
+        // ---- factor and solve
+        int orig, fact;
+        bad = stlsq_joint_factor<false>(A, DP, n, lane, orig, c, pivot_floor, fact);
+        if (!bad) {
+            stlsq_joint_back(A, DP, n, lane, orig, c);
+            if (on) {
+                const int eo = sel[orig];
+                xs[(eo >> 8) * p + (eo & 255)] = (float)c;
+            }
+        }
+    }
+    n_out = n;
+    return bad;
+}
+
 // One workgroup of ONE wave per problem.  The regulariser's R couples the equation rows -- v^T R v has entries between
 // (j, k) and (j', k') for j != j' -- so a pass is one joint system of n <= d p <= 64 unknowns, the constrained kernel's
 // situation: the factorisation, one lane per position of the pivot order, is a single wave's work whatever d is, the
@@ -72,46 +125,8 @@ __global__ __launch_bounds__(WAVE) void stlsq_symreg_kernel(const double* __rest
     stlsq_wave_sync();
     int near = 0, passes = 0, fell = 0;
     for (int it = 0; it < max_iter; ++it) {
-        // ---- support
-        int n = 0;
-        for (int j = 0; j < d; ++j) {
-            const unsigned long long mj = M[j];
-            if ((mj >> lane) & 1ull) sel[n + __popcll(mj & ((1ull << lane) - 1ull))] = (j << 8) | lane;
-            n += __popcll(mj);
-        }
-        if (lane < DP) xs[lane] = 0.0f;
-        stlsq_wave_sync();
-        bool bad = false;
-        if (n > 0) {
-            const bool on = lane < n;
-            const int eb = on ? sel[lane] : 0;
-            const int jb = eb >> 8, kb = eb & 255;
-            const int ob = jb * p + kb;
-            // ---- system
-            for (int a = 0; a < n; ++a) {
-                const int ea = __builtin_amdgcn_readfirstlane(sel[a]);
-                const int ja = ea >> 8, ka = ea & 255;
-                if (on && a <= lane) {
-                    const double block = ja == jb ? G[(long)ka * F + kb] + (ka == kb ? g2 : 0.0) : 0.0;
-                    A[a * DP + lane] = block + w_sym * Rv[((long)ja * p + ka) * DP + ob];
-                }
-            }
-            double c = on ? G[(long)kb * F + p + jb] : 0.0;
-            stlsq_wave_sync();
-            for (int a = 0; a < n; ++a)
-                if (on && a < lane) A[lane * DP + a] = A[a * DP + lane];
-            stlsq_wave_sync();
-            // ---- factor and solve
-            int orig, fact;
-            bad = stlsq_joint_factor<false>(A, DP, n, lane, orig, c, pivot_floor, fact);
-            if (!bad) {
-                stlsq_joint_back(A, DP, n, lane, orig, c);
-                if (on) {
-                    const int eo = sel[orig];
-                    xs[(eo >> 8) * p + (eo & 255)] = (float)c;
-                }
-            }
-        }
+        int n;
+        const bool bad = stlsqs_pass_solve(G, Rv, d, p, g2, w_sym, pivot_floor, M, lane, A, sel, xs, n);
         passes = it + 1;
         if (bad) {
             fell = 1;

@@ -159,6 +159,10 @@ _SIGNATURES = {
     "symode_stlsq_path": (c_int, [c_void_p, c_void_p, c_long, c_long, c_long, c_int, c_int, c_long, ctypes.c_double, ctypes.c_double,
                                   ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "symode_stlsq_path_symreg": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, c_int, c_int, c_long, c_void_p,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
@@ -192,6 +196,7 @@ class TrainerGrid(ctypes.Structure):
 
 STLSQ_HYPER = 2                                             # columns of a symode_stlsq_sweep hyper row: gamma, threshold
 STLSQ_SYMREG_HYPER = 3                                      # ... of a symode_stlsq_sweep_symreg row: gamma, threshold, w_sym
+STLSQ_PATH_SYMREG_HYPER = 2                                 # ... of a symode_stlsq_path_symreg row: gamma, w_sym
 
 ADAM_PLAIN, ADAM_REVERSED, ADAM_LATENT = 0, 1, 2              # SYMODE_ADAM_* of include/symode.h
 ADAM_HYPER = 4                                              # columns of a hyper row: lr, w_reg, threshold, w_sym
@@ -1468,6 +1473,69 @@ class HipEngine:
             import numpy as np
             return parts(buf.cpu().numpy(), np.float32, np.int32)
         return parts(buf, torch.float32, torch.int32)
+
+    def stlsq_path_symreg(self, G, R, V, n_points, gamma, w_sym, tol, floor_rel, hyper=None, n_problems=None, *, d, pivot_floor,
+                          near_band=1e-4, to_host=False, keep_path=False):
+        """``stlsq_path`` with the reversed symmetry regulariser in ONE launch (symode_stlsq_path_symreg): backward elimination
+        over the JOINT (d, p) support of the minimiser of mse + w_sym * reg, n0 = d p <= 64 entries, from the full library to
+        the empty model, every model scored on the held-out matrix, the sparsest one within ``tol`` of the best kept.  G, V,
+        ``tol``, ``floor_rel``, ``near_band``, ``to_host`` and ``keep_path`` as ``stlsq_path``; R and ``pivot_floor`` as
+        ``stlsq_sweep_symreg``; ``hyper`` (n_problems, 2) fp32 on the device, row s = problem s's [gamma, w_sym].  The launch
+        takes gamma and w_sym in fp32 with or without a table.
+        Returns a dict of device tensors, one chain per PROBLEM (not per equation row): Xi (n_problems, d, p) fp32, mask uint8,
+        order (n_problems, n0) int32 flat indices j p + k, mse_train, reg_train, mse_val (n_problems, n0+1) fp64, best, near,
+        fell (n_problems,) int32 -- a problem with ``fell`` set is possibly rank deficient and the host's to solve -- and
+        path_xi (n_problems, n0+1, d, p) fp32 (with ``to_host=True`` only when ``keep_path``)."""
+        G = self._dev(G, "G", torch.float64)
+        V = self._dev(V, "V", torch.float64)
+        R = self._dev(R, "R", torch.float64)
+        d = int(d)
+        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
+            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
+        if V.dim() != 3 or V.shape[1:] != G.shape[1:] or V.device != G.device:
+            raise SymodeError(f"V must be (n_val_sets, p + d, p + d) = (n_val_sets, {G.shape[1]}, {G.shape[2]}) on {G.device}, "
+                              f"got {tuple(V.shape)} on {V.device}")
+        n_sets, p = G.shape[0], G.shape[1] - d
+        n0 = d * p
+        if tuple(R.shape) != (n_sets, n0, n0) or R.device != G.device:
+            raise SymodeError(f"R must be (n_sets, d p, d p) = ({n_sets}, {n0}, {n0}) fp64 on {G.device}, got {tuple(R.shape)}")
+        if hyper is not None:
+            hyper = self._dev(hyper, "hyper")
+            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_PATH_SYMREG_HYPER or hyper.device != G.device:
+                raise SymodeError(f"hyper must be (n_problems, {STLSQ_PATH_SYMREG_HYPER}) fp32 on {G.device}: one row [gamma, w_sym] "
+                                  f"per problem")
+            if n_problems is not None and int(n_problems) != hyper.shape[0]:
+                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
+            n_problems = hyper.shape[0]
+        S = n_sets if n_problems is None else int(n_problems)
+        sizes = [8 * S * (n0 + 1)] * 3 + [4 * S * n0, 4 * S * n0, 4 * S, 4 * S, 4 * S, S * n0]
+        cuts = [0]
+        for n in sizes:
+            cuts.append(cuts[-1] + n)
+        buf = torch.empty(max(cuts[-1], 0), dtype=torch.uint8, device=G.device)    # fp64 first, bytes last: every part aligned
+        path = torch.empty(max(S, 0), n0 + 1, d, p, dtype=torch.float32, device=G.device)
+
+        def parts(b, f64, f32, i32):
+            tr, rg, va, xi, order, best, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
+            return dict(Xi=xi.view(f32).reshape(S, d, p), mask=mask.reshape(S, d, p), order=order.view(i32).reshape(S, n0),
+                        mse_train=tr.view(f64).reshape(S, n0 + 1), reg_train=rg.view(f64).reshape(S, n0 + 1),
+                        mse_val=va.view(f64).reshape(S, n0 + 1), best=best.view(i32), near=near.view(i32), fell=fell.view(i32))
+
+        o = parts(buf, torch.float64, torch.float32, torch.int32)
+        self._check(self.lib.symode_stlsq_path_symreg(
+            self._ptr(G), self._ptr(R), self._ptr(V), n_sets, V.shape[0], S, d, p, int(n_points), self._ptr(hyper), float(gamma),
+            float(w_sym), float(tol), float(floor_rel), float(near_band), float(pivot_floor), self._ptr(path), self._ptr(o["order"]),
+            self._ptr(o["mse_train"]), self._ptr(o["reg_train"]), self._ptr(o["mse_val"]), self._ptr(o["best"]), self._ptr(o["Xi"]),
+            self._ptr(o["mask"]), self._ptr(o["near"]), self._ptr(o["fell"]), self._stream(G)),
+            "symode_stlsq_path_symreg")
+        if to_host:
+            import numpy as np
+            o = parts(buf.cpu().numpy(), np.float64, np.float32, np.int32)
+            if keep_path:
+                o["path_xi"] = path.cpu().numpy()
+            return o
+        o["path_xi"] = path
+        return o
 
     def quad_closure(self, G, R, xi, mask, inv_count, w_sym=1.0, hyper=None, n_sets=None):
         """The closure as a quadratic form of fixed fp64 matrices: G (S, p+d, p+d) augmented Gram, R (S, d p, d p) or None,

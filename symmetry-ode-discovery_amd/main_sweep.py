@@ -87,6 +87,16 @@ aggregate are those of ``--method stlsq``; ``eval_results/<save_dir>/path.npz`` 
 seeds.  --threshold is not used.  Not covered, and refused by name: the constrained and the regularised fits, --wsindy, the grids,
 --lstsq_driver gelsy, --use_latent.
 
+``--symreg_path [--path_tol v]`` (with --method stlsq --device_stlsq --w_sym_reg > 0 --sym_reg_type r --load_laligan ...
+--fix_laligan) is that path for the fit with the reversed symmetry regulariser, EquivSINDy-r: [G | R | count] are built as under
+--symreg_stlsq (ONE all-reduce), the validation set's matrix as under --stlsq_path, and ONE launch (symode_stlsq_path_symreg,
+``SeedSweepSTLSQ.solve_path(rev=(R, w_sym))``) walks per seed ONE chain over the joint (d, p) support of d p <= 64 entries --
+the regulariser couples the rows --, scores every model's mse on the validation matrix (the regulariser is scored on the
+training set only) and keeps the sparsest model within path_tol of the best.  --stlsq_grid takes w_sym_reg=... and
+w_sindy_reg=... under it (a threshold axis is refused: the path asks for no threshold).  ``eval_results/<save_dir>/path.npz``
+holds order, mse_train, reg_train, mse_val, best and near of all problems.  It is a flag of its own: without it every argument
+combination answers word for word what it answered before.
+
 ``--fold_linear_action`` lets the closure of the reversed regulariser fold a linear group action g(x) = J x into its
 coefficients where the data are found to be one (``BatchedClosure(linear_action=None)``): a faster kernel and the same
 closure up to rounding, not bit for bit -- which is why it has to be asked for here.
@@ -149,6 +159,8 @@ LBFGS_GRID_NAMES = {'lr_sindy': 'lr', 'w_sindy_reg': 'w_reg', 'threshold': 'thre
 STLSQ_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg'}      # --stlsq_grid name -> SeedSweepSTLSQ.solve(hyper=) key
 # ... under --symreg_stlsq: the weight of the reversed regulariser as a third axis
 SYMREG_STLSQ_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg', 'w_sym_reg': 'w_sym'}
+# ... under --symreg_path: SeedSweepSTLSQ.solve_path(hyper=) keys; the path asks for no threshold
+SYMREG_PATH_GRID_NAMES = {'w_sindy_reg': 'w_reg', 'w_sym_reg': 'w_sym'}
 WSINDY_GRID_NAMES = {'threshold': 'threshold', 'w_sindy_reg': 'w_reg'}     # --wsindy_grid name -> SeedSweepWSINDy.solve(hyper=) key
 MAX_GRID_PROBLEMS = 65535                                  # problems of one device trainer
 
@@ -185,7 +197,7 @@ def _grid_problem(problem, n_seeds):
 
 def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None, device_stlsq=False,
              stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False, min_norm_stlsq=False, symreg_stlsq=False,
-             stlsq_path=False, path_tol=None):
+             stlsq_path=False, path_tol=None, symreg_path=False):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
@@ -203,10 +215,19 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     and --stlsq_grid reads SYMREG_STLSQ_GRID_NAMES.
     ``stlsq_path``, ``path_tol``: the ``--stlsq_path`` flag and the ``--path_tol`` value (None: not given); off, every answer
     is what it was.  On, its own rules (``_refusal_stlsq_path``) come first; what they let through is a plain
-    ``--method stlsq --device_stlsq`` run, which the rules below judge as they always did."""
+    ``--method stlsq --device_stlsq`` run, which the rules below judge as they always did.
+    ``symreg_path``: the ``--symreg_path`` flag; off (the default), every answer is what it was.  On, its own rules
+    (``_refusal_symreg_path``) come first -- before those of --stlsq_path and --symreg_stlsq, which it refuses by name --,
+    --path_tol is its tolerance, the rule that keeps the symmetry regulariser out of --method stlsq does not apply, and
+    --stlsq_grid reads SYMREG_PATH_GRID_NAMES."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
-    if path_tol is not None and not stlsq_path:
+    if symreg_path:
+        why = _refusal_symreg_path(args, method, engine, device_stlsq, stlsq_path, symreg_stlsq, equiv_stlsq, min_norm_stlsq,
+                                   wsindy or wsindy_grid, grid or lbfgs_grid, stlsq_grid, path_tol)
+        if why is not None:
+            return why
+    if path_tol is not None and not stlsq_path and not symreg_path:
         return ('--path_tol needs --stlsq_path: it is the tolerance of the sparsity path (the sparsest model within path_tol of '
                 'the best held-out error); the threshold loop takes --threshold')
     if stlsq_path:
@@ -255,7 +276,7 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
                 'block of seeds, python -m symode_amd.main_sweep --seed <first> --n_seeds <count> ... per process')
     if engine is None and str(args.get('device')) == 'cpu':
         return 'symode_amd runs the SINDy path on the GPU only (no CPU fallback): a HIP device is required'
-    if method == 'stlsq' and args['w_sym_reg'] > 0 and not symreg_stlsq:
+    if method == 'stlsq' and args['w_sym_reg'] > 0 and not symreg_stlsq and not symreg_path:
         return '--method stlsq sweeps the plain least-squares fit (use --method lbfgs with the symmetry regulariser)'
     if method == 'stlsq' and args.get('eq_constraint') and not equiv_stlsq:
         return '--method stlsq sweeps the unconstrained library (use --method lbfgs for EquivSINDy-c)'
@@ -264,7 +285,9 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
                 '--sindy_optimizer adam (with the default --method lbfgs), L-BFGS and STLSQ fits have no epoch order')
     if device_stlsq or stlsq_grid:
         why = _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid,
-                                    SYMREG_STLSQ_GRID_NAMES if symreg_stlsq else STLSQ_GRID_NAMES)
+                                    SYMREG_PATH_GRID_NAMES if symreg_path else
+                                    SYMREG_STLSQ_GRID_NAMES if symreg_stlsq else STLSQ_GRID_NAMES,
+                                    '--symreg_path' if symreg_path else '--symreg_stlsq')
         if why is not None:
             return why
     if grid and lbfgs_grid:
@@ -404,9 +427,61 @@ def _refusal_stlsq_path(args, method, engine, device_stlsq, equiv_stlsq, min_nor
     return None
 
 
-def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid, names=STLSQ_GRID_NAMES):
+def _refusal_symreg_path(args, method, engine, device_stlsq, stlsq_path, symreg_stlsq, equiv_stlsq, min_norm_stlsq, wsindy,
+                         other_grid, stlsq_grid, path_tol):
+    """The rules of --symreg_path that the arguments alone decide (d p <= 64 is known once the library is: ``_fit_stlsq``)."""
+    if wsindy:
+        return ('--symreg_path is the regularised sparsity path of --method stlsq: the weak-SINDy sweep (--wsindy) has no symmetry '
+                'regulariser (drop one of them)')
+    if method != 'stlsq':
+        return ('--symreg_path is the sparsity path of the sequential least-squares sweep with the reversed symmetry regulariser: '
+                'it needs --method stlsq')
+    if not device_stlsq:
+        return ('--symreg_path needs --device_stlsq: the path of every seed is one launch on the device (the host route of '
+                '--method stlsq runs the threshold loop of the plain fit)')
+    if stlsq_path:
+        return ('--symreg_path does not go with --stlsq_path: they are two paths, the regularised joint one and the plain one per '
+                'equation row (give one of them)')
+    if symreg_stlsq:
+        return ('--symreg_path does not go with --symreg_stlsq: the path asks for no threshold, the threshold loop for one (give '
+                'one of them)')
+    if args.get('eq_constraint') or equiv_stlsq or min_norm_stlsq:
+        return ('--symreg_path does not go with --eq_constraint / --equiv_stlsq / --min_norm_stlsq: the path under the equivariance '
+                'constraint goes rank deficient and is not covered (drop them, or fit with --equiv_stlsq and a threshold)')
+    if not args['w_sym_reg'] > 0:
+        return ('--symreg_path needs --w_sym_reg > 0: it is the path of the fit with the symmetry regulariser (--stlsq_path is the '
+                'path of the plain least-squares fit)')
+    if args['sym_reg_type'] != 'r':
+        return (f"--symreg_path covers the reversed symmetry regulariser only (--sym_reg_type r), not '{args['sym_reg_type']}': "
+                'the other regularisers are not quadratic in the coefficients')
+    if args['load_laligan'] is None:
+        return ('--symreg_path needs --load_laligan: the regulariser\'s matrices are built from the group action of a saved '
+                'LaLiGAN')
+    if not args['fix_laligan']:
+        return '--symreg_path needs --fix_laligan: g(x), J_g(x) are computed once, from a frozen LaLiGAN'
+    if other_grid:
+        return ('--symreg_path does not go with --grid / --lbfgs_grid / --wsindy_grid: they are the grids of other sweeps (its own '
+                'is --stlsq_grid w_sym_reg=... / w_sindy_reg=...)')
+    if args.get('lstsq_driver') == 'gelsy':
+        return ('--symreg_path fits with the full-rank driver (gels) only: the rank rule of --lstsq_driver gelsy has no '
+                'regularised form')
+    if args['use_latent']:
+        return '--symreg_path does not cover latent fits (--use_latent)'
+    if engine is None and str(args.get('device')) == 'cpu':
+        return '--symreg_path runs on the GPU only (no CPU fallback): a HIP device is required'
+    if path_tol is not None and not (np.isfinite(path_tol) and path_tol >= 0):
+        return f'--path_tol {path_tol:g}: the tolerance of the sparsity path must be a finite number >= 0'
+    if any(str(spec).partition('=')[0] == 'threshold' for spec in stlsq_grid or ()):
+        return ('--symreg_path does not take --stlsq_grid threshold=...: the path visits every support a threshold could reach and '
+                'asks for no threshold (its axes are w_sym_reg and w_sindy_reg)')
+    return None
+
+
+def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq, stlsq_grid, names=STLSQ_GRID_NAMES,
+                          sym_flag='--symreg_stlsq'):
     """The rules of --device_stlsq and --stlsq_grid (``_refusal``, which has applied the rules of --method stlsq itself).
-    ``names``: the axes of the grid (SYMREG_STLSQ_GRID_NAMES under --symreg_stlsq, whose w_sym_reg values must be > 0)."""
+    ``names``: the axes of the grid (SYMREG_STLSQ_GRID_NAMES under --symreg_stlsq, whose w_sym_reg values must be > 0;
+    SYMREG_PATH_GRID_NAMES under --symreg_path, ``sym_flag`` then names that flag)."""
     given = ' and '.join(flag for flag, on in (('--device_stlsq', device_stlsq), ('--stlsq_grid', stlsq_grid)) if on)
     if method != 'stlsq':
         return (f'{given}: the device fit of the sequential-threshold least-squares sweep and its grid need --method stlsq '
@@ -429,7 +504,7 @@ def _refusal_device_stlsq(args, method, grid, lbfgs_grid, n_seeds, device_stlsq,
     for name, axis in axes:
         if name == 'w_sym_reg' and not all(v > 0 for v in axis):
             return (f'--stlsq_grid w_sym_reg={",".join(f"{v:g}" for v in axis)}: every value must be > 0 (a sweep without the '
-                    'regulariser is another run, without --symreg_stlsq)')
+                    f'regulariser is another run, without {sym_flag})')
         if not all(v >= 0 for v in axis):
             return f'--stlsq_grid {name}={",".join(f"{v:g}" for v in axis)}: every value must be >= 0'
     n_points = int(np.prod([len(axis) for _, axis in axes]))
@@ -511,13 +586,15 @@ def _fit_stlsq(ctx):
         if getattr(ctx, 'min_norm_stlsq', False):
             fit['min_norm'] = True
     names, column, laligan = STLSQ_GRID_NAMES, {}, None
-    if getattr(ctx, 'symreg_stlsq', False):
-        # --symreg_stlsq: library and LaLiGAN are the template's, as the L-BFGS sweep builds it
+    symreg_path = getattr(ctx, 'symreg_path', False)
+    if getattr(ctx, 'symreg_stlsq', False) or symreg_path:
+        # --symreg_stlsq / --symreg_path: library and LaLiGAN are the template's, as the L-BFGS sweep builds it
         template, _, laligan = _template(ctx)
         lib = (template.poly_order, template.include_sine, template.include_exp)
         n_coef = template.latent_dim * template.coef.p
         if n_coef > SYMREG_STLSQ_MAX_COEFS:
-            raise SystemExit(f'--symreg_stlsq: the library has d p = {template.latent_dim} x {template.coef.p} = {n_coef} '
+            flag = '--symreg_path' if symreg_path else '--symreg_stlsq'
+            raise SystemExit(f'{flag}: the library has d p = {template.latent_dim} x {template.coef.p} = {n_coef} '
                              f'coefficients, the device fit takes at most {SYMREG_STLSQ_MAX_COEFS}; use --method lbfgs')
     rows = _rows(ctx)
     sw = SeedSweepSTLSQ(ctx.x_all, ctx.dx_all, *lib, n_seeds=len(ctx.seeds), subsample=args['lbfgs_subsample'], seed0=args['seed'],
@@ -536,6 +613,8 @@ def _fit_stlsq(ctx):
         sw.set_grams(stats.G, stats.count)
         fit = dict(rev=(stats.R, args['w_sym_reg'] / args['w_sindy_x']))     # the weight relative to the MSE, as _fit_lbfgs
         names, column = SYMREG_STLSQ_GRID_NAMES, {'w_sym_reg': lambda v: v / args['w_sindy_x']}
+    if symreg_path:
+        return _fit_symreg_path(ctx, sw, lib, fit['rev'], column)
     n_seeds, points = len(ctx.seeds), getattr(ctx, 'grid', None)
     if points is not None:
         # --stlsq_grid: G points on common seeds, problem g * n_seeds + k = point g on seed k's matrices
@@ -577,6 +656,40 @@ def _fit_stlsq_path(ctx, sw, lib):
                                                          for j in range(size.shape[1])),
              f'near-tie eliminations: {int((record["near"] > 0).sum())} of {len(ctx.seeds)} problems',
              f'--threshold ({args["threshold"]:g}) is not used by the path']
+    return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
+
+
+def _fit_symreg_path(ctx, sw, lib, rev, column):
+    """--symreg_path: [G | R | count] as ``_fit_stlsq`` builds them under --symreg_stlsq (``rev`` = (R, w_sym)), the validation
+    set's matrix as ``_fit_stlsq_path`` forms it (every rank from the whole set: no collective), ONE symode_stlsq_path_symreg
+    launch (``SeedSweepSTLSQ.solve_path(rev=...)``) -- under --stlsq_grid over G points x S seeds, ``column`` the map from an
+    axis' values to the launch's.  Rank 0 also writes eval_results/<save_dir>/path.npz: the record's arrays of all problems."""
+    args, val = ctx.args, ctx.val
+    tol = PATH_TOL if ctx.path_tol is None else ctx.path_tol
+    n_seeds, points = len(ctx.seeds), getattr(ctx, 'grid', None)
+    hyper = None
+    if points is not None:
+        hyper = {SYMREG_PATH_GRID_NAMES[name]: [column.get(name, float)(point[name]) for point in points for _ in ctx.seeds]
+                 for name in points[0]}
+    V = sw.val_grams(val.x.to(ctx.dev), val.dx.to(ctx.dev))
+    Xi, mask, record = sw.solve_path(args['w_sindy_reg'], V, tol, rev=rev, hyper=hyper)
+    if ctx.rank == 0:
+        eval_dir = f'eval_results/{args["save_dir"]}'
+        os.makedirs(eval_dir, exist_ok=True)
+        np.savez(f'{eval_dir}/path.npz', seeds=np.asarray(ctx.seeds), path_tol=tol,
+                 **{k: record[k] for k in ('order', 'mse_train', 'reg_train', 'mse_val', 'best', 'near')})
+    n0 = sw.d * sw.p
+    size = n0 - record['best']                                            # (n_problems,): entries the chosen model keeps
+    lines = [f'{n_seeds} seeds x {sw.n_points} points (over {ctx.world} rank(s)), regularised sparsity path of {n0 + 1} models per '
+             f'problem (one chain over the {sw.d} rows), scored on {val.x.shape[0]} validation points, path_tol {tol:g}'
+             + ('' if points is None else f', {len(points)} grid points on their Gram matrices')]
+    if points is None:
+        lines.append(f'chosen support size: {int(size.min())}-{int(size.max())} of {n0}')
+    else:
+        lines += [f'grid {g}: chosen support size: {int(size[g * n_seeds:(g + 1) * n_seeds].min())}-'
+                  f'{int(size[g * n_seeds:(g + 1) * n_seeds].max())} of {n0}' for g in range(len(points))]
+    lines += [f'near-tie eliminations: {int((record["near"] > 0).sum())} of {len(size)} problems',
+              f'--threshold ({args["threshold"]:g}) is not used by the path']
     return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
 
 
@@ -871,6 +984,7 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     min_norm_stlsq = _pop_flag(argv, '--min_norm_stlsq')
     symreg_stlsq = _pop_flag(argv, '--symreg_stlsq')
     stlsq_path = _pop_flag(argv, '--stlsq_path')
+    symreg_path = _pop_flag(argv, '--symreg_path')
     path_tol = _pop(argv, '--path_tol', None, float)
     fold_linear_action = _pop_flag(argv, '--fold_linear_action')
     args = vars(get_args(argv=argv))
@@ -878,7 +992,7 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
                    device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None, wsindy=wsindy, wsindy_grid=wsindy_grid or None,
                    equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq, stlsq_path=stlsq_path,
-                   path_tol=path_tol)
+                   path_tol=path_tol, symreg_path=symreg_path)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -900,13 +1014,13 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
                           engine=engine, kw={} if engine is None else {'engine': engine}, grid=None,
                           device_stlsq=device_stlsq, fold_linear_action=fold_linear_action, train=train_dataset,
                           equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq,
-                          stlsq_path=stlsq_path, path_tol=path_tol, val=val_dataset)
+                          stlsq_path=stlsq_path, path_tol=path_tol, val=val_dataset, symreg_path=symreg_path)
     if wsindy_grid:
         ctx.grid_names = WSINDY_GRID_NAMES
         ctx.grid_axes = _parse_grid(wsindy_grid, WSINDY_GRID_NAMES, '--wsindy_grid')[0]
         ctx.grid = _grid_points(ctx.grid_axes)
     elif stlsq_grid:
-        ctx.grid_names = SYMREG_STLSQ_GRID_NAMES if symreg_stlsq else STLSQ_GRID_NAMES
+        ctx.grid_names = SYMREG_PATH_GRID_NAMES if symreg_path else SYMREG_STLSQ_GRID_NAMES if symreg_stlsq else STLSQ_GRID_NAMES
         ctx.grid_axes = _parse_grid(stlsq_grid, ctx.grid_names, '--stlsq_grid')[0]
         ctx.grid = _grid_points(ctx.grid_axes)
     elif grid or lbfgs_grid:

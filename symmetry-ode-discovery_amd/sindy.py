@@ -484,6 +484,71 @@ def stlsq_path_from_gram(G, V, gamma, tol, floor_rel, near_band, d, n_points=0):
     return Xi, mask, dict(order=order, rss_train=rss_train, rss_val=rss_val, best=best, near=near, path_xi=path)
 
 
+def stlsq_path_symreg_select(mse_val, V, d, tol, floor_rel):
+    """The step symode_stlsq_path_symreg keeps, ``stlsq_path_select`` on the joint chain: the LARGEST t with
+    mse_val[t] <= (1 + tol) max(min mse_val, 0) + floor_rel Vyy, Vyy = sum_j V[p+j][p+j] (the empty model's error, j ascending)."""
+    p = V.shape[0] - d
+    vyy = 0.0
+    for j in range(d):
+        vyy += V[p + j, p + j]
+    return stlsq_path_select(mse_val, vyy, tol, floor_rel)
+
+
+def stlsq_path_symreg_from_gram(G, R, V, gamma, w_sym, tol, floor_rel, near_band, d, n_points=0):
+    """The sparsity path of ONE problem with the reversed symmetry regulariser in numpy, the host twin of
+    symode_stlsq_path_symreg: ONE chain over the joint (d, p) support (R couples the rows) from the full library to the empty
+    model -- solve ``stlsq_symreg_system`` on the active entries (``lstsq_normal(..., 'gels')``, with its minimum-norm
+    fallback and RuntimeWarning on a singular support), round to fp32, score the model (mse on the training matrix G and the
+    held-out matrix V: the rows' ``stlsq_path_rss`` summed from 0.0, rows ascending; reg = v^T R v on the training R, q_b over
+    the support ascending, then the r_b ascending -- the regulariser is not scored on held-out data), drop the active entry
+    with the smallest |coefficient| (fp32 compare, the lowest flat index j p + k of equals) -- then keep the sparsest model
+    whose held-out error is within ``tol`` of the best (``stlsq_path_symreg_select``).  ``near`` counts the eliminations whose
+    runner-up was within ``near_band``.
+    Returns (Xi (d, p) float32, mask (d, p) bool, record) with record = dict(order (d p,) int32 flat indices, mse_train,
+    reg_train, mse_val (d p + 1,) float64, best int, near int, path_xi (d p + 1, d, p) float32): per problem, not per row."""
+    G, V = np.asarray(G, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    p = G.shape[0] - d
+    n0 = d * p
+    R = np.asarray(R, dtype=np.float64).reshape(n0, n0)
+    path = np.zeros((n0 + 1, d, p), dtype=np.float32)
+    order = np.zeros(n0, dtype=np.int32)
+    mse_train, reg_train, mse_val = np.zeros(n0 + 1), np.zeros(n0 + 1), np.zeros(n0 + 1)
+    active = np.ones((d, p), dtype=bool)
+    near = 0
+    for t in range(n0 + 1):
+        flat = np.nonzero(active.reshape(-1))[0]
+        if len(flat):
+            A, b = stlsq_symreg_system(G, R, active, gamma, w_sym, d)
+            w, _ = lstsq_normal(A, b, d * (int(n_points) + p), 'gels')
+            path[t][active] = np.asarray(w, dtype=np.float64).astype(np.float32)
+        w64 = path[t].astype(np.float64)
+        for H, out in ((G, mse_train), (V, mse_val)):
+            e = 0.0
+            for j in range(d):
+                e += stlsq_path_rss(H, p, j, np.nonzero(active[j])[0], w64[j])
+            out[t] = e
+        v, e = w64.reshape(-1), 0.0
+        for b_ in flat:
+            q = 0.0
+            for a in flat:
+                q += R[b_, a] * v[a]
+            e += v[b_] * q
+        reg_train[t] = e
+        if len(flat):
+            av = np.abs(path[t].reshape(-1)[flat])
+            out = int(np.argmin(av))                             # the first of equals: the lowest flat index
+            if len(flat) > 1:
+                up = np.delete(av, out).min()
+                near += int(float(up) - float(av[out]) < near_band)
+            order[t] = flat[out]
+            active.reshape(-1)[flat[out]] = False
+    best = stlsq_path_symreg_select(mse_val, V, d, tol, floor_rel)
+    mask = np.zeros(n0, dtype=bool)
+    mask[order[best:]] = True                                   # the entries that leave at step best or later are active there
+    return path[best].copy(), mask.reshape(d, p), dict(order=order, mse_train=mse_train, reg_train=reg_train, mse_val=mse_val,
+                                                       best=np.int32(best), near=near, path_xi=path)
+
+
 def _mask_on_host(regressor):
     """Boolean host copy of the mask without a device round trip when the mask on the device is still the tensor this
     module uploaded last (the mirror keeps that tensor alive, so an equal address means the same storage; in-place

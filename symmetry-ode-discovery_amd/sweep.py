@@ -20,7 +20,7 @@ from .coef_map import CoefMap
 from .engine import LBFGS_ACCEPT, LBFGS_BEGIN, get_engine, library_flags
 from . import lstsq as _lstsq
 from .sindy import (NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_constrained_from_gram, stlsq_path_from_gram,
-                    stlsq_solve_from_gram, stlsq_symreg_from_gram, weak_test_functions)
+                    stlsq_path_symreg_from_gram, stlsq_solve_from_gram, stlsq_symreg_from_gram, weak_test_functions)
 
 
 def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
@@ -264,7 +264,7 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         dev = self.x.device
         return self.engine.aug_gram(x_val.to(dev).contiguous()[None], dx_val.to(dev).contiguous()[None], self.order, self.flags)
 
-    def solve_path(self, w_sindy_reg, val_gram, tol, floor_rel=1e-10, device=True, keep_path=False):
+    def solve_path(self, w_sindy_reg, val_gram, tol, floor_rel=1e-10, device=True, keep_path=False, rev=None, hyper=None):
         """The sparsity path for every seed: backward elimination from the full library to the empty model (solve, drop the
         smallest coefficient, solve again), every model scored on the held-out matrix ``val_gram`` ((n_val, p+d, p+d) fp64 raw
         sums, host or device, n_val = 1 or S: ``val_grams``), and per equation row the sparsest model kept whose held-out
@@ -276,7 +276,21 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         (sindy.stlsq_path_from_gram) with the RuntimeWarning of the full-rank driver, and only those problems' matrices are
         copied.  ``device=False``: the host twin for every seed.
         Returns (Xi (S, d, p) float32, mask (S, d, p) float32, record) with record = dict(order (S, d, p), rss_train, rss_val
-        (S, d, p+1), best (S, d), near (S,)) and, with ``keep_path=True``, path_xi (S, d, p+1, p)."""
+        (S, d, p+1), best (S, d), near (S,)) and, with ``keep_path=True``, path_xi (S, d, p+1, p).
+        ``rev=(R, w_sym)``: the path of the fit with the reversed symmetry regulariser, EquivSINDy-r (R as ``solve`` takes
+        it).  R couples the equation rows, so there is ONE chain per PROBLEM over the joint (d, p) support of n0 = d p <= 64
+        entries, not one per row: record = dict(order (n_problems, n0) flat indices j p + k, mse_train, reg_train, mse_val
+        (n_problems, n0+1) -- raw sums over the rows; the regulariser is scored on the training set only --, best, near
+        (n_problems,)) and, with ``keep_path=True``, path_xi (n_problems, n0+1, d, p).  ``device=True`` is ONE
+        symode_stlsq_path_symreg launch, a flagged problem goes to sindy.stlsq_path_symreg_from_gram; the ridge weight and
+        w_sym are held in fp32 on both routes, as the launch holds them.  ``hyper={"w_reg": [...], "w_sym": [...]}`` (with
+        ``rev`` and ``device=True``): one value per PROBLEM as in ``solve``, problem s on seed s % S; a column left out takes
+        the scalar argument."""
+        if rev is not None:
+            return self._solve_path_symreg(w_sindy_reg, val_gram, tol, floor_rel, device, keep_path, rev, hyper)
+        if hyper is not None:
+            raise ValueError('solve_path: hyper (a per-problem table of w_reg / w_sym) needs rev=(R, w_sym): the table is the '
+                             "regularised path's")
         S, d, p = self.S, self.d, self.p
         for name, v in (('w_sindy_reg', w_sindy_reg), ('tol', tol), ('floor_rel', floor_rel)):
             if not (np.isfinite(float(v)) and float(v) >= 0):
@@ -312,6 +326,78 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
                 Xi[s], mask[s], rec = twin(G[s].cpu().numpy(), V[s % shape[0]].cpu().numpy())
                 for k in keys:
                     record[k][s] = rec[k]
+            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
+                          RuntimeWarning)
+        return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), record
+
+    def _solve_path_symreg(self, w_sindy_reg, val_gram, tol, floor_rel, device, keep_path, rev, hyper):
+        """``solve_path(rev=...)``: see there."""
+        S, d, p = self.S, self.d, self.p
+        n0 = d * p
+        if n0 > 64:
+            raise ValueError(f'solve_path: rev (the reversed symmetry regulariser): d p = {d} x {p} = {n0} unknowns, the joint '
+                             'system of a step takes at most 64')
+        if len(rev) != 2 or tuple(rev[0].shape) != (S, n0, n0):
+            raise ValueError(f'solve_path: rev must be (R, w_sym) with R (S, d p, d p) = ({S}, {n0}, {n0})')
+        for name, v in (('w_sindy_reg', w_sindy_reg), ('w_sym', rev[1]), ('tol', tol), ('floor_rel', floor_rel)):
+            if not (np.isfinite(float(v)) and float(v) >= 0):
+                raise ValueError(f'solve_path: {name} must be finite and >= 0, got {v}')
+        shape = tuple(val_gram.shape)
+        if len(shape) != 3 or shape[1:] != (p + d, p + d) or shape[0] not in (1, S):
+            raise ValueError(f'solve_path: val_gram must be (n_val, p + d, p + d) = (1 or {S}, {p + d}, {p + d}), got {shape}')
+        f32 = lambda v: float(np.float32(v))                                   # noqa: E731
+        n_problems = S
+        if hyper is not None:
+            if not device:
+                raise ValueError('solve_path: hyper (a per-problem table of w_reg / w_sym) needs device=True: the host route takes '
+                                 'one value each')
+            if not hyper or set(hyper) - {'w_reg', 'w_sym'}:
+                raise ValueError(f'solve_path: hyper: the per-problem columns of the regularised path are w_reg and w_sym, got '
+                                 f'{sorted(hyper)}')
+            lengths = {len(v) for v in hyper.values()}
+            n_problems = lengths.pop()
+            if lengths or n_problems < S or n_problems % S != 0:
+                raise ValueError(f'solve_path: hyper: every column needs one value per problem, a multiple of the {S} seeds (problem '
+                                 f's on seed s % {S}); got lengths {sorted({len(v) for v in hyper.values()})}')
+        w = np.array([float(v) for v in (hyper or {}).get('w_reg', [w_sindy_reg] * n_problems)], dtype=np.float64)
+        wsym = np.array([f32(v) for v in (hyper or {}).get('w_sym', [rev[1]] * n_problems)], dtype=np.float64)
+        if not (np.all(np.isfinite(w)) and np.all(w >= 0) and np.all(np.isfinite(wsym)) and np.all(wsym >= 0)):
+            raise ValueError('solve_path: the ridge weight and w_sym of every problem must be finite and >= 0')
+        gamma = np.array([f32(np.sqrt(v)) for v in w], dtype=np.float64)       # as the launch holds it
+        keys = ('order', 'mse_train', 'reg_train', 'mse_val', 'best', 'near') + (('path_xi',) if keep_path else ())
+
+        def twin(Gs, Rs, Vs, s):
+            return stlsq_path_symreg_from_gram(Gs, Rs, Vs, gamma[s], wsym[s], float(tol), float(floor_rel), NEAR_THRESHOLD_BAND, d,
+                                               self.n_points)
+
+        if not device:
+            G = self.grams()
+            R = rev[0].detach().cpu().numpy() if torch.is_tensor(rev[0]) else np.asarray(rev[0])
+            Vh = val_gram.detach().cpu().numpy() if torch.is_tensor(val_gram) else np.asarray(val_gram, dtype=np.float64)
+            out = [twin(G[s], R[s], Vh[s % shape[0]], s) for s in range(S)]
+            record = {k: np.stack([np.asarray(o[2][k]) for o in out]) for k in keys}
+            record['near'] = record['near'].astype(np.int32)              # (the launch's type)
+            return (torch.from_numpy(np.stack([o[0] for o in out])),
+                    torch.from_numpy(np.stack([o[1] for o in out]).astype(np.float32)), record)
+        G = self.grams(device=True)
+        R = torch.as_tensor(rev[0]).to(device=G.device, dtype=torch.float64).reshape(S, n0, n0).contiguous()
+        V = torch.as_tensor(val_gram).to(device=G.device, dtype=torch.float64).contiguous()
+        table = None
+        if hyper is not None:
+            table = torch.from_numpy(np.stack([gamma, wsym], axis=1).astype(np.float32)).to(G.device)
+        o = self.engine.stlsq_path_symreg(G, R, V, self.n_points, gamma[0], wsym[0], float(tol), float(floor_rel), hyper=table, d=d,
+                                          pivot_floor=_lstsq.SINGULAR_RCOND ** 2, near_band=NEAR_THRESHOLD_BAND, to_host=True,
+                                          keep_path=keep_path)
+        Xi, mask = np.array(o['Xi']), np.asarray(o['mask']).astype(bool)
+        record = {k: np.array(o[k]) for k in keys}
+        if o['fell'].any():
+            # possibly rank deficient: these problems are the host twin's, minimum-norm fallback and warning included
+            import warnings
+            for s in np.nonzero(o['fell'])[0].tolist():
+                k = s % S
+                Xi[s], mask[s], rec = twin(G[k].cpu().numpy(), R[k].cpu().numpy(), V[s % shape[0]].cpu().numpy(), s)
+                for key in keys:
+                    record[key][s] = rec[key]
             warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
                           RuntimeWarning)
         return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), record
