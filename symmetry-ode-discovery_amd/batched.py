@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 
 from .coef_map import CoefMap
-from .engine import get_engine, library_flags
+from .engine import STEP_SLOW, STEP_STALE, get_engine, library_flags, step_key
 
 
 def allreduce_sums(sums, params, group):
@@ -177,9 +177,11 @@ class BatchedClosure:
     def _reduced_key(self):
         """What the reduced form was built from: the keys of ``_gram_for_launch`` and ``_linear_for_launch``, the weight, the
         column set and Q"""
-        x, dx, (gx, jgx, weight), Q = self.x, self.dx, self.sym, self.coef.Q
-        return (x._version, x.data_ptr(), dx._version, dx.data_ptr(), gx._version, gx.data_ptr(), jgx._version, jgx.data_ptr(),
-                weight, self._live, Q._version, Q.data_ptr())
+        return step_key(*self._reduced_operands())
+
+    def _reduced_operands(self):
+        """The five arguments the key is read from, by ``step_key`` here and by the prepared step in every call"""
+        return self.x, self.dx, self.sym, self.coef.Q, self._live
 
     def _reduced_for_launch(self):
         """The prepared step on the reduced form B of the closure ``evaluate`` would launch, built once per ``_reduced_key``
@@ -195,10 +197,33 @@ class BatchedClosure:
         key = self._reduced_key()
         B = self.engine.quad_reduce(aug, lin, self._cj_table, self.order, self.coef, self.sym[2], self.inv_count, self._live)
         self._reduced_step = self.engine.quad_step_plan(B, self.order, self._live, self.coef.r,
-                                                        self.d if self.coef.allow_constant else 0, self._ws_kw['ws'])
+                                                        self.d if self.coef.allow_constant else 0, self._ws_kw['ws'],
+                                                        key=self._reduced_operands())
         self._reduced_seen = key
         self.reduced_builds += 1
         return self._reduced_step
+
+    def _reduced_off_the_straight_path(self, code, step, beta, const, alias):
+        """What ``evaluate`` does with an answer of the prepared step that is neither its result nor None.  STEP_STALE: the
+        form is built again and the step tried once more.  STEP_SLOW (the native plan alone): the operands go through the
+        plan's ``ReducedStep``, which makes them dense or raises; with ``alias`` it writes the plan's buffers.  Any other number
+        is an error code of the launch (``engine._check`` raises).  None: take the one-launch kernel."""
+        door = self.engine.loss_grad_reversed
+        if code == STEP_STALE:
+            step = self._reduced_for_launch()
+            if step is None:
+                return None
+            code = door(None, None, None, None, None, None, self.order, reduced=(step, beta, const, alias) + self._reduced_operands())
+            if code is None or type(code) is tuple:
+                return code
+            if code == STEP_STALE:                           # a key that does not equal itself (a NaN weight)
+                return None
+        if code == STEP_SLOW:
+            slow = step.slow
+            if alias:
+                slow._alias = step.alias_buffers()
+            return door(None, None, None, None, None, None, self.order, reduced=(slow, beta, const, alias))
+        self.engine._check(code, "symode_quad_step")
 
     def _jacobian_for_launch(self):
         """What the closures get as J_g: the compact table when the detection pass found every slab constant, else the
@@ -350,14 +375,20 @@ class BatchedClosure:
         ``sym_buffers`` and ``buffers[0][n:]`` keep their last contents.  A call with a mask, and a call under stream capture
         that finds no valid form, take the one-launch kernel."""
         if self._reduced_on and mask is None and (const is not None or not self.coef.allow_constant):
-            # the step on the reduced form: a comparison of the keys, one packed allocation, one call (engine.ReducedStep)
+            # the step on the reduced form: one call through the engine's door; the prepared step (engine.quad_step_plan) compares
+            # the key of the five operands named here, allocates, launches and returns the views
             step = self._reduced_step
-            if step is None or self._reduced_seen != self._reduced_key():
+            if step is None:
                 step = self._reduced_for_launch()
             if step is not None:
-                out = self.engine.loss_grad_reversed(None, None, None, None, None, None, self.order, reduced=(step, beta, const, alias))
-                if out is not None:
+                out = self.engine.loss_grad_reversed(None, None, None, None, None, None, self.order,
+                                                     reduced=(step, beta, const, alias, self.x, self.dx, self.sym, self.coef.Q, self._live))
+                if type(out) is tuple:
                     return out
+                if out is not None:
+                    out = self._reduced_off_the_straight_path(out, step, beta, const, alias)
+                    if out is not None:
+                        return out
         if self.coef.Q is not None and self.coef.r > 0 and not self.distributed and len(self.chunks) == 1 and self.sym is not None \
                 and self.fuse_sym and self._resid_on and self._linear_for_launch() is not None and self._quad_for_launch() is not None:
             return self.loss_grad_xi(None, mask, alias=alias, live_columns=self._live, coef=(beta, const))

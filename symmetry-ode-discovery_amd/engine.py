@@ -252,14 +252,43 @@ def library_flags(include_sine: bool, include_exp: bool) -> int:
     return (FLAG_SINE if include_sine else 0) | (FLAG_EXP if include_exp else 0)
 
 
+# The native entry of the step on the reduced form (csrc/step_entry.cpp -> _symode_step*.so beside the library).  Optional at
+# import: without it ``quad_step_plan`` hands out the Python ``ReducedStep``, and these two say so.
+try:
+    from . import _symode_step as _step_entry
+    step_entry_loaded, step_entry_error = True, None
+except ImportError as _e:
+    _step_entry, step_entry_loaded, step_entry_error = None, False, f"{type(_e).__name__}: {_e}"
+
+# what a prepared step answers in the place of its result tuple (None: the library's switches refuse the step)
+STEP_STALE, STEP_SLOW = -1001, -1002                      # STALE / SLOW of csrc/step_entry.cpp, clear of the SYMODE_E_* codes
+
+
+def step_entry_enabled() -> bool:
+    """Does ``quad_step_plan`` hand out the native plan?  The module loaded and SYMODE_STEP_ENTRY is not 0; read where a plan is
+    made, not per call."""
+    return step_entry_loaded and os.environ.get("SYMODE_STEP_ENTRY", "1")[:1] != "0"
+
+
+def step_key(x, dx, sym, Q, live):
+    """What a reduced form was built from: (version, pointer) of x, dx, gx, jgx and Q, the weight and the column set; ``sym`` =
+    (gx, jgx, weight).  The native plan reads the same twelve components from the same five arguments."""
+    gx, jgx, weight = sym
+    return (x._version, x.data_ptr(), dx._version, dx.data_ptr(), gx._version, gx.data_ptr(), jgx._version, jgx.data_ptr(),
+            weight, live, Q._version, Q.data_ptr())
+
+
 class ReducedStep:
     """A prepared ``symode_quad_step`` launch on one reduced form B (``HipEngine.quad_step_plan``): the pointers, sizes and
     header arguments that stand while B stands are kept, so that a call is one allocation -- a packed fp32 buffer
     [loss (S) | g_beta (S, r) | g_const (S, d_c)] of which the results are views -- and one ctypes call.  ``alias=True``
-    writes into one buffer of this object instead and returns the same views every time."""
+    writes into one buffer of this object instead and returns the same views every time.
+    This is the step in Python: what ``quad_step_plan`` hands out where the native plan (csrc/step_entry.cpp, which does the
+    same in one call) is not built or SYMODE_STEP_ENTRY=0, and where the native plan sends operands it does not take."""
 
-    def __init__(self, eng, B, order, live, r, dc, ws):
+    def __init__(self, eng, B, order, live, r, dc, ws, key=None):
         self.eng, self.B, self.ws = eng, B, ws                       # kept alive with the pointers below
+        self.key = None if key is None else step_key(*key)
         self.S, self.r, self.dc, self.device = B.shape[0], r, dc, B.device
         self._fn = eng.lib.symode_quad_step
         self._head = (B.data_ptr(), self.S, r + dc, dc, order, live)
@@ -284,9 +313,16 @@ class ReducedStep:
             raise SymodeError(f"{name} has {t.numel()} elements, expected {S}x{w}")
         return t, w
 
-    def __call__(self, beta, const, alias=False):
-        """(loss, g_beta, g_const or None), or None where the library's switches refuse the step (SYMODE_QUAD_REDUCED=0 and
-        the switches of the closure it stands for): the caller then takes that closure's own launch."""
+    def __call__(self, args):
+        """``args`` = (anything, beta, const, alias[, x, dx, sym, Q, live]), the tuple of ``loss_grad_reversed(reduced=)``.
+        (loss, g_beta, g_const or None); None where the library's switches refuse the step (SYMODE_QUAD_REDUCED=0 and the
+        switches of the closure it stands for): the caller then takes that closure's own launch; STEP_STALE where the five
+        key operands are given and ``step_key`` of them is not the key this step was made with."""
+        if len(args) > 4 and step_key(*args[4:]) != self.key:
+            return STEP_STALE
+        return self.step(args[1], args[2], args[3])
+
+    def step(self, beta, const, alias=False):
         beta, ldb = self._rows(beta, self.r, "beta")
         if self.dc:
             const, ldc = self._rows(const, self.dc, "const")
@@ -317,6 +353,8 @@ class HipEngine:
     def __init__(self, path: str = LIB_PATH):
         self.lib = load_library(path)
         self._ws = {}     # (device index, stream) -> scratch tensor (grown on demand, reused)
+        # did the native step entry load, and if not why (the module's own record, also on the instance)
+        self.step_entry_loaded, self.step_entry_error = step_entry_loaded, step_entry_error
 
     # -- plumbing ----------------------------------------------------------------------
     def _check(self, code: int, what: str):
@@ -1006,8 +1044,13 @@ class HipEngine:
                                               self._ptr(g_const), self._ptr(ws), ws.numel() * 8, self._stream(B)), "symode_quad_step")
         return loss, g_beta.reshape(S, r), None if g_const is None else g_const.reshape(S, dc, 1)
 
-    def quad_step_plan(self, B, order, live_columns, r, dc, ws):
-        """The step on B, prepared: everything of ``quad_step`` that cannot change while B stands (``ReducedStep``)."""
+    def quad_step_plan(self, B, order, live_columns, r, dc, ws, key=None):
+        """The step on B, prepared: everything of ``quad_step`` that cannot change while B stands.  ``key`` = (x, dx, sym, Q,
+        live), the operands B was reduced from as a call will name them (``step_key``): a call that names operands of another
+        key answers STEP_STALE.  With a key, where ``step_entry_enabled()``, the result is the native plan
+        (``_symode_step.Plan``: key, row checks, allocation, stream, launch and views in one call; its ``slow`` is the
+        ``ReducedStep`` for operands it does not take); else the ``ReducedStep`` itself.  Both are called with the tuple of
+        ``loss_grad_reversed(reduced=)``."""
         B = self._dev(B, "B", torch.float64)
         K = r + dc
         if B.dim() != 3 or tuple(B.shape[1:]) != (K + 1, K + 1) or r < 1 or dc < 0 or K + 1 > 16:
@@ -1015,7 +1058,11 @@ class HipEngine:
         if ws is None or not ws.is_cuda or ws.dtype != torch.float64 or ws.device != B.device:
             raise SymodeError("the prepared step takes an initialised workspace on B's device (new_workspace)")
         live = (0xFFFFFFFFFFFFFFFF if live_columns is None else int(live_columns)) & 0xFFFFFFFFFFFFFFFF
-        return ReducedStep(self, B, order, live, r, dc, ws)
+        slow = ReducedStep(self, B, order, live, r, dc, ws, key)
+        if key is None or not step_entry_enabled():
+            return slow
+        address = ctypes.cast(self.lib.symode_quad_step, c_void_p).value
+        return _step_entry.Plan(address, B, ws, r, dc, order, live, key, slow)
 
     def _closure_quad_call(self, x, rev, xi, mask, order, flags, w_sym, inv_count, out, ws, live, linear_m, aug, coef, coef_out):
         """The launch of ``loss_grad_reversed(aug=...)``: the arguments of symode_loss_grad_reversed_linear_quad, checked."""
@@ -1116,12 +1163,15 @@ class HipEngine:
         (``xi`` is not read; Q beta in fp64, one rounding to fp32) and also returns the gradient by the variables:
         (loss2, grad, g_beta (S, r), g_const (S, d, 1) or None).  ``coef_out`` = (xi_out or None, g_beta, g_const or None): buffers
         for these, xi_out (S, d, p) receiving the Xi the launch formed.
-        ``reduced`` = (ReducedStep, beta, const, alias): the same closure as a prepared step on its reduced form
-        (``quad_step_plan``).  The call is handed on in the first statement and nothing else is read or checked -- every other
-        argument may be None; it enters here so that whatever wraps this method to watch the reversed closures (a timer, a
-        trace) sees these steps too.  Returns (loss, g_beta, g_const), or None where the library's switches refuse the step."""
+        ``reduced`` = (step, beta, const, alias[, x, dx, sym, Q, live]): the same closure as a prepared step on its reduced
+        form (``quad_step_plan``; the last five name the operands of the step's key).  The call is handed on in the first
+        statement, the tuple as it is, and nothing else is read or checked -- every other argument may be None; it enters here
+        so that whatever wraps this method to watch the reversed closures (a timer, a trace) sees these steps too.  Returns
+        (loss, g_beta, g_const); None where the library's switches refuse the step; STEP_STALE where the key moved; from the
+        native plan also STEP_SLOW (an operand it does not take as it lies: call its ``slow``) or a positive error code of
+        the launch (for ``_check``)."""
         if reduced is not None:
-            return reduced[0](reduced[1], reduced[2], reduced[3])
+            return reduced[0](reduced)
         x, dx = self._dev(x, "x"), self._dev(dx, "dx")
         if x.shape != dx.shape:
             raise SymodeError(f"x {tuple(x.shape)} and dx {tuple(dx.shape)} differ")
