@@ -3,6 +3,7 @@
 // returns a negative code has touched no device memory.
 #include <cmath>
 #include <cstdint>
+#include <initializer_list>
 
 #include "../../include/symode.h"
 #include "closure_quad.hpp"
@@ -38,6 +39,26 @@ const LibOps* find_ops(int d, int order, int flags) {
 }
 
 inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p % a) != 0; }
+template <class... P> inline bool any_null(const P*... p) { return (... || (p == nullptr)); }
+template <class... P> inline bool any_misaligned(size_t a, const P*... p) { return (... || misaligned(p, a)); }
+
+// ---- the size rules the symode_stlsq_* entries share, each stated once (host only; true = SYMODE_E_BADSIZE) ----
+inline bool stlsq_bad_library(int d, int p) { return d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P; }
+// problem s reads set s % n_sets; ``grid``: more problems than sets are allowed (the sweeps: only behind a hyper table)
+inline bool stlsq_bad_problems(long n_sets, long n_problems, bool grid) {
+    return n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L || (!grid && n_problems != n_sets);
+}
+inline bool stlsq_bad_val_sets(long n_val_sets, long n_problems) { return n_val_sets < 1 || n_val_sets > n_problems; }
+// r' = r + (d if allow_constant): beta and, where the model reads it, const
+inline bool stlsq_bad_free(int d, int p, int r, int allow_constant) {
+    const long rr = (long)r + (allow_constant ? d : 0);
+    return r < 1 || rr > STLSQC_MAX_R || rr > (long)d * p;
+}
+inline bool all_finite_nonneg(std::initializer_list<double> values) {
+    for (const double v : values)
+        if (!(v >= 0.0) || !std::isfinite(v)) return false;
+    return true;
+}
 
 // Gram passes are MFMA-bound, not latency-bound: a bounded number of workgroups per launch (default 1024 = 4 per CU:
 // one wave per SIMD cannot cover the LDS round trip between MFMAs; SYMODE_GRAM_GRID for tuning runs) keeps the
@@ -604,13 +625,9 @@ int symode_stlsq_sweep(const double* aug_gram, long n_sets, long n_problems, int
                        double gamma, double threshold, int max_iter, double near_band, float* xi_out, unsigned char* mask_out,
                        int* passes_out, int* near_out, int* fell_out, void* stream) {
     (void)n_points;                     // the rows behind a matrix: gelsy's rank rule reads them, the full-rank driver does not
-    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || max_iter < 1) return SYMODE_E_BADSIZE;
-    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
-    if (!hyper && n_problems != n_sets) return SYMODE_E_BADSIZE;
-    if (!aug_gram || !xi_out || !mask_out || !passes_out || !near_out || !fell_out) return SYMODE_E_NULLPTR;
-    if (misaligned(aug_gram, 8) || misaligned(hyper, 4) || misaligned(xi_out, 4) || misaligned(passes_out, 4) ||
-        misaligned(near_out, 4) || misaligned(fell_out, 4))
-        return SYMODE_E_ALIGN;
+    if (stlsq_bad_library(d, p) || max_iter < 1 || stlsq_bad_problems(n_sets, n_problems, hyper != nullptr)) return SYMODE_E_BADSIZE;
+    if (any_null(aug_gram, xi_out, mask_out, passes_out, near_out, fell_out)) return SYMODE_E_NULLPTR;
+    if (any_misaligned(8, aug_gram) || any_misaligned(4, hyper, xi_out, passes_out, near_out, fell_out)) return SYMODE_E_ALIGN;
     return (int)launch_stlsq_sweep(aug_gram, n_sets, n_problems, d, p, hyper, gamma, threshold, max_iter, near_band, xi_out,
                                    mask_out, passes_out, near_out, fell_out, (hipStream_t)stream);
 }
@@ -620,17 +637,12 @@ int symode_stlsq_path(const double* aug_gram, const double* val_gram, long n_set
                       double* rss_train, double* rss_val, int* best, float* xi_out, unsigned char* mask_out, int* near_out,
                       int* fell_out, void* stream) {
     (void)n_points;                     // as symode_stlsq_sweep: only gelsy's rank rule would read it
-    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P) return SYMODE_E_BADSIZE;
-    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
-    if (n_val_sets < 1 || n_val_sets > n_problems) return SYMODE_E_BADSIZE;
-    for (double v : {gamma, tol, floor_rel, near_band})
-        if (!(v >= 0.0) || !std::isfinite(v)) return SYMODE_E_BADSIZE;
-    if (!aug_gram || !val_gram || !path_xi || !order || !rss_train || !rss_val || !best || !xi_out || !mask_out || !near_out ||
-        !fell_out)
+    if (stlsq_bad_library(d, p) || stlsq_bad_problems(n_sets, n_problems, true) || stlsq_bad_val_sets(n_val_sets, n_problems))
+        return SYMODE_E_BADSIZE;
+    if (!all_finite_nonneg({gamma, tol, floor_rel, near_band})) return SYMODE_E_BADSIZE;
+    if (any_null(aug_gram, val_gram, path_xi, order, rss_train, rss_val, best, xi_out, mask_out, near_out, fell_out))
         return SYMODE_E_NULLPTR;
-    if (misaligned(aug_gram, 8) || misaligned(val_gram, 8) || misaligned(rss_train, 8) || misaligned(rss_val, 8) ||
-        misaligned(path_xi, 4) || misaligned(order, 4) || misaligned(best, 4) || misaligned(xi_out, 4) || misaligned(near_out, 4) ||
-        misaligned(fell_out, 4))
+    if (any_misaligned(8, aug_gram, val_gram, rss_train, rss_val) || any_misaligned(4, path_xi, order, best, xi_out, near_out, fell_out))
         return SYMODE_E_ALIGN;
     return (int)launch_stlsq_path(aug_gram, val_gram, n_sets, n_val_sets, n_problems, d, p, gamma, tol, floor_rel, near_band, path_xi,
                                   order, rss_train, rss_val, best, xi_out, mask_out, near_out, fell_out, (hipStream_t)stream);
@@ -642,16 +654,10 @@ int symode_stlsq_sweep_constrained(const double* aug_gram, long n_sets, long n_p
                                    float* var_out, unsigned char* mask_out, int* passes_out, int* near_out, int* fell_out,
                                    void* stream) {
     (void)n_points;                     // as symode_stlsq_sweep: only gelsy's rank rule would read it
-    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || r < 1 || max_iter < 1) return SYMODE_E_BADSIZE;
-    const long rr = (long)r + (allow_constant ? d : 0);                       // r': beta and, where the model reads it, const
-    if (rr > STLSQC_MAX_R || rr > (long)d * p) return SYMODE_E_BADSIZE;
-    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
-    if (!hyper && n_problems != n_sets) return SYMODE_E_BADSIZE;
-    if (!(pivot_floor >= 0.0) || !std::isfinite(pivot_floor)) return SYMODE_E_BADSIZE;
-    if (!aug_gram || !q_solve || !q_xi || !xi_out || !var_out || !mask_out || !passes_out || !near_out || !fell_out)
-        return SYMODE_E_NULLPTR;
-    if (misaligned(aug_gram, 8) || misaligned(q_solve, 8) || misaligned(q_xi, 4) || misaligned(hyper, 4) || misaligned(xi_out, 4) ||
-        misaligned(var_out, 4) || misaligned(passes_out, 4) || misaligned(near_out, 4) || misaligned(fell_out, 4))
+    if (stlsq_bad_library(d, p) || max_iter < 1 || stlsq_bad_free(d, p, r, allow_constant)) return SYMODE_E_BADSIZE;
+    if (stlsq_bad_problems(n_sets, n_problems, hyper != nullptr) || !all_finite_nonneg({pivot_floor})) return SYMODE_E_BADSIZE;
+    if (any_null(aug_gram, q_solve, q_xi, xi_out, var_out, mask_out, passes_out, near_out, fell_out)) return SYMODE_E_NULLPTR;
+    if (any_misaligned(8, aug_gram, q_solve) || any_misaligned(4, q_xi, hyper, xi_out, var_out, passes_out, near_out, fell_out))
         return SYMODE_E_ALIGN;
     return (int)launch_stlsq_constrained(aug_gram, n_sets, n_problems, d, p, q_solve, q_xi, r, allow_constant ? 1 : 0, hyper, gamma,
                                          threshold, max_iter, near_band, pivot_floor, xi_out, var_out, mask_out, passes_out,
@@ -664,18 +670,13 @@ int symode_stlsq_sweep_minnorm(const double* aug_gram, long n_sets, long n_probl
                                unsigned char* mask_out, int* passes_out, int* near_out, int* fell_out, int* trunc_out, int* rank_out,
                                void* stream) {
     (void)n_points;                     // as symode_stlsq_sweep: only gelsy's DEFAULT rank rule would read it
-    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || r < 1 || max_iter < 1) return SYMODE_E_BADSIZE;
-    const long rr = (long)r + (allow_constant ? d : 0);
-    if (rr > STLSQC_MAX_R || rr > (long)d * p) return SYMODE_E_BADSIZE;
-    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
-    if (!hyper && n_problems != n_sets) return SYMODE_E_BADSIZE;
+    if (stlsq_bad_library(d, p) || max_iter < 1 || stlsq_bad_free(d, p, r, allow_constant)) return SYMODE_E_BADSIZE;
+    if (stlsq_bad_problems(n_sets, n_problems, hyper != nullptr)) return SYMODE_E_BADSIZE;
     if (!std::isfinite(rcond) || !(rcond > 0.0) || !(rcond < 1.0)) return SYMODE_E_BADSIZE;
-    if (!aug_gram || !q_solve || !q_xi || !xi_out || !var_out || !mask_out || !passes_out || !near_out || !fell_out || !trunc_out ||
-        !rank_out)
+    if (any_null(aug_gram, q_solve, q_xi, xi_out, var_out, mask_out, passes_out, near_out, fell_out, trunc_out, rank_out))
         return SYMODE_E_NULLPTR;
-    if (misaligned(aug_gram, 8) || misaligned(q_solve, 8) || misaligned(q_xi, 4) || misaligned(hyper, 4) || misaligned(xi_out, 4) ||
-        misaligned(var_out, 4) || misaligned(passes_out, 4) || misaligned(near_out, 4) || misaligned(fell_out, 4) ||
-        misaligned(trunc_out, 4) || misaligned(rank_out, 4))
+    if (any_misaligned(8, aug_gram, q_solve) ||
+        any_misaligned(4, q_xi, hyper, xi_out, var_out, passes_out, near_out, fell_out, trunc_out, rank_out))
         return SYMODE_E_ALIGN;
     return (int)launch_stlsq_minnorm(aug_gram, n_sets, n_problems, d, p, q_solve, q_xi, r, allow_constant ? 1 : 0, hyper, gamma,
                                      threshold, max_iter, near_band, rcond, xi_out, var_out, mask_out, passes_out, near_out, fell_out,
@@ -687,16 +688,12 @@ int symode_stlsq_sweep_symreg(const double* aug_gram, const double* rev_gram, lo
                               double near_band, double pivot_floor, float* xi_out, unsigned char* mask_out, int* passes_out,
                               int* near_out, int* fell_out, void* stream) {
     (void)n_points;                     // as symode_stlsq_sweep: only gelsy's rank rule would read it
-    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || (long)d * p > STLSQS_MAX_DP || max_iter < 1) return SYMODE_E_BADSIZE;
-    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
-    if (!hyper && n_problems != n_sets) return SYMODE_E_BADSIZE;
-    const double values[4] = {(double)(float)gamma, (double)(float)threshold, (double)(float)w_sym, pivot_floor};   // as the launch holds them
-    for (const double v : values)
-        if (!(v >= 0.0) || !std::isfinite(v)) return SYMODE_E_BADSIZE;
-    if (!aug_gram || !rev_gram || !xi_out || !mask_out || !passes_out || !near_out || !fell_out) return SYMODE_E_NULLPTR;
-    if (misaligned(aug_gram, 8) || misaligned(rev_gram, 8) || misaligned(hyper, 4) || misaligned(xi_out, 4) ||
-        misaligned(passes_out, 4) || misaligned(near_out, 4) || misaligned(fell_out, 4))
-        return SYMODE_E_ALIGN;
+    if (stlsq_bad_library(d, p) || (long)d * p > STLSQS_MAX_DP || max_iter < 1) return SYMODE_E_BADSIZE;
+    if (stlsq_bad_problems(n_sets, n_problems, hyper != nullptr)) return SYMODE_E_BADSIZE;
+    // gamma, threshold and w_sym as the launch holds them
+    if (!all_finite_nonneg({(double)(float)gamma, (double)(float)threshold, (double)(float)w_sym, pivot_floor})) return SYMODE_E_BADSIZE;
+    if (any_null(aug_gram, rev_gram, xi_out, mask_out, passes_out, near_out, fell_out)) return SYMODE_E_NULLPTR;
+    if (any_misaligned(8, aug_gram, rev_gram) || any_misaligned(4, hyper, xi_out, passes_out, near_out, fell_out)) return SYMODE_E_ALIGN;
     // the three values in fp32, as a row of the table holds them
     return (int)launch_stlsq_symreg(aug_gram, rev_gram, n_sets, n_problems, d, p, hyper, (float)gamma, (float)threshold, (float)w_sym,
                                     max_iter, near_band, pivot_floor, xi_out, mask_out, passes_out, near_out, fell_out,
@@ -709,18 +706,14 @@ int symode_stlsq_path_symreg(const double* aug_gram, const double* rev_gram, con
                              double* reg_train, double* mse_val, int* best, float* xi_out, unsigned char* mask_out, int* near_out,
                              int* fell_out, void* stream) {
     (void)n_points;                     // as symode_stlsq_sweep: only gelsy's rank rule would read it
-    if (d < 1 || d > STLSQ_MAX_D || p < 1 || p > STLSQ_MAX_P || (long)d * p > STLSQS_MAX_DP) return SYMODE_E_BADSIZE;
-    if (n_sets < 1 || n_problems < n_sets || n_problems > 2147483647L) return SYMODE_E_BADSIZE;
-    if (n_val_sets < 1 || n_val_sets > n_problems) return SYMODE_E_BADSIZE;
-    const double values[6] = {(double)(float)gamma, (double)(float)w_sym, tol, floor_rel, near_band, pivot_floor};   // as the launch holds them
-    for (const double v : values)
-        if (!(v >= 0.0) || !std::isfinite(v)) return SYMODE_E_BADSIZE;
-    if (!aug_gram || !rev_gram || !val_gram || !path_xi || !order || !mse_train || !reg_train || !mse_val || !best || !xi_out ||
-        !mask_out || !near_out || !fell_out)
+    if (stlsq_bad_library(d, p) || (long)d * p > STLSQS_MAX_DP) return SYMODE_E_BADSIZE;
+    if (stlsq_bad_problems(n_sets, n_problems, true) || stlsq_bad_val_sets(n_val_sets, n_problems)) return SYMODE_E_BADSIZE;
+    // gamma and w_sym as the launch holds them
+    if (!all_finite_nonneg({(double)(float)gamma, (double)(float)w_sym, tol, floor_rel, near_band, pivot_floor})) return SYMODE_E_BADSIZE;
+    if (any_null(aug_gram, rev_gram, val_gram, path_xi, order, mse_train, reg_train, mse_val, best, xi_out, mask_out, near_out, fell_out))
         return SYMODE_E_NULLPTR;
-    if (misaligned(aug_gram, 8) || misaligned(rev_gram, 8) || misaligned(val_gram, 8) || misaligned(mse_train, 8) ||
-        misaligned(reg_train, 8) || misaligned(mse_val, 8) || misaligned(hyper, 4) || misaligned(path_xi, 4) || misaligned(order, 4) ||
-        misaligned(best, 4) || misaligned(xi_out, 4) || misaligned(near_out, 4) || misaligned(fell_out, 4))
+    if (any_misaligned(8, aug_gram, rev_gram, val_gram, mse_train, reg_train, mse_val) ||
+        any_misaligned(4, hyper, path_xi, order, best, xi_out, near_out, fell_out))
         return SYMODE_E_ALIGN;
     // the two values in fp32, as a row of the table holds them
     return (int)launch_stlsq_path_symreg(aug_gram, rev_gram, val_gram, n_sets, n_val_sets, n_problems, d, p, hyper, (float)gamma,

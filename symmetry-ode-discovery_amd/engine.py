@@ -8,6 +8,7 @@ GPU or a CPU tensor raises.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import weakref
 from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_void_p
@@ -197,6 +198,65 @@ class TrainerGrid(ctypes.Structure):
 STLSQ_HYPER = 2                                             # columns of a symode_stlsq_sweep hyper row: gamma, threshold
 STLSQ_SYMREG_HYPER = 3                                      # ... of a symode_stlsq_sweep_symreg row: gamma, threshold, w_sym
 STLSQ_PATH_SYMREG_HYPER = 2                                 # ... of a symode_stlsq_path_symreg row: gamma, w_sym
+
+_PACKED = {"f8": (8, torch.float64, "<f8"), "f4": (4, torch.float32, "<f4"), "i4": (4, torch.int32, "<i4"), "u1": (1, torch.uint8, "u1")}
+
+
+def packed_layout(fields, S, n_tail=None):
+    """Where the small outputs of one STLSQ launch lie in the ONE uint8 buffer they share, so that a caller on the host fetches
+    all of them in one copy.  ``fields``: (name, "f8" | "f4" | "i4" | "u1", per-problem shape) in the order the caller wants them
+    back; each holds S problems.  The parts are placed by descending item size -- fp64, then fp32 and int32, bytes last -- so
+    every part starts at a multiple of its own item size; ``n_tail`` int32 (None: no tail) ride 4-aligned behind the last byte
+    field.  A plain function of sizes.  Returns (bytes, views): ``views(buf)`` gives {name: typed (S, *shape) view} in the
+    fields' order, "tail" last, of a torch uint8 tensor or of the numpy uint8 array one copy of it made."""
+    spans, at = {}, 0
+    for name, kind, shape in sorted(fields, key=lambda f: -_PACKED[f[1]][0]):
+        n = _PACKED[kind][0] * S
+        for extent in shape:
+            n *= extent
+        spans[name] = (at, at + n)
+        at += n
+    at = -(-at // 4) * 4                                                # the tail, int32-aligned behind the last byte field
+    end = at + 4 * (n_tail or 0)
+    # per part: its span, its type (None: the buffer's own bytes) and its shape (None: the flat (S,) the span already is)
+    plan = [(name,) + spans[name] + (None if kind == "u1" else _PACKED[kind], (S,) + tuple(shape) if shape else None)
+            for name, kind, shape in fields]
+    if n_tail is not None:
+        plan.append(("tail", at, end, _PACKED["i4"], None))
+
+    def views(buf):
+        which = 1 if isinstance(buf, torch.Tensor) else 2
+        out = {}
+        for name, lo, hi, kind, shape in plan:
+            part = buf[lo:hi] if kind is None else buf[lo:hi].view(kind[which])
+            out[name] = part if shape is None else part.reshape(shape)
+        return out
+
+    return end, views
+
+
+def stlsq_fields(entry, d, p, r1=0):
+    """The small outputs of the launch ``entry`` as ``packed_layout`` takes them, in the order its wrapper returns them; ``r1`` =
+    r' of the constrained fits, n0 = d p the joint support of the regularised path."""
+    n0 = d * p
+    sweep = [("xi", "f4", (d, p)), ("mask", "u1", (d, p)), ("passes", "i4", ()), ("near", "i4", ()), ("fell", "i4", ())]
+    return {
+        "symode_stlsq_sweep": sweep,
+        "symode_stlsq_sweep_symreg": sweep,
+        "symode_stlsq_sweep_constrained": sweep + [("var", "f4", (r1,))],
+        "symode_stlsq_sweep_minnorm": sweep + [("var", "f4", (r1,)), ("trunc", "i4", ()), ("rank", "i4", ())],
+        "symode_stlsq_path": [("Xi", "f4", (d, p)), ("mask", "u1", (d, p)), ("order", "i4", (d, p)), ("rss_train", "f8", (d, p + 1)),
+                              ("rss_val", "f8", (d, p + 1)), ("best", "i4", (d,)), ("near", "i4", ()), ("fell", "i4", ())],
+        "symode_stlsq_path_symreg": [("Xi", "f4", (d, p)), ("mask", "u1", (d, p)), ("order", "i4", (n0,)), ("mse_train", "f8", (n0 + 1,)),
+                                     ("reg_train", "f8", (n0 + 1,)), ("mse_val", "f8", (n0 + 1,)), ("best", "i4", ()),
+                                     ("near", "i4", ()), ("fell", "i4", ())],
+    }[entry]
+
+
+@functools.lru_cache(maxsize=4096)
+def _stlsq_layout(entry, S, d, p, r1, n_tail):
+    """``packed_layout`` of a launch's ``stlsq_fields``: a function of six sizes, worked out once per shape"""
+    return packed_layout(stlsq_fields(entry, d, p, r1), S, n_tail)
 
 ADAM_PLAIN, ADAM_REVERSED, ADAM_LATENT = 0, 1, 2              # SYMODE_ADAM_* of include/symode.h
 ADAM_HYPER = 4                                              # columns of a hyper row: lr, w_reg, threshold, w_sym
@@ -388,6 +448,58 @@ class HipEngine:
     @staticmethod
     def _stream(t: torch.Tensor):
         return c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    # -- the operands of the symode_stlsq_* launches, each rule stated once (the tensors have been through _dev) --
+    @staticmethod
+    def _stlsq_G(G, d):
+        """(n_sets, p) of the augmented Gram matrices"""
+        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
+            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
+        return G.shape[0], G.shape[1] - d
+
+    @staticmethod
+    def _stlsq_V(V, G):
+        if V.dim() != 3 or V.shape[1:] != G.shape[1:] or V.device != G.device:
+            raise SymodeError(f"V must be (n_val_sets, p + d, p + d) = (n_val_sets, {G.shape[1]}, {G.shape[2]}) on {G.device}, "
+                              f"got {tuple(V.shape)} on {V.device}")
+
+    @staticmethod
+    def _stlsq_R(R, G, n_sets, n0):
+        if tuple(R.shape) != (n_sets, n0, n0) or R.device != G.device:
+            raise SymodeError(f"R must be (n_sets, d p, d p) = ({n_sets}, {n0}, {n0}) fp64 on {G.device}, got {tuple(R.shape)}")
+
+    def _stlsq_Q(self, q_solve, q_xi, allow_constant, G, d, p):
+        """(q_solve, q_xi, r, r') of the constrained fits"""
+        q_solve, q_xi = self._dev(q_solve, "q_solve", torch.float64), self._dev(q_xi, "q_xi")
+        if q_xi.dim() != 2 or q_xi.shape[0] != d * p or q_xi.device != G.device:
+            raise SymodeError(f"q_xi must be (d p, r) = ({d * p}, r) fp32 on {G.device}, got {tuple(q_xi.shape)}")
+        r = q_xi.shape[1]
+        R = r + (d if allow_constant else 0)
+        if tuple(q_solve.shape) != (d * p, R) or q_solve.device != G.device:
+            raise SymodeError(f"q_solve must be (d p, r') = ({d * p}, {R}) fp64 on {G.device}, got {tuple(q_solve.shape)}")
+        return q_solve, q_xi, r, R
+
+    def _stlsq_hyper(self, hyper, n_problems, G, columns, row):
+        """(hyper, S): the per-problem table of ``columns`` values (``row`` names them) and the number of problems, which
+        defaults to the table's rows, or to G's sets without a table"""
+        if hyper is not None:
+            hyper = self._dev(hyper, "hyper")
+            if hyper.dim() != 2 or hyper.shape[1] != columns or hyper.device != G.device:
+                raise SymodeError(f"hyper must be (n_problems, {columns}) fp32 on {G.device}: one row [{row}] per problem")
+            if n_problems is not None and int(n_problems) != hyper.shape[0]:
+                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
+            n_problems = hyper.shape[0]
+        return hyper, G.shape[0] if n_problems is None else int(n_problems)
+
+    def _stlsq_outputs(self, G, entry, S, d, p, r1=0, tail=None):
+        """The outputs of the launch ``entry`` in one allocation (``packed_layout``), the tail copied in: ({name: device view},
+        fetch) with ``fetch(to_host)`` -> the same views, or numpy views of ONE copy of the buffer."""
+        n_bytes, views = _stlsq_layout(entry, S, d, p, r1, None if tail is None else tail.numel())
+        buf = torch.empty(max(n_bytes, 0), dtype=torch.uint8, device=G.device)
+        out = views(buf)
+        if tail is not None:
+            out["tail"].copy_(self._dev(tail, "tail", torch.int32).reshape(-1))
+        return out, lambda to_host: views(buf.cpu().numpy()) if to_host else out
 
     def lib_size(self, d: int, order: int, flags: int) -> int:
         p = self.lib.symode_lib_size(d, order, flags)
@@ -1271,39 +1383,14 @@ class HipEngine:
         fetches them in the same copy."""
         G = self._dev(G, "G", torch.float64)
         d = int(d)
-        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
-            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
-        n_sets, p = G.shape[0], G.shape[1] - d
-        if hyper is not None:
-            hyper = self._dev(hyper, "hyper")
-            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_HYPER or hyper.device != G.device:
-                raise SymodeError(f"hyper must be (n_problems, {STLSQ_HYPER}) fp32 on {G.device}: one row [gamma, threshold] per problem")
-            if n_problems is not None and int(n_problems) != hyper.shape[0]:
-                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
-            n_problems = hyper.shape[0]
-        S = n_sets if n_problems is None else int(n_problems)
-        # one allocation, [xi | passes | near | fell | mask], so that a caller on the host fetches everything in ONE copy
-        cuts = [0, 4 * S * d * p, 4 * S * (d * p + 1), 4 * S * (d * p + 2), 4 * S * (d * p + 3), 4 * S * (d * p + 3) + S * d * p]
-        at = -(-cuts[-1] // 4) * 4                                      # the tail, int32-aligned behind the mask
-        n_tail = 0 if tail is None else 4 * tail.numel()
-        buf = torch.empty(max(at + n_tail, 0), dtype=torch.uint8, device=G.device)
-
-        def parts(b, f32, i32):
-            xi, passes, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
-            five = xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32)
-            return five if tail is None else five + (b[at:at + n_tail].view(i32),)
-
-        xi, mask, passes, near, fell = parts(buf, torch.float32, torch.int32)[:5]
-        if tail is not None:
-            buf[at:at + n_tail].view(torch.int32).copy_(self._dev(tail, "tail", torch.int32).reshape(-1))
+        n_sets, p = self._stlsq_G(G, d)
+        hyper, S = self._stlsq_hyper(hyper, n_problems, G, STLSQ_HYPER, "gamma, threshold")
+        o, fetch = self._stlsq_outputs(G, "symode_stlsq_sweep", S, d, p, tail=tail)
         self._check(self.lib.symode_stlsq_sweep(self._ptr(G), n_sets, S, d, p, int(n_points), self._ptr(hyper), float(gamma),
-                                                float(threshold), int(max_iter), float(near_band), self._ptr(xi), self._ptr(mask),
-                                                self._ptr(passes), self._ptr(near), self._ptr(fell), self._stream(G)),
+                                                float(threshold), int(max_iter), float(near_band),
+                                                *(o[k].data_ptr() for k in ("xi", "mask", "passes", "near", "fell")), self._stream(G)),
                     "symode_stlsq_sweep")
-        if to_host:
-            import numpy as np
-            return parts(buf.cpu().numpy(), np.float32, np.int32)
-        return parts(buf, torch.float32, torch.int32)
+        return tuple(fetch(to_host).values())
 
     def stlsq_path(self, G, V, n_points, gamma, tol, floor_rel, n_problems=None, *, d, near_band=1e-4, to_host=False,
                    keep_path=False):
@@ -1320,40 +1407,25 @@ class HipEngine:
         G = self._dev(G, "G", torch.float64)
         V = self._dev(V, "V", torch.float64)
         d = int(d)
-        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
-            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
-        if V.dim() != 3 or V.shape[1:] != G.shape[1:] or V.device != G.device:
-            raise SymodeError(f"V must be (n_val_sets, p + d, p + d) = (n_val_sets, {G.shape[1]}, {G.shape[2]}) on {G.device}, "
-                              f"got {tuple(V.shape)} on {V.device}")
-        n_sets, p = G.shape[0], G.shape[1] - d
+        n_sets, p = self._stlsq_G(G, d)
+        self._stlsq_V(V, G)
         S = n_sets if n_problems is None else int(n_problems)
-        sizes = [8 * S * d * (p + 1), 8 * S * d * (p + 1), 4 * S * d * p, 4 * S * d * p, 4 * S * d, 4 * S, 4 * S, S * d * p]
-        cuts = [0]
-        for n in sizes:
-            cuts.append(cuts[-1] + n)
-        buf = torch.empty(max(cuts[-1], 0), dtype=torch.uint8, device=G.device)    # fp64 first, bytes last: every part aligned
+        o, fetch = self._stlsq_outputs(G, "symode_stlsq_path", S, d, p)
         path = torch.empty(max(S, 0), d, p + 1, p, dtype=torch.float32, device=G.device)
-
-        def parts(b, f64, f32, i32):
-            tr, va, xi, order, best, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
-            return dict(Xi=xi.view(f32).reshape(S, d, p), mask=mask.reshape(S, d, p), order=order.view(i32).reshape(S, d, p),
-                        rss_train=tr.view(f64).reshape(S, d, p + 1), rss_val=va.view(f64).reshape(S, d, p + 1),
-                        best=best.view(i32).reshape(S, d), near=near.view(i32), fell=fell.view(i32))
-
-        o = parts(buf, torch.float64, torch.float32, torch.int32)
         self._check(self.lib.symode_stlsq_path(self._ptr(G), self._ptr(V), n_sets, V.shape[0], S, d, p, int(n_points), float(gamma),
-                                               float(tol), float(floor_rel), float(near_band), self._ptr(path), self._ptr(o["order"]),
-                                               self._ptr(o["rss_train"]), self._ptr(o["rss_val"]), self._ptr(o["best"]),
-                                               self._ptr(o["Xi"]), self._ptr(o["mask"]), self._ptr(o["near"]), self._ptr(o["fell"]),
-                                               self._stream(G)),
+                                               float(tol), float(floor_rel), float(near_band), self._ptr(path),
+                                               *(o[k].data_ptr() for k in ("order", "rss_train", "rss_val", "best", "Xi", "mask", "near",
+                                                                           "fell")), self._stream(G)),
                     "symode_stlsq_path")
-        if to_host:
-            import numpy as np
-            o = parts(buf.cpu().numpy(), np.float64, np.float32, np.int32)
-            if keep_path:
-                o["path_xi"] = path.cpu().numpy()
-            return o
-        o["path_xi"] = path
+        return self._with_path(fetch(to_host), path, to_host, keep_path)
+
+    @staticmethod
+    def _with_path(o, path, to_host, keep_path):
+        """path_xi, the one large output of a path launch, beside the small ones: on the host it is fetched only when kept"""
+        if not to_host:
+            o = dict(o, path_xi=path)
+        elif keep_path:
+            o["path_xi"] = path.cpu().numpy()
         return o
 
     def stlsq_sweep_constrained(self, G, n_points, gamma, threshold, max_iter, q_solve, q_xi, allow_constant, hyper=None,
@@ -1366,53 +1438,24 @@ class HipEngine:
         Returns (Xi (n_problems, d, p) fp32 -- of the last solve, unmasked --, mask uint8, passes, near, fell int32, var
         (n_problems, r') fp32 = [beta | const]) and, behind them, the tail; a problem with ``fell`` set is possibly rank
         deficient and the host's to solve."""
+        return self._stlsq_sweep_q("symode_stlsq_sweep_constrained", pivot_floor, (), G, n_points, gamma, threshold, max_iter, q_solve,
+                                   q_xi, allow_constant, hyper, n_problems, d, near_band, to_host, tail)
+
+    def _stlsq_sweep_q(self, entry, floor, more, G, n_points, gamma, threshold, max_iter, q_solve, q_xi, allow_constant, hyper, n_problems,
+                       d, near_band, to_host, tail):
+        """The constrained launch and its rank-revealing mode: they differ by the entry, by what ``floor`` means (pivot_floor,
+        rcond) and by the int32 outputs ``more`` behind var."""
         G = self._dev(G, "G", torch.float64)
         d = int(d)
-        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
-            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
-        n_sets, p = G.shape[0], G.shape[1] - d
-        q_solve, q_xi = self._dev(q_solve, "q_solve", torch.float64), self._dev(q_xi, "q_xi")
-        if q_xi.dim() != 2 or q_xi.shape[0] != d * p or q_xi.device != G.device:
-            raise SymodeError(f"q_xi must be (d p, r) = ({d * p}, r) fp32 on {G.device}, got {tuple(q_xi.shape)}")
-        r = q_xi.shape[1]
-        R = r + (d if allow_constant else 0)
-        if tuple(q_solve.shape) != (d * p, R) or q_solve.device != G.device:
-            raise SymodeError(f"q_solve must be (d p, r') = ({d * p}, {R}) fp64 on {G.device}, got {tuple(q_solve.shape)}")
-        if hyper is not None:
-            hyper = self._dev(hyper, "hyper")
-            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_HYPER or hyper.device != G.device:
-                raise SymodeError(f"hyper must be (n_problems, {STLSQ_HYPER}) fp32 on {G.device}: one row [gamma, threshold] per problem")
-            if n_problems is not None and int(n_problems) != hyper.shape[0]:
-                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
-            n_problems = hyper.shape[0]
-        S = n_sets if n_problems is None else int(n_problems)
-        # one allocation, [xi | var | passes | near | fell | mask]: a caller on the host fetches everything in ONE copy
-        cuts = [0, 4 * S * d * p]
-        for width in (R, 1, 1, 1):
-            cuts.append(cuts[-1] + 4 * S * width)
-        cuts.append(cuts[-1] + S * d * p)
-        at = -(-cuts[-1] // 4) * 4                                      # the tail, int32-aligned behind the mask
-        n_tail = 0 if tail is None else 4 * tail.numel()
-        buf = torch.empty(max(at + n_tail, 0), dtype=torch.uint8, device=G.device)
-
-        def parts(b, f32, i32):
-            xi, var, passes, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
-            six = (xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32),
-                   var.view(f32).reshape(S, R))
-            return six if tail is None else six + (b[at:at + n_tail].view(i32),)
-
-        xi, mask, passes, near, fell, var = parts(buf, torch.float32, torch.int32)[:6]
-        if tail is not None:
-            buf[at:at + n_tail].view(torch.int32).copy_(self._dev(tail, "tail", torch.int32).reshape(-1))
-        self._check(self.lib.symode_stlsq_sweep_constrained(
+        n_sets, p = self._stlsq_G(G, d)
+        q_solve, q_xi, r, R = self._stlsq_Q(q_solve, q_xi, allow_constant, G, d, p)
+        hyper, S = self._stlsq_hyper(hyper, n_problems, G, STLSQ_HYPER, "gamma, threshold")
+        o, fetch = self._stlsq_outputs(G, entry, S, d, p, R, tail)
+        self._check(getattr(self.lib, entry)(
             self._ptr(G), n_sets, S, d, p, int(n_points), self._ptr(q_solve), self._ptr(q_xi), r, 1 if allow_constant else 0,
-            self._ptr(hyper), float(gamma), float(threshold), int(max_iter), float(near_band), float(pivot_floor), self._ptr(xi),
-            self._ptr(var), self._ptr(mask), self._ptr(passes), self._ptr(near), self._ptr(fell), self._stream(G)),
-            "symode_stlsq_sweep_constrained")
-        if to_host:
-            import numpy as np
-            return parts(buf.cpu().numpy(), np.float32, np.int32)
-        return parts(buf, torch.float32, torch.int32)
+            self._ptr(hyper), float(gamma), float(threshold), int(max_iter), float(near_band), float(floor),
+            *(o[k].data_ptr() for k in ("xi", "var", "mask", "passes", "near", "fell") + more), self._stream(G)), entry)
+        return tuple(fetch(to_host).values())
 
     def stlsq_sweep_minnorm(self, G, n_points, gamma, threshold, max_iter, q_solve, q_xi, allow_constant, hyper=None,
                             n_problems=None, *, d, rcond, near_band=1e-4, to_host=False, tail=None):
@@ -1424,54 +1467,8 @@ class HipEngine:
         Returns (Xi, mask, passes, near, fell, var, trunc, rank) and, behind them, the tail: ``trunc`` (n_problems,) int32 the
         passes solved with rank < n, ``rank`` the rank of the last pass's system; ``fell`` is set only where the factor of
         Wm Wm^T met a diagonal that is not positive (the host's to solve)."""
-        G = self._dev(G, "G", torch.float64)
-        d = int(d)
-        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
-            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
-        n_sets, p = G.shape[0], G.shape[1] - d
-        q_solve, q_xi = self._dev(q_solve, "q_solve", torch.float64), self._dev(q_xi, "q_xi")
-        if q_xi.dim() != 2 or q_xi.shape[0] != d * p or q_xi.device != G.device:
-            raise SymodeError(f"q_xi must be (d p, r) = ({d * p}, r) fp32 on {G.device}, got {tuple(q_xi.shape)}")
-        r = q_xi.shape[1]
-        R = r + (d if allow_constant else 0)
-        if tuple(q_solve.shape) != (d * p, R) or q_solve.device != G.device:
-            raise SymodeError(f"q_solve must be (d p, r') = ({d * p}, {R}) fp64 on {G.device}, got {tuple(q_solve.shape)}")
-        if hyper is not None:
-            hyper = self._dev(hyper, "hyper")
-            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_HYPER or hyper.device != G.device:
-                raise SymodeError(f"hyper must be (n_problems, {STLSQ_HYPER}) fp32 on {G.device}: one row [gamma, threshold] per problem")
-            if n_problems is not None and int(n_problems) != hyper.shape[0]:
-                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
-            n_problems = hyper.shape[0]
-        S = n_sets if n_problems is None else int(n_problems)
-        # one allocation, [xi | var | passes | near | fell | trunc | rank | mask]: a caller on the host fetches everything in ONE copy
-        cuts = [0, 4 * S * d * p]
-        for width in (R, 1, 1, 1, 1, 1):
-            cuts.append(cuts[-1] + 4 * S * width)
-        cuts.append(cuts[-1] + S * d * p)
-        at = -(-cuts[-1] // 4) * 4                                      # the tail, int32-aligned behind the mask
-        n_tail = 0 if tail is None else 4 * tail.numel()
-        buf = torch.empty(max(at + n_tail, 0), dtype=torch.uint8, device=G.device)
-
-        def parts(b, f32, i32):
-            xi, var, passes, near, fell, trunc, rank, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
-            eight = (xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32),
-                     var.view(f32).reshape(S, R), trunc.view(i32), rank.view(i32))
-            return eight if tail is None else eight + (b[at:at + n_tail].view(i32),)
-
-        xi, mask, passes, near, fell, var, trunc, rank = parts(buf, torch.float32, torch.int32)[:8]
-        if tail is not None:
-            buf[at:at + n_tail].view(torch.int32).copy_(self._dev(tail, "tail", torch.int32).reshape(-1))
-        self._check(self.lib.symode_stlsq_sweep_minnorm(
-            self._ptr(G), n_sets, S, d, p, int(n_points), self._ptr(q_solve), self._ptr(q_xi), r, 1 if allow_constant else 0,
-            self._ptr(hyper), float(gamma), float(threshold), int(max_iter), float(near_band), float(rcond), self._ptr(xi),
-            self._ptr(var), self._ptr(mask), self._ptr(passes), self._ptr(near), self._ptr(fell), self._ptr(trunc), self._ptr(rank),
-            self._stream(G)),
-            "symode_stlsq_sweep_minnorm")
-        if to_host:
-            import numpy as np
-            return parts(buf.cpu().numpy(), np.float32, np.int32)
-        return parts(buf, torch.float32, torch.int32)
+        return self._stlsq_sweep_q("symode_stlsq_sweep_minnorm", rcond, ("trunc", "rank"), G, n_points, gamma, threshold, max_iter,
+                                   q_solve, q_xi, allow_constant, hyper, n_problems, d, near_band, to_host, tail)
 
     def stlsq_sweep_symreg(self, G, R, n_points, gamma, threshold, w_sym, max_iter, hyper=None, n_problems=None, *, d, pivot_floor,
                            near_band=1e-4, to_host=False, tail=None):
@@ -1485,44 +1482,17 @@ class HipEngine:
         and, behind them, the tail; a problem with ``fell`` set is possibly rank deficient and the host's to solve."""
         G = self._dev(G, "G", torch.float64)
         d = int(d)
-        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
-            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
-        n_sets, p = G.shape[0], G.shape[1] - d
+        n_sets, p = self._stlsq_G(G, d)
         R = self._dev(R, "R", torch.float64)
-        if tuple(R.shape) != (n_sets, d * p, d * p) or R.device != G.device:
-            raise SymodeError(f"R must be (n_sets, d p, d p) = ({n_sets}, {d * p}, {d * p}) fp64 on {G.device}, got {tuple(R.shape)}")
-        if hyper is not None:
-            hyper = self._dev(hyper, "hyper")
-            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_SYMREG_HYPER or hyper.device != G.device:
-                raise SymodeError(f"hyper must be (n_problems, {STLSQ_SYMREG_HYPER}) fp32 on {G.device}: one row [gamma, threshold, "
-                                  f"w_sym] per problem")
-            if n_problems is not None and int(n_problems) != hyper.shape[0]:
-                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
-            n_problems = hyper.shape[0]
-        S = n_sets if n_problems is None else int(n_problems)
-        # one allocation, [xi | passes | near | fell | mask], so that a caller on the host fetches everything in ONE copy
-        cuts = [0, 4 * S * d * p, 4 * S * (d * p + 1), 4 * S * (d * p + 2), 4 * S * (d * p + 3), 4 * S * (d * p + 3) + S * d * p]
-        at = -(-cuts[-1] // 4) * 4                                      # the tail, int32-aligned behind the mask
-        n_tail = 0 if tail is None else 4 * tail.numel()
-        buf = torch.empty(max(at + n_tail, 0), dtype=torch.uint8, device=G.device)
-
-        def parts(b, f32, i32):
-            xi, passes, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
-            five = xi.view(f32).reshape(S, d, p), mask.reshape(S, d, p), passes.view(i32), near.view(i32), fell.view(i32)
-            return five if tail is None else five + (b[at:at + n_tail].view(i32),)
-
-        xi, mask, passes, near, fell = parts(buf, torch.float32, torch.int32)[:5]
-        if tail is not None:
-            buf[at:at + n_tail].view(torch.int32).copy_(self._dev(tail, "tail", torch.int32).reshape(-1))
+        self._stlsq_R(R, G, n_sets, d * p)
+        hyper, S = self._stlsq_hyper(hyper, n_problems, G, STLSQ_SYMREG_HYPER, "gamma, threshold, w_sym")
+        o, fetch = self._stlsq_outputs(G, "symode_stlsq_sweep_symreg", S, d, p, tail=tail)
         self._check(self.lib.symode_stlsq_sweep_symreg(
             self._ptr(G), self._ptr(R), n_sets, S, d, p, int(n_points), self._ptr(hyper), float(gamma), float(threshold), float(w_sym),
-            int(max_iter), float(near_band), float(pivot_floor), self._ptr(xi), self._ptr(mask), self._ptr(passes), self._ptr(near),
-            self._ptr(fell), self._stream(G)),
+            int(max_iter), float(near_band), float(pivot_floor), *(o[k].data_ptr() for k in ("xi", "mask", "passes", "near", "fell")),
+            self._stream(G)),
             "symode_stlsq_sweep_symreg")
-        if to_host:
-            import numpy as np
-            return parts(buf.cpu().numpy(), np.float32, np.int32)
-        return parts(buf, torch.float32, torch.int32)
+        return tuple(fetch(to_host).values())
 
     def stlsq_path_symreg(self, G, R, V, n_points, gamma, w_sym, tol, floor_rel, hyper=None, n_problems=None, *, d, pivot_floor,
                           near_band=1e-4, to_host=False, keep_path=False):
@@ -1540,52 +1510,20 @@ class HipEngine:
         V = self._dev(V, "V", torch.float64)
         R = self._dev(R, "R", torch.float64)
         d = int(d)
-        if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[1] <= d:
-            raise SymodeError(f"G must be (n_sets, p + d, p + d) with d = {d}, got {tuple(G.shape)}")
-        if V.dim() != 3 or V.shape[1:] != G.shape[1:] or V.device != G.device:
-            raise SymodeError(f"V must be (n_val_sets, p + d, p + d) = (n_val_sets, {G.shape[1]}, {G.shape[2]}) on {G.device}, "
-                              f"got {tuple(V.shape)} on {V.device}")
-        n_sets, p = G.shape[0], G.shape[1] - d
+        n_sets, p = self._stlsq_G(G, d)
+        self._stlsq_V(V, G)
         n0 = d * p
-        if tuple(R.shape) != (n_sets, n0, n0) or R.device != G.device:
-            raise SymodeError(f"R must be (n_sets, d p, d p) = ({n_sets}, {n0}, {n0}) fp64 on {G.device}, got {tuple(R.shape)}")
-        if hyper is not None:
-            hyper = self._dev(hyper, "hyper")
-            if hyper.dim() != 2 or hyper.shape[1] != STLSQ_PATH_SYMREG_HYPER or hyper.device != G.device:
-                raise SymodeError(f"hyper must be (n_problems, {STLSQ_PATH_SYMREG_HYPER}) fp32 on {G.device}: one row [gamma, w_sym] "
-                                  f"per problem")
-            if n_problems is not None and int(n_problems) != hyper.shape[0]:
-                raise SymodeError(f"hyper has {hyper.shape[0]} rows for {n_problems} problems")
-            n_problems = hyper.shape[0]
-        S = n_sets if n_problems is None else int(n_problems)
-        sizes = [8 * S * (n0 + 1)] * 3 + [4 * S * n0, 4 * S * n0, 4 * S, 4 * S, 4 * S, S * n0]
-        cuts = [0]
-        for n in sizes:
-            cuts.append(cuts[-1] + n)
-        buf = torch.empty(max(cuts[-1], 0), dtype=torch.uint8, device=G.device)    # fp64 first, bytes last: every part aligned
+        self._stlsq_R(R, G, n_sets, n0)
+        hyper, S = self._stlsq_hyper(hyper, n_problems, G, STLSQ_PATH_SYMREG_HYPER, "gamma, w_sym")
+        o, fetch = self._stlsq_outputs(G, "symode_stlsq_path_symreg", S, d, p)
         path = torch.empty(max(S, 0), n0 + 1, d, p, dtype=torch.float32, device=G.device)
-
-        def parts(b, f64, f32, i32):
-            tr, rg, va, xi, order, best, near, fell, mask = (b[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:]))
-            return dict(Xi=xi.view(f32).reshape(S, d, p), mask=mask.reshape(S, d, p), order=order.view(i32).reshape(S, n0),
-                        mse_train=tr.view(f64).reshape(S, n0 + 1), reg_train=rg.view(f64).reshape(S, n0 + 1),
-                        mse_val=va.view(f64).reshape(S, n0 + 1), best=best.view(i32), near=near.view(i32), fell=fell.view(i32))
-
-        o = parts(buf, torch.float64, torch.float32, torch.int32)
         self._check(self.lib.symode_stlsq_path_symreg(
             self._ptr(G), self._ptr(R), self._ptr(V), n_sets, V.shape[0], S, d, p, int(n_points), self._ptr(hyper), float(gamma),
-            float(w_sym), float(tol), float(floor_rel), float(near_band), float(pivot_floor), self._ptr(path), self._ptr(o["order"]),
-            self._ptr(o["mse_train"]), self._ptr(o["reg_train"]), self._ptr(o["mse_val"]), self._ptr(o["best"]), self._ptr(o["Xi"]),
-            self._ptr(o["mask"]), self._ptr(o["near"]), self._ptr(o["fell"]), self._stream(G)),
+            float(w_sym), float(tol), float(floor_rel), float(near_band), float(pivot_floor), self._ptr(path),
+            *(o[k].data_ptr() for k in ("order", "mse_train", "reg_train", "mse_val", "best", "Xi", "mask", "near", "fell")),
+            self._stream(G)),
             "symode_stlsq_path_symreg")
-        if to_host:
-            import numpy as np
-            o = parts(buf.cpu().numpy(), np.float64, np.float32, np.int32)
-            if keep_path:
-                o["path_xi"] = path.cpu().numpy()
-            return o
-        o["path_xi"] = path
-        return o
+        return self._with_path(fetch(to_host), path, to_host, keep_path)
 
     def quad_closure(self, G, R, xi, mask, inv_count, w_sym=1.0, hyper=None, n_sets=None):
         """The closure as a quadratic form of fixed fp64 matrices: G (S, p+d, p+d) augmented Gram, R (S, d p, d p) or None,

@@ -45,6 +45,55 @@ def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
     return torch.sort(idx, dim=1).values.to(dtype)
 
 
+SINGULAR_WORDS = 'singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead'
+
+
+def _hyper_columns(hyper, defaults, S, prefix, named, named_empty):
+    """A ``hyper`` dict of per-problem columns read against ``defaults`` {column: the scalar argument it stands in for}:
+    (n_problems, {column: one value per problem}), a column left out filled from its scalar; without a table one problem per
+    seed.  ``prefix`` and ``named`` / ``named_empty`` (the table names a column that is not allowed / no column at all) word
+    the refusals as each caller has them."""
+    n_problems = S
+    if hyper is not None:
+        if set(hyper) - set(defaults) or not hyper:
+            raise ValueError(f"{prefix}hyper: the per-problem columns of {named if hyper else named_empty}, got {sorted(hyper)}")
+        lengths = {len(v) for v in hyper.values()}
+        n_problems = lengths.pop()
+        if lengths or n_problems < S or n_problems % S != 0:
+            raise ValueError(f'{prefix}hyper: every column needs one value per problem, a multiple of the {S} seeds (problem s '
+                             f'on seed s % {S}); got lengths {sorted({len(v) for v in hyper.values()})}')
+    return n_problems, {k: (hyper or {}).get(k, [v] * n_problems) for k, v in defaults.items()}
+
+
+def _in_fp32(values):
+    """per-problem values as a launch holds them: rounded to fp32 (kept in fp64 for the host twins)"""
+    return np.array([float(np.float32(v)) for v in values], dtype=np.float64)
+
+
+class _HostSets:
+    """Host copies of single sets of device matrices, made when first asked for: at most one device-to-host copy per
+    (matrix, set), and only for the sets touched."""
+
+    def __init__(self, **matrices):
+        self.matrices, self.held = matrices, {}
+
+    def __call__(self, name, k):
+        if (name, k) not in self.held:
+            self.held[name, k] = self.matrices[name][k].cpu().numpy()
+        return self.held[name, k]
+
+
+def _flagged_to_host(fell, solve_on_host, also=False):
+    """The problems a launch flagged go to the host, ``solve_on_host(s)`` each; where there was one (or ``also``), the
+    RuntimeWarning of the full-rank driver that names the minimum-norm answer."""
+    flagged = np.nonzero(fell)[0].tolist()
+    for s in flagged:
+        solve_on_host(s)
+    if flagged or also:
+        import warnings
+        warnings.warn(SINGULAR_WORDS, RuntimeWarning)
+
+
 class _DeviceSTLSQ:
     """The device fit of a sweep whose problems are (p+d, p+d) fp64 matrices on the device: what SeedSweepSTLSQ and
     SeedSweepWSINDy share.  The class supplies engine, S, d, p, n_points and ``grams(device=True)``."""
@@ -88,110 +137,68 @@ class _DeviceSTLSQ:
         per pass the minimiser of mse + w_sym * reg; ``hyper`` then also takes a ``w_sym`` column, and the launch holds that
         value in fp32 as well.  A problem it flags is solved by the host loop with the minimum-norm rule on every pass."""
         S, d, p = self.S, self.d, self.p
-        f32 = lambda v: float(np.float32(v))                                   # noqa: E731
-        n_problems = S
-        if hyper is not None:
-            unknown = set(hyper) - ({'w_reg', 'threshold'} if rev is None else {'w_reg', 'threshold', 'w_sym'})
-            if unknown and rev is not None:
-                raise ValueError('hyper: the per-problem columns of the STLSQ sweep with the reversed regulariser are w_reg, '
-                                 f'threshold and w_sym, got {sorted(hyper)}')
-            if unknown or not hyper:
-                raise ValueError(f"hyper: the per-problem columns of the STLSQ sweep are w_reg and threshold, got {sorted(hyper)}")
-            lengths = {len(v) for v in hyper.values()}
-            n_problems = lengths.pop()
-            if lengths or n_problems < S or n_problems % S != 0:
-                raise ValueError(f'hyper: every column needs one value per problem, a multiple of the {S} seeds (problem s '
-                                 f'on seed s % {S}); got lengths {sorted({len(v) for v in hyper.values()})}')
-        w = np.array([f32(v) for v in (hyper or {}).get('w_reg', [w_sindy_reg] * n_problems)], dtype=np.float64)
-        thr = np.array([f32(v) for v in (hyper or {}).get('threshold', [threshold] * n_problems)], dtype=np.float64)
+        defaults = {'w_reg': w_sindy_reg, 'threshold': threshold}
+        named = 'the STLSQ sweep are w_reg and threshold'
+        if rev is not None:
+            defaults['w_sym'] = rev[1]
+        n_problems, col = _hyper_columns(hyper, defaults, S, '', named if rev is None else 'the STLSQ sweep with the reversed '
+                                         'regulariser are w_reg, threshold and w_sym', named)
+        w, thr = _in_fp32(col['w_reg']), _in_fp32(col['threshold'])
         if not (np.all(np.isfinite(w)) and np.all(np.isfinite(thr)) and np.all(w >= 0) and np.all(thr >= 0)):
             raise ValueError('the ridge weight and the threshold of every problem must be finite and >= 0')
         if rev is not None:
-            wsym = np.array([f32(v) for v in (hyper or {}).get('w_sym', [rev[1]] * n_problems)], dtype=np.float64)
+            wsym = _in_fp32(col['w_sym'])
             if not (np.all(np.isfinite(wsym)) and np.all(wsym >= 0)):
                 raise ValueError('the weight w_sym of the reversed regulariser must be finite and >= 0 for every problem')
-        G = self.grams(device=True)
-        table = None
+        G, R = self.grams(device=True), None
+        # the launch: (engine method, its operands, its own keywords, how many items it returns, where ``trunc`` is among them)
+        floor = _lstsq.SINGULAR_RCOND ** 2
         if rev is not None:
             R = torch.as_tensor(rev[0]).to(device=G.device, dtype=torch.float64).reshape(S, d * p, d * p).contiguous()
-            if hyper is not None:
-                table = torch.from_numpy(np.stack([w, thr, wsym], axis=1).astype(np.float32)).to(G.device)
-        elif hyper is not None:
-            table = torch.from_numpy(np.stack([w, thr], axis=1).astype(np.float32)).to(G.device)
-        trunc = np.zeros(n_problems, dtype=np.int32)
-        if rev is not None:
-            Xi, m8, p32, near, fell, *flags = self.engine.stlsq_sweep_symreg(
-                G, R, self.n_points, w[0], thr[0], wsym[0], max_iter, hyper=table, d=d, pivot_floor=_lstsq.SINGULAR_RCOND ** 2,
-                near_band=NEAR_THRESHOLD_BAND, to_host=True, tail=self._fetch_with_fit)
-        elif coef is not None and min_norm:
-            q_solve, q_xi = (torch.from_numpy(q).to(G.device) for q in (coef.solve_matrix(), coef.xi_matrix()))
-            Xi, m8, p32, near, fell, _, trunc, _, *flags = self.engine.stlsq_sweep_minnorm(
-                G, self.n_points, w[0], thr[0], max_iter, q_solve, q_xi, coef.allow_constant, hyper=table, d=d,
-                rcond=_lstsq.SINGULAR_RCOND, near_band=NEAR_THRESHOLD_BAND, to_host=True, tail=self._fetch_with_fit)
-        elif coef is not None:
-            q_solve, q_xi = (torch.from_numpy(q).to(G.device) for q in (coef.solve_matrix(), coef.xi_matrix()))
-            Xi, m8, p32, near, fell, _, *flags = self.engine.stlsq_sweep_constrained(
-                G, self.n_points, w[0], thr[0], max_iter, q_solve, q_xi, coef.allow_constant, hyper=table, d=d,
-                pivot_floor=_lstsq.SINGULAR_RCOND ** 2, near_band=NEAR_THRESHOLD_BAND, to_host=True, tail=self._fetch_with_fit)
+            rows = [w, thr, wsym]
+            launch, args, own, n_out, at_trunc = ('stlsq_sweep_symreg', (G, R, self.n_points, w[0], thr[0], wsym[0], max_iter),
+                                                  {'pivot_floor': floor}, 5, None)
         else:
-            Xi, m8, p32, near, fell, *flags = self.engine.stlsq_sweep(G, self.n_points, w[0], thr[0], max_iter, hyper=table, d=d,
-                                                                      near_band=NEAR_THRESHOLD_BAND, to_host=True,    # one copy back
-                                                                      tail=self._fetch_with_fit)
-        if flags:
-            self._fetched(flags[0])
-        Xi, mask, passes = np.array(Xi), np.asarray(m8).astype(bool), np.asarray(p32).astype(np.int64)
-        near = np.array(near)
+            rows = [w, thr]
+            launch, args, own, n_out, at_trunc = 'stlsq_sweep', (G, self.n_points, w[0], thr[0], max_iter), {}, 5, None
+            if coef is not None:
+                q_solve, q_xi = (torch.from_numpy(q).to(G.device) for q in (coef.solve_matrix(), coef.xi_matrix()))
+                args += (q_solve, q_xi, coef.allow_constant)
+                launch, own, n_out, at_trunc = (('stlsq_sweep_minnorm', {'rcond': _lstsq.SINGULAR_RCOND}, 8, 6) if min_norm
+                                                else ('stlsq_sweep_constrained', {'pivot_floor': floor}, 6, None))
+        table = None if hyper is None else torch.from_numpy(np.stack(rows, axis=1).astype(np.float32)).to(G.device)
+        out = getattr(self.engine, launch)(*args, hyper=table, d=d, near_band=NEAR_THRESHOLD_BAND, to_host=True,           # one copy back
+                                           tail=self._fetch_with_fit, **own)
+        if len(out) > n_out:
+            self._fetched(out[n_out])
+        Xi, mask, passes = np.array(out[0]), np.asarray(out[1]).astype(bool), np.asarray(out[2]).astype(np.int64)
+        near, fell = np.array(out[3]), out[4]
+        trunc = np.zeros(n_problems, dtype=np.int32) if at_trunc is None else out[at_trunc]
         self.near_threshold = []
-        held, held_rev = {}, {}                                         # set -> its (p+d, p+d) matrix on the host; ... its R
-
-        def on_host(s):
-            k = s % S
-            if k not in held:
-                held[k] = G[k].cpu().numpy()
-            return held[k]
-
-        def rev_on_host(s):
-            if rev is None:
-                return None
-            k = s % S
-            if k not in held_rev:
-                held_rev[k] = R[k].cpu().numpy()
-            return held_rev[k], wsym[s]
-
+        held = _HostSets(G=G, R=R)
+        on_host = lambda s: held('G', s % S)                                              # noqa: E731
+        rev_on_host = lambda s: None if rev is None else (held('R', s % S), wsym[s])      # noqa: E731
         self.rank_truncated = np.array(trunc) > 0                       # (n_problems,): a pass solved with rank < n on the device
-        if rev is not None:
-            if fell.any():
+
+        def flagged(s):
+            if rev is not None or coef is not None:
                 # possibly rank deficient: the host loop from the full mask, the minimum-norm rule on every pass
-                import warnings
-                for s in np.nonzero(fell)[0].tolist():
-                    self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm', Xi, mask, passes, rev=rev_on_host(s))
-                    near[s] = 0                                          # (its near-threshold record is the loop's)
-                warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
-                              RuntimeWarning)
-        elif coef is not None and (fell.any() or self.rank_truncated.any()):
-            # possibly rank deficient: the host loop from the full mask, the minimum-norm rule on every pass
-            import warnings
-            for s in np.nonzero(fell)[0].tolist():
-                self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm', Xi, mask, passes, coef)
+                self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm', Xi, mask, passes, coef, rev_on_host(s))
                 near[s] = 0                                              # (its near-threshold record is the loop's)
-            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
-                          RuntimeWarning)
-        elif fell.any():
-            # a pivot that was not positive: these problems are the host loop's, rank-revealing fallback and warning included
-            import warnings
-            lib = _lstsq._native()
-            for s in np.nonzero(fell)[0].tolist():
-                Gs = np.ascontiguousarray(on_host(s), dtype=np.float64)[None]
-                xi1, m1 = np.zeros((1, d, p), dtype=np.float32), np.ones((1, d, p), dtype=np.uint8)
-                p1, n1, f1 = (np.zeros(1, dtype=np.int32) for _ in range(3))
-                rc = lib.symode_host_stlsq_sweep(Gs.ctypes.data, 1, d, p, int(self.n_points), float(w[s]), float(thr[s]), int(max_iter),
-                                                 1, float(NEAR_THRESHOLD_BAND), xi1.ctypes.data, m1.ctypes.data, p1.ctypes.data,
-                                                 n1.ctypes.data, f1.ctypes.data)
-                if rc != 0:
-                    raise RuntimeError(f'symode_host_stlsq_sweep failed with code {rc}')
-                Xi[s], mask[s], passes[s], near[s] = xi1[0], m1[0].astype(bool), p1[0], n1[0]
-            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
-                          RuntimeWarning)
+                return
+            # a pivot that was not positive: the problem is the host loop's, rank-revealing fallback included
+            Gs = np.ascontiguousarray(on_host(s), dtype=np.float64)[None]
+            xi1, m1 = np.zeros((1, d, p), dtype=np.float32), np.ones((1, d, p), dtype=np.uint8)
+            p1, n1, f1 = (np.zeros(1, dtype=np.int32) for _ in range(3))
+            rc = _lstsq._native().symode_host_stlsq_sweep(Gs.ctypes.data, 1, d, p, int(self.n_points), float(w[s]), float(thr[s]),
+                                                          int(max_iter), 1, float(NEAR_THRESHOLD_BAND), xi1.ctypes.data, m1.ctypes.data,
+                                                          p1.ctypes.data, n1.ctypes.data, f1.ctypes.data)
+            if rc != 0:
+                raise RuntimeError(f'symode_host_stlsq_sweep failed with code {rc}')
+            Xi[s], mask[s], passes[s], near[s] = xi1[0], m1[0].astype(bool), p1[0], n1[0]
+
+        # (the constrained fit names the minimum-norm answer also where the launch itself gave it: a rank-truncated pass)
+        _flagged_to_host(fell, flagged, also=coef is not None and self.rank_truncated.any())
         for s in np.nonzero(near)[0].tolist():
             self._replay(s, on_host(s), w[s], thr[s], max_iter, 'min_norm' if trunc[s] > 0 else 'gels', Xi, mask, passes, coef,
                          rev_on_host(s))
@@ -299,35 +306,48 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         if len(shape) != 3 or shape[1:] != (p + d, p + d) or shape[0] not in (1, S):
             raise ValueError(f'solve_path: val_gram must be (n_val, p + d, p + d) = (1 or {S}, {p + d}, {p + d}), got {shape}')
         gamma = float(np.sqrt(float(w_sindy_reg)))
-        keys = ('order', 'rss_train', 'rss_val', 'best', 'near') + (('path_xi',) if keep_path else ())
 
-        def twin(Gs, Vs):
-            xi, m, rec = stlsq_path_from_gram(Gs, Vs, gamma, float(tol), float(floor_rel), NEAR_THRESHOLD_BAND, d, self.n_points)
-            return xi, m, rec
+        def twin(s, Gs, Vs, Rs):
+            return stlsq_path_from_gram(Gs, Vs, gamma, float(tol), float(floor_rel), NEAR_THRESHOLD_BAND, d, self.n_points)
 
+        def launch(G, V, R):
+            return self.engine.stlsq_path(G, V, self.n_points, gamma, float(tol), float(floor_rel), d=d, near_band=NEAR_THRESHOLD_BAND,
+                                          to_host=True, keep_path=keep_path)
+
+        return self._path_fit(device, keep_path, ('order', 'rss_train', 'rss_val', 'best', 'near'), twin, launch, val_gram)
+
+    def _path_fit(self, device, keep_path, keys, twin, launch, val_gram, R=None):
+        """The two routes of a sparsity path, whatever the fit.  ``device=False``: every seed through ``twin(s, G_s, V_s, R_s)``
+        -> (Xi, mask, record), stacked.  ``device=True``: ``launch(G, V, R)`` on the device matrices, one fetch, and the
+        problems it flagged patched from the twin (with the full-rank driver's warning), only their matrices copied.
+        ``keys``: what the record keeps."""
+        S, n_val = self.S, val_gram.shape[0]
+        keys += ('path_xi',) if keep_path else ()
         if not device:
             G = self.grams()
+            Rh = R if R is None else R.detach().cpu().numpy() if torch.is_tensor(R) else np.asarray(R)
             Vh = val_gram.detach().cpu().numpy() if torch.is_tensor(val_gram) else np.asarray(val_gram, dtype=np.float64)
-            out = [twin(G[s], Vh[s % shape[0]]) for s in range(S)]
+            out = [twin(s, G[s], Vh[s % n_val], None if R is None else Rh[s]) for s in range(S)]
             record = {k: np.stack([np.asarray(o[2][k]) for o in out]) for k in keys}
             record['near'] = record['near'].astype(np.int32)              # (the launch's type)
             return (torch.from_numpy(np.stack([o[0] for o in out])),
                     torch.from_numpy(np.stack([o[1] for o in out]).astype(np.float32)), record)
         G = self.grams(device=True)
+        if R is not None:
+            R = torch.as_tensor(R).to(device=G.device, dtype=torch.float64).reshape(S, self.d * self.p, self.d * self.p).contiguous()
         V = torch.as_tensor(val_gram).to(device=G.device, dtype=torch.float64).contiguous()
-        o = self.engine.stlsq_path(G, V, self.n_points, gamma, float(tol), float(floor_rel), d=d, near_band=NEAR_THRESHOLD_BAND,
-                                   to_host=True, keep_path=keep_path)
+        o = launch(G, V, R)
         Xi, mask = np.array(o['Xi']), np.asarray(o['mask']).astype(bool)
         record = {k: np.array(o[k]) for k in keys}
-        if o['fell'].any():
-            # a pivot that was not positive: these problems are the host twin's, minimum-norm fallback and warning included
-            import warnings
-            for s in np.nonzero(o['fell'])[0].tolist():
-                Xi[s], mask[s], rec = twin(G[s].cpu().numpy(), V[s % shape[0]].cpu().numpy())
-                for k in keys:
-                    record[k][s] = rec[k]
-            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
-                          RuntimeWarning)
+        held = _HostSets(G=G, V=V, R=R)
+
+        def flagged(s):
+            # possibly rank deficient: the problem is the host twin's, minimum-norm fallback included
+            Xi[s], mask[s], rec = twin(s, held('G', s % S), held('V', s % n_val), None if R is None else held('R', s % S))
+            for k in keys:
+                record[k][s] = rec[k]
+
+        _flagged_to_host(o['fell'], flagged)
         return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), record
 
     def _solve_path_symreg(self, w_sindy_reg, val_gram, tol, floor_rel, device, keep_path, rev, hyper):
@@ -345,62 +365,28 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
         shape = tuple(val_gram.shape)
         if len(shape) != 3 or shape[1:] != (p + d, p + d) or shape[0] not in (1, S):
             raise ValueError(f'solve_path: val_gram must be (n_val, p + d, p + d) = (1 or {S}, {p + d}, {p + d}), got {shape}')
-        f32 = lambda v: float(np.float32(v))                                   # noqa: E731
-        n_problems = S
-        if hyper is not None:
-            if not device:
-                raise ValueError('solve_path: hyper (a per-problem table of w_reg / w_sym) needs device=True: the host route takes '
-                                 'one value each')
-            if not hyper or set(hyper) - {'w_reg', 'w_sym'}:
-                raise ValueError(f'solve_path: hyper: the per-problem columns of the regularised path are w_reg and w_sym, got '
-                                 f'{sorted(hyper)}')
-            lengths = {len(v) for v in hyper.values()}
-            n_problems = lengths.pop()
-            if lengths or n_problems < S or n_problems % S != 0:
-                raise ValueError(f'solve_path: hyper: every column needs one value per problem, a multiple of the {S} seeds (problem '
-                                 f's on seed s % {S}); got lengths {sorted({len(v) for v in hyper.values()})}')
-        w = np.array([float(v) for v in (hyper or {}).get('w_reg', [w_sindy_reg] * n_problems)], dtype=np.float64)
-        wsym = np.array([f32(v) for v in (hyper or {}).get('w_sym', [rev[1]] * n_problems)], dtype=np.float64)
+        if hyper is not None and not device:
+            raise ValueError('solve_path: hyper (a per-problem table of w_reg / w_sym) needs device=True: the host route takes '
+                             'one value each')
+        named = 'the regularised path are w_reg and w_sym'
+        _, col = _hyper_columns(hyper, {'w_reg': w_sindy_reg, 'w_sym': rev[1]}, S, 'solve_path: ', named, named)
+        w, wsym = np.array([float(v) for v in col['w_reg']], dtype=np.float64), _in_fp32(col['w_sym'])
         if not (np.all(np.isfinite(w)) and np.all(w >= 0) and np.all(np.isfinite(wsym)) and np.all(wsym >= 0)):
             raise ValueError('solve_path: the ridge weight and w_sym of every problem must be finite and >= 0')
-        gamma = np.array([f32(np.sqrt(v)) for v in w], dtype=np.float64)       # as the launch holds it
-        keys = ('order', 'mse_train', 'reg_train', 'mse_val', 'best', 'near') + (('path_xi',) if keep_path else ())
+        gamma = _in_fp32(np.sqrt(w))                                           # as the launch holds it
 
-        def twin(Gs, Rs, Vs, s):
+        def twin(s, Gs, Vs, Rs):
             return stlsq_path_symreg_from_gram(Gs, Rs, Vs, gamma[s], wsym[s], float(tol), float(floor_rel), NEAR_THRESHOLD_BAND, d,
                                                self.n_points)
 
-        if not device:
-            G = self.grams()
-            R = rev[0].detach().cpu().numpy() if torch.is_tensor(rev[0]) else np.asarray(rev[0])
-            Vh = val_gram.detach().cpu().numpy() if torch.is_tensor(val_gram) else np.asarray(val_gram, dtype=np.float64)
-            out = [twin(G[s], R[s], Vh[s % shape[0]], s) for s in range(S)]
-            record = {k: np.stack([np.asarray(o[2][k]) for o in out]) for k in keys}
-            record['near'] = record['near'].astype(np.int32)              # (the launch's type)
-            return (torch.from_numpy(np.stack([o[0] for o in out])),
-                    torch.from_numpy(np.stack([o[1] for o in out]).astype(np.float32)), record)
-        G = self.grams(device=True)
-        R = torch.as_tensor(rev[0]).to(device=G.device, dtype=torch.float64).reshape(S, n0, n0).contiguous()
-        V = torch.as_tensor(val_gram).to(device=G.device, dtype=torch.float64).contiguous()
-        table = None
-        if hyper is not None:
-            table = torch.from_numpy(np.stack([gamma, wsym], axis=1).astype(np.float32)).to(G.device)
-        o = self.engine.stlsq_path_symreg(G, R, V, self.n_points, gamma[0], wsym[0], float(tol), float(floor_rel), hyper=table, d=d,
-                                          pivot_floor=_lstsq.SINGULAR_RCOND ** 2, near_band=NEAR_THRESHOLD_BAND, to_host=True,
-                                          keep_path=keep_path)
-        Xi, mask = np.array(o['Xi']), np.asarray(o['mask']).astype(bool)
-        record = {k: np.array(o[k]) for k in keys}
-        if o['fell'].any():
-            # possibly rank deficient: these problems are the host twin's, minimum-norm fallback and warning included
-            import warnings
-            for s in np.nonzero(o['fell'])[0].tolist():
-                k = s % S
-                Xi[s], mask[s], rec = twin(G[k].cpu().numpy(), R[k].cpu().numpy(), V[s % shape[0]].cpu().numpy(), s)
-                for key in keys:
-                    record[key][s] = rec[key]
-            warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
-                          RuntimeWarning)
-        return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), record
+        def launch(G, V, R):
+            table = None if hyper is None else torch.from_numpy(np.stack([gamma, wsym], axis=1).astype(np.float32)).to(G.device)
+            return self.engine.stlsq_path_symreg(G, R, V, self.n_points, gamma[0], wsym[0], float(tol), float(floor_rel), hyper=table,
+                                                 d=d, pivot_floor=_lstsq.SINGULAR_RCOND ** 2, near_band=NEAR_THRESHOLD_BAND,
+                                                 to_host=True, keep_path=keep_path)
+
+        return self._path_fit(device, keep_path, ('order', 'mse_train', 'reg_train', 'mse_val', 'best', 'near'), twin, launch,
+                              val_gram, rev[0])
 
     def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None, coef=None, min_norm=False,
               rev=None):
@@ -494,8 +480,7 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
                 raise RuntimeError(f'symode_host_stlsq_sweep failed with code {rc}')
             if fell.any():
                 import warnings
-                warnings.warn('singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead',
-                              RuntimeWarning)
+                warnings.warn(SINGULAR_WORDS, RuntimeWarning)
             mask, passes = m8.astype(bool), p32.astype(np.int64)
             todo = [int(s) for s in np.nonzero(near)[0]]
         for s in todo:

@@ -273,3 +273,38 @@ def test_the_device_route_refuses_values_and_columns_by_name(monkeypatch):
         sw.solve(0.0, 0.05, rev=(R_, 1.0), device=True, hyper={"threshold": [0.1, -0.1, 0.1]})
     with pytest.raises(ValueError, match="hyper: the per-problem columns of the STLSQ sweep are w_reg and threshold, got"):
         sw.solve(0.0, 0.05, device=True, lstsq_driver="gels", hyper={"lr": [1.0] * 3})        # without rev: the words it had
+
+
+def test_the_words_of_the_device_routes_are_whole(monkeypatch):
+    """The refusals of ``_solve_device``, ``solve_path`` and ``_solve_path_symreg`` that read a ``hyper`` table, character for
+    character as they stood before the table got one parser."""
+    import re
+    sw, R_ = _sweep()
+    monkeypatch.setattr(type(sw), "grams", _untouchable("grams"))
+    V, rev = np.zeros((1, sw.p + 2, sw.p + 2)), (R_, 1.0)
+    solve = lambda **kw: sw.solve(0.0, 0.05, rev=rev, device=True, **kw)                       # noqa: E731
+    path = lambda *a, **kw: sw.solve_path(0.0, V, *(a or (0.02,)), **kw)                       # noqa: E731
+    for call, words in [
+        (lambda: solve(hyper={"lr": [1.0] * 3}),
+         "hyper: the per-problem columns of the STLSQ sweep with the reversed regulariser are w_reg, threshold and w_sym, got ['lr']"),
+        (lambda: solve(hyper={}), "hyper: the per-problem columns of the STLSQ sweep are w_reg and threshold, got []"),
+        (lambda: solve(hyper={"w_sym": [1.0, float("nan"), 1.0]}),
+         "the weight w_sym of the reversed regulariser must be finite and >= 0 for every problem"),
+        (lambda: solve(hyper={"w_sym": [1.0] * 4}),
+         "hyper: every column needs one value per problem, a multiple of the 3 seeds (problem s on seed s % 3); got lengths [4]"),
+        (lambda: solve(hyper={"w_sym": [1.0] * 3, "w_reg": [0.0] * 6}),
+         "hyper: every column needs one value per problem, a multiple of the 3 seeds (problem s on seed s % 3); got lengths [3, 6]"),
+        (lambda: solve(hyper={"w_sym": [-1.0] * 3, "threshold": [float("inf")] * 3}),               # the threshold is read first
+         "the ridge weight and the threshold of every problem must be finite and >= 0"),
+        (lambda: path(hyper={"w_sym": [1.0] * 3}),
+         "solve_path: hyper (a per-problem table of w_reg / w_sym) needs rev=(R, w_sym): the table is the regularised path's"),
+        (lambda: path(device=False, rev=rev, hyper={"lr": [1.0]}),                                  # the route before the columns
+         "solve_path: hyper (a per-problem table of w_reg / w_sym) needs device=True: the host route takes one value each"),
+        (lambda: path(rev=rev, hyper={}), "solve_path: hyper: the per-problem columns of the regularised path are w_reg and w_sym, got []"),
+        (lambda: path(rev=rev, hyper={"w_sym": [1.0] * 4}),
+         "solve_path: hyper: every column needs one value per problem, a multiple of the 3 seeds (problem s on seed s % 3); got lengths [4]"),
+        (lambda: path(rev=rev, hyper={"w_reg": [0.0, -1.0, 0.0]}), "solve_path: the ridge weight and w_sym of every problem must be finite and >= 0"),
+        (lambda: path(float("nan")), "solve_path: tol must be finite and >= 0, got nan"),
+    ]:
+        with pytest.raises(ValueError, match="^" + re.escape(words) + "$"):
+            call()
