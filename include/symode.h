@@ -1057,6 +1057,52 @@ int symode_stlsq_path_symreg(const double* aug_gram, const double* rev_gram, con
                              double* mse_train, double* reg_train, double* mse_val, int* best, float* xi_out,
                              unsigned char* mask_out, int* near_out, int* fell_out, void* stream);
 
+/* Block-bootstrap replicas of Gram matrices ON THE DEVICE, one launch (all pointers device memory).  A Gram matrix is a sum over
+ * rows, so a bootstrap replica that resamples whole chunks of a seed's rows is an integer-weighted sum of the chunks' matrices.
+ * chunk (n_seeds, n_chunks, n, n) fp64; seeds (n_seeds) 64-bit integers; out (n_seeds * n_replicas, n, n) fp64, replica b of seed
+ * k at index k * n_replicas + b; counts_out NULL or (n_seeds * n_replicas, n_chunks) ints.  With C = n_chunks:
+ *   draw   w = seed_words(seed_words(seeds[k]) + b) modulo 2^64 and, for t = 0 .. C-1, u = subsample_key(low32(w), high32(w), t)
+ *          (the two counter hashes of symode_seeded_subsamples, csrc/adam_order.hpp); draw t lands on chunk (u * C) >> 32 in
+ *          64-bit arithmetic, which is < C; count[c] = the draws that landed on c, so every row of counts sums to C;
+ *   sum    out[e] = 0.0, then out[e] = out[e] + (double)count[c] * chunk[k, c, e] for c ascending, chunks with count 0 skipped,
+ *          one multiply and one add per term, nothing contracted; each of the n^2 entries by itself, so a symmetric input gives
+ *          a symmetric output, and a replica does not depend on the seeds or the replica count it is launched with.
+ * n is generic: p + d for the augmented matrices, d p for the regulariser's.
+ * Refused before any GPU work: n_chunks < 1 or > 1024, n < 1 or > 68, n_replicas < 1, n_seeds < 1, n_seeds * n_replicas >= 2^31
+ * (what symode_stlsq_sweep refuses as a problem count) (SYMODE_E_BADSIZE); chunk, seeds or out NULL (SYMODE_E_NULLPTR); chunk,
+ * seeds or out not 8-byte, counts_out not 4-byte aligned (SYMODE_E_ALIGN).
+ * Added to ABI version 8 (nothing existing changed).
+ * replaces: nothing in the reference (the block bootstrap of ensemble SINDy on Gram matrices). */
+int symode_gram_resample(const double* chunk, const long long* seeds, long n_seeds, int n_chunks, int n, int n_replicas, double* out,
+                         int* counts_out, void* stream);
+
+/* Bagging of the device STLSQ fit: aggregate the replica fits of every seed and refit on the terms that survive often enough, all
+ * problems in one launch (all pointers device memory).  aug_gram (n_seeds, p+d, p+d) fp64, each seed's OWN matrix; rep_xi
+ * (n_seeds * n_replicas, d, p) fp32, rep_mask (same shape) bytes and rep_fell (n_seeds * n_replicas) ints are the xi_out, mask_out
+ * and fell_out of symode_stlsq_sweep on the n_seeds * n_replicas matrices of symode_gram_resample.  Problem s works on seed
+ * k = s % n_seeds at the inclusion level tau_table[s] (n_problems ints), or tau_milli for all when tau_table is NULL, in
+ * thousandths, 0 .. 1000: a grid of levels is more problems on the same replica outputs.  p <= 64, d <= 4.
+ *   statistics  over the seed's replicas b ascending, one with rep_fell set left out: valid = the replicas that remain; per term,
+ *               count = the valid replicas whose mask keeps it and, over those, in fp64: sum from 0.0, mean = sum / count, ss =
+ *               sum from 0.0 of (x - mean)^2 in a second pass, std = sqrt(ss / count); count == 0: mean = std = 0;
+ *   inclusion   a term is kept iff valid > 0 and 1000 count >= tau valid (integers, exact);
+ *   refit       per equation row, one pass of symode_stlsq_sweep's solve on the kept support from aug_gram[k] with ridge gamma,
+ *               rounded to fp32; an empty row is zeros.  A pivot that is not > 0 sets fell_out[s] = 1 (the row is then zeros;
+ *               the caller solves the problem on the host); nothing else is flagged.
+ * xi_out (n_problems, d, p) fp32, mask_out (n_problems, d, p) bytes (the kept terms), fell_out (n_problems) ints; written by the
+ * problems s < n_seeds only: count_out (n_seeds, d, p) ints, valid_out (n_seeds) ints, mean_out, std_out (n_seeds, d, p) fp64.
+ * tau = 0 is bit for bit symode_stlsq_sweep with max_iter = 1 and threshold = 0 on the same matrix (while a replica is valid).
+ * Refused before any GPU work: d < 1, d > 4, p < 1, p > 64, n_seeds < 1, n_problems < n_seeds, >= 2^31 or not a multiple of
+ * n_seeds, n_replicas < 1, n_seeds * n_replicas >= 2^31, tau_table NULL with tau_milli outside 0 .. 1000 (the caller checks a
+ * table before it uploads it), gamma < 0 or not finite (SYMODE_E_BADSIZE); any pointer but tau_table NULL (SYMODE_E_NULLPTR);
+ * aug_gram, mean_out or std_out not 8-byte, tau_table or another fp32 / int array not 4-byte aligned (SYMODE_E_ALIGN).
+ * Added to ABI version 8 (nothing existing changed).
+ * replaces: nothing in the reference (aggregation and refit of ensemble SINDy). */
+int symode_stlsq_bag(const double* aug_gram, long n_seeds, long n_problems, int d, int p, int n_replicas, const float* rep_xi,
+                     const unsigned char* rep_mask, const int* rep_fell, const int* tau_table, int tau_milli, double gamma,
+                     float* xi_out, unsigned char* mask_out, int* fell_out, int* count_out, int* valid_out, double* mean_out,
+                     double* std_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,11 +8,13 @@
 #include "../../include/symode.h"
 #include "closure_quad.hpp"
 #include "closure_reduced.hpp"
+#include "gram_resample.hpp"
 #include "jconst.hpp"
 #include "linear_action.hpp"
 #include "ops_table.hpp"
 #include "quad_closure.hpp"
 #include "stlsq.hpp"
+#include "stlsq_bag.hpp"
 #include "stlsq_constrained.hpp"
 #include "stlsq_path.hpp"
 #include "stlsq_symreg.hpp"
@@ -646,6 +648,33 @@ int symode_stlsq_path(const double* aug_gram, const double* val_gram, long n_set
         return SYMODE_E_ALIGN;
     return (int)launch_stlsq_path(aug_gram, val_gram, n_sets, n_val_sets, n_problems, d, p, gamma, tol, floor_rel, near_band, path_xi,
                                   order, rss_train, rss_val, best, xi_out, mask_out, near_out, fell_out, (hipStream_t)stream);
+}
+
+int symode_gram_resample(const double* chunk, const long long* seeds, long n_seeds, int n_chunks, int n, int n_replicas, double* out,
+                         int* counts_out, void* stream) {
+    if (n_chunks < 1 || n_chunks > RESAMPLE_MAX_CHUNKS || n < 1 || n > RESAMPLE_MAX_N || n_replicas < 1 || n_seeds < 1 ||
+        n_seeds > 2147483647L)
+        return SYMODE_E_BADSIZE;
+    if (stlsq_bad_problems(n_seeds, n_seeds * n_replicas, true)) return SYMODE_E_BADSIZE;   // the replicas are the sweep's problems
+    if (any_null(chunk, seeds, out)) return SYMODE_E_NULLPTR;
+    if (any_misaligned(8, chunk, seeds, out) || any_misaligned(4, counts_out)) return SYMODE_E_ALIGN;
+    return (int)launch_gram_resample(chunk, seeds, n_seeds, n_chunks, n, n_replicas, out, counts_out, (hipStream_t)stream);
+}
+
+int symode_stlsq_bag(const double* aug_gram, long n_seeds, long n_problems, int d, int p, int n_replicas, const float* rep_xi,
+                     const unsigned char* rep_mask, const int* rep_fell, const int* tau_table, int tau_milli, double gamma,
+                     float* xi_out, unsigned char* mask_out, int* fell_out, int* count_out, int* valid_out, double* mean_out,
+                     double* std_out, void* stream) {
+    if (stlsq_bad_library(d, p) || stlsq_bad_problems(n_seeds, n_problems, true) || n_problems % n_seeds != 0) return SYMODE_E_BADSIZE;
+    if (n_replicas < 1 || stlsq_bad_problems(n_seeds, n_seeds * n_replicas, true)) return SYMODE_E_BADSIZE;
+    if (!tau_table && (tau_milli < 0 || tau_milli > STLSQ_BAG_TAU_MAX)) return SYMODE_E_BADSIZE;
+    if (!all_finite_nonneg({gamma})) return SYMODE_E_BADSIZE;
+    if (any_null(aug_gram, rep_xi, rep_mask, rep_fell, xi_out, mask_out, fell_out, count_out, valid_out, mean_out, std_out))
+        return SYMODE_E_NULLPTR;
+    if (any_misaligned(8, aug_gram, mean_out, std_out) || any_misaligned(4, rep_xi, rep_fell, tau_table, xi_out, fell_out, count_out, valid_out))
+        return SYMODE_E_ALIGN;
+    return (int)launch_stlsq_bag(aug_gram, n_seeds, n_problems, d, p, n_replicas, rep_xi, rep_mask, rep_fell, tau_table, tau_milli, gamma,
+                                 xi_out, mask_out, fell_out, count_out, valid_out, mean_out, std_out, (hipStream_t)stream);
 }
 
 int symode_stlsq_sweep_constrained(const double* aug_gram, long n_sets, long n_problems, int d, int p, long n_points,

@@ -164,6 +164,9 @@ _SIGNATURES = {
                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                          ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "symode_gram_resample": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "symode_stlsq_bag": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                 ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "symode_host_lstsq_normal": (c_int, [c_void_p, c_void_p, c_int, c_int, c_long, c_int, ctypes.c_double, c_void_p, c_void_p]),
 }
 
@@ -250,6 +253,9 @@ def stlsq_fields(entry, d, p, r1=0):
         "symode_stlsq_path_symreg": [("Xi", "f4", (d, p)), ("mask", "u1", (d, p)), ("order", "i4", (n0,)), ("mse_train", "f8", (n0 + 1,)),
                                      ("reg_train", "f8", (n0 + 1,)), ("mse_val", "f8", (n0 + 1,)), ("best", "i4", ()),
                                      ("near", "i4", ()), ("fell", "i4", ())],
+        # (count, valid, mean and std are per seed: the launch writes the first n_seeds rows of theirs)
+        "symode_stlsq_bag": [("xi", "f4", (d, p)), ("mask", "u1", (d, p)), ("fell", "i4", ()), ("count", "i4", (d, p)),
+                             ("valid", "i4", ()), ("mean", "f8", (d, p)), ("std", "f8", (d, p))],
     }[entry]
 
 
@@ -1391,6 +1397,69 @@ class HipEngine:
                                                 *(o[k].data_ptr() for k in ("xi", "mask", "passes", "near", "fell")), self._stream(G)),
                     "symode_stlsq_sweep")
         return tuple(fetch(to_host).values())
+
+    def gram_resample(self, chunk, seeds, n_replicas, want_counts=False):
+        """Block-bootstrap replicas of Gram matrices in ONE launch (symode_gram_resample).  ``chunk`` (n_seeds, n_chunks, n, n) fp64
+        on the device, the Gram matrices of every seed's chunks of rows; ``seeds`` (n_seeds,) int64 on the device, or a list of
+        integers.  Returns (n_seeds * n_replicas, n, n) fp64 on the device, replica b of seed k at k * n_replicas + b: the sum of
+        the seed's chunk matrices weighted by how often each of the n_chunks draws of (seed, b) landed on it.
+        ``want_counts=True``: (replicas, counts (n_seeds * n_replicas, n_chunks) int32 on the device)."""
+        chunk = self._dev(chunk, "chunk", torch.float64)
+        if chunk.dim() != 4 or chunk.shape[2] != chunk.shape[3]:
+            raise SymodeError(f"chunk must be (n_seeds, n_chunks, n, n), got {tuple(chunk.shape)}")
+        if not isinstance(seeds, torch.Tensor):
+            seeds = torch.tensor([int(v) for v in seeds], dtype=torch.int64).to(chunk.device)
+        seeds = self._dev(seeds, "seeds", torch.int64)
+        S, C, n, _ = chunk.shape
+        if tuple(seeds.shape) != (S,) or seeds.device != chunk.device:
+            raise SymodeError(f"seeds must be ({S},) int64 on {chunk.device}, got {tuple(seeds.shape)} on {seeds.device}")
+        B = int(n_replicas)
+        out = torch.empty(max(S * B, 0), n, n, dtype=torch.float64, device=chunk.device)
+        counts = torch.empty(max(S * B, 0), C, dtype=torch.int32, device=chunk.device) if want_counts else None
+        self._check(self.lib.symode_gram_resample(self._ptr(chunk), self._ptr(seeds), S, C, n, B, self._ptr(out), self._ptr(counts),
+                                                  self._stream(chunk)), "symode_gram_resample")
+        return (out, counts) if want_counts else out
+
+    def stlsq_bag(self, G, rep_xi, rep_mask, rep_fell, n_replicas, gamma, tau_milli=1000, tau_table=None, *, d, to_host=False):
+        """Aggregate the replica fits of every seed and refit on the terms kept, ONE launch (symode_stlsq_bag).  G (n_seeds, p+d,
+        p+d) fp64 on the device, each seed's own matrix; ``rep_xi`` (n_seeds * n_replicas, d, p) fp32, ``rep_mask`` (same) uint8 and
+        ``rep_fell`` (n_seeds * n_replicas,) int32 on the device: Xi, mask and fell of ``stlsq_sweep`` on ``gram_resample``'s
+        matrices.  ``tau_milli``: the inclusion level in thousandths for all problems (one per seed); ``tau_table`` (n_problems,)
+        int32 on the device or a list of integers: problem s is seed s % n_seeds at level tau_table[s], every value in 0 .. 1000
+        (a list is checked here; a device tensor is the caller's to have checked).
+        Returns (Xi (n_problems, d, p) fp32, mask (n_problems, d, p) uint8, fell (n_problems,) int32, count (n_seeds, d, p) int32,
+        valid (n_seeds,) int32, mean, std (n_seeds, d, p) fp64) as device tensors; ``to_host=True``: numpy arrays after one copy
+        of the one buffer they share."""
+        G = self._dev(G, "G", torch.float64)
+        d = int(d)
+        n_seeds, p = self._stlsq_G(G, d)
+        B = int(n_replicas)
+        rep_xi, rep_mask = self._dev(rep_xi, "rep_xi"), self._dev(rep_mask, "rep_mask", torch.uint8)
+        rep_fell = self._dev(rep_fell, "rep_fell", torch.int32)
+        rows = n_seeds * max(B, 0)
+        if tuple(rep_xi.shape) != (rows, d, p) or rep_mask.shape != rep_xi.shape or tuple(rep_fell.shape) != (rows,):
+            raise SymodeError(f"rep_xi, rep_mask must be (n_seeds * n_replicas, d, p) = ({rows}, {d}, {p}) and rep_fell ({rows},), got "
+                              f"{tuple(rep_xi.shape)}, {tuple(rep_mask.shape)}, {tuple(rep_fell.shape)}")
+        if any(t.device != G.device for t in (rep_xi, rep_mask, rep_fell)):
+            raise SymodeError(f"the replica outputs must lie on {G.device}")
+        S = n_seeds
+        if tau_table is not None:
+            if not isinstance(tau_table, torch.Tensor):
+                values = [int(v) for v in tau_table]
+                if any(v < 0 or v > 1000 for v in values):
+                    raise SymodeError(f"tau_table: every inclusion level must lie in 0 .. 1000 thousandths, got {values}")
+                tau_table = torch.tensor(values, dtype=torch.int32).to(G.device)
+            tau_table = self._dev(tau_table, "tau_table", torch.int32)
+            if tau_table.dim() != 1 or tau_table.device != G.device:
+                raise SymodeError(f"tau_table must be (n_problems,) int32 on {G.device}")
+            S = tau_table.shape[0]
+        o, fetch = self._stlsq_outputs(G, "symode_stlsq_bag", S, d, p)
+        self._check(self.lib.symode_stlsq_bag(self._ptr(G), n_seeds, S, d, p, B, self._ptr(rep_xi), self._ptr(rep_mask),
+                                              self._ptr(rep_fell), self._ptr(tau_table), int(tau_milli), float(gamma),
+                                              *(o[k].data_ptr() for k in ("xi", "mask", "fell", "count", "valid", "mean", "std")),
+                                              self._stream(G)), "symode_stlsq_bag")
+        o = fetch(to_host)
+        return tuple(o[k] for k in ("xi", "mask", "fell")) + tuple(o[k][:n_seeds] for k in ("count", "valid", "mean", "std"))
 
     def stlsq_path(self, G, V, n_points, gamma, tol, floor_rel, n_problems=None, *, d, near_band=1e-4, to_host=False,
                    keep_path=False):

@@ -97,6 +97,18 @@ w_sindy_reg=... under it (a threshold axis is refused: the path asks for no thre
 holds order, mse_train, reg_train, mse_val, best and near of all problems.  It is a flag of its own: without it every argument
 combination answers word for word what it answered before.
 
+``--bagging B [--bag_chunks C] [--bag_inclusion v1,v2,...]`` (with --method stlsq --device_stlsq) is block-bootstrap bagging of
+the threshold fit, ensemble SINDy (``SeedSweepSTLSQ.solve_bagged``): per seed B replicas, each a resample with replacement of the
+C (default 128) chunks of the seed's time-ordered rows, are fit by the threshold loop (--threshold, --w_sindy_reg, --num_epochs
+as ever), a term is kept when the share of replicas it survives in reaches the inclusion level, and the model is refit on that
+support from the seed's own matrix.  Four launches whatever B: the chunk matrices (one gather), the replica matrices
+(symode_gram_resample), the n_seeds x B replica fits (symode_stlsq_sweep), aggregation and refit (symode_stlsq_bag).  The levels
+are multiples of 0.001 in [0, 1] (default BAG_INCLUSION; profiles/stlsq_bag.txt: how it was chosen, and where bagging loses);
+several levels are a grid on the same replica fits -- problem order, result files and table are ``--grid``'s.
+``eval_results/<save_dir>/bag.npz`` holds count, valid, mean, std and fell of all seeds.  Opt-in: without --bagging every argument
+combination answers word for word what it answered before.  Not covered, and refused by name: the constrained and the
+regularised fits, both paths, --wsindy, the other grids, --lstsq_driver gelsy, --use_latent, more than one rank.
+
 ``--fold_linear_action`` lets the closure of the reversed regulariser fold a linear group action g(x) = J x into its
 coefficients where the data are found to be one (``BatchedClosure(linear_action=None)``): a faster kernel and the same
 closure up to rounding, not bit for bit -- which is why it has to be asked for here.
@@ -197,7 +209,7 @@ def _grid_problem(problem, n_seeds):
 
 def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=None, n_seeds=None, device_stlsq=False,
              stlsq_grid=None, wsindy=False, wsindy_grid=None, equiv_stlsq=False, min_norm_stlsq=False, symreg_stlsq=False,
-             stlsq_path=False, path_tol=None, symreg_path=False):
+             stlsq_path=False, path_tol=None, symreg_path=False, bagging=None, bag_chunks=None, bag_inclusion=None):
     """None when main_sweep covers the run, else why not -- for a config it does not cover, with the per-seed command to run
     instead.  A pure function of its arguments: ``world`` the number of ranks, ``engine`` the injected test engine, if any.
     ``--method stlsq`` is accepted with ``--sindy_optimizer lbfgs`` only, as before the Adam sweep existed; the Adam rules
@@ -219,9 +231,18 @@ def _refusal(args, method='lbfgs', world=1, engine=None, grid=None, lbfgs_grid=N
     ``symreg_path``: the ``--symreg_path`` flag; off (the default), every answer is what it was.  On, its own rules
     (``_refusal_symreg_path``) come first -- before those of --stlsq_path and --symreg_stlsq, which it refuses by name --,
     --path_tol is its tolerance, the rule that keeps the symmetry regulariser out of --method stlsq does not apply, and
-    --stlsq_grid reads SYMREG_PATH_GRID_NAMES."""
+    --stlsq_grid reads SYMREG_PATH_GRID_NAMES.
+    ``bagging``, ``bag_chunks``, ``bag_inclusion``: the ``--bagging`` and ``--bag_chunks`` values and the ``--bag_inclusion``
+    string (None: not given); without them every answer is what it was.  Given, their own rules (``_refusal_bagging``) come
+    first and are all of them: what they let through is a plain ``--method stlsq --device_stlsq`` run on one rank."""
     if method not in ('lbfgs', 'stlsq'):
         return f'--method {method}: lbfgs or stlsq'
+    if bagging is not None or bag_chunks is not None or bag_inclusion is not None:
+        why = _refusal_bagging(args, method, world, engine, n_seeds, device_stlsq, bagging, bag_chunks, bag_inclusion,
+                               equiv_stlsq or min_norm_stlsq, symreg_stlsq, stlsq_path or path_tol is not None, symreg_path,
+                               wsindy or wsindy_grid, grid or lbfgs_grid or stlsq_grid)
+        if why is not None:
+            return why
     if symreg_path:
         why = _refusal_symreg_path(args, method, engine, device_stlsq, stlsq_path, symreg_stlsq, equiv_stlsq, min_norm_stlsq,
                                    wsindy or wsindy_grid, grid or lbfgs_grid, stlsq_grid, path_tol)
@@ -390,6 +411,79 @@ def _refusal_symreg_stlsq(args, method, device_stlsq, wsindy, equiv_stlsq, min_n
                 'regularised form')
     if args['use_latent']:
         return '--symreg_stlsq does not cover latent fits (--use_latent)'
+    return None
+
+
+BAG_CHUNKS = 128                                           # --bag_chunks' default
+BAG_INCLUSION = 1.0                                        # --bag_inclusion's default (profiles/stlsq_bag.txt: how it was chosen)
+
+
+def _parse_inclusion(text):
+    """``--bag_inclusion v1,v2,...`` -> ([levels], None), or (None, why not): multiples of 0.001 in [0, 1], none twice."""
+    from .sweep import inclusion_milli
+    try:
+        values = [float(v) for v in str(text).split(',')]
+        milli = inclusion_milli(values)
+    except ValueError:
+        return None, (f'--bag_inclusion {text}: the inclusion levels must be a non-empty comma-separated list of multiples of 0.001 '
+                      'in [0, 1] (the share of replicas a term has to survive in)')
+    if len(set(milli)) != len(milli):
+        return None, f'--bag_inclusion {text}: a level is given twice'
+    return [t / 1000 for t in milli], None
+
+
+def _refusal_bagging(args, method, world, engine, n_seeds, device_stlsq, bagging, bag_chunks, bag_inclusion, constrained, symreg_stlsq,
+                     stlsq_path, symreg_path, wsindy, any_grid):
+    """The rules of --bagging, --bag_chunks and --bag_inclusion, all decided by the arguments alone."""
+    if bagging is None:
+        given = ' and '.join(flag for flag, v in (('--bag_chunks', bag_chunks), ('--bag_inclusion', bag_inclusion)) if v is not None)
+        return (f'{given} needs --bagging B: they are the chunk count and the inclusion levels of the bagged threshold fit (B '
+                'bootstrap replicas per seed)')
+    if wsindy:
+        return ('--bagging is the bagged fit of --method stlsq: the weak-SINDy sweep (--wsindy) is not covered (drop one of them)')
+    if method != 'stlsq':
+        return ('--bagging is block-bootstrap bagging of the sequential-threshold least-squares sweep (ensemble SINDy): it needs '
+                '--method stlsq')
+    if not device_stlsq:
+        return ('--bagging needs --device_stlsq: replicas, replica fits and refit are launches on the device (the host route of '
+                '--method stlsq fits one subsample per seed)')
+    if args.get('eq_constraint') or constrained:
+        return ('--bagging does not go with --eq_constraint / --equiv_stlsq / --min_norm_stlsq: bagging under the equivariance '
+                'constraint is not covered (drop them, or fit with --equiv_stlsq)')
+    if args['w_sym_reg'] > 0 or symreg_stlsq or symreg_path:
+        return ('--bagging does not go with --w_sym_reg > 0 / --symreg_stlsq / --symreg_path: bagging with the symmetry regulariser '
+                'needs a joint refit over the rows and is not covered (drop them, or fit with --symreg_stlsq)')
+    if stlsq_path:
+        return ('--bagging does not go with --stlsq_path / --path_tol: the replicas are fit by the threshold loop, the path asks '
+                'for no threshold (give one of them)')
+    if any_grid:
+        return ('--bagging does not go with --grid / --lbfgs_grid / --stlsq_grid / --wsindy_grid: its own grid is the list of '
+                'inclusion levels, --bag_inclusion v1,v2,... (drop the grid)')
+    if args.get('lstsq_driver') == 'gelsy':
+        return ('--bagging fits with the full-rank driver (gels) only: the rank rule of --lstsq_driver gelsy runs on the host '
+                'route (drop one of them)')
+    if args['use_latent']:
+        return '--bagging does not cover latent fits (--use_latent)'
+    if engine is None and str(args.get('device')) == 'cpu':
+        return '--bagging runs on the GPU only (no CPU fallback): a HIP device is required'
+    if world > 1:
+        return ('--bagging runs in one process: the chunk matrices of the replicas are not all-reduced over ranks yet (give every '
+                'GPU its own block of seeds, python -m symode_amd.main_sweep --seed <first> --n_seeds <count> ... per process)')
+    if bagging < 1:
+        return f'--bagging {bagging}: the number of bootstrap replicas per seed must be >= 1'
+    if bag_chunks is not None and not 1 <= bag_chunks <= 1024:
+        return f'--bag_chunks {bag_chunks}: a seed\'s rows are cut into 1 .. 1024 chunks'
+    levels = [BAG_INCLUSION]
+    if bag_inclusion is not None:
+        levels, why = _parse_inclusion(bag_inclusion)
+        if why is not None:
+            return why
+    if n_seeds is not None and n_seeds * bagging > MAX_GRID_PROBLEMS:
+        return (f'--bagging: {n_seeds} seeds x {bagging} replicas = {n_seeds * bagging} replica problems, one launch takes at most '
+                f'{MAX_GRID_PROBLEMS}')
+    if n_seeds is not None and n_seeds * len(levels) > MAX_GRID_PROBLEMS:
+        return (f'--bag_inclusion: {len(levels)} levels x {n_seeds} seeds = {n_seeds * len(levels)} problems, one launch takes at most '
+                f'{MAX_GRID_PROBLEMS}')
     return None
 
 
@@ -601,6 +695,8 @@ def _fit_stlsq(ctx):
                         group=ctx.group, engine=ctx.engine, idx=rows, idx_sorted=True)
     if getattr(ctx, 'stlsq_path', False):
         return _fit_stlsq_path(ctx, sw, lib)
+    if getattr(ctx, 'bagging', None) is not None:
+        return _fit_bagging(ctx, sw, lib)
     if laligan is not None:
         # [G | R | count] as _fit_lbfgs builds them under --gram_closure: no per-seed copy of the points, ONE all-reduce
         from .gram_closure import GramStatistics
@@ -656,6 +752,31 @@ def _fit_stlsq_path(ctx, sw, lib):
                                                          for j in range(size.shape[1])),
              f'near-tie eliminations: {int((record["near"] > 0).sum())} of {len(ctx.seeds)} problems',
              f'--threshold ({args["threshold"]:g}) is not used by the path']
+    return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
+
+
+def _fit_bagging(ctx, sw, lib):
+    """--bagging: the seeds' matrices as ``_fit_stlsq`` builds them and four launches (``SeedSweepSTLSQ.solve_bagged``); the
+    levels of --bag_inclusion are ``ctx.grid`` (one level: no grid).  Rank 0 also writes eval_results/<save_dir>/bag.npz: count,
+    valid, mean, std and fell of all seeds."""
+    args = ctx.args
+    B, C, levels = ctx.bagging, ctx.bag_chunks, ctx.bag_levels
+    if C > sw.m_local:
+        raise SystemExit(f'--bag_chunks {C}: a seed holds {sw.m_local} rows, every chunk needs at least one')
+    Xi, mask, record = sw.solve_bagged(args['w_sindy_reg'], args['threshold'], B, n_chunks=C, inclusion=levels,
+                                       max_iter=max(1, args['num_epochs']))
+    n_seeds = len(ctx.seeds)
+    if ctx.rank == 0:
+        eval_dir = f'eval_results/{args["save_dir"]}'
+        os.makedirs(eval_dir, exist_ok=True)
+        np.savez(f'{eval_dir}/bag.npz', seeds=np.asarray(ctx.seeds), n_replicas=B, n_chunks=C, inclusion=np.asarray(levels),
+                 **{k: record[k] for k in ('count', 'valid', 'mean', 'std', 'fell')})
+    size = mask.sum(dim=(1, 2)).to(torch.int64).reshape(len(levels), n_seeds)
+    valid = record['valid']
+    lines = [f'{n_seeds} seeds x {sw.n_points} points (over {ctx.world} rank(s)), bagged: {B} replicas of {C} chunks x '
+             f'{sw.m_local // C} rows per seed, valid replicas {int(valid.min())}-{int(valid.max())} of {B}, support size '
+             + ', '.join(f'{int(size[g].min())}-{int(size[g].max())} at inclusion {level:g}' for g, level in enumerate(levels))
+             + f', refits solved on the host: {int(record["fell"].sum())}']
     return SimpleNamespace(Xi=Xi, mask=mask, lib=lib, lines=lines)
 
 
@@ -986,13 +1107,16 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
     stlsq_path = _pop_flag(argv, '--stlsq_path')
     symreg_path = _pop_flag(argv, '--symreg_path')
     path_tol = _pop(argv, '--path_tol', None, float)
+    bagging = _pop(argv, '--bagging', None, int)
+    bag_chunks = _pop(argv, '--bag_chunks', None, int)
+    bag_inclusion = _pop(argv, '--bag_inclusion', None, str)
     fold_linear_action = _pop_flag(argv, '--fold_linear_action')
     args = vars(get_args(argv=argv))
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     why = _refusal(args, method, world, engine, grid=grid or None, lbfgs_grid=lbfgs_grid or None, n_seeds=n_seeds,
                    device_stlsq=device_stlsq, stlsq_grid=stlsq_grid or None, wsindy=wsindy, wsindy_grid=wsindy_grid or None,
                    equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq, stlsq_path=stlsq_path,
-                   path_tol=path_tol, symreg_path=symreg_path)
+                   path_tol=path_tol, symreg_path=symreg_path, bagging=bagging, bag_chunks=bag_chunks, bag_inclusion=bag_inclusion)
     if why is not None:
         raise SystemExit(why)
     group = init_ranks(args, world, one_gpu, backend, set_device=engine is None)
@@ -1015,6 +1139,14 @@ def main(argv=None, engine=None, backend='nccl', one_gpu=False):
                           device_stlsq=device_stlsq, fold_linear_action=fold_linear_action, train=train_dataset,
                           equiv_stlsq=equiv_stlsq, min_norm_stlsq=min_norm_stlsq, symreg_stlsq=symreg_stlsq,
                           stlsq_path=stlsq_path, path_tol=path_tol, val=val_dataset, symreg_path=symreg_path)
+    if bagging is not None:
+        ctx.bagging, ctx.bag_chunks = bagging, BAG_CHUNKS if bag_chunks is None else bag_chunks
+        ctx.bag_levels = [BAG_INCLUSION] if bag_inclusion is None else _parse_inclusion(bag_inclusion)[0]
+        if len(ctx.bag_levels) > 1:                                 # several levels: a grid on the same replica fits
+            ctx.grid_names = {'bag_inclusion': 'inclusion'}
+            ctx.grid_axes = [('bag_inclusion', ctx.bag_levels)]
+            ctx.grid = _grid_points(ctx.grid_axes)
+            args['bag_inclusion'] = ctx.bag_levels[0]               # (the report reads an axis' scalar from args)
     if wsindy_grid:
         ctx.grid_names = WSINDY_GRID_NAMES
         ctx.grid_axes = _parse_grid(wsindy_grid, WSINDY_GRID_NAMES, '--wsindy_grid')[0]

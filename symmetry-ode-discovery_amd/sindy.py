@@ -484,6 +484,55 @@ def stlsq_path_from_gram(G, V, gamma, tol, floor_rel, near_band, d, n_points=0):
     return Xi, mask, dict(order=order, rss_train=rss_train, rss_val=rss_val, best=best, near=near, path_xi=path)
 
 
+def stlsq_bag_statistics(rep_xi, rep_mask, rep_fell):
+    """The statistics of symode_stlsq_bag for ONE seed in numpy, in its order of operations: over the replicas b ascending, one
+    with ``rep_fell`` set left out, valid = the replicas that remain; per term count = the valid replicas that keep it and, over
+    those in fp64, sum from 0.0, mean = sum / count, ss = the sum from 0.0 of (x - mean)^2 in a second pass, std =
+    sqrt(ss / count); count == 0 gives mean = std = 0.  rep_xi (B, d, p) fp32, rep_mask (B, d, p), rep_fell (B,).
+    Returns (count (d, p) int32, valid int, mean, std (d, p) float64)."""
+    rep_xi, rep_mask = np.asarray(rep_xi, dtype=np.float32), np.asarray(rep_mask) != 0
+    ok = [b for b in range(rep_xi.shape[0]) if not rep_fell[b]]
+    shape = rep_xi.shape[1:]
+    count, total = np.zeros(shape, dtype=np.int32), np.zeros(shape)
+    for b in ok:
+        count += rep_mask[b]
+        total = np.where(rep_mask[b], total + rep_xi[b].astype(np.float64), total)
+    some = count > 0
+    mean = np.where(some, total / np.maximum(count, 1), 0.0)
+    ss = np.zeros(shape)
+    for b in ok:
+        dev = rep_xi[b].astype(np.float64) - mean
+        ss = np.where(rep_mask[b], ss + dev * dev, ss)
+    std = np.where(some, np.sqrt(ss / np.maximum(count, 1)), 0.0)
+    return count, len(ok), mean, std
+
+
+def stlsq_bag_from_gram(G_seed, rep_xi, rep_mask, rep_fell, tau_milli, gamma, d, n_points=0):
+    """Aggregation and refit of ONE bagged problem in numpy, the host twin of symode_stlsq_bag: the replica fits of a seed
+    (rep_xi (B, d, p) fp32, rep_mask (B, d, p), rep_fell (B,)) are counted (``stlsq_bag_statistics``), a term is kept iff
+    valid > 0 and 1000 count >= tau_milli valid (integers), and every equation row is refit on its kept support from the seed's
+    OWN matrix G_seed (p+d, p+d) with ridge ``gamma`` (``lstsq_normal(..., 'gels')``, with its minimum-norm fallback and
+    RuntimeWarning on a singular support), rounded to fp32; an empty row is zeros.  ``n_points``: the rows behind G_seed (only
+    the rank-revealing fallback reads it).
+    Returns (Xi (d, p) float32, mask (d, p) bool, record) with record = dict(count (d, p) int32, valid int, mean, std (d, p)
+    float64)."""
+    tau_milli = int(tau_milli)
+    if not 0 <= tau_milli <= 1000:
+        raise ValueError(f'tau_milli (the inclusion level in thousandths) must lie in 0 .. 1000, got {tau_milli}')
+    G = np.asarray(G_seed, dtype=np.float64)
+    p = G.shape[0] - d
+    count, valid, mean, std = stlsq_bag_statistics(rep_xi, rep_mask, rep_fell)
+    mask = (1000 * count.astype(np.int64) >= tau_milli * valid) & (valid > 0)
+    Gtt = G[:p, :p] + (gamma * gamma) * np.eye(p)
+    Xi = np.zeros((d, p), dtype=np.float32)
+    for j in range(d):
+        sel = np.nonzero(mask[j])[0]
+        if len(sel):
+            w, _ = lstsq_normal(Gtt[np.ix_(sel, sel)], G[sel, p + j], int(n_points) + len(sel), 'gels')
+            Xi[j, sel] = np.asarray(w, dtype=np.float64).astype(np.float32)
+    return Xi, mask, dict(count=count, valid=valid, mean=mean, std=std)
+
+
 def stlsq_path_symreg_select(mse_val, V, d, tol, floor_rel):
     """The step symode_stlsq_path_symreg keeps, ``stlsq_path_select`` on the joint chain: the LARGEST t with
     mse_val[t] <= (1 + tol) max(min mse_val, 0) + floor_rel Vyy, Vyy = sum_j V[p+j][p+j] (the empty model's error, j ascending)."""

@@ -19,8 +19,10 @@ import torch.distributed as dist
 from .coef_map import CoefMap
 from .engine import LBFGS_ACCEPT, LBFGS_BEGIN, get_engine, library_flags
 from . import lstsq as _lstsq
-from .sindy import (NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_constrained_from_gram, stlsq_path_from_gram,
-                    stlsq_path_symreg_from_gram, stlsq_solve_from_gram, stlsq_symreg_from_gram, weak_test_functions)
+from .device_adam import _seed_words, _subsample_key
+from .sindy import (NEAR_THRESHOLD_BAND, near_threshold_cases, stlsq_bag_from_gram, stlsq_constrained_from_gram,
+                    stlsq_path_from_gram, stlsq_path_symreg_from_gram, stlsq_solve_from_gram, stlsq_symreg_from_gram,
+                    weak_test_functions)
 
 
 def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
@@ -43,6 +45,53 @@ def seeded_subsamples(n, m, seeds, device, dtype=torch.int64):
         row.uniform_(generator=g)
     idx = torch.topk(keys, m, dim=1, largest=False, sorted=False).indices
     return torch.sort(idx, dim=1).values.to(dtype)
+
+
+BAG_MAX_CHUNKS = 1024                   # RESAMPLE_MAX_CHUNKS of csrc/gram_resample.hpp
+BAG_MAX_REPLICA_PROBLEMS = 2 ** 31 - 1  # what symode_stlsq_sweep takes as a problem count
+
+
+def resample_counts(seed, b, n_chunks):
+    """How often each of ``n_chunks`` chunks is drawn for bootstrap replica ``b`` of ``seed``: the draw of symode_gram_resample
+    (csrc/gram_resample.hpp) in Python integer arithmetic, constant for constant.  w = seed_words(seed_words(seed) + b) modulo
+    2^64; draw t = 0 .. C-1 is u = subsample_key(low32(w), high32(w), t) and lands on chunk (u * C) >> 32.  Returns (C,) int32,
+    which sums to C."""
+    C = int(n_chunks)
+    lo, hi = _seed_words(int(seed))
+    lo, hi = _seed_words(((hi << 32) | lo) + int(b))
+    counts = np.zeros(C, dtype=np.int32)
+    for t in range(C):
+        counts[(_subsample_key(lo, hi, t) * C) >> 32] += 1
+    return counts
+
+
+def resample_grams(chunk, seeds, n_replicas):
+    """symode_gram_resample in numpy: chunk (S, C, n, n) fp64 -> ((S B, n, n) fp64, counts (S B, C) int32), replica b of seed k at
+    k B + b, each the sum from 0.0 over c ascending of count[c] * chunk[k, c], chunks that were not drawn skipped."""
+    chunk = np.asarray(chunk, dtype=np.float64)
+    S, C = chunk.shape[:2]
+    B = int(n_replicas)
+    out, counts = np.zeros((S * B,) + chunk.shape[2:]), np.zeros((S * B, C), dtype=np.int32)
+    for k in range(S):
+        for b in range(B):
+            counts[k * B + b] = resample_counts(seeds[k], b, C)
+            for c in np.nonzero(counts[k * B + b])[0]:
+                out[k * B + b] = out[k * B + b] + float(counts[k * B + b, c]) * chunk[k, c]
+    return out, counts
+
+
+def inclusion_milli(inclusion):
+    """The inclusion levels of a bagged fit in thousandths: a value or a list of values in [0, 1], each a multiple of 0.001."""
+    values = [inclusion] if np.isscalar(inclusion) else list(inclusion)
+    if not values:
+        raise ValueError('inclusion: at least one level is needed')
+    milli = []
+    for v in values:
+        t = int(round(float(v) * 1000)) if np.isfinite(float(v)) else -1
+        if not 0 <= t <= 1000 or abs(float(v) * 1000 - t) > 1e-6:
+            raise ValueError(f'inclusion: every level must be a multiple of 0.001 in [0, 1], got {v!r}')
+        milli.append(t)
+    return milli
 
 
 SINGULAR_WORDS = 'singular normal equations under the full-rank (gels) driver: minimum-norm solution returned instead'
@@ -233,6 +282,8 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
             self.idx = seeded_subsamples(self.n_local, m, [1_000_003 * (seed0 + s) + rank for s in range(n_seeds)],
                                          x.device, dtype=torch.int32)
             self.m_local = m
+        # what the bootstrap replicas of ``solve_bagged`` are keyed by: the seed of each problem, the rank left out
+        self.seeds = [1_000_003 * (seed0 + s) for s in range(n_seeds)]
         self._gram, self._gram_dev = None, None
 
     def grams(self, device=False):
@@ -387,6 +438,103 @@ class SeedSweepSTLSQ(_DeviceSTLSQ):
 
         return self._path_fit(device, keep_path, ('order', 'mse_train', 'reg_train', 'mse_val', 'best', 'near'), twin, launch,
                               val_gram, rev[0])
+
+    def chunk_grams(self, n_chunks):
+        """(S, C, p+d, p+d) fp64 on the device: for every seed the augmented Gram matrices of C = ``n_chunks`` chunks of its
+        rows, ONE symode_aug_gram_gather launch.  Seed k's ascending rows idx[k, :C L], L = m // C, are viewed as an (S C, L)
+        table: chunk c holds rows c L .. (c + 1) L - 1 of the seed's subsample, neighbours in time.  The rows beyond C L --
+        fewer than C of them -- are in no chunk: they take part in the seed's own matrix (``grams``), on which the bagged
+        model is refit, and in no replica."""
+        C = int(n_chunks)
+        if not 1 <= C <= BAG_MAX_CHUNKS:
+            raise ValueError(f'n_chunks = {C}: the chunk counts of a replica take 1 .. {BAG_MAX_CHUNKS} chunks')
+        if C > self.m_local:
+            raise ValueError(f'n_chunks = {C} chunks need at least one row each: a seed holds m = {self.m_local} rows')
+        if self.group is not None and dist.get_world_size(self.group) > 1:
+            raise ValueError('chunk_grams: more than one rank is not covered (the chunk matrices would need their own all-reduce)')
+        L = self.m_local // C
+        table = self.idx[:, :C * L].reshape(self.S * C, L).contiguous()
+        G = self.engine.aug_gram_gather(self.x, self.dx, table, self.order, self.flags)
+        return G.reshape(self.S, C, self.p + self.d, self.p + self.d)
+
+    def solve_bagged(self, w_sindy_reg, threshold, n_replicas, n_chunks=128, inclusion=1.0, max_iter=10, device=True):
+        """Block-bootstrap bagging of the threshold fit (ensemble SINDy) for every seed: B = ``n_replicas`` replicas of a seed's
+        data, each a resample with replacement of the seed's C = ``n_chunks`` chunks of rows (``chunk_grams``), are fit by the
+        threshold loop; a term is kept when the share of replicas it survives in reaches ``inclusion``; the model is refit
+        on that support from the seed's own matrix.  Four launches whatever B and the number of levels: the chunk matrices
+        (symode_aug_gram_gather), the replica matrices (symode_gram_resample), the S B replica fits (symode_stlsq_sweep with
+        this ridge weight, threshold and ``max_iter``), aggregation and refit (symode_stlsq_bag).  ``inclusion``: a value, or a
+        list of G values -- the grid, problem (g, k) = g S + k is seed k at level g; multiples of 0.001 in [0, 1].
+        Returns (Xi (G S, d, p) float32, mask (G S, d, p) float32, record) with record = dict(count (S, d, p) int32, valid (S,)
+        int32, mean, std (S, d, p) float64 -- per term the replicas that keep it, and mean and standard deviation of its
+        coefficient over those -- fell (G S,) bool: the refits the launch handed to the host; all False with ``device=False``).  A replica whose fit met a pivot
+        that is not positive is left out (``valid`` counts the rest); a refit that did is solved by the host twin
+        (sindy.stlsq_bag_from_gram: the minimum-norm answer, with the full-rank driver's RuntimeWarning).  The launches take
+        ridge weight and threshold in fp32, as ``solve(device=True)`` does.
+        ``device=False``: resample, replica fits (symode_host_stlsq_sweep, full-rank driver), aggregation and refit in numpy on
+        the chunk matrices of the one gather launch."""
+        S, d, p = self.S, self.d, self.p
+        B = int(n_replicas)
+        if B < 1:
+            raise ValueError(f'n_replicas = {B}: a bagged fit needs at least one replica')
+        if S * B > BAG_MAX_REPLICA_PROBLEMS:
+            raise ValueError(f'{S} seeds x {B} replicas are more than the {BAG_MAX_REPLICA_PROBLEMS} problems of one launch')
+        milli = inclusion_milli(inclusion)
+        w, thr = _in_fp32([w_sindy_reg])[0], _in_fp32([threshold])[0]
+        if not (np.isfinite(w) and np.isfinite(thr) and w >= 0 and thr >= 0):
+            raise ValueError('the ridge weight and the threshold must be finite and >= 0')
+        max_iter = max(1, int(max_iter))
+        chunk = self.chunk_grams(n_chunks)
+        G = self.grams(device=True)
+        tau = [t for t in milli for _ in range(S)]
+        if device:
+            rep = self.engine.gram_resample(chunk, self.seeds, B)
+            rxi, rmask, _, _, rfell = self.engine.stlsq_sweep(rep, self.n_points, w, thr, max_iter, d=d,
+                                                              near_band=NEAR_THRESHOLD_BAND)
+            out = self.engine.stlsq_bag(G, rxi, rmask, rfell, B, w, tau_table=tau, d=d, to_host=True)          # one copy back
+            Xi, mask, fell = np.array(out[0]), np.asarray(out[1]).astype(bool), np.array(out[2])
+            record = dict(count=np.array(out[3]), valid=np.array(out[4]), mean=np.array(out[5]), std=np.array(out[6]))
+            held = _HostSets(G=G)
+            replicas = None
+
+            def on_host(s):
+                nonlocal replicas
+                if replicas is None:                                # the replica fits come to the host only when a refit fell
+                    replicas = tuple(t.cpu().numpy() for t in (rxi, rmask, rfell))
+                k = s % S
+                return held('G', k), tuple(t[k * B:(k + 1) * B] for t in replicas)
+        else:
+            rep, _ = resample_grams(chunk.cpu().numpy(), self.seeds, B)
+            rxi, rm8 = np.zeros((S * B, d, p), dtype=np.float32), np.ones((S * B, d, p), dtype=np.uint8)
+            rp, rn, rfell = (np.zeros(S * B, dtype=np.int32) for _ in range(3))
+            rep = np.ascontiguousarray(rep)
+            lib = _lstsq._native()
+            if not lib:
+                raise RuntimeError('solve_bagged(device=False) fits the replicas with symode_host_stlsq_sweep: build the library')
+            rc = lib.symode_host_stlsq_sweep(rep.ctypes.data, S * B, d, p, int(self.n_points), float(w), float(thr), max_iter, 1,
+                                             float(NEAR_THRESHOLD_BAND), rxi.ctypes.data, rm8.ctypes.data, rp.ctypes.data,
+                                             rn.ctypes.data, rfell.ctypes.data)
+            if rc != 0:
+                raise RuntimeError(f'symode_host_stlsq_sweep failed with code {rc}')
+            Gh = self.grams()
+            Xi, mask = np.zeros((len(tau), d, p), dtype=np.float32), np.zeros((len(tau), d, p), dtype=bool)
+            record = None
+            on_host = lambda s: (Gh[s % S], tuple(t[(s % S) * B:(s % S + 1) * B] for t in (rxi, rm8, rfell)))      # noqa: E731
+
+        def twin(s):
+            Gs, (xi_b, mask_b, fell_b) = on_host(s)
+            Xi[s], mask[s], rec = stlsq_bag_from_gram(Gs, xi_b, mask_b, fell_b, tau[s], float(w), d, self.n_points)
+            return rec
+
+        if device:
+            _flagged_to_host(fell, twin)
+        else:
+            recs = [twin(s) for s in range(len(tau))]
+            record = {k: np.stack([np.asarray(r[k]) for r in recs[:S]]) for k in ('count', 'valid', 'mean', 'std')}
+            record['valid'] = record['valid'].astype(np.int32)
+            fell = np.zeros(len(tau), dtype=np.int32)               # (nothing is handed over: the twin's own fallback answers)
+        record['fell'] = np.asarray(fell) != 0
+        return torch.from_numpy(Xi), torch.from_numpy(mask.astype(np.float32)), record
 
     def solve(self, w_sindy_reg, threshold, max_iter=10, lstsq_driver=None, device=False, hyper=None, coef=None, min_norm=False,
               rev=None):
